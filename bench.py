@@ -10,29 +10,40 @@ once per `--round-steps` steps and once at the end of the timed region
 (`fm_fedavg_allreduce` of the C ABI).  "image" = one dataset sample consumed by
 the step (it carries two views).
 
-usage: python bench.py --gpus N --steps K --warmup W
+usage: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 without a torchrun environment: this process starts the N ranks itself
   (python -m torch.distributed.run ... bench.py, one rank per GPU) before touching
   the GPU and exits with their code.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the outputs of the last timed step when
+--dump-outputs is given, and prints the line: `ms_per_step` is the wall time of one timed step.  Everything else is
+measured only with --full (below).
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller in its last step, as DIR/<name>.npy
+(float32 / float64): `loss` and the model state (`state`, `counters`) of a training step, `features` and `logits` of
+conv_fwd.  Inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
 Arithmetic: operands, accumulators and stored tensors are fp32 (`dtype` "f32"); the conv GEMMs form every fp32 product as
 six exact bf16 partial products on the bf16 matrix pipe (csrc/split3.h; as close to float64 as the fp32-MFMA
 kernels, tests/test_kernels_gpu.py).  `roofline.peak` is that form's roofline (bf16 dense peak / 6); --products 0 (fm_config.reserved[2]
-= 1) runs the fp32 matrix pipe instead, and the default run times that too (leg `stage1_fp32_mfma_pipe`, `value_on_fp32_mfma_pipe`).
+= 1) runs the fp32 matrix pipe instead, and a --full run times that too (leg `stage1_fp32_mfma_pipe`, `value_on_fp32_mfma_pipe`).
 
-The ONE line of a default N = 1 run carries, after the headline fields:
+--full adds, after the timed steps: `cpu_baseline` (the oracle on this host) and the separate one-stream roofline pass
+(see Streams); and on a default N = 1 run the line also carries:
   sustained      the same step repeated back to back for >= --sustain-s seconds (steady clock)
   legs           every other BASELINE config and BASELINE.md section-4 leg, each with its own
                  `roofline` and `cpu_baseline` (oracle on this host): the headline step on the fp32 pipe, conv forward bs 256, stage 1
                  with C = 14, LocalUpdate.train, stage-2 step, EfficientNet-B0 fp32 bs 256 / bf16
                  bs 512, prototype pass over N = 5 000, cosine tagging + top-k at N = 5 000 for
                  C = 5 / 14, FedAvg of 8 client states.  --no-legs skips them.
+  The full record (legs with their per-kernel tables) is also written to bench_legs.json in the working directory.
 
 Streams: the engine's default mode enqueues the frozen teacher's forward and the weight gradients on its own
 side stream (same bits as one stream, +3-4 %); that is what `value` times.  Co-running kernels stretch each
 other's launch windows, so the per-kernel durations behind `roofline` come from a ONE-stream engine: a short
-separate pass after the timed region on rank 0 (roofline.measured_in says so), or the timed region itself with
---one-stream -- the form to run under rocprofv3, whose per-kernel averages then agree with the line.
+separate pass after the timed region on rank 0 with --full (roofline.measured_in says so), or the timed region itself with
+--one-stream -- the form to run under rocprofv3, whose per-kernel averages then agree with the line.  Without --full a
+default-mode line has no roofline.
 
 Single legs (same JSON contract, named in config.workload):
   --workload conv_fwd --batch 256     eval-mode forward only: the north-star "conv forward at
@@ -147,6 +158,11 @@ def parse(argv=None):
     ap.add_argument("--profile-every", type=int, default=4,
                     help="HIP events bracket the conv launches of every Nth timed step (each pair costs ~3 us of "
                          "stream time: on every step that is 0.7 ms of a 39-ms ResNet-18 step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: cpu_baseline, the one-stream roofline pass, "
+                         "the sustained repeat, the legs, bench_legs.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -273,6 +289,24 @@ def read_families(eng):
     return [eng.profile_read(f) for f in range(NFAM)]
 
 
+DUMP_BYTES = 60 * 10**6                 # --dump-outputs stays under 64 MB with the .npy headers (ResNet-18 state: 44.75 MB)
+
+
+def write_outputs(path, arrays):
+    """arrays {name: float32 / float64 ndarray} -> path/<name>.npy.  Beyond DUMP_BYTES in all, the largest array is replaced
+    by a fixed, seeded sample of its flattened elements (in index order) that brings the total within the limit."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays[big].reshape(-1)
+        k = (DUMP_BYTES - (total - a.nbytes)) // a.itemsize
+        arrays[big] = a[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def one_stream_roofline_pass(args, eng, step_fn, max_images, dev):
     """ResNet-18: per-kernel durations from a second engine in stream mode 1 (every kernel alone on the chip), same state,
     same inputs, HIP events around every conv launch of `--roofline-steps` steps.  Returns (families, ms_per_step), or
@@ -352,7 +386,9 @@ def run_workload(args, rank, world, dev, dist, cpu_cand=None, cpu_budget_s=6.0):
         rccl_ranks = comm_init(eng)
         if rccl_ranks != world:
             raise SystemExit(f"[bench] library RCCL communicator has {rccl_ranks} ranks, --gpus {world}")
-    # Efficient_b0: the engine draws drop-connect / dropout multipliers before every train step
+    # Efficient_b0: the engine draws drop-connect / dropout multipliers before every train step, from its own seeded
+    # generator so that a run's inputs (and --dump-outputs) depend on its arguments only
+    eng.stochastic_generator = torch.Generator(device=dev).manual_seed(2037 + rank)
 
     # synthetic client data resident in HBM (seed = reference default, utils/options.py:10)
     g = torch.Generator(device=dev).manual_seed(1037 + rank)
@@ -452,6 +488,13 @@ def run_workload(args, rank, world, dev, dist, cpu_cand=None, cpu_budget_s=6.0):
         eng.profile_enable(False)
     lv = losses.cpu().numpy()
     assert np.isfinite(lv).all(), "non-finite loss in the benchmark"
+    if args.dump_outputs and rank == 0:
+        if args.workload == "conv_fwd":
+            outputs = {"features": feat_out.cpu().numpy(), "logits": logit_out.cpu().numpy()}
+        else:
+            flat_out, cnt_out = eng.get_state()
+            outputs = {"loss": lv[-1:].copy(), "state": flat_out, "counters": cnt_out.astype(np.float64)}
+        write_outputs(args.dump_outputs, outputs)
 
     # ---- sustained repeat: the same step back to back for >= sustain seconds (steady clock; a sub-second timed region never
     # reaches the state a training run lives in, and the driver's gpu_busy sampler cannot see it)
@@ -481,7 +524,8 @@ def run_workload(args, rank, world, dev, dist, cpu_cand=None, cpu_budget_s=6.0):
         assert np.isfinite(losses.cpu().numpy()).all(), "non-finite loss in the sustained repeat"
 
     roof = None
-    if not args.no_profile and rank == 0:        # (ranks != 0 build no second engine: the line is rank 0's)
+    # (ranks != 0 build no second engine: the line is rank 0's; without --full only the timed region's own events are read)
+    if not args.no_profile and rank == 0 and (in_region or args.full):
         sampled, one_stream_ms = None, None
         if in_region:
             fams = fams_region
@@ -584,7 +628,7 @@ def run_workload(args, rank, world, dev, dist, cpu_cand=None, cpu_budget_s=6.0):
     if sustained is not None:
         out["sustained"] = sustained
         out["sustained_ms_per_step"] = sustained["sustained_ms_per_step"]
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, cpu_cand, cpu_budget_s)
     else:
         out["cpu_baseline"] = None
@@ -760,6 +804,7 @@ def run_legs(args, dev, cand):
     def step_leg(**kw):
         a = copy.copy(args)
         a.steps, a.warmup, a.roofline_steps, a.one_stream, a._sustain = args.leg_steps, 5, 6, False, False
+        a.dump_outputs = None                    # the outputs on disk are the headline workload's
         for k, v in kw.items():
             setattr(a, k, v)
         out = run_workload(a, 0, 1, dev, None, cand, 5.0)
@@ -907,10 +952,11 @@ def compact_leg(name, leg):
 
 
 def emit(out, path="bench_legs.json"):
-    """legs (short lines) first, the full record to `path`, the parsed line LAST."""
+    """legs (short lines) first, the full record to `path` (None: not written), the parsed line LAST."""
     try:                                            # the full record first: nothing below may cost it
-        with open(path, "w") as f:
-            json.dump(out, f, indent=1)
+        if path is not None:
+            with open(path, "w") as f:
+                json.dump(out, f, indent=1)
     except OSError as ex:
         print(f"[bench] could not write {path}: {ex}", file=sys.stderr)
     for name, leg in (out.get("legs") or {}).items():
@@ -941,10 +987,10 @@ def main():
 
     headline = (args.workload == "stage1" and args.model == "Resnet18" and args.batch == 128 and args.classes == 5
                 and args.hw == 224 and not args.one_stream)
-    args._sustain = headline and world == 1 and args.sustain_s > 0
+    args._sustain = args.full and headline and world == 1 and args.sustain_s > 0
     out = run_workload(args, rank, world, dev, dist)
     if rank == 0:
-        if headline and world == 1 and not args.no_legs:
+        if args.full and headline and world == 1 and not args.no_legs:
             best = None
             if out.get("cpu_baseline"):
                 best = [out["cpu_baseline"]["threads"]]          # the legs' CPU baselines run at the headline's best thread count
@@ -955,7 +1001,7 @@ def main():
                 # the figure of that arithmetic beside `value` without digging into `legs`
                 out["value_on_fp32_mfma_pipe"] = {"value": f32["value"], "ms_per_step": f32["ms_per_step"],
                                                   "roofline_frac_of_fp32_mfma_peak": (f32.get("roofline") or {}).get("frac")}
-        emit(out)
+        emit(out, "bench_legs.json" if args.full else None)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
+import numpy as np  # noqa: E402
 import pytest  # noqa: E402
 
 RECORDS = [os.path.join(ROOT, "profiles", "r04", "bench_gpus1_with_legs.json"), os.path.join(ROOT, "profiles", "r05", "bench_legs.json"),
@@ -90,3 +91,17 @@ def test_oversized_fields_are_truncated_not_fatal(canned):
            "cpu_baseline": {"value": 1, "unit": "u", "cores": 1, "kind": "port", "sample": "s" * 9000}}
     s = bench.compact_leg("big", leg)
     assert len(s) <= 1500 and json.loads(s)["value"] == 1.0
+
+
+def test_dumped_outputs_stay_within_the_bound_and_repeat(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, at most DUMP_BYTES of data in all; past it the largest array becomes the
+    same seeded sample on every run.  A plain run leaves --full off."""
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    got = []
+    for run in ("a", "b"):
+        arrays = {"loss": np.ones(1, np.float32), "state": np.arange(2000, dtype=np.float32), "counters": np.zeros(4)}
+        bench.write_outputs(str(tmp_path / run), arrays)
+        got.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("loss", "state", "counters")})
+    assert sum(a.nbytes for a in got[0].values()) <= 4000 and got[0]["state"].dtype == np.float32
+    assert np.array_equal(got[0]["state"], got[1]["state"]) and np.all(np.diff(got[0]["state"]) > 0)
+    assert not bench.parse(["--steps", "3"]).full and bench.parse(["--full"]).full

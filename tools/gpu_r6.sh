@@ -10,7 +10,7 @@ if [ -z "$SKIP" ]; then
   timeout 2400 python3 -m pytest tests -m gpu -q 2>&1 | tail -40 > $OUT/pytest.log; tail -4 $OUT/pytest.log
   cp gpurun_out/parity_*.json $OUT/ 2>/dev/null
 fi
-timeout 600 python3 bench.py > $OUT/bench_stdout.txt 2> $OUT/bench_err.log; tail -1 $OUT/bench_stdout.txt | cut -c1-600
+timeout 600 python3 bench.py --full > $OUT/bench_stdout.txt 2> $OUT/bench_err.log; tail -1 $OUT/bench_stdout.txt | cut -c1-600
 cp bench_legs.json $OUT/bench_legs.json 2>/dev/null
 timeout 240 bash tools/prof_stats.sh ${TAG}_s1 --steps 30 --warmup 3 --no-legs --sustain-s 0 > $OUT/prof_s1.log 2>&1
 timeout 240 bash tools/prof_stats.sh ${TAG}_cf --workload conv_fwd --batch 256 --steps 60 --warmup 3 > $OUT/prof_cf.log 2>&1
