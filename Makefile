@@ -8,12 +8,9 @@ LIB   := fedmlp_amd/libfedmlp_hip.so
 
 all: $(LIB)
 
-# make TUNING=1: the kernels' tuning knobs (common.h fm_tune) become environment switches -- for measurements only
-TUNEFLAG := $(if $(TUNING),-DFM_TUNING,)
-
 build/%.o: fedmlp_amd/csrc/%.hip $(HDR)
 	@mkdir -p build
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function $(TUNEFLAG) -c $< -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -c $< -o $@
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJ)

@@ -23,21 +23,11 @@ __device__ __forceinline__ float fm_swish_f32(float v)
 }
 #endif
 
-// Tuning knobs of the kernels (tile orders, split counts, variant choices that were measured and settled): the shipped
-// library uses the defaults; a `make TUNING=1` build (-DFM_TUNING) reads them from the environment for measurements.
-// The few RUNTIME switches the shipped library does read are listed in DESIGN.md section 9, each with the test that
-// exercises it (FM_MFMA_SPLIT, FM_PLANES, FM_IGEMM_BLOCKS, FM_STEM_PACKED, FM_BN_MASK_FROM_Y, FM_EW_ROWS / FM_EW_ROWS_F32,
-// FM_DW_GENERIC, FM_FUSE_GATE; FM_DEBUG_REUSE_PLANES belongs to the timing probes of the test hooks).
-inline int fm_tune(const char* name, int dflt)
-{
-#ifdef FM_TUNING
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
+// Tile orders, split counts and variant choices of the kernels are settled constants in the code: an A/B arm lives in a
+// branch or a variant build, and the losing arm is deleted before merge.  The few RUNTIME switches the library does read are
+// listed in DESIGN.md section 9, each with the test that exercises it (FM_MFMA_SPLIT, FM_PLANES, FM_IGEMM_BLOCKS,
+// FM_STEM_PACKED, FM_BN_MASK_FROM_Y, FM_EW_ROWS / FM_EW_ROWS_F32, FM_DW_GENERIC, FM_FUSE_GATE; FM_DEBUG_REUSE_PLANES belongs
+// to the timing probes of the test hooks).
 
 // The ResNet conv GEMMs (igemm.hip, wgrad.hip) form their fp32 products either on the fp32 matrix pipe (0) or as exact bf16
 // partial products on the bf16 matrix pipe (9 = all nine, 6 = without the three below 2^-24 of the product; split3.h).  The form is
@@ -181,10 +171,9 @@ struct IgemmParams {
     // floats per row of W when that is not nsteps * KS (the packed stem in 32-k stages: rows of 176 floats walked as 6 x 32 --
     // the 16 floats past a row's end meet the zero-page chunks of X); 0 = nsteps * KS
     int wrow = 0;
-    // pconv.hip scheduling switches (set by launch_pconv): bit 0 = waves 4-7 issue a step's DMA behind its last column's MFMAs
-    // instead of in front of them (their SIMD partners 0-3 issue in front: one of a pair computes while the other issues),
-    // bit 1 = s_setprio 1 for waves 4-7, bit 2 = s_setprio 1 for waves 0-3
-    int pc_flags = 0;
+    // pconv.hip (set by launch_pconv): 1 = the lost-part test hook is armed (fm_debug_lose_part): the stream-K part is not
+    // announced and the finisher's wait is short
+    int lose_part = 0;
     // pconv.hip: where a stream-K finisher reports a part that never arrived (its wait is bounded): a device word the optimizer
     // kernel reads (a step with a lost part does not update the weights) and its host-mapped twin the next API call checks
     int* err = nullptr;
@@ -221,7 +210,6 @@ struct PwgradParams {
     int pix_per_split;           // multiple of 32 (set by the launcher)
     int tilesM, tilesN, nblk_n;  // set by the launcher
     int sp;                      // product form: 6 / 9
-    int pw_flags = 0;            // bit 0: waves 4-7 issue a step's DMA behind the step's last MFMAs (their SIMD partners in front of them)
     // pwgrad_ring.hip (set by its launcher): images, padded positions in all, positions per split (multiple of 32), splits,
     // blocks of a split share an XCD, ceil(2^32 / (Wi + 1)), ceil(2^32 / (Hi + 1))
     int nimg, Qtot, q_per_split, splits, xcd_remap;

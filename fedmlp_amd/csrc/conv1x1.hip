@@ -237,13 +237,11 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(const IgemmParams p
 // shapes the streaming kernel takes (also asked by the engine before it hands over a gate prologue)
 bool conv1x1_stream_takes(int Ci, int M, int Co)
 {
-    static const int enabled = fm_tune("FM_STREAM1X1", 1);
-    return enabled && Ci <= 256 && Ci % 16 == 0 && Co == M;
+    return Ci <= 256 && Ci % 16 == 0 && Co == M;
 }
 bool launch_conv1x1_stream(const IgemmParams& p, int groups, hipStream_t s)
 {
-    static const int enabled = fm_tune("FM_STREAM1X1", 1);
-    if (!enabled || p.stem_kw || p.ntaps != 1 || p.dh[0] != 0 || p.dw[0] != 0) return false;
+    if (p.stem_kw || p.ntaps != 1 || p.dh[0] != 0 || p.dw[0] != 0) return false;
     if (p.sg != 1 || p.os != 1 || p.oh0 != 0 || p.ow0 != 0) return false;
     if (p.Hg != p.Ho || p.Wg != p.Wo || p.Hi != p.Ho || p.Wi != p.Wo) return false;
     if (p.Ci > 256 || p.Ci % 16 != 0 || p.Co != p.M) return false;
@@ -255,10 +253,8 @@ bool launch_conv1x1_stream(const IgemmParams& p, int groups, hipStream_t s)
     // virtual tiles per block: enough pixels that staging the weight slice (MT*K*4 B) stays ~10 % of the block's
     // traffic, but no more -- small blocks launched in order keep the concurrently running ones on
     // neighbouring memory (DRAM locality, tools/ew_bw.hip)
-    static const int vt_env = fm_tune("FM_STREAM_VT", 0);
     const int bnv = igemm_tile_n(p.M);
-    int vt = std::max(1, (int)((10LL * MT * p.Ci + (long long)bnv * (p.Ci + MT) - 1) / ((long long)bnv * (p.Ci + MT))));
-    if (vt_env > 0) vt = vt_env;
+    const int vt = std::max(1, (int)((10LL * MT * p.Ci + (long long)bnv * (p.Ci + MT) - 1) / ((long long)bnv * (p.Ci + MT))));
     const int bpg = (p.tilesN + vt - 1) / vt;
     // split-product form (split3.h) while its weight planes fit two blocks per CU
     const int sp = p.Ci <= 192 ? p.sp : 0;

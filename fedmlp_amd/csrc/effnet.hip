@@ -561,7 +561,8 @@ static inline int rowu_grid(int nchunk, int nrg, int xr)
     const int ngroups = (nrg + xr - 1) / xr;
     return (ngroups + 7) / 8 * 8 * nchunk * xr;
 }
-static inline int rowu_xr() { static const int v = fm_tune("FM_DW_XR", 4); return v; }
+constexpr int DW_XR = 4;          // row groups per XCD batch
+constexpr int DW_RPB = 16;        // row steps per block of the row-uniform kernels without statistics
 // ST = 2 (data gradient of a block with an expand conv): the BN0-backward sums  S1 = sum dz*swish'(v),  S2 = sum dz*swish'(v)*xhat
 // (dz = the gradient this kernel stores, v = y_e*scale+shift, xhat = (y_e-mean)*istd) are taken here as well: y_e is read
 // at the output positions, the separate reduction pass over (dz, y_e) is gone.  bnq = {mean, istd, scale, shift} [groups][C].
@@ -712,8 +713,9 @@ __global__ __launch_bounds__(256) void dw_rowu_kernel(const T* __restrict__ x, c
     }
 }
 // stride-2 forward in the same row-uniform form: a wave step = one output row (img, oh), lanes = (4-column block of the
-// output row, channel quad); K input rows of 6 + K columns each, double-buffered (K is odd: the last row is peeled).
-template <int K, typename T, bool PF, int ST = 0>
+// output row, channel quad); K input rows of 6 + K columns each, double-buffered (K is odd: the last row is peeled; fp32 5x5:
+// 0.44 -> 0.32 ms with the second row buffer).
+template <int K, typename T, int ST = 0>
 __global__ __launch_bounds__(256) void dw_rowu_s2_kernel(const T* __restrict__ x, const float* __restrict__ w, T* __restrict__ y,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          int nrows, int Hi, int Wi, int Ho, int Wo, int C, int act, int nchunk,
@@ -752,7 +754,7 @@ __global__ __launch_bounds__(256) void dw_rowu_s2_kernel(const T* __restrict__ x
         f32x4 acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        raw_t ra[NIN], rb[PF ? NIN : 1];
+        raw_t ra[NIN], rb[NIN];
         auto load = [&](raw_t (&dst)[NIN], int kh) {
             const rsrc_t r = row_rsrc(x, img, ih0 + kh, Hi, in_row);
 #pragma unroll
@@ -769,23 +771,15 @@ __global__ __launch_bounds__(256) void dw_rowu_s2_kernel(const T* __restrict__ x
 #pragma unroll
                 for (int kw = 0; kw < K; ++kw) acc[j] += xin[2 * j + kw] * wr[kw];
         };
-        if constexpr (PF) {
-            load(ra, 0);
+        load(ra, 0);
 #pragma unroll 1
-            for (int kh = 0; kh < K - 1; kh += 2) {
-                load(rb, kh + 1);
-                comp(ra, kh);
-                load(ra, kh + 2);
-                comp(rb, kh + 1);
-            }
-            comp(ra, K - 1);
-        } else {
-#pragma unroll 1
-            for (int kh = 0; kh < K; ++kh) {
-                load(ra, kh);
-                comp(ra, kh);
-            }
+        for (int kh = 0; kh < K - 1; kh += 2) {
+            load(rb, kh + 1);
+            comp(ra, kh);
+            load(ra, kh + 2);
+            comp(rb, kh + 1);
         }
+        comp(ra, K - 1);
         const rsrc_t ro = row_rsrc(y, img, oh, Ho, out_row);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -948,9 +942,8 @@ static bool dw_rowu_launch(const T* x, const float* w, T* y, const float* scale,
 {
     const int WB = (W + 3) / 4, HB = (H + 1) / 2, Q = C / 4;
     const int nchunk = (WB * Q + 63) / 64, nrp = imgs * HB;
-    static const int rpb_env = fm_tune("FM_DW_RPB", 16);
-    int rpb = std::max(4, rpb_env);
-    const int xr = rowu_xr();
+    int rpb = DW_RPB;
+    const int xr = DW_XR;
     const BnQuad nobn{nullptr, nullptr, nullptr, nullptr};
     const T* noy = nullptr;
     if (st && st->pool) {          // eval: blocks stay inside one image, one record each, summed per image
@@ -991,14 +984,11 @@ static bool dw_rowu_s2_launch(const T* x, const float* w, T* y, const float* sca
 {
     const int WB = (Wo + 3) / 4, Q = C / 4;
     const int nchunk = (WB * Q + 63) / 64, nrows = imgs * Ho;
-    static const int rpb_env = fm_tune("FM_DW_RPB", 16);
-    static const int pf_env = fm_tune("FM_DW_PF", -1);
-    int rpb = std::max(4, rpb_env);
-    const bool pf = pf_env >= 0 ? pf_env != 0 : true;      // fp32 5x5 stride 2: 0.44 -> 0.32 ms with the second row buffer
+    int rpb = DW_RPB;
     if (st && st->pool) {
         rpb = dw_pool_rpb(Ho);
         const int gpi = Ho / rpb;
-        hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, true, 3>), dim3(nchunk * gpi * imgs), dim3(256), 0, s, x, w, y, scale, shift, nrows, Hi,
+        hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, 3>), dim3(nchunk * gpi * imgs), dim3(256), 0, s, x, w, y, scale, shift, nrows, Hi,
                            Wi, Ho, Wo, C, act, nchunk, rpb, reinterpret_cast<f32x4*>(st->rec));
         hipLaunchKernelGGL(dw_rowu_wgrad_reduce, dim3((Q + 15) / 16, 1, imgs), dim3(256), 0, s, reinterpret_cast<const f32x4*>(st->rec),
                            st->pool, 1, Q, WB, nchunk, gpi, 1);
@@ -1008,7 +998,7 @@ static bool dw_rowu_s2_launch(const T* x, const float* w, T* y, const float* sca
         const int nrg_g = dw_stats_rowgroups(nrows / st->groups, nchunk, st->groups);
         if (nrg_g) {
             rpb = nrows / st->groups / nrg_g;
-            hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, true, 1>), dim3(nchunk * nrg_g * st->groups), dim3(256), 0, s, x, w, y, scale,
+            hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, 1>), dim3(nchunk * nrg_g * st->groups), dim3(256), 0, s, x, w, y, scale,
                                shift, nrows, Hi, Wi, Ho, Wo, C, act, nchunk, rpb, reinterpret_cast<f32x4*>(st->rec));
             hipLaunchKernelGGL(dw_rowu_wgrad_reduce, dim3((Q + 15) / 16 * DW_ST_SPLITS, 2, st->groups), dim3(256), 0, s,
                                reinterpret_cast<const f32x4*>(st->rec), st->out, 2, Q, WB, nchunk, nrg_g, DW_ST_SPLITS);
@@ -1016,8 +1006,7 @@ static bool dw_rowu_s2_launch(const T* x, const float* w, T* y, const float* sca
         }
     }
     const dim3 grid(nchunk * ((nrows + rpb - 1) / rpb));
-    if (pf) hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, true>), grid, dim3(256), 0, s, x, w, y, scale, shift, nrows, Hi, Wi, Ho, Wo, C, act, nchunk, rpb);
-    else hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T, false>), grid, dim3(256), 0, s, x, w, y, scale, shift, nrows, Hi, Wi, Ho, Wo, C, act, nchunk, rpb);
+    hipLaunchKernelGGL((dw_rowu_s2_kernel<K, T>), grid, dim3(256), 0, s, x, w, y, scale, shift, nrows, Hi, Wi, Ho, Wo, C, act, nchunk, rpb);
     return false;
 }
 template <int K, typename T>
@@ -1026,8 +1015,7 @@ static bool dw_rowu_dgrad_s2_launch(const T* dy, const float* w, T* dx, int imgs
 {
     const int WB = (Wi + 3) / 4, Q = C / 4;
     const int nchunk = (WB * Q + 63) / 64, nrows = imgs * Hi;
-    static const int rpb_env = fm_tune("FM_DW_RPB", 16);
-    int rpb = std::max(4, rpb_env);
+    int rpb = DW_RPB;
     if (st && st->ye && nrows % st->groups == 0) {
         const int nrg_g = dw_stats_rowgroups(nrows / st->groups, nchunk, st->groups);
         if (nrg_g) {
@@ -1051,7 +1039,6 @@ static bool dw_fwd_t(const T* x, const float* w, T* y, const float* scale, const
                      int Ho, int Wo, int C, int K, int stride, int pad_t, int pad_l, int act, hipStream_t s,
                      const float* psc = nullptr, const float* psh = nullptr, int ipg = 1, const DwStats* st = nullptr)
 {
-    if (!fm_tune("FM_DW_STATS", 1)) st = nullptr;
     const dim3 blk(256);
     if (!psc && stride == 1 && dw_blk_ok(K, stride, Hi, Wi, pad_t, pad_l)) {
         if (K == 3) return dw_rowu_launch<3, T>(x, w, y, scale, shift, imgs, Hi, Wi, C, act, 0, s, st);
@@ -1120,7 +1107,6 @@ template <typename T>
 static bool dw_dgrad_t(const T* dy, const float* w, T* dx, int imgs, int Hi, int Wi, int Ho, int Wo, int C, int K,
                        int stride, int pad_t, int pad_l, hipStream_t s, const DwStats* st = nullptr)
 {
-    if (!fm_tune("FM_DW_STATS", 1)) st = nullptr;
     const dim3 blk(256);
     if (stride == 1 && dw_blk_ok(K, stride, Hi, Wi, pad_t, pad_l)) {
         // stride 1: dx = dy (*) rot180(w), the forward kernel with the rotated kernel (Hi == Ho, Wi == Wo)
@@ -1475,8 +1461,8 @@ static void dw_rowu_wgrad_launch(const T* dy, const T* x, float* part, float* ou
     constexpr int RB = S == 1 ? 2 : 1;
     const int WB = (Wo + 3) / 4, HB = (Ho + RB - 1) / RB, Q = C / 4;
     const int nchunk = (WB * Q + 63) / 64, nsteps = imgs * HB;
-    static const int tgt = fm_tune("FM_DW_WG_BLOCKS", 2048);
-    int spb = std::max(8, (int)(((int64_t)nsteps * nchunk + tgt - 1) / tgt));
+    constexpr int TGT = 2048;         // blocks
+    int spb = std::max(8, (int)(((int64_t)nsteps * nchunk + TGT - 1) / TGT));
     spb = (spb + 3) / 4 * 4;
     const int nrg = (nsteps + spb - 1) / spb;
     hipLaunchKernelGGL((dw_rowu_wgrad_kernel<K, S, T>), dim3(nchunk * nrg), dim3(256), 0, s, dy, x, reinterpret_cast<f32x4*>(part),
@@ -1505,14 +1491,15 @@ static void dw_wgrad_full(const T* dy, const T* x, float* part, float* out, int 
     // Measured per layer (ms, 1024 bf16 / 512 fp32 images): bf16 every layer 1.9-4x faster than the lane = (pixel lane,
     // quad) kernels below (block 3: 1.41 -> 0.41, block 9: 0.89 -> 0.22; sum 10.5 -> 4.1); fp32 gains on the 5x5 layers
     // (0.33 -> 0.17) and loses on the wide 3x3 ones (112x112x32: 0.35 -> 0.63, one row of lookahead is too little in
-    // flight for 16-B loads), so fp32 3x3 keeps the older kernels.  FM_DW_WG_ROWU: 0 never / 1 this rule / 2 always.
-    static const int mode = fm_tune("FM_DW_WG_ROWU", 1);
-    const bool pick = mode == 2 || (mode == 1 && (sizeof(T) == 2 || K == 5));
+    // flight for 16-B loads), so fp32 3x3 keeps the older kernels.
+    const bool pick = sizeof(T) == 2 || K == 5;
     if (pick && dw_blk_ok(K, stride, Hi, Wi, pad_t, pad_l) && Wi == stride * Wo && Hi == stride * Ho) {
-        if (K == 3 && stride == 1) dw_rowu_wgrad_launch<3, 1, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
-        else if (K == 3) dw_rowu_wgrad_launch<3, 2, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
-        else if (stride == 1) dw_rowu_wgrad_launch<5, 1, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
-        else dw_rowu_wgrad_launch<5, 2, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
+        if (K == 5 && stride == 1) dw_rowu_wgrad_launch<5, 1, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
+        else if (K == 5) dw_rowu_wgrad_launch<5, 2, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
+        else if constexpr (sizeof(T) == 2) {
+            if (stride == 1) dw_rowu_wgrad_launch<3, 1, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
+            else dw_rowu_wgrad_launch<3, 2, T>(dy, x, part, out, imgs, Hi, Wi, Ho, Wo, C, s);
+        }
         return;
     }
     dw_wgrad_t(dy, x, part, imgs, Hi, Wi, Ho, Wo, C, K, stride, pad_t, pad_l, s);

@@ -597,8 +597,7 @@ void k_stem_pool_bwd(const float* dpooled, const float* pooled, const uint8_t* i
 int bn_bwd_blocks(int pix_per_group)
 {
     // blocks per group of the channel reductions (<= 1024: ws_part is sized for that)
-    static const int cap = std::min(1024, std::max(1, fm_tune("FM_BN_BLOCKS", 1024)));
-    return max(1, min(cap, cdiv(pix_per_group, 64)));
+    return max(1, min(1024, cdiv(pix_per_group, 64)));
 }
 
 // ---- stem: max-pool backward + BatchNorm backward without the dense intermediate ------------------------------------
@@ -625,14 +624,11 @@ __global__ void stem_pool_bn_reduce_kernel(const float* __restrict__ dp, const f
     // fma(y0, gamma istd, beta - mean gamma istd) of its argmax, so xhat = (pooled - beta) / gamma -- instead of a 4-byte gather of
     // y0 out of the dense map per element (the gathers touched every line of the 112 x 112 map: the pass read 0.4 GB more than
     // its inputs).  A channel whose |gamma| is small keeps the gather (the division would magnify pooled's rounding).
-    f32x4 ga = {0.f, 0.f, 0.f, 0.f}, be = ga;
-    bool fast[4] = {false, false, false, false};
-    if (gamma) {
-        ga = *reinterpret_cast<const f32x4*>(gamma + cq * 4);
-        be = *reinterpret_cast<const f32x4*>(beta + cq * 4);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + cq * 4);
+    const f32x4 be = *reinterpret_cast<const f32x4*>(beta + cq * 4);
+    bool fast[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) fast[k] = fabsf(ga[k]) >= 0.0625f;
-    }
+    for (int k = 0; k < 4; ++k) fast[k] = fabsf(ga[k]) >= 0.0625f;
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
     for (int t0 = blockIdx.x * TP; t0 < npool; t0 += nblk * TP)
         for (int pp = t0 + pl; pp < min(npool, t0 + TP); pp += P) {
@@ -671,10 +667,10 @@ __global__ void stem_pool_bn_reduce_kernel(const float* __restrict__ dp, const f
         *reinterpret_cast<f32x4*>(o + C) = s2;
     }
 }
-// round 6, even H and W: one thread = the 2 x 2 dense positions (2 oh + a, 2 ow + b) of one pooled index and channel quad.  They
+// round 6: one thread = the 2 x 2 dense positions (2 oh + a, 2 ow + b) of one pooled index and channel quad.  They
 // are covered by the four windows (oh + i, ow + j) only -- window (i, j) reaches position (a, b) when i <= a and j <= b, with the
 // window-local code (a - 2 i + 1) * 3 + (b - 2 j + 1) -- so a thread reads four windows' (argmax code, pooled value, gradient) for
-// four outputs where the per-position kernel below read 2.25 windows per output, and does its index arithmetic once for four.
+// four outputs where a per-position kernel read 2.25 windows per output, and does its index arithmetic once for four.
 __global__ __launch_bounds__(256) void stem_pool_bn_apply2_kernel(const float* __restrict__ dp, const float* __restrict__ pooled,
                                                                   const uint8_t* __restrict__ idx, const float* __restrict__ y,
                                                                   const float* __restrict__ ca, const float* __restrict__ cb,
@@ -730,49 +726,6 @@ __global__ __launch_bounds__(256) void stem_pool_bn_apply2_kernel(const float* _
             *reinterpret_cast<f32x4*>(dy + od) = a4 * acc + b4 * yy + c4v;
         }
 }
-__global__ void stem_pool_bn_apply_kernel(const float* __restrict__ dp, const float* __restrict__ pooled,
-                                          const uint8_t* __restrict__ idx, const float* __restrict__ y,
-                                          const float* __restrict__ ca, const float* __restrict__ cb,
-                                          const float* __restrict__ cc, float* __restrict__ dy, int imgs_per_group, int H,
-                                          int W, int C)
-{
-    const int g = blockIdx.y;
-    const int Hp = H / 2, Wp = W / 2, Q = C >> 2;
-    const int64_t n = (int64_t)imgs_per_group * H * W * Q;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int cq = (int)(i % Q);
-    int64_t t = i / Q;
-    const int iw = (int)(t % W); t /= W;
-    const int ih = (int)(t % H);
-    const int img = g * imgs_per_group + (int)(t / H);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int oh_lo = ih >> 1, oh_hi = (ih + 1) >> 1;      // equal when ih is even
-    const int ow_lo = iw >> 1, ow_hi = (iw + 1) >> 1;
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-        if (oh >= Hp) continue;
-        const int kh = ih - (2 * oh - 1);
-        for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-            if (ow >= Wp) continue;
-            const int kw = iw - (2 * ow - 1);
-            const size_t o = ((size_t)(img * Hp + oh) * Wp + ow) * C + cq * 4;
-            const uchar4 c4 = *reinterpret_cast<const uchar4*>(idx + o);
-            const f32x4 pv = *reinterpret_cast<const f32x4*>(pooled + o);
-            const f32x4 gg = *reinterpret_cast<const f32x4*>(dp + o);
-            const int code = kh * 3 + kw;
-            if (c4.x == code && pv[0] > 0.f) acc[0] += gg[0];
-            if (c4.y == code && pv[1] > 0.f) acc[1] += gg[1];
-            if (c4.z == code && pv[2] > 0.f) acc[2] += gg[2];
-            if (c4.w == code && pv[3] > 0.f) acc[3] += gg[3];
-        }
-    }
-    const size_t od = ((size_t)(img * H + ih) * W + iw) * C + cq * 4;
-    const f32x4 yy = *reinterpret_cast<const f32x4*>(y + od);
-    const f32x4 a4 = *reinterpret_cast<const f32x4*>(ca + g * C + cq * 4);
-    const f32x4 b4 = *reinterpret_cast<const f32x4*>(cb + g * C + cq * 4);
-    const f32x4 c4v = *reinterpret_cast<const f32x4*>(cc + g * C + cq * 4);
-    *reinterpret_cast<f32x4*>(dy + od) = a4 * acc + b4 * yy + c4v;
-}
 int stem_pool_bn_blocks(int pooled_per_group) { return bn_bwd_blocks(pooled_per_group); }
 void k_stem_pool_bn_reduce(const float* dpooled, const float* pooled, const uint8_t* idx, const float* y, const float* mean,
                            const float* istd, float* part, int groups, int imgs_per_group, int H, int W, int C, hipStream_t s,
@@ -786,15 +739,9 @@ void k_stem_pool_bn_apply(const float* dpooled, const float* pooled, const uint8
                           const float* cb, const float* cc, float* dy, int groups, int imgs_per_group, int H, int W, int C,
                           hipStream_t s)
 {
-    static const int blocks2 = fm_tune("FM_STEM_APPLY_2X2", 1);
-    if (blocks2 && H % 2 == 0 && W % 2 == 0) {
-        const int64_t n2 = (int64_t)imgs_per_group * (H / 2) * (W / 2) * (C / 4);
-        hipLaunchKernelGGL(stem_pool_bn_apply2_kernel, dim3(cdiv(n2, 256), groups), dim3(256), 0, s, dpooled, pooled, idx, y, ca, cb,
-                           cc, dy, imgs_per_group, H, W, C);
-        return;
-    }
-    const int64_t n = (int64_t)imgs_per_group * H * W * (C / 4);
-    hipLaunchKernelGGL(stem_pool_bn_apply_kernel, dim3(cdiv(n, 256), groups), dim3(256), 0, s, dpooled, pooled, idx, y, ca, cb,
+    // (H and W are even: fm_create takes inputs in multiples of 32, the stem halves them)
+    const int64_t n2 = (int64_t)imgs_per_group * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(stem_pool_bn_apply2_kernel, dim3(cdiv(n2, 256), groups), dim3(256), 0, s, dpooled, pooled, idx, y, ca, cb,
                        cc, dy, imgs_per_group, H, W, C);
 }
 

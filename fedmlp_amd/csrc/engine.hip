@@ -312,9 +312,8 @@ int aalloc(fm_engine* e, float** p, size_t n) { return dalloc(e, p, e->precision
 hipError_t create_side_stream(hipStream_t* st)
 {
     int least = 0, greatest = 0;
-    const int pr = fm_tune("FM_SIDE_PRIO", 1);         // tuning builds: 1 lowest (shipped), 0 default, -1 highest
-    if (!pr || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, pr > 0 ? least : greatest);
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, least);
 }
 
 int upload_tab(fm_engine* e, const std::vector<int4>& h, int4** d)
@@ -1283,8 +1282,8 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
     // tiles * splits <= 512 = ONE round of the 512 block slots: with the weight gradients on the side stream next to the
     // BN-backward / data-gradient chain, a second round of their blocks holds slots the main stream's next GEMM is waiting for
     // (two-stream step 36.8 -> 36.3 ms; one stream: 38.5 either way; 384: 37.3, 640: 37.4, 1024 = round 2's choice)
-    static const int wg_slots = fm_tune("FM_WGRAD_SLOTS", 512);
-    int splits = std::max(1, wg_slots / tiles);
+    constexpr int WG_SLOTS = 512;
+    int splits = std::max(1, WG_SLOTS / tiles);
     const int max_by_pix = std::max(1, p.npix / 256);
     const int max_by_mem = (int)std::max<size_t>(1, e->slab_floats / c.w_numel);
     splits = std::max(1, std::min(splits, std::min(max_by_pix, max_by_mem)));
@@ -1549,42 +1548,32 @@ void backward_and_step(fm_engine* e, int groups, int B)
         if (pm && !last) bn_bwd(e, blk.c2, ga, nullptr, nullptr, ga, groups, B, false, gbp, blk.outp);
         else bn_bwd(e, blk.c2, ga, blk.out, pm ? nullptr : GB, ga, groups, B, false, gbp);
         if (blk.ds >= 0) { guard(1, par); bn_bwd(e, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, false, gcp); }
-        // Where a weight gradient enters the side stream.  lag = 0: as soon as its dy exists, i.e. beside the data gradient of the
-        // SAME conv -- two GEMMs share the CUs, and the BatchNorm-backward passes that follow run with nothing beside them.
-        // lag = 1 (round 6): behind that data gradient, i.e. beside the NEXT BatchNorm-backward passes of the main stream: a
-        // streaming kernel lives beside a GEMM's waves on a CU (the GEMMs leave it the registers since their K-steps run row-major),
-        // two GEMMs do not (LDS).  Same kernels, same bits; the buffer guards are the same events.
-        static const int lag = fm_tune("FM_WGRAD_LAG", 1);
-        const unsigned short* inp = pm ? (b == 0 ? e->p0p : e->blocks[b - 1].outp) : nullptr;
-        auto wgrad_c2 = [&]() {
-            side_begin(0, par);
-            conv_wgrad(e, blk.c2, blk.z1, GB, imgs, nullptr, 0, pm ? blk.z1p : nullptr, gbp);
-            side_end(0, par);
-        };
-        auto wgrad_c1 = [&]() {
-            side_begin(2, par);
-            conv_wgrad(e, blk.c1, in, GD, imgs, nullptr, 0, inp, gdp);
-            side_end(2, par);
-        };
-        auto wgrad_ds = [&]() {
-            side_begin(1, par);
-            conv_wgrad(e, blk.ds, in, GC, imgs, nullptr, 0, inp, gcp);
-            side_end(1, par);
-        };
-        if (!lag) wgrad_c2();
+        // Where a weight gradient enters the side stream (round 6): behind the data gradient of the same conv, i.e. beside the
+        // NEXT BatchNorm-backward passes of the main stream: a streaming kernel lives beside a GEMM's waves on a CU (the GEMMs leave
+        // it the registers since their K-steps run row-major), two GEMMs do not (LDS).  Entering as soon as its dy exists put two
+        // GEMMs beside each other and left the BatchNorm-backward passes that follow with nothing beside them.
         guard(2, par);
         conv_dgrad(e, blk.c2, S, GB, GD, imgs, nullptr, false, gbp);
-        if (lag) wgrad_c2();
+        side_begin(0, par);
+        conv_wgrad(e, blk.c2, blk.z1, GB, imgs, nullptr, 0, pm ? blk.z1p : nullptr, gbp);
+        side_end(0, par);
         if (pm) bn_bwd(e, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, true, gdp, blk.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
         else bn_bwd(e, blk.c1, GD, blk.z1, GD, nullptr, groups, B, true);
-        if (!lag) { wgrad_c1(); if (blk.ds >= 0) wgrad_ds(); }
         if (blk.ds >= 0) {
             conv_dgrad(e, blk.ds, S, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
             conv_dgrad(e, blk.c1, S, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
         } else {
             conv_dgrad(e, blk.c1, S, GD, ge, imgs, ga, false, gdp);
         }
-        if (lag) { wgrad_c1(); if (blk.ds >= 0) wgrad_ds(); }
+        const unsigned short* inp = pm ? (b == 0 ? e->p0p : e->blocks[b - 1].outp) : nullptr;
+        side_begin(2, par);
+        conv_wgrad(e, blk.c1, in, GD, imgs, nullptr, 0, inp, gdp);
+        side_end(2, par);
+        if (blk.ds >= 0) {
+            side_begin(1, par);
+            conv_wgrad(e, blk.ds, in, GC, imgs, nullptr, 0, inp, gcp);
+            side_end(1, par);
+        }
         std::swap(ga, ge);
     }
     const Conv& c0 = e->convs[0];
@@ -1592,10 +1581,8 @@ void backward_and_step(fm_engine* e, int groups, int B)
         // max-pool backward + BatchNorm backward of the stem in two passes, without the dense intermediate (elementwise.hip)
         Bn& b0 = e->bns[0];
         const int pooled_pg = B * (c0.hout / 2) * (c0.wout / 2), pix = B * c0.hout * c0.wout;
-        static const int from_pooled = fm_tune("FM_STEM_XHAT_FROM_POOLED", 1);
         k_stem_pool_bn_reduce(ga, e->p0, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, e->st,
-                              from_pooled ? e->state + e->off_gamma + b0.ch_off : nullptr,
-                              from_pooled ? e->state + e->off_beta + b0.ch_off : nullptr);
+                              e->state + e->off_gamma + b0.ch_off, e->state + e->off_beta + b0.ch_off);
         k_bn_bwd_finalize(e->ws_part, groups, stem_pool_bn_blocks(pooled_pg), 64, pix, e->state + e->off_gamma + b0.ch_off,
                           b0.mean, b0.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b0.ch_off,
                           e->grad + e->off_beta + b0.ch_off, e->st);
@@ -1618,8 +1605,7 @@ void backward_and_step(fm_engine* e, int groups, int B)
 bool fuse_for(fm_engine* e, const MBConv& m)
 {
     if (e->precision) return e->fuse_gate && pw_tiles_m(m.cout_p, m.ce_p) <= 2;
-    static const int on = fm_tune("FM_F32_TRAIN_GATE", 1);
-    return on && pw_proj_bwd_f32_nch(m.ce_p, m.cout_p, 1, m.hout * m.wout) > 0 && conv1x1_stream_takes(m.ce_p, m.cout_p, m.cout_p);
+    return pw_proj_bwd_f32_nch(m.ce_p, m.cout_p, 1, m.hout * m.wout) > 0 && conv1x1_stream_takes(m.ce_p, m.cout_p, m.cout_p);
 }
 
 // BN over an arbitrary NHWC tensor (depthwise output): statistics by chan_reduce, then the same finalize

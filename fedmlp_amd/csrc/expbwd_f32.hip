@@ -165,8 +165,6 @@ int launch_pw_exp_bwd_f32(const PwExpBwdF32Params& w, size_t slab_floats, hipStr
     const int nrt = w.L / 16, cc = w.S / 16;
     const bool shape = (nrt == 6 || nrt == 9) && (cc == 1 || cc == 2);
     if (!shape || (w.L & 15) || (w.S & 15) || w.pix_per_group % 16 != 0 || w.npix % 16 != 0 || w.groups < 1 || w.groups > 2) return 0;
-    static const int on = fm_tune("FM_PW_EXP_BWD_F32", 1);
-    if (!on) return 0;
     ExpBwdF32Args a{};
     a.dA = w.dA; a.Ye = w.Ye; a.X = w.X; a.W = w.W; a.res = w.res; a.dX = w.dX; a.slab = w.slab;
     a.ca = w.ca; a.cb = w.cb; a.cc = w.cc; a.sc = w.sc; a.sh = w.sh;

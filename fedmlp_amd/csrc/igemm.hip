@@ -553,8 +553,7 @@ void launch_igemm(IgemmParams p, int groups, hipStream_t s)
     }
     // K per LDS stage: 32 (two stages) stages a whole 128-B line per DMA row -- the L1 hands out whole
     // lines, so the 64-B rows of the 16-k stages use half of what it moves.  Needs Ci % 32 == 0.
-    static const int ks32_mode = fm_tune("FM_KS32", 2);
-    const bool ks32 = !p.stem_kw && p.Ci % 32 == 0 && (ks32_mode == 2 || (ks32_mode == 1 && p.M < 128));
+    const bool ks32 = !p.stem_kw && p.Ci % 32 == 0;
     if (ks32) p.nsteps /= 2;           // the caller counts 16-k steps
     const int split = p.sp;
     // the packed 7x7 stem in the split form: 11 steps of 16 k become 6 of 32, the rows of W keep their 176 floats
@@ -566,9 +565,8 @@ void launch_igemm(IgemmParams p, int groups, hipStream_t s)
     p.tapcode = 0;
     for (int t = 0; t < p.ntaps; ++t)      // taps of 3x3 / 1x1 convs and of their dgrad parity classes lie in [-1, 1]
         p.tapcode |= (unsigned long long)(((p.dh[t] + 1) & 3) | (((p.dw[t] + 1) & 3) << 2)) << (4 * t);
-    static const int tn_fast = fm_tune("FM_TN_FAST", 2);
     // weights of one M-tile: BM rows x K floats; beyond ~1 MB per M-tile the all-M-tiles working set no longer fits L2
-    p.tn_fast = tn_fast == 1 ? 1 : (tn_fast == 2 ? (p.tilesM > 1 && (long long)p.M * p.nsteps * 64 > (2LL << 20)) : 0);
+    p.tn_fast = p.tilesM > 1 && (long long)p.M * p.nsteps * 64 > (2LL << 20);
     // persistent grid: every block slot whenever there are >= 4 K-steps for each of them, otherwise
     // one tile per block.  FM_IGEMM_BLOCKS overrides the grid (tests force odd splits so that every
     // fix-up path runs on small shapes).
@@ -587,10 +585,9 @@ void launch_igemm(IgemmParams p, int groups, hipStream_t s)
     else if (p.stem_kw)
         hipLaunchKernelGGL((igemm_kernel<64, 256, 4, 1>), grid, dim3(256), LDS_S, s, p);
     else if (p.M >= 128) {
-        static const int planes = fm_tune("FM_WPLANES", 1);
-        if (ks32 && split == 9 && p.Wsp && planes)
+        if (ks32 && split == 9 && p.Wsp)
             hipLaunchKernelGGL((igemm_kernel<128, 128, 2, 0, 2, 32, 9, 1>), grid, dim3(256), LDS_P, s, p);
-        else if (ks32 && split == 6 && p.Wsp && planes)
+        else if (ks32 && split == 6 && p.Wsp)
             hipLaunchKernelGGL((igemm_kernel<128, 128, 2, 0, 2, 32, 6, 1>), grid, dim3(256), LDS_P, s, p);
         else if (ks32 && split == 9) hipLaunchKernelGGL((igemm_kernel<128, 128, 2, 0, 2, 32, 9>), grid, dim3(256), LDS_L, s, p);
         else if (ks32 && split == 6) hipLaunchKernelGGL((igemm_kernel<128, 128, 2, 0, 2, 32, 6>), grid, dim3(256), LDS_L, s, p);
@@ -598,10 +595,9 @@ void launch_igemm(IgemmParams p, int groups, hipStream_t s)
         else hipLaunchKernelGGL((igemm_kernel<128, 128, 2, 0>), grid, dim3(256), LDS_L, s, p);
     }
     else {
-        static const int planes = fm_tune("FM_WPLANES", 1);
-        if (ks32 && split == 9 && p.Wsp && planes)
+        if (ks32 && split == 9 && p.Wsp)
             hipLaunchKernelGGL((igemm_kernel<64, 192, 4, 0, 2, 32, 9, 1>), grid, dim3(256), LDS_PT, s, p);
-        else if (ks32 && split == 6 && p.Wsp && planes)
+        else if (ks32 && split == 6 && p.Wsp)
             hipLaunchKernelGGL((igemm_kernel<64, 192, 4, 0, 2, 32, 6, 1>), grid, dim3(256), LDS_PT, s, p);
         else if (ks32 && split == 9) hipLaunchKernelGGL((igemm_kernel<64, 192, 4, 0, 2, 32, 9>), grid, dim3(256), LDS_T, s, p);
         else if (ks32 && split == 6) hipLaunchKernelGGL((igemm_kernel<64, 192, 4, 0, 2, 32, 6>), grid, dim3(256), LDS_T, s, p);

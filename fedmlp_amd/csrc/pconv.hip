@@ -297,8 +297,6 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
     };
 
     if (w >= wend) return;                       // (a block whose range is empty: the grid was rounded up)
-    if ((p.pc_flags & 2) && wave >= 4) __builtin_amdgcn_s_setprio(1);
-    if ((p.pc_flags & 4) && wave < 4) __builtin_amdgcn_s_setprio(1);
     Seg cur;
     decode(cur);
     lead(cur);
@@ -358,7 +356,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
             if (tid == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // keep: the fence's own wait may be dropped
-                if (!(p.pc_flags & 8)) __hip_atomic_fetch_add(p.counters + pend_tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (!p.lose_part) __hip_atomic_fetch_add(p.counters + pend_tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             pend_tile = -1;
         }
@@ -418,8 +416,9 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
         PC_T(2);
         int ib = 0;                            // stage slot of the current step
         // the two waves of a SIMD (w, w + 4) run this loop in lockstep between barriers: when both issue a step's DMA at the same
-        // point the matrix pipe idles behind them.  `late`: waves 4-7 issue theirs BEHIND the last column's MFMAs
-        const bool late = (p.pc_flags & 1) && wave >= 4;
+        // point the matrix pipe idles behind them.  `late`: waves 4-7 issue theirs BEHIND the last column's MFMAs (measured: -0.6 %
+        // of a step; s_setprio 1 for either half of the waves instead: +0.3 %)
+        const bool late = wave >= 4;
         {
             // ---- one K-step, row-major.  At its start: row 0 of A(s) in A0[0], B(s) columns 0 .. 3 in Bb (columns 1 .. 3 possibly
             // still in flight: counted waits in pass 0).  Pass r = row r's 24 MFMAs with row r + 1 read behind them.  The barrier
@@ -571,7 +570,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
                     // bounded (a few seconds: the parts were stored a whole range ago; only a block that was never scheduled can be
                     // missing): a lost part must not hang the GPU -- it POISONS the tile instead (NaN: the step's loss says so)
                     int got = 0;
-                    const int spins = (p.pc_flags & 8) ? (1 << 8) : (1 << 22);        // (bit 3: the test hook's short wait)
+                    const int spins = p.lose_part ? (1 << 8) : (1 << 22);        // (the test hook's short wait)
                     for (int it = 0; it < spins && !got; ++it) {
                         got = __hip_atomic_load(p.counters + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == need;
                         if (!got) __builtin_amdgcn_s_sleep(4);
@@ -742,7 +741,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
         if (tid == 0) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(p.pc_flags & 8)) __hip_atomic_fetch_add(p.counters + pend_tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!p.lose_part) __hip_atomic_fetch_add(p.counters + pend_tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 #undef PC_SYNC_LDS
@@ -834,11 +833,10 @@ bool pconv_takes(int M, int Ci, long long xp_pix, int Wi)
 }
 
 // tap-row sharing applies to: 3x3, stride 1, the taps in three groups of one kernel row each whose column shifts cover -1, 0, +1
-// (forward convs and their data gradients alike); FM_PCONV_TS=0 (tuning builds) keeps the per-tap stages
+// (forward convs and their data gradients alike)
 bool pconv_uses_ts(const IgemmParams& p)
 {
-    static const int ts_on = fm_tune("FM_PCONV_TS", 1);
-    bool ts = ts_on && p.ntaps == 9 && p.sg == 1 && p.Hg == p.Hi && p.Wg == p.Wi;
+    bool ts = p.ntaps == 9 && p.sg == 1 && p.Hg == p.Hi && p.Wg == p.Wi;
     for (int j = 0; ts && j < 3; ++j) {
         ts = p.dh[3 * j] == p.dh[3 * j + 1] && p.dh[3 * j] == p.dh[3 * j + 2];
         int seen = 0;
@@ -877,8 +875,7 @@ void launch_pconv(IgemmParams p, int groups, hipStream_t s)
     for (int t = 0; t < p.ntaps; ++t)      // taps of 3x3 / 1x1 convs and of their dgrad parity classes lie in [-1, 1]
         p.tapcode |= (unsigned long long)(((p.dh[t] + 1) & 3) | (((p.dw[t] + 1) & 3) << 2)) << (4 * t);
     // weights of one M-tile: BM rows x K x 6 B; beyond ~1 MB per M-tile the all-M-tiles working set no longer fits L2
-    static const int tn_fast = fm_tune("FM_TN_FAST", 2);
-    p.tn_fast = tn_fast == 1 ? 1 : (tn_fast == 2 ? (p.tilesM > 1 && (long long)p.M * p.nsteps * 192 > (3LL << 20)) : 0);
+    p.tn_fast = p.tilesM > 1 && (long long)p.M * p.nsteps * 192 > (3LL << 20);
     // persistent grid: every CU whenever there are >= 4 K-steps for each of them, otherwise one tile per block.
     // FM_IGEMM_BLOCKS overrides the grid (tests force odd splits so that every fix-up path runs on small shapes).
     static const int forced = getenv("FM_IGEMM_BLOCKS") ? atoi(getenv("FM_IGEMM_BLOCKS")) : 0;
@@ -893,8 +890,7 @@ void launch_pconv(IgemmParams p, int groups, hipStream_t s)
     // by <= 2 %; only for slices that do not fit beside the rest (the 256-channel layers' 1.8 MB: 278 -> 326 MB, not taken).
     // Measured and not kept: the M-tiles of a pixel tile as sibling blocks on one XCD (every slice live on every XCD: 770 MB);
     // the non-temporal hint on the activation rows (their kernel-row re-reads miss: step +1.1 ms).
-    static const int quant_on = fm_tune("FM_PCONV_QUANT", 1);
-    if (quant_on && forced <= 0 && p.steps_per_block > p.nsteps / 2 && (long long)p.nsteps * 128 * 192 > (2LL << 20)) {
+    if (forced <= 0 && p.steps_per_block > p.nsteps / 2 && (long long)p.nsteps * 128 * 192 > (2LL << 20)) {
         for (int P = 1; P <= 12; ++P) {
             if (p.nsteps % P) continue;
             const int q = p.nsteps / P;
@@ -904,10 +900,9 @@ void launch_pconv(IgemmParams p, int groups, hipStream_t s)
     }
     dim3 grid(nblk);
     // tap-row sharing: 3x3, stride 1, the taps in three groups of one kernel row each whose column shifts cover -1, 0, +1
-    // (forward convs and their data gradients alike); FM_PCONV_TS=0 (tuning builds) keeps the per-tap stages
+    // (forward convs and their data gradients alike)
     const bool ts = pconv_uses_ts(p);
-    static const int pc_flags = fm_tune("FM_PCONV_FLAGS", 1);      // (measured: 1 = -0.6 % of a step, 2 / 4 = +0.3 %)
-    p.pc_flags = (pc_flags & 7) | (g_lose_part ? 8 : 0);
+    p.lose_part = g_lose_part ? 1 : 0;
     if (ts) {
         if (p.M >= 128) {
             if (p.sp == 9) hipLaunchKernelGGL((pconv_kernel<4, 4, 2, 9, true>), grid, dim3(512), LDS_LT, s, p);

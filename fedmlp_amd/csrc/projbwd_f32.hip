@@ -225,9 +225,8 @@ static int proj_bwd_f32_slice(int L) { return L == 32 ? 32 : (L % 48 == 0 ? 48 :
 // pooling records per image; 0 = shape not handled (the caller runs the separate passes)
 int pw_proj_bwd_f32_nch(int L, int S, int imgs, int HW)
 {
-    static const int on = fm_tune("FM_PW_PROJ_BWD_F32", 1);
     const int ls = proj_bwd_f32_slice(L);
-    if (!on || !ls || L / ls > 3 || (S != 16 && S != 32 && S != 48) || imgs < 1 || HW % 16 != 0) return 0;
+    if (!ls || L / ls > 3 || (S != 16 && S != 32 && S != 48) || imgs < 1 || HW % 16 != 0) return 0;
     const int tpi = (HW + 31) / 32;
     return std::max(1, std::min(std::min(16, tpi), (2048 + imgs - 1) / imgs));
 }

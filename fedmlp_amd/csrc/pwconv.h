@@ -23,7 +23,7 @@ struct PwParams {
     const float* psh;
     const float* gate;    // prologue: [imgs][K] or null (no prologue at all)
     int HW;               // pixels per image (gate row = global pixel / HW)
-    int tiles_m, xcd;     // set by the launcher: M-tiles of the launch; 1 = XCD-aware block order
+    int tiles_m;          // set by the launcher: M-tiles of the launch
     const void* zeros;    // >= 16 B of zeros on the device (DMA source of padded chunks in the LDS-tiled form)
 };
 // nblk the launcher will use (statistics layout); pro = the launch has an operand prologue (PwParams::gate != null),

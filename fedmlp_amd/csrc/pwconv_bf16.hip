@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * NW) void pw_conv_bf16_kernel(const PwParams p)
     int bx, by;
     {
         const int id = blockIdx.x, nby = p.nblk * p.groups, tm = p.tiles_m;
-        const int full = p.xcd ? (nby >> 3) << 3 : 0;
+        const int full = (nby >> 3) << 3;
         if (id < full * tm) {
             const int q = id / (8 * tm), r = id - q * 8 * tm;
             bx = r >> 3;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void pw_gemm_bf16_kernel(const PwParams p)
     int bx, by;                                             // M-tile, (group, pixel tile): the M-tiles of one pixel tile on ONE XCD
     {
         const int id = blockIdx.x, nby = p.nblk * p.groups, tm = p.tiles_m;
-        const int full = p.xcd ? (nby >> 3) << 3 : 0;
+        const int full = (nby >> 3) << 3;
         if (id < full * tm) {
             const int q = id / (8 * tm), r = id - q * 8 * tm;
             bx = r >> 3;
@@ -583,7 +583,7 @@ struct WgArgs {
     const float* psh;
     const float* gate;
     int HW, pix_per_group;
-    int tilesL, nsplit, xcd;   // launch geometry (1-D grid)
+    int tilesL, nsplit;   // launch geometry (1-D grid)
 };
 constexpr int WG_STRIDE_BIG = 160;          // 64 channels x 2 B = 128 B of data per pixel row, padded to 32 B x 5
 
@@ -604,12 +604,12 @@ __global__ __launch_bounds__(256) void pw_wgrad_bf16_kernel(const WgArgs p)
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     // 1-D grid -> (64-channel tile of Big, pixel split).  The tiles of a split all re-read the split's Small rows: block
-    // ids are arranged so that they are congruent mod 8 = on ONE XCD's L2 (p.xcd; same scheme as pw_conv_bf16_kernel)
+    // ids are arranged so that they are congruent mod 8 = on ONE XCD's L2 (same scheme as pw_conv_bf16_kernel)
     int tile, split;
     const int nsplit = p.nsplit;
     {
         const int T = p.tilesL, id = blockIdx.x;
-        const int full = p.xcd ? (nsplit >> 3) << 3 : 0;
+        const int full = (nsplit >> 3) << 3;
         if (id < full * T) {
             const int q = id >> 3, x = id & 7;
             split = (q / T) * 8 + x;
@@ -1250,15 +1250,14 @@ __global__ void cast_weights_kernel(const float* __restrict__ state, bf16* __res
 }  // namespace
 
 // ---- launchers ------------------------------------------------------------------------------------------
-// row tiles per block: 4 (64 channels).  K > 640: the slice is 86-147 KB -- one 8-wave block per CU (FM_PW_W8=0: two
+// row tiles per block: 4 (64 channels).  K > 640: the slice is 86-147 KB -- one 8-wave block per CU (it replaced two
 // 4-wave blocks of 32-channel tiles, the round-2 first form)
 bool pw_gemm_takes(int M, int K, bool pro, bool plain, int HW);
 int pw_gemm_blocks(int npix_per_group);
-static int pw_w8() { static const int v = fm_tune("FM_PW_W8", 1); return v; }
 static int pw_rt(int M, int K)
 {
     (void)M;
-    return (K <= 640 || (pw_w8() && K <= 1152)) ? 4 : 2;          // K = 1280 (head dgrad): 164 KB, stays 32-channel
+    return K <= 1152 ? 4 : 2;          // K = 1280 (head dgrad): 164 KB, stays 32-channel
 }
 static int pw_ppb(int npix_per_group, int groups, int M, int K)
 {
@@ -1306,8 +1305,6 @@ static void pw_launch_t(const PwParams& p, bool pro, dim3 grid, size_t lds, hipS
     else pw_launch_m<RT, P, KB, NW, 0>(p, pro, grid, lds, s);                  // data gradient (+ residual)
 }
 // ---- LDS-tiled GEMM form (pw_gemm_bf16_kernel) ----------------------------------------------------------------------------
-static int pw_gemm_on() { static const int v = fm_tune("FM_PW_GEMM", 1); return v; }
-static int pw_gemm_pro_on() { static const int v = fm_tune("FM_PW_GEMM_PRO", 1); return v; }
 static int pw_gemm_bm(int M) { return M <= 64 ? 64 : 128; }
 // Taken for (1) the plain-store form with K >= 64 (the data gradients: no statistics, no affine).  Measured inside the bf16 bs-512
 // step (one stream, tools/op_profile.py): expand / project / head data gradients 2.24 -> 1.80 ms per step; the train (statistics)
@@ -1316,17 +1313,17 @@ static int pw_gemm_bm(int M) { return M <= 64 ? 64 : 128; }
 // the streaming kernel folds its statistics once per ~1 000 pixels) and the K = 672 / 1152 project forwards did not move;
 // (2) the project convs WITH an operand prologue and K >= 240 (blocks 4-10, M <= 128 = one M-tile): the prologue runs once per
 // element instead of once per 64-channel tile, and a tile is 4-11 stages long.
+constexpr int PW_GEMM_PRO_MINK = 240;
+// (256 = blocks 11-14, M = 192, as two 128-channel tiles with the gate fused instead of a materialised a_s: measured slower,
+// project forward 2.52 -> 2.85 ms and its weight gradient 1.59 -> 1.84 ms per step against 0.16 ms of se_scale saved)
+constexpr int PW_GEMM_PRO_MAXM = 128;
 static bool pw_gemm_pro_shape(int M, int K)
 {
-    static const int mink = fm_tune("FM_PW_GEMM_PRO_MINK", 240);
-    // (256 = blocks 11-14, M = 192, as two 128-channel tiles with the gate fused instead of a materialised a_s: measured slower,
-    // project forward 2.52 -> 2.85 ms and its weight gradient 1.59 -> 1.84 ms per step against 0.16 ms of se_scale saved)
-    static const int maxm = fm_tune("FM_PW_GEMM_PRO_MAXM", 128);
-    return pw_gemm_pro_on() && K >= mink && M <= maxm;
+    return K >= PW_GEMM_PRO_MINK && M <= PW_GEMM_PRO_MAXM;
 }
 bool pw_gemm_takes(int M, int K, bool pro, bool plain, int HW)
 {
-    if ((M & 15) || (K & 15) || !pw_gemm_on()) return false;
+    if ((M & 15) || (K & 15)) return false;
     return pro ? (pw_gemm_pro_shape(M, K) && HW >= 32) : (plain && K >= 64);     // (a wave's 32 pixels span at most two images)
 }
 constexpr int PW_GEMM_BP = 128;
@@ -1349,8 +1346,6 @@ static bool launch_pw_gemm(PwParams p, hipStream_t s)
     p.ppb = PW_GEMM_BP;
     p.nblk = pw_gemm_blocks(p.npix);
     p.tiles_m = (p.M + BM - 1) / BM;
-    static const int xcd = fm_tune("FM_PW_XCD", 1);
-    p.xcd = xcd;
     const dim3 grid(p.tiles_m * p.nblk * p.groups);
     if (!p.gate) {                                              // data gradients
         if (BM == 64) pw_gemm_launch_m<64, 0, 0>(p, grid, s); else pw_gemm_launch_m<128, 0, 0>(p, grid, s);
@@ -1377,18 +1372,13 @@ void launch_pw_conv(PwParams p, hipStream_t s)
     const bool pro = p.gate != nullptr;
     size_t lds = (size_t)(p.K >> 5) * RT * 1024 + (size_t)RT * 512 + (pro ? (size_t)2 * p.K * 4 : 0);
     lds = std::max<size_t>(lds, (size_t)8 * MT * 2 * 4);
-    static const int xcd = fm_tune("FM_PW_XCD", 1);
     p.tiles_m = (p.M + MT - 1) / MT;
-    p.xcd = xcd;
     const dim3 grid(p.tiles_m * p.nblk * p.groups);
-    // FM_PW_SMALLK: 0 = P 2 everywhere; 2 (default) = 4 pixel groups x 2 k-chunks for K <= 64 (2 waves per SIMD kept:
-    // block 1's expand conv 1.07 -> 0.90 ms, the K <= 64 layers together -1.0 ms per step); 1 = 8 groups for K <= 32
-    // (372 registers = 1 wave per SIMD: slower than 2).  Outputs are bit-identical across the settings; the BN partial
-    // sums are taken in a different (still fixed) order.
-    static const int smallk = fm_tune("FM_PW_SMALLK", 2);
-    if (RT == 4 && smallk == 3 && p.K <= 64) pw_launch_t<4, 1, 2>(p, pro, grid, lds, s);
-    else if (RT == 4 && smallk == 4 && p.K <= 64) pw_launch_t<4, 2, 2>(p, pro, grid, lds, s);
-    else if (RT == 4 && smallk && p.K <= 64) pw_launch_t<4, 4, 2>(p, pro, grid, lds, s);
+    // K <= 64: 4 pixel groups x 2 k-chunks (2 waves per SIMD kept: against 2 pixel groups everywhere, block 1's expand conv
+    // 1.07 -> 0.90 ms, the K <= 64 layers together -1.0 ms per step; 8 groups for K <= 32 took 372 registers = 1 wave per
+    // SIMD and were slower).  Outputs are bit-identical across these forms; the BN partial sums are taken in a different
+    // (still fixed) order.
+    if (RT == 4 && p.K <= 64) pw_launch_t<4, 4, 2>(p, pro, grid, lds, s);
     else if (RT == 4 && p.K > 640) pw_launch_t<4, 2, 4, 8>(p, pro, grid, lds, s);
     else if (RT == 4) pw_launch_t<4, 2, 4>(p, pro, grid, lds, s);
     else pw_launch_t<2, 2, 4>(p, pro, grid, lds, s);
@@ -1419,13 +1409,12 @@ int launch_pw_wgrad(const PwWgradParams& w, size_t slab_floats, hipStream_t s)
     a.psc = w.psc; a.psh = w.psh; a.gate = w.gate; a.HW = w.HW; a.pix_per_group = w.pix_per_group;
     const int cc = a.S / 16;
     {   // small high-resolution layers: the barrier-free one-wave-per-tile kernel
-        static const int wave_on = fm_tune("FM_PW_WG_WAVE", 1);
         const int nrt = a.L / 16;
         const bool shape = (nrt == 2 && cc == 1) || (nrt == 6 && (cc == 1 || cc == 2)) || (nrt == 9 && cc == 2);
         // measured (ms, 1024 images): without prologue 96x16 0.77 -> 0.55, 144x32 0.35 -> 0.31; with the gate prologue 32x16
         // 0.89 -> 0.65 but 96x32 0.48 -> 0.69 and 144x32 0.68 -> 1.26 (all of a tile's BN / gate operands per lane: 204-276
         // registers), so the prologue variants keep the block kernel except for the smallest shape
-        if (wave_on && shape && (w.gate == nullptr || nrt == 2)) {
+        if (shape && (w.gate == nullptr || nrt == 2)) {
             a.strideS = odd32(2 * a.S);
             const int strideB = odd32(2 * a.L);
             const int tsteps = (w.npix + 31) / 32;
@@ -1464,18 +1453,15 @@ int launch_pw_wgrad(const PwWgradParams& w, size_t slab_floats, hipStream_t s)
     // Splits of the pixel axis.  Every split leaves an fp32 [M][K] partial that reduce_slabs reads back.  The late,
     // channel-heavy layers (1 152 x 192: 885 KB per split) run 512 blocks of >= 32 steps -- at 2 048 blocks they moved
     // more slab bytes than activations (bf16 bs-512 step 59.1 -> 58.3 ms) -- while layers whose partial is small
-    // (<= FM_PW_WG_SMALL_KB, default 64: the early high-resolution ones, 24 x 96 = 12 KB) keep 2 048 blocks of >= 8 steps:
+    // (<= 64 KB: the early high-resolution ones, 24 x 96 = 12 KB) keep 2 048 blocks of >= 8 steps:
     // their gate / BN prologue is issue-bound and needs every SIMD busy (at 512 blocks the two largest ran 0.78 -> 1.9 ms).
-    static const int wg_blocks = fm_tune("FM_PW_WG_BLOCKS", 512);
-    static const int wg_minsteps = fm_tune("FM_PW_WG_MINSTEPS", 32);
-    static const int wg_small_kb = fm_tune("FM_PW_WG_SMALL_KB", 64);
-    const bool small_partial = (size_t)w.M * w.K * 4 <= ((size_t)wg_small_kb << 10);
-    int splits = std::max(1, (small_partial ? 2048 : wg_blocks) / tilesL);
-    splits = std::min(splits, std::max(1, tsteps / (small_partial ? 8 : wg_minsteps)));
+    constexpr int WG_BLOCKS = 512, WG_MINSTEPS = 32, WG_SMALL_KB = 64;
+    const bool small_partial = (size_t)w.M * w.K * 4 <= ((size_t)WG_SMALL_KB << 10);
+    int splits = std::max(1, (small_partial ? 2048 : WG_BLOCKS) / tilesL);
+    splits = std::min(splits, std::max(1, tsteps / (small_partial ? 8 : WG_MINSTEPS)));
     splits = (int)std::min<size_t>(splits, std::max<size_t>(1, slab_floats / ((size_t)w.M * w.K)));
     const size_t lds = (size_t)2 * (32 * WG_STRIDE_BIG + 32 * a.strideS);
-    static const int xcd = fm_tune("FM_PW_XCD", 1);
-    a.tilesL = tilesL; a.nsplit = splits; a.xcd = xcd;
+    a.tilesL = tilesL; a.nsplit = splits;
     const dim3 grid(tilesL * splits);
     const bool pro = w.gate != nullptr;
     switch (CCi) {
@@ -1498,8 +1484,6 @@ int launch_pw_exp_bwd(const PwExpBwdParams& w, size_t slab_floats, hipStream_t s
     const int nrt = w.L / 16, cc = w.S / 16;
     const bool shape = (nrt == 6 && cc == 1) || (nrt == 9 && cc == 2);
     if (!shape || (w.L & 15) || (w.S & 15) || w.pix_per_group % 32 != 0 || w.npix % 32 != 0 || w.groups < 1 || w.groups > 2) return 0;
-    static const int on = fm_tune("FM_PW_EXP_BWD", 1);
-    if (!on) return 0;
     ExpBwdArgs a{};
     a.dA = w.dA; a.Ye = w.Ye; a.X = w.X; a.Wt = w.Wt; a.res = w.res; a.dX = w.dX; a.slab = w.slab;
     a.ca = w.ca; a.cb = w.cb; a.cc = w.cc; a.sc = w.sc; a.sh = w.sh;
@@ -1526,10 +1510,8 @@ int launch_pw_exp_bwd(const PwExpBwdParams& w, size_t slab_floats, hipStream_t s
 static int proj_bwd_slice(int L) { return L == 32 ? 32 : (L % 48 == 0 ? 48 : 0); }
 int pw_proj_bwd_nch(int L, int S, int imgs, int HW)
 {
-    static const int on = fm_tune("FM_PW_PROJ_BWD", 1), ragged = fm_tune("FM_PW_PROJ_RAGGED", 1);
     const int ls = proj_bwd_slice(L);
-    if (!on || !ls || L / ls > 5 || (S != 16 && S != 32 && S != 48) || imgs < 1) return 0;
-    if (HW % 32 != 0 && (!ragged || HW % 16 != 0)) return 0;
+    if (!ls || L / ls > 5 || (S != 16 && S != 32 && S != 48) || imgs < 1 || HW % 16 != 0) return 0;
     const int tpi = (HW + 31) / 32;
     return std::max(1, std::min(std::min(16, tpi), (2048 + imgs - 1) / imgs));
 }
@@ -1547,8 +1529,8 @@ int launch_pw_proj_bwd(const PwProjBwdParams& w, int phase, size_t slab_floats, 
     const int nrw = nsl == 1 ? 4 : (nsl == 2 ? 2 : 1);               // run lanes per block: 4 x 1, 2 x 2, 1 x 3..5 waves
     const int nwaves = nsl * nrw;
     const int nruns = w.imgs * nch;
-    static const int cap = fm_tune("FM_PW_PROJ_BLOCKS", 1024);
-    int nblk = std::max(1, std::min(cap, (nruns + nrw - 1) / nrw));
+    constexpr int PROJ_BLOCKS = 1024;
+    int nblk = std::max(1, std::min(PROJ_BLOCKS, (nruns + nrw - 1) / nrw));
     if (phase == 0) nblk = (int)std::min<size_t>(nblk, std::max<size_t>(1, slab_floats / ((size_t)nrw * w.L * w.S)));
     const size_t lds = (size_t)w.L * a.strideW + (size_t)nwaves * 32 * (a.strideB + a.strideS);
 #define PROJ_BWD(N, C, PH)                                                                                              \

@@ -248,7 +248,10 @@ __global__ __launch_bounds__(512, 2) void pwgrad_kernel(const PwgradParams p)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            const bool late = (p.pw_flags & 1) && wave >= 4;        // (as pconv.hip: waves 4-7 issue behind the last pass's MFMAs)
+            // (as pconv.hip: waves 4-7 issue behind the last pass's MFMAs; measured: -0.2 ms per step).  Opaque to the optimizer:
+            // two copies of the DMA addressing specialised on the wave index spill SGPRs
+            int late = wave >> 2;         // (eight waves)
+            asm("" : "+s"(late));
             if (!late && (FULL || s + 2 < nsteps)) { issueA(sl); issueB(sl); }
             if (more) PW_READA(sl1, 0, A0[0]);
             __builtin_amdgcn_sched_barrier(0);
@@ -321,8 +324,6 @@ int launch_pwgrad(PwgradParams p, size_t slab_floats, hipStream_t s)
 #undef PW_ATTR
         attr_done = true;
     }
-    static const int flags = fm_tune("FM_PWGRAD_FLAGS", 1);      // (measured: -0.2 ms per step)
-    p.pw_flags = flags;
     p.nblk_n = p.ksz * p.ksz * (p.Ci >> 5);
     const int nb = pwgrad_tile_nb(p.nblk_n), bm = pwgrad_tile_m(p.M);
     p.tilesM = p.M / bm;

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void pwgrad_ring_kernel(const PwgradParams 
             asm volatile("" ::: "memory");
             // (as pconv.hip: the two waves of a SIMD would issue their DMA at the same point; waves 4-7 issue theirs behind the step's
             // last MFMAs -- still three instructions per wave and step, which is what the counted wait above relies on)
-            const bool late = (p.pw_flags & 1) && wave >= 4;
+            const bool late = wave >= 4;
             if (!late) { issueA(s + 3, slot0); issueB(s + 7); }
             const unsigned a_nxt = (unsigned)(slot1 * SA);
             PR_COLUMN(4, PR_READA(a_nxt, 0, An[0]))
@@ -285,13 +285,13 @@ __global__ __launch_bounds__(512, 2) void pwgrad_ring_kernel(const PwgradParams 
 
 // the ring form takes: 3x3, stride 1, pad 1; whole 64-channel tiles on both sides; rows short enough for the ring (a tap shift of
 // W + 2 positions within the 64 the ring keeps behind the current step); maps from 28 pixels wide up -- below that the padding
-// positions cost more MFMA work than the form saves (measured with the tuning build's FM_PWGRAD_RING_MINW=7: 14 x 14 maps 369 vs
-// 346 us, 7 x 7 maps 366 vs 342 us per launch at 256 images; FM_PWGRAD_RING=0 there keeps pwgrad.hip everywhere).
+// positions cost more MFMA work than the form saves (measured with a minimum width of 7: 14 x 14 maps 369 vs 346 us, 7 x 7 maps
+// 366 vs 342 us per launch at 256 images, against pwgrad.hip).
+constexpr int PR_MIN_W = 28;
 bool pwgrad_ring_takes(const PwgradParams& p)
 {
-    static const int on = fm_tune("FM_PWGRAD_RING", 1), minw = fm_tune("FM_PWGRAD_RING_MINW", 28);
-    if (!on || p.ksz != 3 || p.pad != 1 || p.stride != 1 || p.Ho != p.Hi || p.Wo != p.Wi) return false;
-    if (p.M % 64 != 0 || p.Ci % 64 != 0 || p.Wi + 2 > 64 || p.Wi < minw) return false;
+    if (p.ksz != 3 || p.pad != 1 || p.stride != 1 || p.Ho != p.Hi || p.Wo != p.Wi) return false;
+    if (p.M % 64 != 0 || p.Ci % 64 != 0 || p.Wi + 2 > 64 || p.Wi < PR_MIN_W) return false;
     const long long nimg = p.npix / ((long long)p.Ho * p.Wo);
     return nimg * (p.Hi + 1) * (p.Wi + 1) + p.Wi + 2 < (1LL << 24);
 }
@@ -320,8 +320,6 @@ int launch_pwgrad_ring(PwgradParams p, size_t slab_floats, hipStream_t s)
     splits = (int)std::min<size_t>((size_t)splits, std::max<size_t>(1, slab_floats / ((size_t)p.M * p.Nw)));
     if (splits >= 8) splits -= splits % 8;
     p.xcd_remap = splits % 8 == 0 ? 1 : 0;
-    static const int flags = fm_tune("FM_PWGRAD_FLAGS", 1);      // (measured: -0.2 ms per step)
-    p.pw_flags = flags;
     p.q_per_split = (((p.Qtot + splits - 1) / splits) + 31) & ~31;
     p.splits = splits;
     if (p.sp == 9) hipLaunchKernelGGL((pwgrad_ring_kernel<9>), dim3(tiles * splits), dim3(512), PR_LDS, s, p);

@@ -268,11 +268,10 @@ void k_stem_weight_planes(const float* w, unsigned short* dst, int Kw, hipStream
 }
 
 // 7x7 / stride 2 / pad 3 on an input whose output rows are 112 pixels (7 column tiles of 16) in multiples of four rows, 64 output
-// channels, planes of the whole framed batch below 2 GB (FM_STEM_ROWS=0 in a tuning build keeps igemm.hip's stem form)
+// channels, planes of the whole framed batch below 2 GB
 bool stem_rows_takes(int k, int stride, int cout, int hout, int wout, long long plane_bytes)
 {
-    static const int on = fm_tune("FM_STEM_ROWS", 1);
-    return on && k == 7 && stride == 2 && cout == 64 && wout == 112 && hout % 4 == 0 && 3 * plane_bytes < 0x7ff00000LL;
+    return k == 7 && stride == 2 && cout == 64 && wout == 112 && hout % 4 == 0 && 3 * plane_bytes < 0x7ff00000LL;
 }
 int stem_rows_stats_tiles(int imgs_per_group, int hout) { return imgs_per_group * (hout / 4); }
 

@@ -342,7 +342,7 @@ struct SkinnyParams {
     // gather != 0: the X operand is the im2col row of a stem conv (Ci = 4): 16-B chunk c of a row is
     // input pixel (oh*stride + c/kw_p - pad, ow*stride + c%kw_p - pad), valid while c%kw_p < k
     int gather, Hi, Wi, Ho, Wo, stride, pad, k, kw_p;
-    int tilesL, nsplit, xcd;   // launch geometry of the 1-D grid
+    int tilesL, nsplit;   // launch geometry of the 1-D grid
 };
 
 template <int CC>
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void wgrad_skinny_kernel(const SkinnyParams p)
     const int nsplit = p.nsplit;
     {
         const int T = p.tilesL, id = blockIdx.x;
-        const int full = p.xcd ? (nsplit >> 3) << 3 : 0;
+        const int full = (nsplit >> 3) << 3;
         if (id < full * T) {
             const int q = id >> 3, x = id & 7;
             split = (q / T) * 8 + x;
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(256) void wgrad_skinny_split_kernel(const SkinnyPar
     const int nsplit = p.nsplit;
     {
         const int T = p.tilesL, id = blockIdx.x;
-        const int full = p.xcd ? (nsplit >> 3) << 3 : 0;
+        const int full = (nsplit >> 3) << 3;
         if (id < full * T) {
             const int q = id >> 3, x = id & 7;
             split = (q / T) * 8 + x;
@@ -618,8 +618,7 @@ int launch_wgrad_skinny(const WgradParams& w, size_t slab_floats, hipStream_t s)
     splits = (int)std::min<size_t>(splits, std::max<size_t>(1, slab_floats / ((size_t)w.M * w.Nw)));
     p.pix_per_split = (((w.npix + splits - 1) / splits) + 31) & ~31;
     splits = (w.npix + p.pix_per_split - 1) / p.pix_per_split;
-    static const int xcd = fm_tune("FM_PW_XCD", 1);
-    p.tilesL = tilesL; p.nsplit = splits; p.xcd = xcd;
+    p.tilesL = tilesL; p.nsplit = splits;
     dim3 grid(tilesL * splits);
     const int cc = (S + 15) / 16;
     const int sp = w.sp;
@@ -640,9 +639,8 @@ int launch_wgrad_skinny(const WgradParams& w, size_t slab_floats, hipStream_t s)
 // (ResNet layer 1: 576 = 3 x 192) and 256 otherwise for the 64-row tiles
 int wgrad_tile_n(int M, int Nw)
 {
-    static const int t192 = fm_tune("FM_WGRAD192", 1);
     if (M >= 128) return 128;
-    return (t192 && (Nw % 192 == 0 || Nw <= 192)) ? 192 : 256;      // Nw = 176: the packed 7x7 stem
+    return ((Nw % 192 == 0 || Nw <= 192)) ? 192 : 256;      // Nw = 176: the packed 7x7 stem
 }
 
 // false: the split is too large for the kernel's 32-bit buffer offsets (nothing launched; the caller reports the error)
