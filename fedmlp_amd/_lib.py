@@ -66,6 +66,11 @@ SYMBOLS = {
     "fm_augment": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, _P]),
     "fm_forward_train": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
     "fm_backward_step": (C.c_int, [_P, _P]),
+    "fm_backward_grads": (C.c_int, [_P, _P, _P]),
+    "fm_forward_recompute": (C.c_int, [_P, _P, _P, _I32]),
+    "fm_zero_grad": (C.c_int, [_P]),
+    "fm_adam_step": (C.c_int, [_P, C.POINTER(FmAdam)]),
+    "fm_get_grads": (C.c_int, [_P, _P]),
     "fm_teacher_axpby": (C.c_int, [_P, C.c_float, C.c_float]),
     "fm_teacher_swap": (C.c_int, [_P]),
     "fm_set_stochastic": (C.c_int, [_P, _P, _P]),

@@ -366,7 +366,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, int groups, 
             scale[g * C + ch] = sc;
             shift[g * C + ch] = be - (float)mu * sc;
             const double unb = count > 1 ? var * n / (n - 1.0) : var;
-            if (!keep_running) {
+            if (!keep_running && run_mean) {       // run_mean null: a recomputed forward (fm_forward_recompute)
                 run_mean[ch] = (1.f - momentum) * run_mean[ch] + momentum * (float)mu;
                 run_var[ch] = (1.f - momentum) * run_var[ch] + momentum * (float)unb;
             }
@@ -959,6 +959,24 @@ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, f
     const int64_t n4 = n / 4;     // engine pads the parameter arena to a multiple of 4
     hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, p, g, m, v, n4, lr, b1, b2,
                        eps, wd, bc1, bc2_sqrt, skip);
+}
+
+// gradient accumulator of the autograd path (fm_backward_grads): acc = g when the accumulator is empty (a copy, so one backward
+// after fm_zero_grad holds exactly the fused path's gradients), acc += g after it; one streaming float4 pass over the arena
+__global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4, int copy,
+                                       const int* __restrict__ skip)
+{
+    if (skip && *skip) return;      // a lost stream-K part poisoned g (adam_kernel): the accumulator stays as it is
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        reinterpret_cast<f32x4*>(acc)[i] = copy ? gg : reinterpret_cast<const f32x4*>(acc)[i] + gg;
+    }
+}
+void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip)
+{
+    const int64_t n4 = n / 4;     // engine pads the parameter arena to a multiple of 4
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, acc, g, n4, copy ? 1 : 0, skip);
 }
 
 // out[i] = sum_s slab[s][i]; block = 64 float4 columns x 16 split lanes, lanes combined through

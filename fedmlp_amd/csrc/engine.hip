@@ -141,6 +141,13 @@ struct fm_engine {
     float *se_dgp = nullptr, *se_drp = nullptr, *se_ds = nullptr, *se_pool = nullptr, *hfeat = nullptr;
     const float *dc_dev = nullptr, *drop_dev = nullptr;   // caller-owned stochastic multipliers (or null)
     int pending_views = 0, pending_B = 0;                 // fm_forward_train awaiting fm_backward_step
+    // autograd path (fm_backward_grads / fm_adam_step): d loss / d feature of the backward being enqueued (caller-owned, or
+    // null), the gradient accumulator (NP floats, allocated on first use; `gacc_full` false = empty, the next backward copies),
+    // and bn_frozen: a recomputed forward (fm_forward_recompute) leaves running statistics and counters as they are
+    const float* dfeat_dev = nullptr;
+    float* gacc = nullptr;
+    bool gacc_full = false;
+    bool bn_frozen = false;
     std::vector<int64_t> tcounters;                       // the teacher's num_batches_tracked
     std::vector<StateEntry> entries;
     int n_bn_ch = 0;
@@ -1303,11 +1310,12 @@ void bn_fwd_finalize(fm_engine* e, int ci, int groups, int imgs_per_group)
     const Conv& c = e->convs[ci];
     const int bi = c.bn;
     Bn& b = e->bns[bi];
+    const bool run = !e->bn_frozen;
     k_bn_finalize(e->ws_stats, groups, stats_tiles(e, ci, imgs_per_group, groups), b.C, imgs_per_group * c.hout * c.wout,
                   e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
-                  e->state + e->off_rm + b.ch_off, e->state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale,
-                  b.shift, e->bn_eps, e->bn_mom, e->st, e->dev_err);
-    e->counters[bi] += groups;
+                  run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
+                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, e->st, e->dev_err);
+    if (run) e->counters[bi] += groups;
 }
 
 // backward through BN bi: dz (+ optional relu mask source z) -> dy ; optional masked grad out
@@ -1487,21 +1495,23 @@ void ensure_teacher_shadow(fm_engine* e)
     e->twb_dirty = false;
 }
 
-// optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2)
-void adam_step(fm_engine* e)
+// optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2); g = e->grad (fused steps)
+// or the autograd path's accumulator (fm_adam_step)
+void adam_step(fm_engine* e, const float* g)
 {
     e->adam_t += 1;
     const double bc1 = 1.0 - pow((double)e->hp.beta1, (double)e->adam_t);
     const double bc2 = 1.0 - pow((double)e->hp.beta2, (double)e->adam_t);
-    k_adam(e->state, e->grad, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
+    k_adam(e->state, g, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
            e->hp.weight_decay, (float)bc1, (float)sqrt(bc2), e->st, e->dev_err);
     e->ev_dirty = true;
     e->wpack_dirty = true;
     ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
 }
 
-// backward from e->dlogits through the graph saved by forward_train, then Adam
-void backward_and_step(fm_engine* e, int groups, int B)
+// backward from e->dlogits (and e->dfeat_dev) through the graph saved by forward_train into e->grad, then Adam unless
+// step is false (fm_backward_grads)
+void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
 {
     const int imgs = groups * B;
     const float* S = e->state;
@@ -1532,7 +1542,7 @@ void backward_and_step(fm_engine* e, int groups, int B)
     };
     auto guard = [&](int k, int par) { if (sw) soft(e, hipStreamWaitEvent(main_st, e->ev_c[k][par], 0)); };
     k_fc_bwd(e->dlogits, e->feat, S + e->off_fcw, nullptr, e->grad + e->off_fcw, e->grad + e->off_fcb, e->GA, DT_F32, imgs,
-             512, e->C, cl.hout * cl.wout, e->st);
+             512, e->C, cl.hout * cl.wout, e->st, e->dfeat_dev);
     float *ga = e->GA, *ge = e->GE;
     for (int b = (int)e->blocks.size() - 1; b >= 0; --b) {
         Block& blk = e->blocks[b];
@@ -1593,7 +1603,7 @@ void backward_and_step(fm_engine* e, int groups, int B)
         soft(e, hipEventRecord(e->ev_wdone, e->st2));
         soft(e, hipStreamWaitEvent(main_st, e->ev_wdone, 0));
     }
-    adam_step(e);      // optimizer.step()
+    if (step) adam_step(e, e->grad);      // optimizer.step()
 }
 
 // =============================== EfficientNet-B0 graph =================================
@@ -1616,11 +1626,12 @@ void bn_fwd_tensor(fm_engine* e, int bi, const float* y, int groups, int pix_per
     if (!sums_ready)
         k_chan_reduce(nullptr, e->dt, y, e->dt, nullptr, nullptr, nullptr, nullptr, nullptr, e->ws_part, groups, pix_per_group,
                       HW, b.C, 0, 0, nullptr, nullptr, e->st);
+    const bool run = !e->bn_frozen;
     k_bn_finalize(e->ws_part, groups, sums_ready ? dw_stats_tiles() : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
                   e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
-                  e->state + e->off_rm + b.ch_off, e->state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale, b.shift,
-                  e->bn_eps, e->bn_mom, e->st);
-    e->counters[bi] += groups;
+                  run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
+                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, e->st);
+    if (run) e->counters[bi] += groups;
 }
 
 // backward through act(bn(y))*rowscale: dz -> dy (may alias dz); writes dgamma/dbeta
@@ -1759,7 +1770,7 @@ void eff_forward_eval(fm_engine* e, const float* S, float* evs, float* evh, bool
 }
 
 
-void eff_backward_and_step(fm_engine* e, int groups, int B)
+void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
 {
     const int imgs = groups * B;
     const float* S = e->state;
@@ -1793,7 +1804,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B)
     auto guard = [&](int k, int par) { if (sw) soft(e, hipStreamWaitEvent(main_st, e->ev_c[k][par], 0)); };
     e->ctx = 500;
     { OP("k_fc_bwd"); k_fc_bwd(e->dlogits, h, S + e->off_fcw, e->drop_dev, G + e->off_fcw, G + e->off_fcb, e->T_mid, e->dt, imgs, e->D, e->C,
-             HWh, e->st); }
+             HWh, e->st, e->dfeat_dev); }
     { OP("bnact_bwd"); bnact_bwd(e, e->bn_head, e->T_mid, ch.y, e->T_mid, nullptr, groups, B * HWh, HWh, 2); }
     { OP("conv_wgrad"); conv_wgrad(e, e->c_head, e->mbs.back().out, e->T_mid, imgs); }
     float *go = e->GA, *gi = e->GB;
@@ -1950,15 +1961,19 @@ void eff_backward_and_step(fm_engine* e, int groups, int B)
         soft(e, hipEventRecord(e->ev_wdone, e->st2));
         soft(e, hipStreamWaitEvent(main_st, e->ev_wdone, 0));
     }
-    { OP("adam_step"); adam_step(e); }
+    if (step) { OP("adam_step"); adam_step(e, e->grad); }
 }
 
 // model dispatch
-void net_forward_train(fm_engine* e, int groups, int B)
+// update_running false (fm_forward_recompute): the same launches and saved tensors, BN running statistics and
+// num_batches_tracked counters left as they are
+void net_forward_train(fm_engine* e, int groups, int B, bool update_running = true)
 {
     ensure_packed(e);
+    e->bn_frozen = !update_running;
     if (e->model == 1) eff_forward_train(e, groups, B);
     else forward_train(e, groups, B);
+    e->bn_frozen = false;
 }
 void net_forward_eval(fm_engine* e, bool teacher, int imgs)
 {
@@ -2007,11 +2022,31 @@ int teacher_forward_side(fm_engine* e, int imgs)
     HIPCHK(hipEventRecord(e->ev_t, e->st2));
     return FM_OK;
 }
-void net_backward_and_step(fm_engine* e, int groups, int B)
+void net_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
 {
     ensure_packed(e);
-    if (e->model == 1) eff_backward_and_step(e, groups, B);
-    else backward_and_step(e, groups, B);
+    if (e->model == 1) eff_backward_and_step(e, groups, B, step);
+    else backward_and_step(e, groups, B, step);
+}
+
+// an engine-layout gradient arena (e->grad or the accumulator) -> dst in state_dict order (conv weights OIHW, BN running
+// statistics as zeros; e->nf_sd floats), enqueued on e->st
+int grads_to_state_dict(fm_engine* e, const float* src, float* dst)
+{
+    size_t off = 0;
+    for (auto& en : e->entries) {
+        if (en.kind == 0) {
+            k_ohwi_to_oihw(src + en.eng_off, dst + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->st, en.Ostride);
+            off += en.n;
+        } else if (en.kind == 1) {
+            if (en.eng_off < e->NP)
+                HIPCHK(hipMemcpyAsync(dst + off, src + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->st));
+            else
+                HIPCHK(hipMemsetAsync(dst + off, 0, en.n * 4, e->st));
+            off += en.n;
+        }
+    }
+    return FM_OK;
 }
 
 ClassVec to_cv(const float* h, int C)
@@ -2601,6 +2636,67 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
     return FM_OK;
 }
 
+int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->pending_views > 0, "fm_backward_grads without a preceding fm_forward_train / fm_forward_recompute");
+    const int views = e->pending_views, B = e->pending_B;
+    if (!e->gacc) DALLOC(e->gacc, e->NP);          // first use: fused-only users never pay for the accumulator
+    const size_t nz = (size_t)views * B * e->C * 4;
+    if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->st));
+    else HIPCHK(hipMemsetAsync(e->dlogits, 0, nz, e->st));
+    e->dfeat_dev = dfeat_dev;
+    net_backward_and_step(e, views, B, false);     // e->grad, every weight gradient joined to the main stream
+    e->dfeat_dev = nullptr;
+    k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->st, e->dev_err);
+    e->pending_views = 0;
+    STEP_DONE(e);
+    e->gacc_full = true;
+    return FM_OK;
+}
+
+int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev, int32_t B)
+{
+    ARGCHK(e && x1_dev, "null");
+    const int views = x2_dev ? 2 : 1;
+    ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
+    const float* xs[2] = {x1_dev, x2_dev};
+    to_nhwc4(e, xs, views, B);
+    net_forward_train(e, views, B, false);
+    e->pending_views = views; e->pending_B = B;
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_zero_grad(fm_engine* e)
+{
+    ARGCHK(e, "null engine");
+    e->gacc_full = false;
+    return FM_OK;
+}
+
+int fm_adam_step(fm_engine* e, const fm_adam* hp)
+{
+    ARGCHK(e && hp, "null");
+    e->hp = *hp;
+    if (!e->gacc_full) return FM_OK;               // torch.optim.Adam skips parameters whose .grad is None
+    adam_step(e, e->gacc);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_get_grads(fm_engine* e, float* dev_out)
+{
+    ARGCHK(e && dev_out, "null");
+    if (!e->gacc_full) HIPCHK(hipMemsetAsync(dev_out, 0, (size_t)e->nf_sd * 4, e->st));
+    else {
+        const int rc = grads_to_state_dict(e, e->gacc, dev_out);
+        if (rc != FM_OK) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
 {
     ARGCHK(e, "null engine");
@@ -2796,19 +2892,8 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
 int fm_debug_get_grads(fm_engine* e, float* host_f32)
 {
     ARGCHK(e && host_f32, "null");
-    size_t off = 0;
-    for (auto& en : e->entries) {
-        if (en.kind == 0) {
-            k_ohwi_to_oihw(e->grad + en.eng_off, e->stage_sd + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->st, en.Ostride);
-            off += en.n;
-        } else if (en.kind == 1) {
-            if (en.eng_off < e->NP)
-                HIPCHK(hipMemcpyAsync(e->stage_sd + off, e->grad + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->st));
-            else
-                HIPCHK(hipMemsetAsync(e->stage_sd + off, 0, en.n * 4, e->st));
-            off += en.n;
-        }
-    }
+    const int rc = grads_to_state_dict(e, e->grad, e->stage_sd);
+    if (rc != FM_OK) return rc;
     HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
     return FM_OK;

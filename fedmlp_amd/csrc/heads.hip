@@ -99,28 +99,38 @@ __global__ void fc_bwd_w_kernel(const float* __restrict__ dz, const float* __res
         if (threadIdx.x == 0) db[k] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
     }
 }
+// dfeat (autograd path, fm_backward_grads): d loss / d feature, where the feature is the pooled tensor BEFORE the dropout
+// multiplier (EfficientNet-B0's `feature`; ResNet-18 has no mask).  Null: the fused steps' arithmetic, unchanged.
 template <typename T>
 __global__ void fc_bwd_x_kernel(const float* __restrict__ dz, const float* __restrict__ W,
-                                const float* __restrict__ mask, T* __restrict__ dout, int D, int C, int HW)
+                                const float* __restrict__ mask, const float* __restrict__ dfeat, T* __restrict__ dout, int D,
+                                int C, int HW)
 {
     const int img = blockIdx.x;
     const float inv = 1.f / (float)HW;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float s = 0.f;
         for (int k = 0; k < C; ++k) s += dz[(size_t)img * C + k] * W[(size_t)k * D + d];
-        s *= inv;
-        if (mask) s *= mask[(size_t)img * D + d];      // dropout multiplier on the pooled feature
+        if (dfeat) {                                       // d pooled = mask * (dz W) + dfeat, spread over HW
+            if (mask) s *= mask[(size_t)img * D + d];
+            s = (s + dfeat[(size_t)img * D + d]) * inv;
+        } else {
+            s *= inv;
+            if (mask) s *= mask[(size_t)img * D + d];      // dropout multiplier on the pooled feature
+        }
         for (int p = 0; p < HW; ++p) dout[((size_t)img * HW + p) * D + d] = (T)s;
     }
 }
 void k_fc_bwd(const float* dz, const float* feat, const float* W, const float* mask, float* dW, float* db,
-              void* dout, int dt, int imgs, int D, int C, int HW, hipStream_t s)
+              void* dout, int dt, int imgs, int D, int C, int HW, hipStream_t s, const float* dfeat)
 {
     hipLaunchKernelGGL(fc_bwd_w_kernel, dim3(C, (D + 63) / 64), dim3(256), 0, s, dz, feat, dW, db, imgs, D, C);
     if (dt == DT_F32)
-        hipLaunchKernelGGL(fc_bwd_x_kernel<float>, dim3(imgs), dim3(256), 0, s, dz, W, mask, reinterpret_cast<float*>(dout), D, C, HW);
+        hipLaunchKernelGGL(fc_bwd_x_kernel<float>, dim3(imgs), dim3(256), 0, s, dz, W, mask, dfeat, reinterpret_cast<float*>(dout), D,
+                           C, HW);
     else
-        hipLaunchKernelGGL(fc_bwd_x_kernel<bf16>, dim3(imgs), dim3(256), 0, s, dz, W, mask, reinterpret_cast<bf16*>(dout), D, C, HW);
+        hipLaunchKernelGGL(fc_bwd_x_kernel<bf16>, dim3(imgs), dim3(256), 0, s, dz, W, mask, dfeat, reinterpret_cast<bf16*>(dout), D,
+                           C, HW);
 }
 
 // ------------------------------------------------------------ losses -----------

@@ -74,7 +74,7 @@ void k_augment(const uint8_t* cache, const int* idx, const int* params, float* o
 void k_bn_finalize(const float* stats, int groups, int tiles, int C, int count,
                    const float* gamma, const float* beta, float* run_mean, float* run_var,
                    float* mean, float* istd, float* scale, float* shift, float eps, float momentum,
-                   hipStream_t s, const int* skip = nullptr);    // *skip != 0: the running statistics are not updated
+                   hipStream_t s, const int* skip = nullptr);    // *skip != 0 or run_mean null: the running statistics are not updated
 // eval-mode folded affine for all BN channels at once
 void k_bn_eval_affine(const float* gamma, const float* beta, const float* run_mean, const float* run_var,
                       float* scale, float* shift, int n, float eps, hipStream_t s);
@@ -174,9 +174,10 @@ void k_add_inplace(void* y, const void* a, int dt, int64_t n, hipStream_t s);
 void k_avgpool(const void* x, int dt, float* feat, int imgs, int HW, int C, hipStream_t s);
 void k_fc_fwd(const float* feat, const float* W, const float* b, float* logits, int imgs, int D, int C,
               hipStream_t s);
-// dW[k][d], db[k] written; dout[img][hw][d] = (sum_k dz[img][k] W[k][d]) * mask[img][d] / HW  (mask optional)
+// dW[k][d], db[k] written; dout[img][hw][d] = ((sum_k dz[img][k] W[k][d]) * mask[img][d] + dfeat[img][d]) / HW
+// (mask optional; dfeat optional: d loss / d feature of the pooled feature, entering after the dropout multiplier)
 void k_fc_bwd(const float* dz, const float* feat, const float* W, const float* mask, float* dW, float* db,
-              void* dout, int dt, int imgs, int D, int C, int HW, hipStream_t s);
+              void* dout, int dt, int imgs, int D, int C, int HW, hipStream_t s, const float* dfeat = nullptr);
 
 // ---- losses (one block; deterministic) -------------------------------------------
 void k_loss_bce(const float* z, const float* y, ClassVec pos_w, int B, int C, float inv_norm,
@@ -193,6 +194,8 @@ void k_loss_fixmatch(const float* z, const float* y, ClassVec pos_w, ClassVec po
 void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
             float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s, const int* skip = nullptr);   // *skip != 0: no update
 void k_reduce_slabs(const float* slab, float* out, int splits, int64_t n, hipStream_t s);
+// acc = g (copy) or acc += g over n floats (n a multiple of 4); *skip != 0: no update
+void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip = nullptr);
 
 // ---- prototypes / tagging ----------------------------------------------------------
 void k_proto_accumulate(const float* feat, const float* logits, const float* labels, int B, int D, int C,

@@ -73,6 +73,17 @@ class Engine:
         # install their own draws with set_stochastic().
         self.stochastic = model == "Efficient_b0"
         self.stochastic_generator = None
+        # serial: bumped by every call that enqueues work -- any of them may overwrite the activations a train-mode forward
+        # saved (fm_forward_eval writes the feature the backward reads), so an autograd node whose forward is no longer the
+        # engine's last call recomputes it (model.HipNet).  weights_version: bumped by every call that may change the
+        # resident weights (steps, optimizer, set_state, FedAvg, a torch write through state_tensor()).
+        self.serial = 0
+        self.weights_version = 0
+
+    def _enqueue(self, weights=False):
+        self.serial += 1
+        if weights:
+            self.weights_version += 1
 
     def close(self):
         if getattr(self, "h", None):
@@ -110,6 +121,7 @@ class Engine:
         flat = np.ascontiguousarray(flat, dtype=np.float32)
         counters = np.ascontiguousarray(counters, dtype=np.int64)
         assert flat.size == self.nf and counters.size == self.ni
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_set_state(self.h, flat.ctypes.data_as(C.c_void_p),
                                          counters.ctypes.data_as(C.c_void_p)))
 
@@ -123,6 +135,7 @@ class Engine:
     def state_tensor(self):
         """torch view of the engine-layout device state (for the RCCL all-reduce)."""
         p, n = C.c_void_p(), C.c_int64()
+        self._enqueue(weights=True)              # the caller may write the state through the view
         _lib.check(self.lib.fm_state_device(self.h, C.byref(p), C.byref(n)))
         return _device_view(p.value, n.value, self.device)
 
@@ -132,6 +145,7 @@ class Engine:
         return c
 
     def state_scale(self, w):
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_state_scale(self.h, C.c_float(w)))
 
     def fedavg_fold(self, states, dict_len, out=None):
@@ -144,6 +158,7 @@ class Engine:
         ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in states])
         dst = self.state_tensor() if out is None else out
         self._check_stream()
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_fedavg_fold(self.h, ptrs, _lib.fvec(dict_len, K), K, _ptr(dst)))
         return dst
 
@@ -157,10 +172,12 @@ class Engine:
                                f"{cur:#x}: call the engine under the stream it was created on")
 
     def teacher_snapshot(self):
+        self._enqueue()
         _lib.check(self.lib.fm_teacher_snapshot(self.h))
 
     def adam_reset(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4):
         hp = _lib.FmAdam(lr, betas[0], betas[1], eps, weight_decay)
+        self._enqueue()
         _lib.check(self.lib.fm_adam_reset(self.h, C.byref(hp)))
 
     def sync(self):
@@ -176,6 +193,7 @@ class Engine:
     def forward_eval_into(self, x, feat, logits, teacher=False):
         """net(x) in eval mode into caller-owned [B,D] / [B,C] device buffers (no allocation)."""
         self._check_stream()
+        self._enqueue()
         _lib.check(self.lib.fm_forward_eval(self.h, _ptr(x), x.shape[0], int(teacher), _ptr(feat), _ptr(logits)))
         return feat, logits
 
@@ -201,6 +219,7 @@ class Engine:
 
     def fedavg_allreduce(self, w):
         """state <- sum_ranks w_rank * state_rank on the engine stream (ncclAllReduce in the library)."""
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_fedavg_allreduce(self.h, C.c_float(w)))
 
     def fedavg_tao(self, t, n_i, negative_mask):
@@ -224,6 +243,7 @@ class Engine:
 
     def step_bce(self, x, y, pos_weight, bs_norm, loss_out):
         self._check_stream()
+        self._enqueue(weights=True)
         self._draw(x.shape[0])
         _lib.check(self.lib.fm_step_bce(self.h, _ptr(x), _ptr(y), x.shape[0],
                                         _lib.fvec(pos_weight, self.n_classes), int(bs_norm),
@@ -231,6 +251,7 @@ class Engine:
 
     def step_stage1(self, x1, x2, y, active_mask, annotation_num, bs_norm, loss_out):
         self._check_stream()
+        self._enqueue(weights=True)
         self._draw(2 * x1.shape[0])
         _lib.check(self.lib.fm_step_stage1(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0],
                                            _lib.fvec(active_mask, self.n_classes),
@@ -238,6 +259,7 @@ class Engine:
 
     def step_stage2(self, x, y, distill, loss_out):
         self._check_stream()
+        self._enqueue(weights=True)
         self._draw(x.shape[0])
         _lib.check(self.lib.fm_step_stage2(self.h, _ptr(x), _ptr(y), _ptr(distill), x.shape[0],
                                            _ptr(loss_out)))
@@ -245,6 +267,7 @@ class Engine:
     def step_fixmatch(self, xw, xs, y, pos_weight, pos_weight_unk, active_mask, annotation_num,
                       bs_norm, loss_out):
         self._check_stream()
+        self._enqueue(weights=True)
         n = self.n_classes
         self._draw(2 * xw.shape[0])
         _lib.check(self.lib.fm_step_fixmatch(
@@ -256,29 +279,78 @@ class Engine:
     # ---- generic split step (rank-4 baselines: loss head computed by the host mirror) -----------
     def forward_train(self, x1, x2=None):
         self._check_stream()
+        self._enqueue()
         views = 1 if x2 is None else 2
         B = x1.shape[0]
         self._draw(views * B)
         feat = torch.empty((views * B, self.feature_dim), device=self.device, dtype=torch.float32)
         logits = torch.empty((views * B, self.n_classes), device=self.device, dtype=torch.float32)
         _lib.check(self.lib.fm_forward_train(self.h, _ptr(x1), _ptr(x2), B, _ptr(feat), _ptr(logits)))
+        self._pending_rows = views * B
         return feat, logits
 
     def backward_step(self, dlogits):
         self._check_stream()
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_backward_step(self.h, _ptr(dlogits.contiguous().float())))
 
+    # ---- autograd path: backward into the gradient accumulator, optimizer step apart (model.HipNet, optim.Adam) -----
+    def forward_recompute(self, x1, x2=None):
+        """The train-mode forward of x1 (and x2) again, for a following backward_grads: same saved tensors, BN running
+        statistics and counters untouched, no outputs.  The caller installs the draws of the original forward."""
+        self._check_stream()
+        self._enqueue()
+        _lib.check(self.lib.fm_forward_recompute(self.h, _ptr(x1), _ptr(x2), x1.shape[0]))
+        self._pending_rows = (1 if x2 is None else 2) * x1.shape[0]
+
+    def backward_grads(self, dlogits=None, dfeat=None):
+        """Backward of the pending forward_train / forward_recompute from d loss / d logits [views*B, C] and d loss / d feature
+        [views*B, D] (None = zero); the parameter gradients are added to the engine's accumulator, no optimizer step."""
+        self._check_stream()
+        self._enqueue()
+        dz = None if dlogits is None else dlogits.detach().contiguous().float()
+        df = None if dfeat is None else dfeat.detach().contiguous().float()
+        rows = getattr(self, "_pending_rows", 0)
+        if dz is not None and tuple(dz.shape) != (rows, self.n_classes):
+            raise ValueError(f"backward_grads: dlogits {tuple(dz.shape)}, the pending forward's logits are {(rows, self.n_classes)}")
+        if df is not None and tuple(df.shape) != (rows, self.feature_dim):
+            raise ValueError(f"backward_grads: dfeat {tuple(df.shape)}, the pending forward's feature is {(rows, self.feature_dim)}")
+        _lib.check(self.lib.fm_backward_grads(self.h, _ptr(dz), _ptr(df)))
+
+    def zero_grad(self):
+        _lib.check(self.lib.fm_zero_grad(self.h))
+
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """torch.optim.Adam (coupled L2) over the accumulator with the engine's moments (adam_reset zeroes them)."""
+        self._check_stream()
+        self._enqueue(weights=True)
+        hp = _lib.FmAdam(lr, betas[0], betas[1], eps, weight_decay)
+        _lib.check(self.lib.fm_adam_step(self.h, C.byref(hp)))
+
+    def grads(self):
+        """The accumulator in state_dict order (conv weights OIHW, BN running statistics as zeros) as a cuda fp32 tensor
+        of get_state()'s float length; enqueued, not synchronised."""
+        self._check_stream()
+        self._enqueue()
+        out = torch.empty(self.nf, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.fm_get_grads(self.h, _ptr(out)))
+        return out
+
     def teacher_axpby(self, w_teacher, w_student):
+        self._enqueue()
         _lib.check(self.lib.fm_teacher_axpby(self.h, C.c_float(w_teacher), C.c_float(w_student)))
 
     def teacher_swap(self):
+        self._enqueue(weights=True)
         _lib.check(self.lib.fm_teacher_swap(self.h))
 
     def proto_reset(self):
+        self._enqueue()
         _lib.check(self.lib.fm_proto_reset(self.h))
 
     def proto_accumulate(self, feat, logits, labels, active_mask, negative_mask, L, U):
         n = self.n_classes
+        self._enqueue()
         _lib.check(self.lib.fm_proto_accumulate(self.h, _ptr(feat), _ptr(logits), _ptr(labels),
                                                 feat.shape[0], _lib.fvec(active_mask, n),
                                                 _lib.fvec(negative_mask, n), C.c_float(L),
@@ -287,6 +359,7 @@ class Engine:
     def proto_finalize(self, zero_guard, n_local, active_mask):
         proto = np.empty((2 * self.n_classes, self.feature_dim), np.float32)
         t = np.empty(self.n_classes, np.float64)
+        self._enqueue()
         _lib.check(self.lib.fm_proto_finalize(self.h, int(zero_guard), int(n_local),
                                               _lib.fvec(active_mask, self.n_classes),
                                               proto.ctypes.data_as(C.c_void_p),
@@ -297,6 +370,7 @@ class Engine:
         N = feat.shape[0]
         sim = torch.empty((len(classes), N), device=self.device, dtype=torch.float32)
         if len(classes) and N:
+            self._enqueue()
             cls = (C.c_int32 * len(classes))(*[int(c) for c in classes])
             _lib.check(self.lib.fm_cos_tag(self.h, _ptr(feat), N, _ptr(proto), cls, len(classes),
                                            _ptr(sim)))
@@ -307,6 +381,7 @@ class Engine:
         cap = max(N, 1)
         top, bot = (C.c_int32 * cap)(), (C.c_int32 * cap)()
         nt, nb = C.c_int32(), C.c_int32()
+        self._enqueue()
         _lib.check(self.lib.fm_select_topk(self.h, _ptr(sim_row), N, float(clean_thr),
                                            float(noise_thr), cap, top, C.byref(nt), bot,
                                            C.byref(nb)))
@@ -333,6 +408,7 @@ class Engine:
         pn = (C.c_int32 * n_cls)(*sizes)
         top, bot = (C.c_int32 * (n_cls * cap))(), (C.c_int32 * (n_cls * cap))()
         nt, nb = (C.c_int32 * n_cls)(), (C.c_int32 * n_cls)()
+        self._enqueue()
         _lib.check(self.lib.fm_select_topk_rows(self.h, _ptr(sims), N, n_cls, rows, pn, stride, float(clean_thr),
                                                 float(noise_thr), cap, top, nt, bot, nb))
         return [(list(top[k * cap:k * cap + nt[k]]), list(bot[k * cap:k * cap + nb[k]])) for k in range(n_cls)]
@@ -345,6 +421,7 @@ class Engine:
         out = torch.empty((B, 3, self.in_h, self.in_w), device=self.device, dtype=torch.float32)
         assert cache_u8.is_cuda and cache_u8.dtype == torch.uint8 and cache_u8.is_contiguous()
         assert params.dtype == torch.int32 and params.shape == (B, 8)
+        self._enqueue()
         _lib.check(self.lib.fm_augment(self.h, C.c_void_p(cache_u8.data_ptr()), _ptr(idx), _ptr(params), B,
                                        _lib.fvec(mean, 3), _lib.fvec(std, 3), _ptr(out)))
         return out
@@ -392,14 +469,17 @@ class Engine:
         return flat
 
     def debug_pw(self, op, conv, x, dy, out, imgs, groups=1, psc=None, psh=None, gate=None, stats=None):
+        self._enqueue()
         _lib.check(self.lib.fm_debug_pw(self.h, op, conv, _ptr(x), _ptr(dy), _ptr(out), imgs, groups, _ptr(psc),
                                         _ptr(psh), _ptr(gate), _ptr(stats)))
 
     def debug_proj_bwd(self, conv, phase, dyp, yd, bn, gate, ds, imgs, groups, out, pool5=None):
+        self._enqueue()
         _lib.check(self.lib.fm_debug_proj_bwd(self.h, conv, phase, _ptr(dyp), _ptr(yd), _ptr(bn), _ptr(gate), _ptr(ds), imgs,
                                               groups, _ptr(out), _ptr(pool5)))
 
     def debug_exp_bwd(self, conv, da, ye, x, res, bn, imgs, groups, dx, dw):
+        self._enqueue()
         _lib.check(self.lib.fm_debug_exp_bwd(self.h, conv, _ptr(da), _ptr(ye), _ptr(x), _ptr(res), _ptr(bn), imgs, groups,
                                              _ptr(dx), _ptr(dw)))
 
@@ -415,6 +495,7 @@ class Engine:
         return self.lib.fm_debug_num_convs(self.h)
 
     def debug_conv(self, op, conv, x, dy, out, imgs, groups=1, stats=None):
+        self._enqueue()
         _lib.check(self.lib.fm_debug_conv(self.h, op, conv, _ptr(x), _ptr(dy), _ptr(out), imgs, groups,
                                           _ptr(stats)))
 

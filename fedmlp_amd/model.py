@@ -5,6 +5,12 @@ the reference's driver touches (main.py:73-77, 181-184, 218-222, 361-366):
 load_state_dict()`` with torchvision key names, ``to()/cuda()/cpu()``,
 ``copy.deepcopy``.
 
+In train mode ``net(x)`` is differentiable: it runs the engine's train-mode
+forward and returns outputs whose autograd node, on ``loss.backward()``, runs the
+engine's backward into a gradient accumulator (``fm_backward_grads``);
+``fedmlp_amd.optim.Adam(net)`` steps the weights from it.  The weights are not
+torch tensors, so ``torch.optim.*(net.parameters())`` does not train a HipNet.
+
 A HipNet is a light state container (host copy of the flat state).  The heavy
 part -- device weights, optimiser moments, activation workspaces -- lives in the
 process-wide HIP engine (fedmlp_amd.engine.get_engine); a net is made resident
@@ -18,6 +24,51 @@ import torch
 
 from . import spec
 from .engine import get_engine
+
+# the train-mode call's autograd node needs one input that requires grad (x usually does not; d/dx is not computed)
+_ANCHOR = torch.zeros((), requires_grad=True)
+
+
+class _TrainCall(torch.autograd.Function):
+    """One train-mode net(x): the engine's forward now (own BN batch statistics, one running-statistics update), its
+    backward into the engine's gradient accumulator when the loss is backpropagated.  The node keeps the input, the engine
+    serial after its forward, the net's weights key and (EfficientNet-B0) its drop-connect / dropout draws: if anything
+    was enqueued on the engine since (another net(x), an eval forward, a rebind), it re-binds the net, re-installs the
+    draws and recomputes the forward (fm_forward_recompute: bit-identical saved tensors, running statistics untouched)."""
+
+    @staticmethod
+    def forward(ctx, anchor, net, eng, x, max_images):
+        feat, logits = eng.forward_train(x)
+        net._mark_dirty()
+        ctx.set_materialize_grads(False)
+        ctx.net, ctx.eng, ctx.x, ctx.max_images = net, eng, x, max_images
+        ctx.serial, ctx.key = eng.serial, net._weights_key()
+        ctx.draws = (getattr(eng, "_dc", None), getattr(eng, "_dr", None)) if eng.model == "Efficient_b0" else None
+        return feat, logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dfeat, dlogits):
+        net = ctx.net
+        if net._weights_key() != ctx.key:
+            raise RuntimeError("HipNet: the net's weights changed between its train-mode forward and this backward (an "
+                               "optimizer step, load_state_dict or FedAvg); run the forward again")
+        eng = net.bind(ctx.x.shape[2], ctx.x.shape[3], ctx.max_images)
+        if getattr(eng, "_grad_owner", None) is not net:     # the accumulator holds another net's gradients
+            eng.zero_grad()
+            eng._grad_owner = net
+        if ctx.draws is not None:
+            prev = (getattr(eng, "_dc", None), getattr(eng, "_dr", None))
+            eng.set_stochastic(*ctx.draws)
+        try:
+            if eng is not ctx.eng or eng.serial != ctx.serial:
+                eng.forward_recompute(ctx.x)
+            eng.backward_grads(dlogits, dfeat)
+        finally:
+            if ctx.draws is not None:
+                eng.set_stochastic(*prev)
+        return None, None, None, None, None
+
 
 _MODEL_ALIASES = {"Resnet18": "Resnet18", "resnet18": "Resnet18", "Efficient_b0": "Efficient_b0"}
 
@@ -42,6 +93,7 @@ class HipNet:
         self.counters = np.ascontiguousarray(counters, dtype=np.int64)
         self.training = True
         self._version = 0
+        self._wver = 0                 # bumped when an engine step / optimizer changes the weights (mark_trained)
         self._engine = None            # engine on which (self, _version) is resident
         self.default_max_images = 128
         self.precision = "fp32"        # activation storage of the engine this net binds to
@@ -88,7 +140,8 @@ class HipNet:
         return LoadResult(missing, unexpected, mismatched)
 
     def parameters(self):
-        """Trainable tensors in state_dict order (views of the host copy)."""
+        """Trainable tensors in state_dict order (views of the host copy).  They are copies, not the weights the engine
+        trains: torch.optim.*(net.parameters()) does not train a HipNet -- use fedmlp_amd.optim.Adam(net)."""
         self._pull()
         off = 0
         for key, shape, dt in spec.entries(self.model, self.n_classes):
@@ -108,19 +161,61 @@ class HipNet:
         return c
 
     def __call__(self, x):
-        """Eval-mode forward on the HIP engine -> (feature[B,D], logits[B,C]) CUDA tensors.
-        (utils/local_training.py:983, 1030, 1227; utils/evaluations.py:25.)  The
-        train-mode forward is not exposed as an autograd graph: the fused training
-        steps live behind LocalUpdate.train*/Engine.step_*."""
-        if self.training:
-            raise NotImplementedError(
-                "HipNet(x) runs the eval-mode forward only; call net.eval() first, or use "
-                "fedmlp_amd.local_training.LocalUpdate / Engine.step_* for training steps")
+        """net(x) on the HIP engine -> (feature[B,D], logits[B,C]) CUDA tensors.
+        Eval mode: the eval-mode forward (utils/local_training.py:983, 1030, 1227; utils/evaluations.py:25).
+        Train mode: one train-mode forward (its own BN batch statistics, one running-statistics update) whose outputs
+        carry an autograd node: loss.backward() adds the parameter gradients to the engine's accumulator (grads(),
+        zero_grad(), fedmlp_amd.optim.Adam).  d/dx is not computed.  Under torch.no_grad() the train forward runs and
+        nothing is recorded.  The fused steps (LocalUpdate.train*, Engine.step_*) remain the fast path."""
         x = torch.as_tensor(x, dtype=torch.float32)
-        eng = self.bind(x.shape[2], x.shape[3], max(self.default_max_images, x.shape[0]))
-        return eng.forward_eval(x.to(eng.device).contiguous())
+        max_images = max(self.default_max_images, x.shape[0])
+        eng = self.bind(x.shape[2], x.shape[3], max_images)
+        x = x.to(eng.device).contiguous()
+        if not self.training:
+            return eng.forward_eval(x)
+        if not torch.is_grad_enabled():
+            out = eng.forward_train(x)
+            self._mark_dirty()
+            return out
+        return _TrainCall.apply(_ANCHOR, self, eng, x.detach(), max_images)
 
     forward = __call__
+
+    # ---- gradients of the train-mode calls (the engine's accumulator) ---------------------------
+    def zero_grad(self, set_to_none=True):
+        eng = self._engine
+        if eng is not None and eng.h and getattr(eng, "_grad_owner", None) is self:
+            eng.zero_grad()
+
+    def grads(self):
+        """OrderedDict trainable key -> CUDA tensor (state_dict order, conv weights OIHW): the gradients loss.backward()
+        accumulated since zero_grad()."""
+        eng = self._engine
+        if eng is None or not eng.h:
+            raise RuntimeError("HipNet.grads(): the net has not run on an engine yet")
+        flat = eng.grads() if getattr(eng, "_grad_owner", None) is self else \
+            torch.zeros(eng.nf, device=eng.device, dtype=torch.float32)
+        out, off = OrderedDict(), 0
+        for key, shape, dt in spec.entries(self.model, self.n_classes):
+            if dt != "f32":
+                continue
+            n = int(np.prod(shape))
+            if spec.is_trainable(key):
+                out[key] = flat[off:off + n].view(tuple(shape))
+            off += n
+        return out
+
+    def _weights_key(self):
+        """Changes whenever the weights do (load_state_dict, an optimizer / engine step): the autograd node's version check."""
+        return self._version, self._wver
+
+    def _bound_engine(self):
+        """The engine whose resident state is this net's, or None."""
+        eng = self._engine
+        if eng is not None and eng.h and getattr(eng, "_owner", None) is self \
+                and getattr(eng, "_owner_version", -1) == self._version:
+            return eng
+        return None
 
     # ---- residency -------------------------------------------------------------------------
     def _touch(self):
@@ -150,6 +245,12 @@ class HipNet:
             eng._dirty = False
 
     def mark_trained(self):
+        """The engine changed this net's weights (a training step, an optimizer step)."""
+        self._wver += 1
+        self._mark_dirty()
+
+    def _mark_dirty(self):
+        """The engine's copy of this net's state moved (a train-mode forward moves the BN running statistics)."""
         if self._engine is not None:
             self._engine._dirty = True
 
@@ -163,6 +264,7 @@ class ResidentNet(HipNet):
         self.model, self.n_classes = engine.model, engine.n_classes
         self.training = True
         self._version = 0
+        self._wver = 0
         self._engine = engine
         self.default_max_images = engine.max_images
         self.precision = engine.precision
@@ -178,7 +280,17 @@ class ResidentNet(HipNet):
         self.flat, self.counters = self._engine.get_state()
 
     def mark_trained(self):
+        self._wver += 1
+
+    def _mark_dirty(self):
         pass
+
+    def _weights_key(self):
+        # the engine is this net's alone: any write of its weights (set_state, FedAvg in place, a step) counts
+        return self._wver, self._engine.weights_version
+
+    def _bound_engine(self):
+        return self._engine
 
     def load_state_dict(self, sd, strict=True):
         if strict:

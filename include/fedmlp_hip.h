@@ -243,6 +243,30 @@ int fm_augment(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, c
 int fm_forward_train(fm_engine* e, const float* x1_dev, const float* x2_dev, int32_t B, float* feat_dev,
                      float* logits_dev);
 int fm_backward_step(fm_engine* e, const float* dlogits_dev);
+
+/* ---- autograd path: train-mode net(x) -> loss.backward() -> optimizer.step() ------------------
+ * Any loss computed by the caller (utils/local_training.py:370-379, 421-455, 520-551, 1294-1319 and a
+ * user's own): the backward is split from the optimizer step by a gradient ACCUMULATOR owned by the
+ * handle (NP floats, allocated on first use; the fused steps and fm_debug_get_grads never touch it).
+ * fm_backward_grads: backward of the pending fm_forward_train / fm_forward_recompute (one or two views)
+ *   from d(loss)/d(logits) [views*B][C] and d(loss)/d(feature) [views*B][D] (either may be NULL =
+ *   zero); the parameter gradients are ADDED to the accumulator (the first backward after
+ *   fm_zero_grad copies them: the same bits as the fused path's gradients); no optimizer step.
+ *   Clears the pending forward.
+ * fm_forward_recompute: the train-mode forward again, so that its saved activations exist for a
+ *   following fm_backward_grads (the engine is deterministic: bit-identical saved tensors); BN
+ *   running statistics and num_batches_tracked are NOT updated, nothing is written out.
+ * fm_zero_grad: empties the accumulator.
+ * fm_adam_step: torch.optim.Adam (coupled L2) over the accumulator with the handle's moments and step
+ *   count (fm_adam_reset zeroes them); hp is read on every call.  An empty accumulator is skipped
+ *   like torch skips parameters whose .grad is None.
+ * fm_get_grads: the accumulator in state_dict order (conv weights OIHW; BN running statistics as
+ *   zeros; fm_state_sizes' n_f32 floats) into a device buffer, enqueued without synchronising. */
+int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev);
+int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev, int32_t B);
+int fm_zero_grad(fm_engine* e);
+int fm_adam_step(fm_engine* e, const fm_adam* hp);
+int fm_get_grads(fm_engine* e, float* dev_out);
 /* teacher <- w_teacher*teacher + w_student*student over every state entry (train_RSCFed's EMA,
  * utils/local_training.py:751-759, weights 0.999 / 0.001). */
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student);
