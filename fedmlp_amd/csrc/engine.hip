@@ -147,6 +147,7 @@ struct fm_engine {
     const float* dfeat_dev = nullptr;
     float* gacc = nullptr;
     bool gacc_full = false;
+    uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
     bool bn_frozen = false;
     std::vector<int64_t> tcounters;                       // the teacher's num_batches_tracked
     std::vector<StateEntry> entries;
@@ -2603,6 +2604,18 @@ int fm_augment(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, c
     ARGCHK(e && cache_dev && idx_dev && params_dev && mean_host && std_host && out_dev && B >= 1, "null");
     k_augment(cache_dev, idx_dev, params_dev, out_dev, B, e->H, e->W, mean_host[0], mean_host[1], mean_host[2],
               std_host[0], std_host[1], std_host[2], e->st);
+    return FM_OK;
+}
+
+int fm_augment_strong(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, const int32_t* params_dev,
+                      const int32_t* strong_dev, int32_t B, const float* mean_host, const float* std_host, float* out_dev)
+{
+    ARGCHK(e && cache_dev && idx_dev && params_dev && strong_dev && mean_host && std_host && out_dev, "null");
+    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    ARGCHK(e->W % 4 == 0 && e->H >= 1, "the strong view packs four pixels of a row per thread: W % 4 == 0");
+    if (!e->strong_ws) DALLOC(e->strong_ws, fm_strong_ws_bytes(e->maxB, e->H, e->W));    // first use: weak-only users never pay for it
+    k_augment_strong(cache_dev, idx_dev, params_dev, strong_dev, e->strong_ws, e->maxB, out_dev, B, e->H, e->W, mean_host[0],
+                     mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], e->st);
     return FM_OK;
 }
 

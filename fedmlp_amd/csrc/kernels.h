@@ -66,6 +66,14 @@ void k_axpby(float* y, const float* x, float a, float b, int64_t n, hipStream_t 
 // fill 0, then horizontal flip, /255, (v-mean)/std   (dataset/dataset.py:40-53 pipeline)
 void k_augment(const uint8_t* cache, const int* idx, const int* params, float* out, int B, int H, int W,
                float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t s);
+// The FixMatch strong view (augment_strong.hip): weak view -> two RandAugmentMC op slots -> cutout -> normalise, five launches.
+// strong[b] = FM_STRONG_RECORD int32 (include/fedmlp_hip.h).  ws = the handle's uint8 workspace of fm_strong_ws_bytes(maxB, H, W):
+// two images [maxB][3][H][W], then per sample FM_STRONG_STAT_BYTES (3 x 256 LUT bytes + the Contrast mean).  W % 4 == 0, B <= maxB.
+#define FM_STRONG_RECORD 20
+#define FM_STRONG_STAT_BYTES 784
+inline size_t fm_strong_ws_bytes(int maxB, int H, int W) { return (size_t)maxB * (2 * (size_t)3 * H * W + FM_STRONG_STAT_BYTES); }
+void k_augment_strong(const uint8_t* cache, const int* idx, const int* params, const int* strong, uint8_t* ws, int maxB,
+                      float* out, int B, int H, int W, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t s);
 
 // ---- batch norm ---------------------------------------------------------------
 // stats: [groups][tiles][2][C] partial (sum, sumsq) from the conv epilogue.

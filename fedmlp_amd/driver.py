@@ -48,17 +48,19 @@ def args_parser():
     p.add_argument("--save_every", type=int, default=0, help="save netglob.state_dict() every N rounds (main.py:237)")
     p.add_argument("--save_dir", default=".")
     p.add_argument("--augment", type=int, default=0,
-                   help="1: uint8 HBM cache + per-sample RandomAffine/HFlip/Normalize kernel (dataset/dataset.py:40-53)")
+                   help="1: uint8 HBM cache + per-sample RandomAffine/HFlip/Normalize kernel (dataset/dataset.py:40-53); "
+                        "2: the same with the FixMatch pair (:63-77): image_aug_2 is weak + RandAugmentMC(2, 10) + cutout")
     return p.parse_args()
 
 
-def AugmentedDeviceDataset(n, C, hw, seed, device):
-    """synthetic uint8 images behind fedmlp_amd.augment.AugmentedDataset (uint8 HBM cache + fm_augment)"""
+def AugmentedDeviceDataset(n, C, hw, seed, device, strong=False):
+    """synthetic uint8 images behind fedmlp_amd.augment.AugmentedDataset (uint8 HBM cache + fm_augment; strong=True:
+    the FixMatch pair, whose second view goes through fm_augment_strong)"""
     from fedmlp_amd.augment import AugmentedDataset
     rs = np.random.RandomState(seed)
     imgs = rs.randint(0, 256, size=(n, 3, hw, hw)).astype(np.uint8)
     targets = (rs.uniform(size=(n, C)) < 0.15).astype(np.float32)
-    return AugmentedDataset(imgs, targets, train=True, generator=torch.Generator().manual_seed(seed))
+    return AugmentedDataset(imgs, targets, train=True, generator=torch.Generator().manual_seed(seed), strong=strong)
 
 
 class DeviceDataset:
@@ -177,7 +179,10 @@ def main():
     n_all = [args.n_local] * args.n_clients
     clients = {}
     for c in mine:                                       # client c annotates class c mod C
-        ds = (AugmentedDeviceDataset if args.augment else DeviceDataset)(args.n_local, C, args.hw, args.seed + 1000 * c, dev)
+        if args.augment:
+            ds = AugmentedDeviceDataset(args.n_local, C, args.hw, args.seed + 1000 * c, dev, strong=args.augment == 2)
+        else:
+            ds = DeviceDataset(args.n_local, C, args.hw, args.seed + 1000 * c, dev)
         pos = [np.where(ds.targets[:, k] == 1)[0] for k in range(C)]
         a = argparse.Namespace(**vars(args))
         clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C])

@@ -426,6 +426,19 @@ class Engine:
                                        _lib.fvec(mean, 3), _lib.fvec(std, 3), _ptr(out)))
         return out
 
+    def augment_strong(self, cache_u8, idx, params, strong, mean, std):
+        """the FixMatch strong view: augment()'s arguments plus the [B,20] int32 records of
+        fedmlp_amd.augment.draw_strong (two RandAugmentMC op slots and the cutout corners) -> fp32 NCHW batch."""
+        B = idx.shape[0]
+        out = torch.empty((B, 3, self.in_h, self.in_w), device=self.device, dtype=torch.float32)
+        assert cache_u8.is_cuda and cache_u8.dtype == torch.uint8 and cache_u8.is_contiguous()
+        assert params.dtype == torch.int32 and params.shape == (B, 8)
+        assert strong.dtype == torch.int32 and strong.shape == (B, 20) and strong.is_contiguous()
+        self._enqueue()
+        _lib.check(self.lib.fm_augment_strong(self.h, C.c_void_p(cache_u8.data_ptr()), _ptr(idx), _ptr(params), _ptr(strong),
+                                              B, _lib.fvec(mean, 3), _lib.fvec(std, 3), _ptr(out)))
+        return out
+
     # ---- measurement ------------------------------------------------------------------
     def profile_enable(self, on):
         _lib.check(self.lib.fm_profile_enable(self.h, int(on)))

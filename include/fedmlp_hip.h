@@ -233,6 +233,25 @@ int fm_select_topk_rows(fm_engine* e, const float* sim_dev, int64_t N, int32_t n
 int fm_augment(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, const int32_t* params_dev,
                int32_t B, const float* mean_host, const float* std_host, float* out_dev);
 
+/* The FixMatch strong view (dataset/dataset.py:63-77) on the same cache: the weak transform above (params_dev, the same
+ * record and bits), then RandAugmentMC(n=2, m=10) of utils/FixMatch.py:205-219 -- two op slots, each skipped or one of the
+ * 14 ops of its pool, applied to the uint8 result of the step before exactly as PIL chains them -- then CutoutAbs(16), /255,
+ * Normalize.  Bit-exact with Pillow 12.2 (tests/golden/augment_strong_pil.npz).  The draws are the caller's; strong_dev[b] is
+ * 20 int32 (80 bytes, 16-byte aligned per sample) holding everything that does not depend on pixels:
+ *   [0..7]   slot 0: {op, p0, p1, p2, p3, p4, p5, 0}        [8..15]  slot 1, the same        [16..19] cutout {x0, y0, x1, y1}
+ *   op: 0 AutoContrast, 1 Brightness, 2 Color, 3 Contrast, 4 Equalize, 5 Identity, 6 Posterize, 7 Rotate, 8 Sharpness, 9 ShearX,
+ *       10 ShearY, 11 Solarize, 12 TranslateX, 13 TranslateY (the pool's order), 14 = slot skipped (its coin came up >= 0.5).
+ *   p0 of Brightness / Color / Contrast / Sharpness: the blend factor v * 0.9 / 10 + 0.05 as fp32 bits;
+ *   p0 of Posterize: the byte mask that keeps int(v * 4 / 10) + 4 bits; p0 of Solarize: the threshold 256 - int(v * 256 / 10);
+ *   p0..p5 of Rotate / ShearX / ShearY / TranslateX / TranslateY: c0..c5 of the op's AFFINE matrix in the 16.16 form above, fill 0
+ *       (Rotate: the matrix Image.rotate builds, cos / sin rounded to 15 places, about (W/2, H/2));
+ *   cutout: the rectangle x0..x1, y0..y1 INCLUSIVE set to (127,127,127); x1 = W or y1 = H is clipped by the image.
+ * Histograms, the Contrast mean and the AutoContrast / Equalize tables are computed on the device, on the image the step before
+ * produced.  Five launches on the engine's stream whatever B and the ops, no host synchronisation.  The uint8 workspace
+ * (max_images x (2 x 3 x H x W + 784) bytes) belongs to the handle and is allocated on the first call.  B <= max_images, W % 4 == 0. */
+int fm_augment_strong(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, const int32_t* params_dev,
+                      const int32_t* strong_dev, int32_t B, const float* mean_host, const float* std_host, float* out_dev);
+
 /* ---- generic train step (the other baselines of main.py's --exp switch) -----
  * train_RSCFed (utils/local_training.py:705-769), train_FedNoRo (:115-234) and train_CBAFed
  * (:236-342) differ from the steps above only in the loss head on the [B,C] logits.  The split
