@@ -118,6 +118,34 @@ template <int NV> __device__ __forceinline__ void ldf(const float* p, f32x4 (&v)
 // all run through it.  stem_kw > 0 selects the 7x7-stem form (Ci = 4): one step
 // = one kernel row, chunk j = kernel column j (valid while j < stem_kw).
 // ---------------------------------------------------------------------------
+// pconv.hip, per-tap kernel: one GEMM of a launch's job table.  A launch walks up to PCONV_MAX_JOBS GEMMs that share the operand
+// shape (M, Hi, Wi, input planes of xp_pix pixels), the output tensor and its stride `os`; the stream-K space of the launch is the
+// concatenation of the jobs' (tile, K-step) spaces.  The caller fills the first group (ntaps, tapcode, cib, icc2, wofs, wofs2, Hg,
+// Wg, oh0, ow0); launch_pconv derives the rest.  A launch without a table (njobs = 0) is one job made from its own fields.
+#define PCONV_MAX_JOBS 5
+struct PconvJob {
+    int ntaps;
+    unsigned long long tapcode;   // 4 bits per tap: (dh+1) | (dw+1)<<2 (pconv_tapcode)
+    int cib, icc2;        // channel blocks of 32 of the K axis in all; blocks icc2 .. cib - 1 take their B operand from Xp2 (channel
+                          // block icc - icc2 of it, same taps) and their weights from wofs2; icc2 = cib: one operand tensor
+    unsigned wofs, wofs2; // byte offsets from Wsp of the weight planes [(channel block, tap)][3][M][32] of the two parts (launch_pconv
+                          // rebases wofs2 to the job's K-step 0)
+    int Hg, Wg;           // virtual output grid per image (the parity classes of an odd-sized input differ)
+    int oh0, ow0;         // output placement: oh = hg*os + oh0
+    // set by launch_pconv
+    int nsteps, k2;       // K-steps per tile (ntaps * cib); first K-step of the second part (ntaps * icc2)
+    int npix;             // imgs_per_group * Hg * Wg
+    float rcpHW, rcpW;    // 1 / (Hg Wg), 1 / Wg
+    int tilesN;           // pixel tiles per group
+    int tile0, step0;     // first tile / first (tile, K-step) of the job in the launch-global numbering
+};
+inline unsigned long long pconv_tapcode(const int* dh, const int* dw, int ntaps)
+{
+    unsigned long long c = 0;          // taps of 3x3 / 1x1 convs and of their dgrad parity classes lie in [-1, 1]
+    for (int t = 0; t < ntaps; ++t) c |= (unsigned long long)(((dh[t] + 1) & 3) | (((dw[t] + 1) & 3) << 2)) << (4 * t);
+    return c;
+}
+
 struct IgemmParams {
     const float* W;       // packed weights [M][nsteps*32]
     const float* X;       // input activations NHWC [imgs][Hi][Wi][Ci]
@@ -178,6 +206,12 @@ struct IgemmParams {
     // kernel reads (a step with a lost part does not update the weights) and its host-mapped twin the next API call checks
     int* err = nullptr;
     int* err_host = nullptr;
+    // pconv.hip, per-tap kernel: the job table (above); Xp2 = the second operand tensor of the jobs that have one (the shape of
+    // Xp); wsp_bytes = extent of the weight planes behind Wsp that the jobs address (set by launch_pconv)
+    int njobs = 0;
+    PconvJob job[PCONV_MAX_JOBS];
+    const unsigned short* Xp2 = nullptr;
+    unsigned wsp_bytes = 0;
 };
 // test hook (fedmlp_hip_debug.h fm_debug_lose_part): the non-finishers of shared stream-K tiles do not announce their parts
 void pconv_debug_lose_part(int on);

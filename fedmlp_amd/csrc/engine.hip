@@ -1221,6 +1221,64 @@ void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx
     }
 }
 
+// The input gradient of a stride-2 residual block, dx = dgrad(c1; dy1) + dgrad(ds; dyd), as ONE launch of the per-tap planes kernel
+// (pconv.hip job table): one job per parity class of the 3x3 conv; the 1x1 downsample's only class, (0,0), has the tap of the
+// 3x3's class (0,0) -- the same dy pixel -- and the same output grid: its K-steps ride behind that job's own, with dyd's planes
+// as the job's second operand.  Every element of dx is written once; nothing is read back.  false = the shapes are not of that
+// kind (or not planes mode): the caller runs the two conv_dgrad calls.
+bool block_dgrad(fm_engine* e, int c1i, int dsi, const float* dy1, const float* dyd, float* dx, int imgs,
+                 const unsigned short* dy1p = nullptr, const unsigned short* dydp = nullptr)
+{
+    Conv& c = e->convs[c1i];
+    Conv& d = e->convs[dsi];
+    const long long xp_pix = (long long)imgs * c.hout * c.wout;
+    if (!e->planes || c.ncls != 4 || d.ncls != 1 || c.cls[0].bm_off < 0 || d.cls[0].bm_off < 0 ||
+        !pconv_takes(c.cin_p, c.cout_p, xp_pix, c.wout))
+        return false;
+    static_assert(PCONV_MAX_JOBS >= 4, "one job per parity class");
+    const DgradClass& d0 = d.cls[0];
+    if (c.stride != 2 || d.stride != 2 || d.k != 1 || d.cin_p != c.cin_p || d.cout_p != c.cout_p || d.hin != c.hin || d.win != c.win ||
+        d.hout != c.hout || d.wout != c.wout || d0.ph != 0 || d0.pw != 0 || d0.dh[0] != 0 || d0.dw[0] != 0)
+        return false;
+    const DgradClass& c0 = c.cls[0];
+    if (c0.ph != 0 || c0.pw != 0 || c0.taps.n != 1 || c0.dh[0] != 0 || c0.dw[0] != 0) return false;
+    if (!dy1p) dy1p = scratch_planes(e, dy1, xp_pix, c.cout_p);
+    if (!dydp) {
+        if ((size_t)xp_pix * d.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return true; }
+        k_split_planes(dyd, e->xp_scratch2, xp_pix, d.cout_p, e->st);
+        dydp = e->xp_scratch2;
+    }
+    if (!dy1p) return true;                    // (scratch_planes reported it)
+    IgemmParams p{};
+    p.Xp = dy1p; p.Xp2 = dydp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d;
+    p.Y = dx; p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+    p.M = c.cin_p;
+    p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
+    p.sg = 1;
+    p.Ho = c.hin; p.Wo = c.win; p.Co = c.cin_p;
+    p.os = c.stride;
+    p.imgs_per_group = imgs;
+    p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
+    p.relu = 0;
+    p.njobs = c.ncls;
+    for (int k = 0; k < c.ncls; ++k) {
+        const DgradClass& q = c.cls[k];
+        PconvJob& j = p.job[k];
+        j.ntaps = q.taps.n; j.tapcode = pconv_tapcode(q.dh, q.dw, q.taps.n);
+        j.cib = j.icc2 = c.cout_p >> 5;
+        j.wofs = j.wofs2 = (unsigned)(q.bm_off * 2);
+        j.Hg = (c.hin - q.ph + c.stride - 1) / c.stride;
+        j.Wg = (c.win - q.pw + c.stride - 1) / c.stride;
+        j.oh0 = q.ph; j.ow0 = q.pw;
+    }
+    p.job[0].cib += d.cout_p >> 5;
+    p.job[0].wofs2 = (unsigned)(d0.bm_off * 2);
+    // family 6 / 7 = pconv_kernel<4 | 2, ..., false>; the launch's algorithmic FLOPs = both convs'
+    ProfScope ps(e, (c.cin_p >= 128 ? 0 : 1) + 6, 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
+    launch_pconv(p, 1, e->st);
+    return true;
+}
+
 // xp / dyp (planes mode): block-major planes of x / dy (null = made here from the fp32 tensors: test hooks)
 void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs, const Prologue* pro = nullptr,
                 int pix_per_group = 0, const unsigned short* xp = nullptr, const unsigned short* dyp = nullptr)
@@ -1571,8 +1629,10 @@ void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
         if (pm) bn_bwd(e, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, true, gdp, blk.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
         else bn_bwd(e, blk.c1, GD, blk.z1, GD, nullptr, groups, B, true);
         if (blk.ds >= 0) {
-            conv_dgrad(e, blk.ds, S, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
-            conv_dgrad(e, blk.c1, S, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
+            if (!block_dgrad(e, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
+                conv_dgrad(e, blk.ds, S, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
+                conv_dgrad(e, blk.c1, S, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
+            }
         } else {
             conv_dgrad(e, blk.c1, S, GD, ge, imgs, ga, false, gdp);
         }
@@ -2981,6 +3041,21 @@ int fm_debug_stem_masks(fm_engine* e, int32_t imgs, int32_t groups, uint8_t* rel
     if (argmax_host) {
         HIPCHK(hipMemcpyAsync(argmax_host, e->idx0, (size_t)imgs * (c0.hout / 2) * (c0.wout / 2) * 64, hipMemcpyDeviceToHost, e->st));
         HIPCHK(hipStreamSynchronize(e->st));
+    }
+    return FM_OK;
+}
+
+int fm_debug_block_dgrad(fm_engine* e, int32_t block, const float* dy1_dev, const float* dyd_dev, float* dx_dev, int32_t imgs)
+{
+    ARGCHK(e && dy1_dev && dyd_dev && dx_dev, "null tensor");
+    ARGCHK(e->model == 0 && !e->precision, "fm_debug_block_dgrad: a precision-0 ResNet-18 engine");
+    ARGCHK(block >= 0 && block < (int)e->blocks.size() && e->blocks[block].ds >= 0, "block has no downsample");
+    ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
+    ensure_packed(e);
+    const Block& blk = e->blocks[block];
+    if (!block_dgrad(e, blk.c1, blk.ds, dy1_dev, dyd_dev, dx_dev, imgs)) {     // (the fp32-operand engine: its two calls)
+        conv_dgrad(e, blk.ds, e->state, dyd_dev, dx_dev, imgs, nullptr, false);
+        conv_dgrad(e, blk.c1, e->state, dy1_dev, dx_dev, imgs, nullptr, true);
     }
     return FM_OK;
 }

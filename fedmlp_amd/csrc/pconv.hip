@@ -128,13 +128,29 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
     const unsigned lds0 = (unsigned)(size_t)smem;              // LDS byte address of the dynamic segment
     const unsigned As = lds0, Bs = lds0 + NS * SA;             // [NS][3][BM][64], [NSB][3][BROWS][64]
 
-    const int nsteps = p.nsteps;                               // K-steps of 32: (channel block, tap), tap-minor
-    const int ntaps = p.ntaps;
-    const int HWg = p.Hg * p.Wg;
-    const int npix = p.imgs_per_group * HWg;
-    const int tiles_pg = p.tilesM * p.tilesN;
     const int Wi = p.Wi;
-    const float rcpHW = 1.0f / (float)HWg, rcpW = 1.0f / (float)p.Wg;
+    // The values of ONE GEMM.  The tap-row-sharing instantiation runs one GEMM per launch: the launch's own fields.  The per-tap
+    // instantiation walks the launch's job table (common.h PconvJob): job jb's entry, read where it is used -- scalar loads
+    // from the kernel arguments, nothing per lane
+    struct JobV {
+        int nsteps, ntaps, k2, icc2;          // nsteps = K-steps of 32 per tile: (channel block, tap), tap-minor
+        unsigned wofs, wofs2;
+        unsigned long long tapcode;
+        int Hg, Wg, HWg, npix, tilesN, oh0, ow0, tile0, step0;
+        float rcpHW, rcpW;
+    };
+    auto jobv = [&](int jb) -> JobV {
+        if constexpr (TS) {
+            (void)jb;
+            const int HWg = p.Hg * p.Wg;
+            return JobV{p.nsteps, p.ntaps, p.nsteps, p.Ci >> 5, 0u, 0u, p.tapcode, p.Hg, p.Wg, HWg, p.imgs_per_group * HWg, p.tilesN,
+                        p.oh0, p.ow0, 0, 0, 1.0f / (float)HWg, 1.0f / (float)p.Wg};
+        } else {
+            const PconvJob& j = p.job[jb];
+            return JobV{j.nsteps, j.ntaps, j.k2, j.icc2, j.wofs, j.wofs2, j.tapcode, j.Hg, j.Wg, j.Hg * j.Wg, j.npix, j.tilesN,
+                        j.oh0, j.ow0, j.tile0, j.step0, j.rcpHW, j.rcpW};
+        }
+    };
 
     // XCD-aware bijective remap of the block id to a range index
     const int nb = gridDim.x, bid = blockIdx.x;
@@ -148,9 +164,14 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
     // are never negative (the launcher keeps the planes below 2 GB: 0x80000000 is out of range for every descriptor)
     constexpr unsigned OOB = 0x80000000u;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(p.Wsp), 0, (unsigned)((size_t)nsteps * 3 * p.M * 64), 0x00020000);
+        const_cast<unsigned short*>(p.Wsp), 0, TS ? (unsigned)((size_t)p.nsteps * 3 * p.M * 64) : p.wsp_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(p.Xp) - (size_t)(Wi + 1) * 64), 0,
+        (unsigned)(((size_t)(p.Ci >> 5) * 3 * p.xp_pix + (size_t)(Wi + 1)) * 64), 0x00020000);
+    // the second operand tensor of a job (K-steps from its k2 on), of the shape of the first (a launch without one: Xp again)
+    const unsigned short* xp2 = TS ? p.Xp : p.Xp2;
+    const __amdgpu_buffer_rsrc_t rsB2 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(xp2) - (size_t)(Wi + 1) * 64), 0,
         (unsigned)(((size_t)(p.Ci >> 5) * 3 * p.xp_pix + (size_t)(Wi + 1)) * 64), 0x00020000);
     const int drow = lane >> 2, chunk = (lane & 3) ^ ((lane >> 3) & 3);
     // fragment reads: row 16r + li of the wave's rows, chunk lg sits in slot lg ^ ((li>>1)&3)
@@ -175,6 +196,12 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
     // A segment = the K-steps [k0, k1) of one tile that this block's range covers, with the per-lane DMA state of the tile
     struct Seg {
         int tile, k0, k1, grp, tn, m0, n0;
+        // the segment's job and what the K loop and the fix-up take from its table entry (scalars; the epilogue reads the rest of
+        // the entry itself: kept live from here, those values cost the 64-row instantiation a stack frame)
+        int jb, nsteps, k2, icc2, ntaps;
+        unsigned wofs, wofs2;
+        unsigned long long tapcode;
+        unsigned tstart;                         // the tile's first step in the launch-global (tile, K-step) space
         unsigned voffA, voffB[RGB], vmask[RGB];
         int icc_b, it_b;                         // (channel block, tap) cursor of the next B step to be issued (TS: it_b = kernel row)
         // TS: lane masks (wave-uniform; the four 16-lane rows of a wave hold the same pixels): bit li = the pixel of lane row li in
@@ -182,14 +209,28 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
         unsigned mLR[FC];
     };
     auto decode = [&](Seg& g) {                  // takes the next segment off the block's range [w, wend)
-        g.tile = (int)((unsigned)w / (unsigned)nsteps);              // (total_steps < 2^31: the launcher checks)
-        g.k0 = (int)(w - (long long)g.tile * nsteps);
+        // the job: w against at most four prefix sums (INT_MAX past the last job); then the tile and the K-step inside the job, as
+        // in a launch of its own
+        g.jb = 0;
+        if constexpr (!TS) {
+#pragma unroll
+            for (int j = 1; j < PCONV_MAX_JOBS; ++j) g.jb += (int)w >= p.job[j].step0 ? 1 : 0;
+        }
+        const JobV J = jobv(g.jb);
+        const int nsteps = J.nsteps, ntaps = J.ntaps, npix = J.npix, HWg = J.HWg;
+        g.nsteps = J.nsteps; g.k2 = J.k2; g.icc2 = J.icc2; g.ntaps = J.ntaps; g.wofs = J.wofs; g.wofs2 = J.wofs2; g.tapcode = J.tapcode;
+        const float rcpHW = J.rcpHW, rcpW = J.rcpW;
+        const int tiles_pg = p.tilesM * J.tilesN;
+        const int tj = (int)((unsigned)(w - J.step0) / (unsigned)nsteps);          // (total_steps < 2^31: the launcher checks)
+        g.k0 = (int)(w - J.step0) - tj * nsteps;
         g.k1 = min(nsteps, g.k0 + (int)(wend - w));
+        g.tstart = (unsigned)w - (unsigned)g.k0;
         w += g.k1 - g.k0;
-        g.grp = g.tile / tiles_pg;
-        const int tl = g.tile - g.grp * tiles_pg;
-        const int tm = p.tn_fast ? tl / p.tilesN : tl % p.tilesM;
-        g.tn = p.tn_fast ? tl % p.tilesN : tl / p.tilesM;
+        g.tile = J.tile0 + tj;                   // launch-global: the tile's arrival counter
+        g.grp = tj / tiles_pg;
+        const int tl = tj - g.grp * tiles_pg;
+        const int tm = p.tn_fast ? tl / J.tilesN : tl % p.tilesM;
+        g.tn = p.tn_fast ? tl % J.tilesN : tl / p.tilesM;
         g.m0 = tm * BM; g.n0 = g.tn * BN;
         // A job j = plane j / GA, row group j % GA; wave takes j = wave + 8 q.  Rows past M never occur (M % BM == 0).
         g.voffA = (unsigned)((g.m0 + drow) * 64 + chunk * 16);
@@ -203,7 +244,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
             const int nn = rv ? n : 0;
             int img, rem, hg, wg;
             pc_divmod(nn, HWg, rcpHW, img, rem);
-            pc_divmod(rem, p.Wg, rcpW, hg, wg);
+            pc_divmod(rem, J.Wg, rcpW, hg, wg);
             const int ih0 = hg * p.sg, iw0 = wg * p.sg;
             unsigned vm = 0;
             if constexpr (TS) {
@@ -216,7 +257,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
             } else {
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
-                    const unsigned f = (unsigned)(p.tapcode >> (4 * t)) & 15u;
+                    const unsigned f = (unsigned)(J.tapcode >> (4 * t)) & 15u;
                     const int ih = ih0 + (int)(f & 3u) - 1, iw = iw0 + (int)(f >> 2) - 1;
                     if (t < ntaps && rv && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)Wi) vm |= 1u << t;
                 }
@@ -232,7 +273,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
                 const int n = g.n0 + wn * (16 * FC) + 16 * c + li;
                 int img, rem, hg, wg;
                 pc_divmod(n, HWg, rcpHW, img, rem);
-                pc_divmod(rem, p.Wg, rcpW, hg, wg);
+                pc_divmod(rem, J.Wg, rcpW, hg, wg);
                 const unsigned bl = (unsigned)__builtin_amdgcn_ballot_w64(wg > 0) & 0xffffu;
                 const unsigned br = (unsigned)__builtin_amdgcn_ballot_w64(wg < p.Wg - 1) & 0xffffu;
                 g.mLR[c] = (unsigned)__builtin_amdgcn_readfirstlane((int)(bl | (br << 16)));
@@ -248,7 +289,12 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
             const int j = wave + 8 * q;
             if ((3 * GA) % 8 != 0 && j >= 3 * GA) break;
             const int plane = j / GA, gr = j % GA;
-            const unsigned so = (unsigned)(((s * 3 + plane) * p.M + 16 * gr) * 64);
+            unsigned so;
+            if constexpr (TS) so = (unsigned)(((s * 3 + plane) * p.M + 16 * gr) * 64);
+            else {
+                // the job's weight planes; from K-step k2 on those of its second part (wofs2 is relative to step 0)
+                so = (unsigned)(((s * 3 + plane) * p.M + 16 * gr) * 64) + (s >= g.k2 ? g.wofs2 : g.wofs);
+            }
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(size_t)(As + slot * SA + j * 1024), 16, g.voffA, so, 0, 0);
         }
     };
@@ -272,20 +318,24 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
             if (++g.it_b == 3) { g.it_b = 0; ++g.icc_b; }
             return;
         }
-        const unsigned f = (unsigned)(p.tapcode >> (4 * g.it_b)) & 15u;
+        const unsigned f = (unsigned)(g.tapcode >> (4 * g.it_b)) & 15u;
         const unsigned tapo = ((f & 3u) * (unsigned)Wi + (f >> 2)) * 64u;           // (dh + 1) * Wi + (dw + 1) pixels
+        // channel blocks from icc2 on come from the second tensor: a scalar compare picks the descriptor and the block inside it
+        const bool sec = g.icc_b >= g.icc2;
+        const int icb = g.icc_b - (sec ? g.icc2 : 0);
+        const __amdgpu_buffer_rsrc_t rs = sec ? rsB2 : rsB;
 #pragma unroll
         for (int i = 0; i < RGB; ++i) {
             if (GB % 8 != 0 && i >= ngrpB) break;
             const unsigned vo = ((g.vmask[i] >> g.it_b) & 1u) ? g.voffB[i] : OOB;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
-                const unsigned so = (unsigned)((size_t)(g.icc_b * 3 + pl) * p.xp_pix * 64) + tapo;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void*)(size_t)(Bs + slot * SB + (pl * GB + wave + 8 * i) * 1024), 16,
+                const unsigned so = (unsigned)((size_t)(icb * 3 + pl) * p.xp_pix * 64) + tapo;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(size_t)(Bs + slot * SB + (pl * GB + wave + 8 * i) * 1024), 16,
                                                          vo, so, 0, 0);
             }
         }
-        if (++g.it_b == ntaps) { g.it_b = 0; ++g.icc_b; }
+        if (++g.it_b == g.ntaps) { g.it_b = 0; ++g.icc_b; }
     };
     // the DMA a segment starts with: steps k0 (both operands) and k0 + 1 (A).  Issued for the NEXT segment before the current
     // one's fix-up / epilogue runs: a tile's pipeline fill hides behind its predecessor's stores (tiles of 2 - 18 K-steps --
@@ -551,8 +601,9 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
         // so it waits on the tile's counter (normally not at all), keeps its own part in registers and sums the parts in segment
         // order (the result does not depend on timing).  The others store their part and announce it AFTER the next segment's
         // pipeline fill has been waited for (the drain of the stores hides behind that wait).
+        const int nsteps = cur.nsteps;
         if (k0 != 0 || k1 != nsteps) {
-            const unsigned t0 = (unsigned)tile * (unsigned)nsteps;
+            const unsigned t0 = cur.tstart;
             const int b_first = (int)(t0 / (unsigned)S), b_last = (int)((t0 + (unsigned)nsteps - 1u) / (unsigned)S);
             if (rbk != b_first) {
                 float* mine = p.slab + (size_t)rbk * 2 * (BM * BN);
@@ -618,6 +669,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
         // ---- epilogue -------------------------------------------------------------
         // acc[r][c][q] = D[m = m0 + wm*16FR + 16r + 4*lg + q][n = n0 + wn*64 + 16c + li]
         const int mbase = m0 + wm * (16 * FR) + 4 * lg;
+        const JobV J = jobv(cur.jb);
         if (p.stats) {
             float* red = fsmem;            // [WN][BM][2]
 #pragma unroll
@@ -652,7 +704,7 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
                     u += red[(ww * BM + ch) * 2 + 0];
                     v += red[(ww * BM + ch) * 2 + 1];
                 }
-                float* st = p.stats + (size_t)(grp * p.tilesN + tn) * 2 * p.M;
+                float* st = p.stats + (size_t)(grp * J.tilesN + tn) * 2 * p.M;
                 st[m0 + ch] = u;
                 st[p.M + m0 + ch] = v;
             }
@@ -666,11 +718,11 @@ __global__ __launch_bounds__(512, PC_WAVES_PER_EU) void pconv_kernel(const Igemm
 #pragma unroll
         for (int c = 0; c < FC; ++c) {
             const int n = n0 + wn * (16 * FC) + 16 * c + li;
-            ok[c] = n < npix;
+            ok[c] = n < J.npix;
             int img, rem, hg, wg;
-            pc_divmod(ok[c] ? n : npix - 1, HWg, rcpHW, img, rem);          // (a pixel past the end reads the last one's, stores nothing)
-            pc_divmod(rem, p.Wg, rcpW, hg, wg);
-            opix[c] = (size_t)((grp * p.imgs_per_group + img) * p.Ho + hg * p.os + p.oh0) * p.Wo + (wg * p.os + p.ow0);
+            pc_divmod(ok[c] ? n : J.npix - 1, J.HWg, J.rcpHW, img, rem);    // (a pixel past the end reads the last one's, stores nothing)
+            pc_divmod(rem, J.Wg, J.rcpW, hg, wg);
+            opix[c] = (size_t)((grp * p.imgs_per_group + img) * p.Ho + hg * p.os + J.oh0) * p.Wo + (wg * p.os + J.ow0);
         }
 #pragma unroll
         for (int r = 0; r < FR; r += 2) {
@@ -836,7 +888,7 @@ bool pconv_takes(int M, int Ci, long long xp_pix, int Wi)
 // (forward convs and their data gradients alike)
 bool pconv_uses_ts(const IgemmParams& p)
 {
-    bool ts = p.ntaps == 9 && p.sg == 1 && p.Hg == p.Hi && p.Wg == p.Wi;
+    bool ts = p.njobs == 0 && p.ntaps == 9 && p.sg == 1 && p.Hg == p.Hi && p.Wg == p.Wi;
     for (int j = 0; ts && j < 3; ++j) {
         ts = p.dh[3 * j] == p.dh[3 * j + 1] && p.dh[3 * j] == p.dh[3 * j + 2];
         int seen = 0;
@@ -868,12 +920,36 @@ void launch_pconv(IgemmParams p, int groups, hipStream_t s)
         set_max_dyn_lds(reinterpret_cast<const void*>(&pconv_kernel<2, 4, 2, 9>), LDS_S, "pconv_kernel<2, 4, 2, 9>");
         attr_done = true;
     }
-    p.nsteps = p.ntaps * (p.Ci >> 5);
-    const long long T = (long long)p.tilesM * p.tilesN * groups;
-    p.total_steps = T * p.nsteps;
-    p.tapcode = 0;
-    for (int t = 0; t < p.ntaps; ++t)      // taps of 3x3 / 1x1 convs and of their dgrad parity classes lie in [-1, 1]
-        p.tapcode |= (unsigned long long)(((p.dh[t] + 1) & 3) | (((p.dw[t] + 1) & 3) << 2)) << (4 * t);
+    const bool ts = pconv_uses_ts(p);
+    p.tapcode = pconv_tapcode(p.dh, p.dw, p.ntaps);
+    if (p.njobs == 0) {        // one GEMM: the launch's own fields
+        p.njobs = 1;
+        PconvJob& j = p.job[0];
+        j.ntaps = p.ntaps; j.tapcode = p.tapcode;
+        j.cib = j.icc2 = p.Ci >> 5; j.wofs = j.wofs2 = 0;
+        j.Hg = p.Hg; j.Wg = p.Wg; j.oh0 = p.oh0; j.ow0 = p.ow0;
+    }
+    if (!p.Xp2) p.Xp2 = p.Xp;
+    // The jobs' (tile, K-step) spaces one behind the other.  What the launch decides once -- tile order, range quantization --
+    // it decides from the job with the most K-steps per tile: the largest weight slice.  (The grouped launches of the stride-2
+    // data gradients stay below both thresholds: at most 64 K-steps of 128 rows.)
+    long long T = 0;
+    p.total_steps = 0; p.nsteps = 0; p.wsp_bytes = 0;
+    for (int k = 0; k < p.njobs; ++k) {
+        PconvJob& j = p.job[k];
+        j.nsteps = j.ntaps * j.cib; j.k2 = j.ntaps * j.icc2;
+        j.npix = p.imgs_per_group * j.Hg * j.Wg;
+        j.rcpHW = 1.0f / (float)(j.Hg * j.Wg); j.rcpW = 1.0f / (float)j.Wg;
+        j.tilesN = (j.npix + 255) / 256;
+        j.tile0 = (int)T; j.step0 = (int)p.total_steps;
+        T += (long long)p.tilesM * j.tilesN * groups;
+        p.total_steps += (long long)p.tilesM * j.tilesN * groups * j.nsteps;
+        p.nsteps = std::max(p.nsteps, j.nsteps);
+        const long long step_bytes = 3LL * p.M * 64;
+        p.wsp_bytes = (unsigned)std::max<long long>(p.wsp_bytes, std::max(j.wofs + j.k2 * step_bytes, j.wofs2 + (j.nsteps - j.k2) * step_bytes));
+        j.wofs2 -= (unsigned)(j.k2 * step_bytes);      // relative to K-step 0 (mod 2^32: the kernel adds the step's own offset back)
+    }
+    for (int k = p.njobs; k < PCONV_MAX_JOBS; ++k) p.job[k].step0 = 0x7fffffff;
     // weights of one M-tile: BM rows x K x 6 B; beyond ~1 MB per M-tile the all-M-tiles working set no longer fits L2
     p.tn_fast = p.tilesM > 1 && (long long)p.M * p.nsteps * 192 > (3LL << 20);
     // persistent grid: every CU whenever there are >= 4 K-steps for each of them, otherwise one tile per block.
@@ -899,9 +975,6 @@ void launch_pconv(IgemmParams p, int groups, hipStream_t s)
         }
     }
     dim3 grid(nblk);
-    // tap-row sharing: 3x3, stride 1, the taps in three groups of one kernel row each whose column shifts cover -1, 0, +1
-    // (forward convs and their data gradients alike)
-    const bool ts = pconv_uses_ts(p);
     p.lose_part = g_lose_part ? 1 : 0;
     if (ts) {
         if (p.M >= 128) {

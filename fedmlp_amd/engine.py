@@ -512,6 +512,11 @@ class Engine:
         _lib.check(self.lib.fm_debug_conv(self.h, op, conv, _ptr(x), _ptr(dy), _ptr(out), imgs, groups,
                                           _ptr(stats)))
 
+    def debug_block_dgrad(self, block, dy1, dyd, dx, imgs):
+        """input gradient of stride-2 basic block `block` from the gradients of its conv1 / downsample outputs (fp32 NHWC)"""
+        self._enqueue()
+        _lib.check(self.lib.fm_debug_block_dgrad(self.h, block, _ptr(dy1), _ptr(dyd), _ptr(dx), imgs))
+
 
 class _CudaArrayView:
     """Minimal __cuda_array_interface__ carrier so torch can alias engine memory."""

@@ -29,6 +29,12 @@ int fm_debug_num_convs(fm_engine* e);
 int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, const float* dy_dev,
                   float* out_dev, int32_t imgs, int32_t groups, float* stats_dev);
 
+/* Input gradient of a stride-2 residual block of ResNet-18 (block = index of the basic block: 2, 4, 6), as backward_and_step
+ * runs it: dx[imgs,hin,win,cin] = dgrad(conv1; dy1) + dgrad(downsample; dyd), dy1 / dyd [imgs,hout,wout,cout] fp32 NHWC on
+ * device.  Planes mode: ONE grouped launch of the per-tap planes kernel (the planes of dy1 / dyd are made inside); every
+ * element of dx is written. */
+int fm_debug_block_dgrad(fm_engine* e, int32_t block, const float* dy1_dev, const float* dyd_dev, float* dx_dev, int32_t imgs);
+
 /* bf16 pointwise-convolution kernels of a precision-1 engine (conv must be a 1x1 convolution):
  * op 0: x bf16 [imgs,h,w,cin_p] -> out bf16 [imgs,h,w,cout_p] raw; stats_dev (optional) per-group (sum, sumsq)
  *       [groups][2][cout_p] fp32; gate_dev != NULL applies the operand prologue

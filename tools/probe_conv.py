@@ -17,6 +17,27 @@ flat, cnt = spec.init_state(model, 5, 1037)
 e.set_state(flat, cnt)
 if layers == [-1]:
     layers = list(range(e.debug_num_convs()))
+if ops == [3]:
+    # op 3: the grouped input gradient of the stride-2 blocks (one launch: four parity classes + the downsample's gradient);
+    # FLOPs = both convs' -- like for like with `op 1` of convs 5 + 7, 10 + 12, 15 + 17
+    for b, c1, ds in ((2, 5, 7), (4, 10, 12), (6, 15, 17)):
+        i1, i2 = e.debug_conv_info(c1), e.debug_conv_info(ds)
+        dy1 = torch.randn((imgs, i1["hout"], i1["wout"], i1["cout_p"]), device="cuda")
+        dyd = torch.randn_like(dy1)
+        dx = torch.empty((imgs, i1["hin"], i1["win"], i1["cin_p"]), device="cuda")
+        flops = 2.0 * i1["hout"] * i1["wout"] * i1["cout"] * i1["cin"] * (i1["k"] ** 2 + i2["k"] ** 2) * imgs
+        for _ in range(3):
+            e.debug_block_dgrad(b, dy1, dyd, dx, imgs)
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        n = 10
+        t0.record()
+        for _ in range(n):
+            e.debug_block_dgrad(b, dy1, dyd, dx, imgs)
+        t1.record(); torch.cuda.synchronize()
+        ms = t0.elapsed_time(t1) / n
+        print(f"block{b} grouped dgrad (convs {c1} + {ds}, two plane splits included): {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TF", flush=True)
+    sys.exit(0)
 for ci in layers:
     info = e.debug_conv_info(ci)
     x = torch.randn((imgs, info["hin"], info["win"], info["cin_p"]), device="cuda")
