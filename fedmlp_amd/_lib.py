@@ -68,6 +68,7 @@ SYMBOLS = {
     "fm_forward_train": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
     "fm_backward_step": (C.c_int, [_P, _P]),
     "fm_backward_grads": (C.c_int, [_P, _P, _P]),
+    "fm_backward_grads_x": (C.c_int, [_P, _P, _P, _P, _P]),
     "fm_forward_recompute": (C.c_int, [_P, _P, _P, _I32]),
     "fm_zero_grad": (C.c_int, [_P]),
     "fm_adam_step": (C.c_int, [_P, C.POINTER(FmAdam)]),

@@ -145,6 +145,11 @@ struct fm_engine {
     // null), the gradient accumulator (NP floats, allocated on first use; `gacc_full` false = empty, the next backward copies),
     // and bn_frozen: a recomputed forward (fm_forward_recompute) leaves running statistics and counters as they are
     const float* dfeat_dev = nullptr;
+    // ... and where it wants d loss / d image of the views written (fm_backward_grads_x; null = not wanted: no launch).  ResNet-18:
+    // the stem's weights as the data gradient's B matrix (stem_dgrad.hip), made on first use and again after the weights change
+    float* dx_out[2] = {nullptr, nullptr};
+    float* stem_dpack = nullptr;
+    bool stem_dpack_stale = true;
     float* gacc = nullptr;
     bool gacc_full = false;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
@@ -400,7 +405,7 @@ int build_tables(fm_engine* e)
         }
         int rc = upload_tab(e, t, &c.tab);
         if (rc) return rc;
-        if (c.cin == 3) continue;          // the stem needs no input gradient
+        if (c.cin == 3) continue;          // the stem's input gradient has its own kernels (stem_dgrad.hip)
         // data-gradient parity classes
         const int s = c.stride;
         for (int ph = 0; ph < s; ++ph)
@@ -1530,6 +1535,7 @@ void forward_eval(fm_engine* e, const float* S, float* evs, float* evh, bool& di
 void ensure_packed(fm_engine* e)
 {
     if (!e->wpack_dirty) return;
+    e->stem_dpack_stale = true;
     if (e->precision) launch_cast_weights(e->state, e->wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, e->st);
     else if (e->n_pack_jobs) k_pack_dgrad_all(e->state, e->pack_jobs, e->n_pack_jobs, e->n_pack_blocks, e->st);
     if (e->planes) {
@@ -1552,6 +1558,34 @@ void ensure_teacher_shadow(fm_engine* e)
     }
     else k_split_weights(e->tstate, e->twsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, e->st);
     e->twb_dirty = false;
+}
+
+// d loss / d image of `imgs` images from the gradient of the stem's raw output (stem_dgrad.hip): dy [imgs][hout][wout][cout_p] in
+// the engine's storage type, dx fp32 NCHW (NHWC through fm_debug_conv).  Written, not accumulated.
+int ensure_stem_dpack(fm_engine* e)
+{
+    if (e->model != 0) return FM_OK;
+    const Conv& c0 = e->convs[0];
+    if (!e->stem_dpack) { DALLOC(e->stem_dpack, stem_dgrad_pack_floats()); e->stem_dpack_stale = true; }
+    if (e->stem_dpack_stale) k_stem_dgrad_pack(e->state + c0.w_off, e->stem_dpack, c0.Kw, c0.kw_p, c0.cin_p, e->st);
+    e->stem_dpack_stale = false;
+    return FM_OK;
+}
+void stem_dgrad(fm_engine* e, const void* dy, float* dx, int imgs, bool nhwc)
+{
+    const Conv& c = e->convs[e->model == 1 ? e->c_stem : 0];
+    if (e->model == 1)
+        k_eff_stem_dgrad(dy, e->dt, e->state + c.w_off, dx, imgs, c.hin, c.win, c.hout, c.wout, c.pad, c.pad, c.Kw, c.kw_p, c.cin_p,
+                         nhwc, e->st);
+    else k_stem_dgrad((const float*)dy, e->stem_dpack, dx, imgs, c.hout, c.wout, c.hin, c.win, nhwc, e->st);
+}
+// the views' input gradients the pending backward was asked for (fm_backward_grads_x), from the stem's complete dy
+void stem_dgrad_views(fm_engine* e, const void* dy, int groups, int B)
+{
+    const Conv& c = e->convs[e->model == 1 ? e->c_stem : 0];
+    const size_t view_bytes = (size_t)B * c.hout * c.wout * c.cout_p * (e->dt == DT_BF16 ? 2 : 4);
+    for (int g = 0; g < groups && g < 2; ++g)
+        if (e->dx_out[g]) stem_dgrad(e, (const char*)dy + g * view_bytes, e->dx_out[g], B, false);
 }
 
 // optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2); g = e->grad (fused steps)
@@ -1659,6 +1693,7 @@ void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
                           e->grad + e->off_beta + b0.ch_off, e->st);
         k_stem_pool_bn_apply(ga, e->p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, e->st);
     }
+    stem_dgrad_views(e, e->dyh0, groups, B);
     conv_wgrad(e, 0, e->x4, e->dyh0, imgs);
     if (sw) {
         soft(e, hipEventRecord(e->ev_wdone, e->st2));
@@ -2017,6 +2052,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
     Conv& cs = e->convs[e->c_stem];
     e->ctx = 399;
     { OP("bnact_bwd"); bnact_bwd(e, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2); }
+    if (e->dx_out[0] || e->dx_out[1]) { OP("stem_dgrad"); stem_dgrad_views(e, go, groups, B); }
     { OP("conv_wgrad"); conv_wgrad(e, e->c_stem, e->x4, go, imgs); }
     if (sw) {                                    // every weight gradient is in G before the optimizer reads it
         soft(e, hipEventRecord(e->ev_wdone, e->st2));
@@ -2711,9 +2747,20 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
 
 int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev)
 {
+    return fm_backward_grads_x(e, dlogits_dev, dfeat_dev, nullptr, nullptr);
+}
+
+int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev, float* dx1_dev, float* dx2_dev)
+{
     ARGCHK(e, "null engine");
-    ARGCHK(e->pending_views > 0, "fm_backward_grads without a preceding fm_forward_train / fm_forward_recompute");
+    ARGCHK(e->pending_views > 0, "fm_backward_grads(_x) without a preceding fm_forward_train / fm_forward_recompute");
     const int views = e->pending_views, B = e->pending_B;
+    ARGCHK(views == 2 || !dx2_dev, "fm_backward_grads_x: dx2 given, but the pending forward has one view");
+    if (dx1_dev || dx2_dev) {                      // first use: the stem's weights as the data gradient's B matrix
+        const int rc = ensure_stem_dpack(e);
+        if (rc != FM_OK) return rc;
+    }
+    e->dx_out[0] = dx1_dev; e->dx_out[1] = dx2_dev;
     if (!e->gacc) DALLOC(e->gacc, e->NP);          // first use: fused-only users never pay for the accumulator
     const size_t nz = (size_t)views * B * e->C * 4;
     if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->st));
@@ -2721,6 +2768,7 @@ int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat
     e->dfeat_dev = dfeat_dev;
     net_backward_and_step(e, views, B, false);     // e->grad, every weight gradient joined to the main stream
     e->dfeat_dev = nullptr;
+    e->dx_out[0] = e->dx_out[1] = nullptr;
     k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->st, e->dev_err);
     e->pending_views = 0;
     STEP_DONE(e);
@@ -3099,9 +3147,13 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
             HIPCHK(hipMemcpy(stats_dev, o.data(), o.size() * 4, hipMemcpyHostToDevice));
         }
     } else if (op == 1) {
-        ARGCHK(dy_dev && c.ncls > 0, "dgrad unavailable for this conv");
+        ARGCHK(dy_dev && (c.ncls > 0 || c.cin == 3), "dgrad unavailable for this conv");
         ensure_packed(e);
-        conv_dgrad(e, conv, e->state, dy_dev, out_dev, imgs, nullptr, false);
+        if (c.cin == 3) {           // the stem: stem_dgrad.hip with its NHWC store, dx [imgs][hin][win][3]
+            const int rc = ensure_stem_dpack(e);
+            if (rc != FM_OK) return rc;
+            stem_dgrad(e, dy_dev, out_dev, imgs, true);
+        } else conv_dgrad(e, conv, e->state, dy_dev, out_dev, imgs, nullptr, false);
     } else if (op == 2) {
         ARGCHK(x_dev && dy_dev, "x/dy");
         conv_wgrad(e, conv, x_dev, dy_dev, imgs);

@@ -108,6 +108,15 @@ void k_stem_pool_bn_reduce(const float* dpooled, const float* pooled, const uint
 void k_stem_pool_bn_apply(const float* dpooled, const float* pooled, const uint8_t* idx, const float* y, const float* ca,
                           const float* cb, const float* cc, float* dy, int groups, int imgs_per_group, int H, int W, int C,
                           hipStream_t s);
+// stem_dgrad.hip: d loss / d image (autograd path only).  ResNet-18: dy [imgs][Ho][Wo][64] fp32 against the repacked stem weights
+// (k_stem_dgrad_pack: stem_dgrad_pack_floats() floats from the engine layout [64][Kw], k = (kh * kw_p + kw) * cin_p + ci);
+// EfficientNet-B0: dy [imgs][Ho][Wo][32] in storage type dt against the engine layout itself.  dx fp32 [imgs][3][H][W], or
+// [imgs][H][W][3] with nhwc_out (fm_debug_conv); every element is written, nothing is accumulated.
+size_t stem_dgrad_pack_floats();
+void k_stem_dgrad_pack(const float* w, float* pack, int Kw, int kw_p, int cin_p, hipStream_t s);
+void k_stem_dgrad(const float* dy, const float* pack, float* dx, int imgs, int Ho, int Wo, int H, int W, int nhwc_out, hipStream_t s);
+void k_eff_stem_dgrad(const void* dy, int dt, const float* w, float* dx, int imgs, int H, int W, int Ho, int Wo, int pad_t,
+                      int pad_l, int Kw, int kw_p, int cin_p, int nhwc_out, hipStream_t s);
 // backward: partial sums of dyh = dz*(z>0) and dyh*xhat -> part[groups][nblk][2][C]
 int bn_bwd_blocks(int pix_per_group);
 // ReLU mask of dz: z > 0 (z = stored post-activation), or, with z null and mask_scale / mask_shift given, y*scale+shift > 0

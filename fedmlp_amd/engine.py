@@ -286,7 +286,7 @@ class Engine:
         feat = torch.empty((views * B, self.feature_dim), device=self.device, dtype=torch.float32)
         logits = torch.empty((views * B, self.n_classes), device=self.device, dtype=torch.float32)
         _lib.check(self.lib.fm_forward_train(self.h, _ptr(x1), _ptr(x2), B, _ptr(feat), _ptr(logits)))
-        self._pending_rows = views * B
+        self._pending_rows, self._pending_B = views * B, B
         return feat, logits
 
     def backward_step(self, dlogits):
@@ -301,11 +301,13 @@ class Engine:
         self._check_stream()
         self._enqueue()
         _lib.check(self.lib.fm_forward_recompute(self.h, _ptr(x1), _ptr(x2), x1.shape[0]))
-        self._pending_rows = (1 if x2 is None else 2) * x1.shape[0]
+        self._pending_rows, self._pending_B = (1 if x2 is None else 2) * x1.shape[0], x1.shape[0]
 
-    def backward_grads(self, dlogits=None, dfeat=None):
+    def backward_grads(self, dlogits=None, dfeat=None, dx=None):
         """Backward of the pending forward_train / forward_recompute from d loss / d logits [views*B, C] and d loss / d feature
-        [views*B, D] (None = zero); the parameter gradients are added to the engine's accumulator, no optimizer step."""
+        [views*B, D] (None = zero); the parameter gradients are added to the engine's accumulator, no optimizer step.
+        dx: a contiguous fp32 device tensor shaped like x1 (or a pair, one per view, either entry None) that receives d loss /
+        d image of that view -- written, not accumulated (fm_backward_grads_x).  None: no input gradient is computed."""
         self._check_stream()
         self._enqueue()
         dz = None if dlogits is None else dlogits.detach().contiguous().float()
@@ -315,7 +317,19 @@ class Engine:
             raise ValueError(f"backward_grads: dlogits {tuple(dz.shape)}, the pending forward's logits are {(rows, self.n_classes)}")
         if df is not None and tuple(df.shape) != (rows, self.feature_dim):
             raise ValueError(f"backward_grads: dfeat {tuple(df.shape)}, the pending forward's feature is {(rows, self.feature_dim)}")
-        _lib.check(self.lib.fm_backward_grads(self.h, _ptr(dz), _ptr(df)))
+        if dx is None:
+            _lib.check(self.lib.fm_backward_grads(self.h, _ptr(dz), _ptr(df)))
+            return
+        dxs = list(dx) if isinstance(dx, (tuple, list)) else [dx]
+        dxs += [None] * (2 - len(dxs))
+        if len(dxs) != 2:
+            raise ValueError("backward_grads: dx is one tensor or a pair of tensors")
+        want = (getattr(self, "_pending_B", 0), 3, self.in_h, self.in_w)
+        for t in dxs:
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
+                                  or t.device.index != torch.cuda.current_device() or tuple(t.shape) != want):
+                raise ValueError(f"backward_grads: dx must be a contiguous fp32 {want} tensor on {self.device}")
+        _lib.check(self.lib.fm_backward_grads_x(self.h, _ptr(dz), _ptr(df), _ptr(dxs[0]), _ptr(dxs[1])))
 
     def zero_grad(self):
         _lib.check(self.lib.fm_zero_grad(self.h))

@@ -10,6 +10,11 @@ forward and returns outputs whose autograd node, on ``loss.backward()``, runs th
 engine's backward into a gradient accumulator (``fm_backward_grads``);
 ``fedmlp_amd.optim.Adam(net)`` steps the weights from it.  The weights are not
 torch tensors, so ``torch.optim.*(net.parameters())`` does not train a HipNet.
+The input is a differentiable argument: when ``x`` requires grad, the same
+backward also forms d loss / d x (``fm_backward_grads_x``: the stem's data
+gradient) and autograd accumulates it into ``x.grad`` -- FGSM / PGD, virtual
+adversarial training, input-gradient penalties, saliency.  An eval-mode call
+records no graph: there is no backward path for eval-mode BatchNorm.
 
 A HipNet is a light state container (host copy of the flat state).  The heavy
 part -- device weights, optimiser moments, activation workspaces -- lives in the
@@ -25,7 +30,8 @@ import torch
 from . import spec
 from .engine import get_engine
 
-# the train-mode call's autograd node needs one input that requires grad (x usually does not; d/dx is not computed)
+# the train-mode call's autograd node needs one input that requires grad, and x usually does not (when it does, the node also
+# returns d loss / d x)
 _ANCHOR = torch.zeros((), requires_grad=True)
 
 
@@ -34,10 +40,12 @@ class _TrainCall(torch.autograd.Function):
     backward into the engine's gradient accumulator when the loss is backpropagated.  The node keeps the input, the engine
     serial after its forward, the net's weights key and (EfficientNet-B0) its drop-connect / dropout draws: if anything
     was enqueued on the engine since (another net(x), an eval forward, a rebind), it re-binds the net, re-installs the
-    draws and recomputes the forward (fm_forward_recompute: bit-identical saved tensors, running statistics untouched)."""
+    draws and recomputes the forward (fm_forward_recompute: bit-identical saved tensors, running statistics untouched).
+    `xin` is the caller's x on the device, a differentiable argument; `x` its detached copy, what the engine reads (and reads
+    again on a recompute).  The input gradient is asked of the engine only when autograd wants it."""
 
     @staticmethod
-    def forward(ctx, anchor, net, eng, x, max_images):
+    def forward(ctx, anchor, xin, net, eng, x, max_images):
         feat, logits = eng.forward_train(x)
         net._mark_dirty()
         ctx.set_materialize_grads(False)
@@ -60,14 +68,18 @@ class _TrainCall(torch.autograd.Function):
         if ctx.draws is not None:
             prev = (getattr(eng, "_dc", None), getattr(eng, "_dr", None))
             eng.set_stochastic(*ctx.draws)
+        dx = torch.empty_like(ctx.x) if ctx.needs_input_grad[1] else None
         try:
             if eng is not ctx.eng or eng.serial != ctx.serial:
                 eng.forward_recompute(ctx.x)
-            eng.backward_grads(dlogits, dfeat)
+            if dx is None:
+                eng.backward_grads(dlogits, dfeat)
+            else:
+                eng.backward_grads(dlogits, dfeat, dx=dx)
         finally:
             if ctx.draws is not None:
                 eng.set_stochastic(*prev)
-        return None, None, None, None, None
+        return None, dx, None, None, None, None
 
 
 _MODEL_ALIASES = {"Resnet18": "Resnet18", "resnet18": "Resnet18", "Efficient_b0": "Efficient_b0"}
@@ -165,19 +177,21 @@ class HipNet:
         Eval mode: the eval-mode forward (utils/local_training.py:983, 1030, 1227; utils/evaluations.py:25).
         Train mode: one train-mode forward (its own BN batch statistics, one running-statistics update) whose outputs
         carry an autograd node: loss.backward() adds the parameter gradients to the engine's accumulator (grads(),
-        zero_grad(), fedmlp_amd.optim.Adam).  d/dx is not computed.  Under torch.no_grad() the train forward runs and
-        nothing is recorded.  The fused steps (LocalUpdate.train*, Engine.step_*) remain the fast path."""
+        zero_grad(), fedmlp_amd.optim.Adam) and, when x requires grad, d loss / d x to x.grad (fp32, the stem's data gradient;
+        nothing is computed for an x that does not).  Under torch.no_grad() the train forward runs and nothing is recorded.
+        An eval-mode call records no graph either way: eval-mode BatchNorm has no backward path in the engine, so x.grad stays
+        None.  The fused steps (LocalUpdate.train*, Engine.step_*) remain the fast path."""
         x = torch.as_tensor(x, dtype=torch.float32)
         max_images = max(self.default_max_images, x.shape[0])
         eng = self.bind(x.shape[2], x.shape[3], max_images)
-        x = x.to(eng.device).contiguous()
+        x = x.to(eng.device).contiguous()       # differentiable ops: a gradient flows back to the caller's tensor
         if not self.training:
             return eng.forward_eval(x)
         if not torch.is_grad_enabled():
             out = eng.forward_train(x)
             self._mark_dirty()
             return out
-        return _TrainCall.apply(_ANCHOR, self, eng, x.detach(), max_images)
+        return _TrainCall.apply(_ANCHOR, x, self, eng, x.detach(), max_images)
 
     forward = __call__
 

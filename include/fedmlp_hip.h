@@ -272,6 +272,12 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev);
  *   zero); the parameter gradients are ADDED to the accumulator (the first backward after
  *   fm_zero_grad copies them: the same bits as the fused path's gradients); no optimizer step.
  *   Clears the pending forward.
+ * fm_backward_grads_x: the same call plus d(loss)/d(image) of the pending forward's views: dx1_dev /
+ *   dx2_dev fp32 [B][3][H][W] like the images fm_forward_train took (NULL = that view's gradient is not
+ *   wanted; dx2_dev must be NULL after a one-view forward).  Each is WRITTEN, not added to, and is
+ *   complete when the call's work on the engine's stream is.  The parameter gradients are bit-identical
+ *   with and without it; without a dx pointer nothing is launched or allocated beyond
+ *   fm_backward_grads (which is this call with both NULL).  fp32-class arithmetic in either precision.
  * fm_forward_recompute: the train-mode forward again, so that its saved activations exist for a
  *   following fm_backward_grads (the engine is deterministic: bit-identical saved tensors); BN
  *   running statistics and num_batches_tracked are NOT updated, nothing is written out.
@@ -282,6 +288,7 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev);
  * fm_get_grads: the accumulator in state_dict order (conv weights OIHW; BN running statistics as
  *   zeros; fm_state_sizes' n_f32 floats) into a device buffer, enqueued without synchronising. */
 int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev);
+int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev, float* dx1_dev, float* dx2_dev);
 int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev, int32_t B);
 int fm_zero_grad(fm_engine* e);
 int fm_adam_step(fm_engine* e, const fm_adam* hp);

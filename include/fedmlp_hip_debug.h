@@ -23,7 +23,9 @@ int fm_debug_conv_info(fm_engine* e, int32_t conv, int32_t* info16);
 int fm_debug_num_convs(fm_engine* e);
 /* op 0: raw forward  x[imgs,hin,win,cin_p] -> out[imgs,hout,wout,cout]; if stats_dev
  *       != NULL also the per-group per-channel (sum, sumsq) [groups][2][cout]
- * op 1: data gradient dy[imgs,hout,wout,cout] -> out[imgs,hin,win,cin]
+ * op 1: data gradient dy[imgs,hout,wout,cout] -> out[imgs,hin,win,cin]; on the stem conv (cin = 3: conv 0 of ResNet-18,
+ *       the first conv of EfficientNet-B0, dy with cout_p channels) the input-gradient kernel of fm_backward_grads_x with its
+ *       NHWC store
  * op 2: weight gradient (x, dy) -> out[cout][Kw] (engine layout)
  * All tensors NHWC fp32 on device; weights are the engine's current state. */
 int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, const float* dy_dev,

@@ -3,7 +3,8 @@ fused fm_step_bce, ResNet-18 at bs 128 x 224^2 by default, measured alternately 
   fused      Engine.step_bce (forward + loss + backward + Adam in one call)
   one_view   one net(x) call, BCE with pos_weight in torch, backward into the accumulator, Adam
   two_views  net(x1), net(x2), one backward over both (the earlier call is recomputed), Adam
-Device events around `--steps` steps after `--warmup`, repeated `--reps` times alternating the three; prints one JSON line
+  one_view_dx  one_view with x.requires_grad: the backward also forms d loss / d x (the stem's data gradient) into x.grad
+Device events around `--steps` steps after `--warmup`, repeated `--reps` times alternating the arms; prints one JSON line
 (median and spread of the repetitions, ms per step)."""
 import argparse
 import json
@@ -66,7 +67,17 @@ def main():
         loss.backward()
         opt.step()
 
-    arms = {"fused": fused, "one_view": one_view, "two_views": two_views}
+    xg = x1.clone().requires_grad_(True)
+
+    def one_view_dx():
+        xg.grad = None
+        _, z = net(xg)
+        loss = crit(z, y) / (B * C)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+
+    arms = {"fused": fused, "one_view": one_view, "two_views": two_views, "one_view_dx": one_view_dx}
     times = {k: [] for k in arms}
     for fn in arms.values():
         for _ in range(a.warmup):
