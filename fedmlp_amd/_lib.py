@@ -73,6 +73,8 @@ SYMBOLS = {
     "fm_zero_grad": (C.c_int, [_P]),
     "fm_adam_step": (C.c_int, [_P, C.POINTER(FmAdam)]),
     "fm_get_grads": (C.c_int, [_P, _P]),
+    "fm_bn_freeze": (C.c_int, [_P, _I32]),
+    "fm_bn_frozen": (C.c_int, [_P]),
     "fm_teacher_axpby": (C.c_int, [_P, C.c_float, C.c_float]),
     "fm_teacher_swap": (C.c_int, [_P]),
     "fm_set_stochastic": (C.c_int, [_P, _P, _P]),

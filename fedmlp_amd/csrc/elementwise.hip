@@ -327,6 +327,10 @@ void k_augment(const uint8_t* cache, const int* idx, const int* params, float* o
 }
 
 // ------------------------------------------------------------ BN forward -------
+// FROZEN (k_bn_finalize_frozen): the statistics of every group are the running ones -- mean = run_mean, istd = 1 / sqrt(run_var
+// + eps) in double, rounded once like the batch form -- so no tile partial is read and run_mean / run_var are only read: `skip`
+// has nothing left to hold back
+template <bool FROZEN>
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, int groups, int tiles, int C, int count,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    float* __restrict__ run_mean, float* __restrict__ run_var,
@@ -340,6 +344,21 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, int groups, 
     const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const bool chv = blockIdx.x * 64 + cl < C;             // C need not be a multiple of 64
     const int ch = chv ? blockIdx.x * 64 + cl : C - 1;
+    if constexpr (FROZEN) {
+        if (sl == 0 && chv) {
+            const float mu = run_mean[ch];
+            const float is = (float)(1.0 / sqrt((double)run_var[ch] + (double)eps));
+            const float sc = gamma[ch] * is;
+            const float sh = beta[ch] - mu * sc;
+            for (int g = 0; g < groups; ++g) {
+                mean[g * C + ch] = mu;
+                istd[g * C + ch] = is;
+                scale[g * C + ch] = sc;
+                shift[g * C + ch] = sh;
+            }
+        }
+        return;
+    }
     for (int g = 0; g < groups; ++g) {
         double s1 = 0.0, s2 = 0.0;
         const float* st = stats + (size_t)g * tiles * 2 * C;
@@ -409,8 +428,16 @@ void k_bn_finalize(const float* stats, int groups, int tiles, int C, int count, 
         src = folded;
         tiles = 32;
     }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, src, groups, tiles, C, count, gamma,
+    hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3((C + 63) / 64), dim3(256), 0, s, src, groups, tiles, C, count, gamma,
                        beta, run_mean, run_var, mean, istd, scale, shift, eps, momentum, skip);
+}
+// frozen statistics: one launch, no fold of tile partials (there are none to read)
+void k_bn_finalize_frozen(int groups, int C, const float* gamma, const float* beta, const float* run_mean,
+                          const float* run_var, float* mean, float* istd, float* scale, float* shift, float eps,
+                          hipStream_t s, const int* skip)
+{
+    hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((C + 63) / 64), dim3(256), 0, s, nullptr, groups, 0, C, 0, gamma, beta,
+                       const_cast<float*>(run_mean), const_cast<float*>(run_var), mean, istd, scale, shift, eps, 0.f, skip);
 }
 
 __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -826,6 +853,9 @@ void k_bn_bwd_reduce(const float* dz, const float* z, const float* y, const floa
                        mask_scale, mask_shift, zh, (long long)groups * pix_per_group);
 }
 
+// FROZEN: the statistics are constants of the graph (running mean / variance), so dy = gamma istd dz: cb = cc = 0.  dgamma /
+// dbeta are the same two sums, taken against the running mean / istd (torch's eval-mode BatchNorm weight gradient).
+template <bool FROZEN>
 __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int groups, int nblk, int C, int count,
                                        const float* __restrict__ gamma, const float* __restrict__ mean,
                                        const float* __restrict__ istd, float* __restrict__ ca,
@@ -853,10 +883,10 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int group
             s2 = red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl];
             const float is = istd[g * C + ch], mu = mean[g * C + ch];
             const float a = gamma[ch] * is;
-            const float b = -a * is * (float)(s2 / (double)count);
+            const float b = FROZEN ? 0.f : -a * is * (float)(s2 / (double)count);
             ca[g * C + ch] = a;
             cb[g * C + ch] = b;
-            cc[g * C + ch] = -b * mu - a * (float)(s1 / (double)count);
+            cc[g * C + ch] = FROZEN ? 0.f : -b * mu - a * (float)(s1 / (double)count);
             dg += s2;
             db += s1;
         }
@@ -869,7 +899,7 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int group
 }
 void k_bn_bwd_finalize(const float* part, int groups, int nblk, int C, int count, const float* gamma,
                        const float* mean, const float* istd, float* ca, float* cb, float* cc, float* dgamma,
-                       float* dbeta, hipStream_t s)
+                       float* dbeta, hipStream_t s, bool frozen)
 {
     const float* src = part;
     if (nblk > 64) {      // fold the per-block partials with many blocks first (same kernel as the forward statistics)
@@ -878,8 +908,12 @@ void k_bn_bwd_finalize(const float* part, int groups, int nblk, int C, int count
         src = folded;
         nblk = 32;
     }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, src, groups, nblk, C, count, gamma,
-                       mean, istd, ca, cb, cc, dgamma, dbeta);
+    if (frozen)
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3((C + 63) / 64), dim3(256), 0, s, src, groups, nblk, C, count, gamma,
+                           mean, istd, ca, cb, cc, dgamma, dbeta);
+    else
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3((C + 63) / 64), dim3(256), 0, s, src, groups, nblk, C, count, gamma,
+                           mean, istd, ca, cb, cc, dgamma, dbeta);
 }
 
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ dz, const float* __restrict__ z,

@@ -143,7 +143,7 @@ struct fm_engine {
     int pending_views = 0, pending_B = 0;                 // fm_forward_train awaiting fm_backward_step
     // autograd path (fm_backward_grads / fm_adam_step): d loss / d feature of the backward being enqueued (caller-owned, or
     // null), the gradient accumulator (NP floats, allocated on first use; `gacc_full` false = empty, the next backward copies),
-    // and bn_frozen: a recomputed forward (fm_forward_recompute) leaves running statistics and counters as they are
+    // and bn_no_update: a recomputed forward (fm_forward_recompute) leaves running statistics and counters as they are
     const float* dfeat_dev = nullptr;
     // ... and where it wants d loss / d image of the views written (fm_backward_grads_x; null = not wanted: no launch).  ResNet-18:
     // the stem's weights as the data gradient's B matrix (stem_dgrad.hip), made on first use and again after the weights change
@@ -153,7 +153,11 @@ struct fm_engine {
     float* gacc = nullptr;
     bool gacc_full = false;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
-    bool bn_frozen = false;
+    bool bn_no_update = false;
+    // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read;
+    // `bn_fixed` is set while such a forward is enqueued (the finalizes take the running statistics), `pending_fixed` is the mode
+    // of the pending forward and `bwd_fixed` is set while ITS backward is enqueued.  The fused fm_step_* never set any of them.
+    bool bn_freeze = false, bn_fixed = false, pending_fixed = false, bwd_fixed = false;
     std::vector<int64_t> tcounters;                       // the teacher's num_batches_tracked
     std::vector<StateEntry> entries;
     int n_bn_ch = 0;
@@ -1368,13 +1372,22 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
     if (c.stem3) k_stem3_mask_grad(e->grad + c.w_off, c.cout_p, e->st);
 }
 
+// frozen statistics: mean / istd / scale / shift of every group from the running statistics, which stay as they are
+void bn_fwd_fixed(fm_engine* e, Bn& b, int groups)
+{
+    k_bn_finalize_frozen(groups, b.C, e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
+                         e->state + e->off_rm + b.ch_off, e->state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale, b.shift,
+                         e->bn_eps, e->st, e->dev_err);
+}
+
 // BN statistics of conv `ci`'s output (partials left in ws_stats by the conv epilogue)
 void bn_fwd_finalize(fm_engine* e, int ci, int groups, int imgs_per_group)
 {
     const Conv& c = e->convs[ci];
     const int bi = c.bn;
     Bn& b = e->bns[bi];
-    const bool run = !e->bn_frozen;
+    if (e->bn_fixed) { bn_fwd_fixed(e, b, groups); return; }
+    const bool run = !e->bn_no_update;
     k_bn_finalize(e->ws_stats, groups, stats_tiles(e, ci, imgs_per_group, groups), b.C, imgs_per_group * c.hout * c.wout,
                   e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
                   run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
@@ -1400,7 +1413,7 @@ void bn_bwd(fm_engine* e, int bi, const float* dz, const float* z, float* dy, fl
     k_bn_bwd_reduce(dz, z, c.y, b.mean, b.istd, e->ws_part, groups, pix, b.C, e->st, msc, msh, zh);
     k_bn_bwd_finalize(e->ws_part, groups, bn_bwd_blocks(pix), b.C, pix, e->state + e->off_gamma + b.ch_off, b.mean,
                       b.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b.ch_off,
-                      e->grad + e->off_beta + b.ch_off, e->st);
+                      e->grad + e->off_beta + b.ch_off, e->st, e->bwd_fixed);
     if (dyp) k_bn_bwd_apply_planes(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyp, dyh_out, groups, pix, b.C, e->st, msc, msh, zh);
     else k_bn_bwd_apply(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyh_out, groups, pix, b.C, e->st, msc, msh);
 }
@@ -1483,7 +1496,7 @@ void forward_train(fm_engine* e, int groups, int B)
     const Conv& cl = e->convs[e->blocks.back().c2];
     k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, e->st);
     k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, e->st);
-    e->ev_dirty = true;      // running stats moved
+    if (!e->bn_fixed) e->ev_dirty = true;      // running stats moved
 }
 
 // eval-mode forward (BN folded into the conv epilogue) of `imgs` images in e->x4
@@ -1690,7 +1703,7 @@ void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
                               e->state + e->off_gamma + b0.ch_off, e->state + e->off_beta + b0.ch_off);
         k_bn_bwd_finalize(e->ws_part, groups, stem_pool_bn_blocks(pooled_pg), 64, pix, e->state + e->off_gamma + b0.ch_off,
                           b0.mean, b0.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b0.ch_off,
-                          e->grad + e->off_beta + b0.ch_off, e->st);
+                          e->grad + e->off_beta + b0.ch_off, e->st, e->bwd_fixed);
         k_stem_pool_bn_apply(ga, e->p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, e->st);
     }
     stem_dgrad_views(e, e->dyh0, groups, B);
@@ -1719,10 +1732,11 @@ bool fuse_for(fm_engine* e, const MBConv& m)
 void bn_fwd_tensor(fm_engine* e, int bi, const float* y, int groups, int pix_per_group, int HW, bool sums_ready = false)
 {
     Bn& b = e->bns[bi];
+    if (e->bn_fixed) { bn_fwd_fixed(e, b, groups); return; }       // (no statistics pass either)
     if (!sums_ready)
         k_chan_reduce(nullptr, e->dt, y, e->dt, nullptr, nullptr, nullptr, nullptr, nullptr, e->ws_part, groups, pix_per_group,
                       HW, b.C, 0, 0, nullptr, nullptr, e->st);
-    const bool run = !e->bn_frozen;
+    const bool run = !e->bn_no_update;
     k_bn_finalize(e->ws_part, groups, sums_ready ? dw_stats_tiles() : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
                   e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
                   run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
@@ -1743,7 +1757,7 @@ void bnact_bwd(fm_engine* e, int bi, const float* dz, const float* y, float* dy,
                       1, act, gate, dsv, e->st);
     k_bn_bwd_finalize(e->ws_part, groups, sums_ready ? sums_ready : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
                       e->state + e->off_gamma + b.ch_off, b.mean, b.istd, e->ca, e->cb, e->cc,
-                      e->grad + e->off_gamma + b.ch_off, e->grad + e->off_beta + b.ch_off, e->st);
+                      e->grad + e->off_gamma + b.ch_off, e->grad + e->off_beta + b.ch_off, e->st, e->bwd_fixed);
     k_bnact_bwd_apply(dz, e->dt, y, ty, e->ca, e->cb, e->cc, b.scale, b.shift, rowscale, dy, groups, pix_per_group, HW,
                       b.C, act, gate, dsv, e->st);
 }
@@ -1817,7 +1831,7 @@ void eff_forward_train(fm_engine* e, int groups, int B)
         h = e->hfeat;
     }
     { OP("k_fc_fwd"); k_fc_fwd(h, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, e->D, e->C, e->st); }
-    e->ev_dirty = true;
+    if (!e->bn_fixed) e->ev_dirty = true;
 }
 
 void eff_forward_eval(fm_engine* e, const float* S, float* evs, float* evh, bool& dirty, int imgs, float* feat,
@@ -1958,7 +1972,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
                 { OP("proj_bwd_apply");
                   k_bn_bwd_finalize(e->ws_part, groups, se_bwd_bn1_splits(B), b1.C, B * HWo, e->state + e->off_gamma + b1.ch_off, b1.mean,
                                     b1.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b1.ch_off, e->grad + e->off_beta + b1.ch_off,
-                                    e->st);
+                                    e->st, e->bwd_fixed);
                   if (launch(1) != 1) soft(e, hipErrorInvalidValue); }      // d y_d
                 pfused = true;
             }
@@ -2011,7 +2025,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
                                   HWi, b0.C, 1, 2, nullptr, nullptr, e->st);
                 k_bn_bwd_finalize(e->ws_part, groups, sums ? dw_stats_tiles() : bn_bwd_blocks(pix), b0.C, pix,
                                   e->state + e->off_gamma + b0.ch_off, b0.mean, b0.istd, e->ca, e->cb, e->cc,
-                                  e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, e->st);
+                                  e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, e->st, e->bwd_fixed);
                 int sk;
                 if (e->precision) {
                     PwExpBwdParams q{};
@@ -2064,13 +2078,16 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
 // model dispatch
 // update_running false (fm_forward_recompute): the same launches and saved tensors, BN running statistics and
 // num_batches_tracked counters left as they are
-void net_forward_train(fm_engine* e, int groups, int B, bool update_running = true)
+// fixed_stats (fm_forward_train / fm_forward_recompute under fm_bn_freeze): every BatchNorm applies its running statistics
+void net_forward_train(fm_engine* e, int groups, int B, bool update_running = true, bool fixed_stats = false)
 {
     ensure_packed(e);
-    e->bn_frozen = !update_running;
+    e->bn_no_update = !update_running;
+    e->bn_fixed = fixed_stats;
     if (e->model == 1) eff_forward_train(e, groups, B);
     else forward_train(e, groups, B);
-    e->bn_frozen = false;
+    e->bn_no_update = false;
+    e->bn_fixed = false;
 }
 void net_forward_eval(fm_engine* e, bool teacher, int imgs)
 {
@@ -2119,11 +2136,14 @@ int teacher_forward_side(fm_engine* e, int imgs)
     HIPCHK(hipEventRecord(e->ev_t, e->st2));
     return FM_OK;
 }
-void net_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
+// fixed_stats: the backward of a forward that ran on frozen statistics (every BatchNorm-backward finalize takes its frozen form)
+void net_backward_and_step(fm_engine* e, int groups, int B, bool step = true, bool fixed_stats = false)
 {
     ensure_packed(e);
+    e->bwd_fixed = fixed_stats;
     if (e->model == 1) eff_backward_and_step(e, groups, B, step);
     else backward_and_step(e, groups, B, step);
+    e->bwd_fixed = false;
 }
 
 // an engine-layout gradient arena (e->grad or the accumulator) -> dst in state_dict order (conv weights OIHW, BN running
@@ -2723,14 +2743,26 @@ int fm_forward_train(fm_engine* e, const float* x1_dev, const float* x2_dev, int
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
     const float* xs[2] = {x1_dev, x2_dev};
     to_nhwc4(e, xs, views, B);
-    net_forward_train(e, views, B);
+    net_forward_train(e, views, B, true, e->bn_freeze);
     if (feat_dev)
         HIPCHK(hipMemcpyAsync(feat_dev, e->feat, (size_t)views * B * e->D * 4, hipMemcpyDeviceToDevice, e->st));
     if (logits_dev)
         HIPCHK(hipMemcpyAsync(logits_dev, e->logits, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->st));
-    e->pending_views = views; e->pending_B = B;
+    e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
     STEP_DONE(e);
     return FM_OK;
+}
+
+int fm_bn_freeze(fm_engine* e, int32_t on)
+{
+    ARGCHK(e, "null engine");
+    e->bn_freeze = on != 0;
+    return FM_OK;
+}
+
+int fm_bn_frozen(fm_engine* e)
+{
+    return e && e->bn_freeze ? 1 : 0;
 }
 
 int fm_backward_step(fm_engine* e, const float* dlogits_dev)
@@ -2739,7 +2771,7 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
     ARGCHK(e->pending_views > 0, "fm_backward_step without a preceding fm_forward_train");
     const int views = e->pending_views, B = e->pending_B;
     HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->st));
-    net_backward_and_step(e, views, B);
+    net_backward_and_step(e, views, B, true, e->pending_fixed);
     e->pending_views = 0;
     STEP_DONE(e);
     return FM_OK;
@@ -2766,7 +2798,7 @@ int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfe
     if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->st));
     else HIPCHK(hipMemsetAsync(e->dlogits, 0, nz, e->st));
     e->dfeat_dev = dfeat_dev;
-    net_backward_and_step(e, views, B, false);     // e->grad, every weight gradient joined to the main stream
+    net_backward_and_step(e, views, B, false, e->pending_fixed);     // e->grad, every weight gradient joined to the main stream
     e->dfeat_dev = nullptr;
     e->dx_out[0] = e->dx_out[1] = nullptr;
     k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->st, e->dev_err);
@@ -2783,8 +2815,8 @@ int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev,
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
     const float* xs[2] = {x1_dev, x2_dev};
     to_nhwc4(e, xs, views, B);
-    net_forward_train(e, views, B, false);
-    e->pending_views = views; e->pending_B = B;
+    net_forward_train(e, views, B, false, e->bn_freeze);
+    e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
     STEP_DONE(e);
     return FM_OK;
 }

@@ -83,6 +83,11 @@ void k_bn_finalize(const float* stats, int groups, int tiles, int C, int count,
                    const float* gamma, const float* beta, float* run_mean, float* run_var,
                    float* mean, float* istd, float* scale, float* shift, float eps, float momentum,
                    hipStream_t s, const int* skip = nullptr);    // *skip != 0 or run_mean null: the running statistics are not updated
+// frozen statistics (fm_bn_freeze): every group gets mean = run_mean, istd = 1 / sqrt(run_var + eps), scale = gamma istd,
+// shift = beta - mean scale.  Reads no partials, writes no running statistics (so `skip` has nothing to hold back); one launch.
+void k_bn_finalize_frozen(int groups, int C, const float* gamma, const float* beta, const float* run_mean,
+                          const float* run_var, float* mean, float* istd, float* scale, float* shift, float eps,
+                          hipStream_t s, const int* skip = nullptr);
 // eval-mode folded affine for all BN channels at once
 void k_bn_eval_affine(const float* gamma, const float* beta, const float* run_mean, const float* run_var,
                       float* scale, float* shift, int n, float eps, hipStream_t s);
@@ -125,9 +130,11 @@ void k_bn_bwd_reduce(const float* dz, const float* z, const float* y, const floa
                      float* part, int groups, int pix_per_group, int C, hipStream_t s,
                      const float* mask_scale = nullptr, const float* mask_shift = nullptr, const unsigned short* zh = nullptr);
 // coefficients ca,cb,cc [groups][C]; dgamma/dbeta written (summed over groups)
+// frozen: mean / istd are the running statistics the forward applied, constants of the graph: ca = gamma istd, cb = cc = 0
+// (dgamma / dbeta are the same sums)
 void k_bn_bwd_finalize(const float* part, int groups, int nblk, int C, int count, const float* gamma,
                        const float* mean, const float* istd, float* ca, float* cb, float* cc,
-                       float* dgamma, float* dbeta, hipStream_t s);
+                       float* dgamma, float* dbeta, hipStream_t s, bool frozen = false);
 // dy = ca*dyh + cb*y + cc ; optionally store dyh
 void k_bn_bwd_apply(const float* dz, const float* z, const float* y, const float* ca, const float* cb,
                     const float* cc, float* dy, float* dyh_out, int groups, int pix_per_group, int C,

@@ -334,6 +334,16 @@ class Engine:
     def zero_grad(self):
         _lib.check(self.lib.fm_zero_grad(self.h))
 
+    def bn_freeze(self, on=True):
+        """Frozen BatchNorm statistics for the NEXT forward_train / forward_recompute (kept until changed): every BatchNorm
+        applies its running statistics, which -- like the num_batches_tracked counters -- stay as they are.  A backward runs
+        in the mode of the forward it belongs to, whatever the flag is by then.  The fused step_* ignore the flag."""
+        _lib.check(self.lib.fm_bn_freeze(self.h, int(bool(on))))
+
+    @property
+    def bn_frozen(self):
+        return bool(self.lib.fm_bn_frozen(self.h))
+
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         """torch.optim.Adam (coupled L2) over the accumulator with the engine's moments (adam_reset zeroes them)."""
         self._check_stream()

@@ -13,8 +13,14 @@ torch tensors, so ``torch.optim.*(net.parameters())`` does not train a HipNet.
 The input is a differentiable argument: when ``x`` requires grad, the same
 backward also forms d loss / d x (``fm_backward_grads_x``: the stem's data
 gradient) and autograd accumulates it into ``x.grad`` -- FGSM / PGD, virtual
-adversarial training, input-gradient penalties, saliency.  An eval-mode call
-records no graph: there is no backward path for eval-mode BatchNorm.
+adversarial training, input-gradient penalties, saliency.  ``net.freeze_bn()``
+makes the train-mode call apply the BatchNorm RUNNING statistics and leave them
+untouched (torch: ``m.eval()`` on every BatchNorm2d of a train-mode net): no
+image's output or gradient depends on the rest of the batch -- fine-tuning a
+checkpoint with small batches, saliency / FGSM / PGD on a trained model.  An
+eval-mode call records no graph (the BN-folded eval forward has no backward);
+``net.train().freeze_bn()`` with no drop-connect / dropout draws installed is
+eval-mode arithmetic with a graph.
 
 A HipNet is a light state container (host copy of the flat state).  The heavy
 part -- device weights, optimiser moments, activation workspaces -- lives in the
@@ -36,18 +42,19 @@ _ANCHOR = torch.zeros((), requires_grad=True)
 
 
 class _TrainCall(torch.autograd.Function):
-    """One train-mode net(x): the engine's forward now (own BN batch statistics, one running-statistics update), its
-    backward into the engine's gradient accumulator when the loss is backpropagated.  The node keeps the input, the engine
-    serial after its forward, the net's weights key and (EfficientNet-B0) its drop-connect / dropout draws: if anything
-    was enqueued on the engine since (another net(x), an eval forward, a rebind), it re-binds the net, re-installs the
-    draws and recomputes the forward (fm_forward_recompute: bit-identical saved tensors, running statistics untouched).
+    """One train-mode net(x): the engine's forward now (own BN batch statistics and one running-statistics update, or --
+    net.freeze_bn() -- the running statistics, left as they are), its backward into the engine's gradient accumulator when
+    the loss is backpropagated.  The node keeps the input, the engine serial after its forward, the net's weights key, its
+    BatchNorm mode and (EfficientNet-B0) its drop-connect / dropout draws: if anything was enqueued on the engine since
+    (another net(x), an eval forward, a rebind), it re-binds the net, re-installs the mode and the draws and recomputes the
+    forward (fm_forward_recompute: bit-identical saved tensors, running statistics untouched), then restores the caller's.
     `xin` is the caller's x on the device, a differentiable argument; `x` its detached copy, what the engine reads (and reads
     again on a recompute).  The input gradient is asked of the engine only when autograd wants it."""
 
     @staticmethod
     def forward(ctx, anchor, xin, net, eng, x, max_images):
-        feat, logits = eng.forward_train(x)
-        net._mark_dirty()
+        feat, logits = net._forward_train(eng, x)
+        ctx.frozen, ctx.stats_ver = net.bn_frozen, net._stats_ver
         ctx.set_materialize_grads(False)
         ctx.net, ctx.eng, ctx.x, ctx.max_images = net, eng, x, max_images
         ctx.serial, ctx.key = eng.serial, net._weights_key()
@@ -61,6 +68,9 @@ class _TrainCall(torch.autograd.Function):
         if net._weights_key() != ctx.key:
             raise RuntimeError("HipNet: the net's weights changed between its train-mode forward and this backward (an "
                                "optimizer step, load_state_dict or FedAvg); run the forward again")
+        if ctx.frozen and net._stats_ver != ctx.stats_ver:
+            raise RuntimeError("HipNet: a batch-statistics train-mode call moved the BatchNorm running statistics between this "
+                               "frozen-BatchNorm forward and its backward; run the forward again")
         eng = net.bind(ctx.x.shape[2], ctx.x.shape[3], ctx.max_images)
         if getattr(eng, "_grad_owner", None) is not net:     # the accumulator holds another net's gradients
             eng.zero_grad()
@@ -71,7 +81,14 @@ class _TrainCall(torch.autograd.Function):
         dx = torch.empty_like(ctx.x) if ctx.needs_input_grad[1] else None
         try:
             if eng is not ctx.eng or eng.serial != ctx.serial:
-                eng.forward_recompute(ctx.x)
+                was = bool(getattr(eng, "bn_frozen", False))
+                if was != ctx.frozen:
+                    eng.bn_freeze(ctx.frozen)
+                try:
+                    eng.forward_recompute(ctx.x)
+                finally:
+                    if was != ctx.frozen:
+                        eng.bn_freeze(was)
             if dx is None:
                 eng.backward_grads(dlogits, dfeat)
             else:
@@ -109,6 +126,8 @@ class HipNet:
         self._engine = None            # engine on which (self, _version) is resident
         self.default_max_images = 128
         self.precision = "fp32"        # activation storage of the engine this net binds to
+        self.bn_frozen = False         # freeze_bn(): train-mode calls apply the BatchNorm running statistics
+        self._stats_ver = 0            # bumped by every call that moves the running statistics alone (a batch-statistics net(x))
 
     # ---- nn.Module-like surface ----------------------------------------------------------
     def train(self, mode=True):
@@ -117,6 +136,14 @@ class HipNet:
 
     def eval(self):
         return self.train(False)
+
+    def freeze_bn(self, mode=True):
+        """Train-mode calls apply every BatchNorm's running statistics and leave them (and num_batches_tracked) as they are,
+        forward and backward -- torch's `for m in net.modules(): if isinstance(m, BatchNorm2d): m.eval()`.  Everything else
+        stays in train mode (EfficientNet-B0's drop-connect / dropout draws apply as installed).  Eval-mode calls and the fused
+        steps (LocalUpdate.train*, Engine.step_*) are not affected."""
+        self.bn_frozen = bool(mode)
+        return self
 
     def to(self, *a, **k):
         return self
@@ -170,17 +197,18 @@ class HipNet:
         c.training = self.training
         c.default_max_images = self.default_max_images
         c.precision = self.precision
+        c.bn_frozen = self.bn_frozen
         return c
 
     def __call__(self, x):
         """net(x) on the HIP engine -> (feature[B,D], logits[B,C]) CUDA tensors.
         Eval mode: the eval-mode forward (utils/local_training.py:983, 1030, 1227; utils/evaluations.py:25).
-        Train mode: one train-mode forward (its own BN batch statistics, one running-statistics update) whose outputs
-        carry an autograd node: loss.backward() adds the parameter gradients to the engine's accumulator (grads(),
+        Train mode: one train-mode forward (its own BN batch statistics and one running-statistics update; after freeze_bn()
+        the running statistics, which then stay as they are) whose outputs carry an autograd node: loss.backward() adds the parameter gradients to the engine's accumulator (grads(),
         zero_grad(), fedmlp_amd.optim.Adam) and, when x requires grad, d loss / d x to x.grad (fp32, the stem's data gradient;
         nothing is computed for an x that does not).  Under torch.no_grad() the train forward runs and nothing is recorded.
-        An eval-mode call records no graph either way: eval-mode BatchNorm has no backward path in the engine, so x.grad stays
-        None.  The fused steps (LocalUpdate.train*, Engine.step_*) remain the fast path."""
+        An eval-mode call records no graph either way, so x.grad stays None: for eval-mode arithmetic with a graph use
+        net.train().freeze_bn() (and install no drop-connect / dropout draws).  The fused steps (LocalUpdate.train*, Engine.step_*) remain the fast path."""
         x = torch.as_tensor(x, dtype=torch.float32)
         max_images = max(self.default_max_images, x.shape[0])
         eng = self.bind(x.shape[2], x.shape[3], max_images)
@@ -188,12 +216,26 @@ class HipNet:
         if not self.training:
             return eng.forward_eval(x)
         if not torch.is_grad_enabled():
-            out = eng.forward_train(x)
-            self._mark_dirty()
-            return out
+            return self._forward_train(eng, x)
         return _TrainCall.apply(_ANCHOR, x, self, eng, x.detach(), max_images)
 
     forward = __call__
+
+    def _forward_train(self, eng, x):
+        """The engine's train-mode forward in this net's BatchNorm mode: the engine's flag is set before it and handed back as
+        the caller left it (the engine remembers the mode of its pending forward, so the backward needs no flag)."""
+        was = bool(getattr(eng, "bn_frozen", False))
+        if was != self.bn_frozen:
+            eng.bn_freeze(self.bn_frozen)
+        try:
+            out = eng.forward_train(x)
+        finally:
+            if was != self.bn_frozen:
+                eng.bn_freeze(was)
+        if not self.bn_frozen:
+            self._stats_ver += 1
+            self._mark_dirty()             # the running statistics moved
+        return out
 
     # ---- gradients of the train-mode calls (the engine's accumulator) ---------------------------
     def zero_grad(self, set_to_none=True):
@@ -282,6 +324,8 @@ class ResidentNet(HipNet):
         self._engine = engine
         self.default_max_images = engine.max_images
         self.precision = engine.precision
+        self.bn_frozen = False
+        self._stats_ver = 0
         self.resident = True
 
     def bind(self, in_h, in_w, max_images, device=None):

@@ -286,7 +286,18 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev);
  *   count (fm_adam_reset zeroes them); hp is read on every call.  An empty accumulator is skipped
  *   like torch skips parameters whose .grad is None.
  * fm_get_grads: the accumulator in state_dict order (conv weights OIHW; BN running statistics as
- *   zeros; fm_state_sizes' n_f32 floats) into a device buffer, enqueued without synchronising. */
+ *   zeros; fm_state_sizes' n_f32 floats) into a device buffer, enqueued without synchronising.
+ * fm_bn_freeze: a handle flag (default 0) that fm_forward_train and fm_forward_recompute read.  While it is set
+ *   every BatchNorm of those forwards applies its RUNNING statistics (mean = running_mean, istd =
+ *   1/sqrt(running_var + eps)) instead of the batch's: running_mean / running_var and num_batches_tracked are
+ *   not touched, and no image's output depends on the rest of the batch.  The pending forward remembers the
+ *   mode it ran in: fm_backward_grads(_x) / fm_backward_step run the matching backward (dy = gamma istd dz
+ *   through every BatchNorm; dgamma / dbeta against the running statistics, torch's eval-mode BatchNorm
+ *   gradients) whatever the flag is by then.  Drop-connect / dropout multipliers apply as installed: freezing
+ *   BatchNorm is not eval mode.  The fused fm_step_* ignore the flag: they always use batch statistics.
+ * fm_bn_frozen: the flag (0 / 1). */
+int fm_bn_freeze(fm_engine* e, int32_t on);
+int fm_bn_frozen(fm_engine* e);
 int fm_backward_grads(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev);
 int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfeat_dev, float* dx1_dev, float* dx2_dev);
 int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev, int32_t B);

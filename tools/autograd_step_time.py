@@ -4,6 +4,7 @@ fused fm_step_bce, ResNet-18 at bs 128 x 224^2 by default, measured alternately 
   one_view   one net(x) call, BCE with pos_weight in torch, backward into the accumulator, Adam
   two_views  net(x1), net(x2), one backward over both (the earlier call is recomputed), Adam
   one_view_dx  one_view with x.requires_grad: the backward also forms d loss / d x (the stem's data gradient) into x.grad
+  one_view_frozen  one_view after net.freeze_bn(): every BatchNorm applies its running statistics, forward and backward
 Device events around `--steps` steps after `--warmup`, repeated `--reps` times alternating the arms; prints one JSON line
 (median and spread of the repetitions, ms per step)."""
 import argparse
@@ -77,7 +78,15 @@ def main():
         loss.backward()
         opt.step()
 
-    arms = {"fused": fused, "one_view": one_view, "two_views": two_views, "one_view_dx": one_view_dx}
+    def one_view_frozen():
+        net.freeze_bn(True)
+        try:
+            one_view()
+        finally:
+            net.freeze_bn(False)
+
+    arms = {"fused": fused, "one_view": one_view, "two_views": two_views, "one_view_dx": one_view_dx,
+            "one_view_frozen": one_view_frozen}
     times = {k: [] for k in arms}
     for fn in arms.values():
         for _ in range(a.warmup):
