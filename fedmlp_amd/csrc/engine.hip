@@ -73,8 +73,8 @@ struct Conv {
     int ncls = 0;
     DgradClass cls[4];
     int bn;                   // index of the BatchNorm that follows
-    long long sp_off = -1;    // bf16 planes of the forward weights inside fm_engine::wsp_f / twsp_f (2-byte units), -1 = none
-    long long bm_off = -1;    // block-major planes of the forward weights inside fm_engine::wbm_f / twbm_f (pconv.hip), -1 = none
+    long long sp_off = -1;    // bf16 planes of the forward weights inside Weights::wsp_f (2-byte units), -1 = none
+    long long bm_off = -1;    // block-major planes of the forward weights inside Weights::wbm_f (pconv.hip), -1 = none
     long long wb_off = -1, wbt_off = -1;   // bf16 shadow of a 1x1 conv's weights [cout_p][cin_p] / transposed (bf16 mode)
     double macs_per_img;      // algorithmic MACs (real k, real cin)
     float* y = nullptr;       // raw conv output (train) [max_images][hout][wout][cout]
@@ -87,14 +87,7 @@ struct Bn {
     float *mean, *istd, *scale, *shift;   // [2][C] train-mode per-group
 };
 
-struct Block {
-    int c1, c2, ds;
-    float* z1 = nullptr;
-    float* out = nullptr;
-    float *t_z1 = nullptr, *t_out = nullptr, *t_dsy = nullptr;     // the side-stream teacher's set (see fm_engine::st2)
-    // planes mode: block-major bf16 planes of z1 / out (what the conv GEMMs read), and the teacher's set
-    unsigned short *z1p = nullptr, *outp = nullptr, *t_z1p = nullptr, *t_outp = nullptr;
-};
+struct Block { int c1, c2, ds; };      // ResNet basic block: conv indices (ds = -1: no downsample)
 
 struct MBConv {               // EfficientNet block (efficientnet-pytorch MBConvBlock)
     int k, s, expand, cin, cout, cin_p, ce, ce_p, cout_p, cs;
@@ -103,11 +96,60 @@ struct MBConv {               // EfficientNet block (efficientnet-pytorch MBConv
     int c_exp = -1, c_proj = -1;          // 1x1 conv indices
     int bn0 = -1, bn1 = -1, bn2 = -1;
     size_t dw_off, w1_off, b1_off, w2_off, b2_off;
-    float *a_e = nullptr, *y_d = nullptr, *a_s = nullptr, *out = nullptr;
-    float *sq = nullptr, *rpre = nullptr, *gate = nullptr;
-    // second set for the teacher's eval forward when it runs on the side stream next to the student's train forward
-    float *t_a_e = nullptr, *t_y_d = nullptr, *t_a_s = nullptr, *t_out = nullptr;
-    float *t_sq = nullptr, *t_rpre = nullptr, *t_gate = nullptr;
+};
+
+// Where a launch goes: a stream and the workspaces only one stream may use at a time.  The engine has two: `main` (the caller's
+// stream) and `side` (teacher forward, weight gradients; st == null in stream mode 1).
+struct Lane {
+    hipStream_t st = nullptr;
+    float* sk_slab = nullptr;         // stream-K fix-up workspace of the conv GEMMs [blocks][2][BM*BN]
+    int* sk_counters = nullptr;
+    float* ws_slab = nullptr;         // partial slabs of the weight gradients (side: stream mode 0 only)
+    // per-block records of the depthwise kernels (BN partial sums; the eval forward's pooling sums).  The main lane's IS its
+    // ws_slab (no weight gradient runs on a lane while a depthwise conv does); the side lane has 64 MB of its own, since its
+    // ws_slab exists only when the weight gradients run there
+    float* rec = nullptr;
+};
+
+// One net's parameters and everything derived from them; two instances, student and teacher (fm_teacher_swap exchanges them)
+struct Weights {
+    float* state = nullptr;               // the state arena (layout at the top of this file)
+    std::vector<int64_t> counters;        // num_batches_tracked per BN
+    float *ev_scale = nullptr, *ev_shift = nullptr;   // eval-mode BN affine of every channel, remade when ev_dirty
+    bool ev_dirty = true;
+    // forward shadows, remade with fm_engine::wpack_dirty (student) / twb_dirty (teacher): bf16 W and W^T of the 1x1 convs (bf16
+    // mode), row-major / block-major bf16 planes of the conv weights (ResNet; split3.h, pconv.hip), the stem's planes (stem_rows.hip)
+    bf16* wb = nullptr;
+    unsigned short *wsp_f = nullptr, *wbm_f = nullptr, *wst = nullptr;
+};
+
+// The tensors a forward writes.  The student's set is what the backward reads; the second set (fm_engine::tacts) exists only
+// with the side stream, for the teacher's eval forward next to the student's train forward.
+struct BlockActs {
+    float *z1 = nullptr, *out = nullptr;
+    float* ds_y = nullptr;            // the downsample conv's output (student: that Conv::y)
+    unsigned short *z1p = nullptr, *outp = nullptr;   // planes mode: block-major bf16 planes of z1 / out (what the conv GEMMs read)
+};
+struct MBActs { float *a_e = nullptr, *y_d = nullptr, *a_s = nullptr, *out = nullptr, *sq = nullptr, *rpre = nullptr, *gate = nullptr; };
+struct Acts {
+    // ResNet-18: the stem's raw output (student: convs[0].y), its pooled output and that one's planes
+    float *stem_y = nullptr, *p0 = nullptr;
+    unsigned short* p0p = nullptr;
+    float* a0 = nullptr;              // EfficientNet: swish(bn(stem))
+    std::vector<BlockActs> blk;
+    std::vector<MBActs> mb;
+    float *T_mid = nullptr, *se_pool = nullptr;   // EfficientNet: head activation; squeeze-excite pooling partials
+};
+
+// BatchNorm mode of a train-mode forward: batch statistics; the same without touching running statistics and counters
+// (fm_forward_recompute); every BatchNorm on its running statistics (fm_bn_freeze)
+enum class BnMode { Batch, BatchNoUpdate, Frozen };
+// what a backward is asked for beyond e->grad from e->dlogits
+struct Bwd {
+    bool frozen = false;              // the forward ran on frozen statistics: every BatchNorm-backward finalize takes its frozen form
+    const float* dfeat = nullptr;     // d loss / d feature (caller-owned, or null)
+    float* dx[2] = {nullptr, nullptr};    // where d loss / d image of the views goes (null = not wanted: no launch)
+    bool step = true;                 // optimizer.step() at the end
 };
 
 struct StateEntry {           // one state_dict entry, in reference key order
@@ -127,7 +169,9 @@ struct OpEv { hipEvent_t a, b; int id; };
 
 struct fm_engine {
     fm_config cfg;
-    hipStream_t st = nullptr;
+    Lane main, side;
+    Weights student, teacher;
+    Acts acts, tacts;
     int C = 0, D = 512, H = 0, W = 0, maxB = 0;
     std::vector<Conv> convs;
     std::vector<Bn> bns;
@@ -136,52 +180,41 @@ struct fm_engine {
     int model = 0, c_stem = 0, c_head = -1, bn_stem = 0, bn_head = -1;
     float bn_eps = 1e-5f, bn_mom = 0.1f;
     int maxC = 512;                   // widest BN (sizes ca/cb/cc and the partial-sum workspace)
-    float *a0 = nullptr;              // EfficientNet: swish(bn(stem))
-    float *T_small = nullptr, *T_mid = nullptr, *T_big = nullptr;
-    float *se_dgp = nullptr, *se_drp = nullptr, *se_ds = nullptr, *se_pool = nullptr, *hfeat = nullptr;
+    float *T_small = nullptr, *T_big = nullptr;       // EfficientNet backward: d y_p, d y_e (d y_d lives in acts.T_mid)
+    float *se_dgp = nullptr, *se_drp = nullptr, *se_ds = nullptr, *hfeat = nullptr;
     const float *dc_dev = nullptr, *drop_dev = nullptr;   // caller-owned stochastic multipliers (or null)
     int pending_views = 0, pending_B = 0;                 // fm_forward_train awaiting fm_backward_step
-    // autograd path (fm_backward_grads / fm_adam_step): d loss / d feature of the backward being enqueued (caller-owned, or
-    // null), the gradient accumulator (NP floats, allocated on first use; `gacc_full` false = empty, the next backward copies),
-    // and bn_no_update: a recomputed forward (fm_forward_recompute) leaves running statistics and counters as they are
-    const float* dfeat_dev = nullptr;
-    // ... and where it wants d loss / d image of the views written (fm_backward_grads_x; null = not wanted: no launch).  ResNet-18:
-    // the stem's weights as the data gradient's B matrix (stem_dgrad.hip), made on first use and again after the weights change
-    float* dx_out[2] = {nullptr, nullptr};
+    // autograd path (fm_backward_grads / fm_adam_step): the gradient accumulator (NP floats, allocated on first use; `gacc_full`
+    // false = empty, the next backward copies).  ResNet-18: the stem's weights as the data gradient's B matrix (stem_dgrad.hip),
+    // made on first use and again after the weights change
     float* stem_dpack = nullptr;
     bool stem_dpack_stale = true;
     float* gacc = nullptr;
     bool gacc_full = false;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
-    bool bn_no_update = false;
-    // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read;
-    // `bn_fixed` is set while such a forward is enqueued (the finalizes take the running statistics), `pending_fixed` is the mode
-    // of the pending forward and `bwd_fixed` is set while ITS backward is enqueued.  The fused fm_step_* never set any of them.
-    bool bn_freeze = false, bn_fixed = false, pending_fixed = false, bwd_fixed = false;
-    std::vector<int64_t> tcounters;                       // the teacher's num_batches_tracked
+    // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read,
+    // `pending_fixed` the mode of the pending forward (its backward takes the same)
+    bool bn_freeze = false, pending_fixed = false;
     std::vector<StateEntry> entries;
     int n_bn_ch = 0;
     size_t NP = 0, NS = 0;            // trainable floats (padded to 4), whole state floats
     size_t off_fcw = 0, off_fcb = 0, off_gamma = 0, off_beta = 0, off_rm = 0, off_rv = 0;
     int64_t nf_sd = 0, ni_sd = 0;     // state_dict sizes
-    float *state = nullptr, *tstate = nullptr, *grad = nullptr, *adam_m = nullptr, *adam_v = nullptr;
-    float *ev_scale = nullptr, *ev_shift = nullptr, *tev_scale = nullptr, *tev_shift = nullptr;
+    float *grad = nullptr, *adam_m = nullptr, *adam_v = nullptr;      // student only, like the data-gradient packs below
     float* stage_sd = nullptr;        // device staging buffer in state_dict order
-    std::vector<int64_t> counters;    // num_batches_tracked per BN
     fm_adam hp{3e-5f, 0.9f, 0.999f, 1e-8f, 5e-4f};
     int64_t adam_t = 0;
-    bool ev_dirty = true, tev_dirty = true;
     // workspaces
-    float *x4 = nullptr, *p0 = nullptr, *dyh0 = nullptr;
+    float *x4 = nullptr, *dyh0 = nullptr;
     float* x3 = nullptr;      // packed stem: zero-framed NHWC3 input [max_images][H + 6][W + 8][3]
     // planes mode at 112-pixel stem rows (stem_rows.hip): the framed input as bf16 planes of four channels per pixel
-    // [3][max_images][H + 6][W + 8][4], and the stem's weight planes [7][3][64][32] of the student and of the teacher
+    // [3][max_images][H + 6][W + 8][4] (the stem's weight planes [7][3][64][32] are Weights::wst)
     bool stem_rows = false;
-    unsigned short *x3p = nullptr, *wst = nullptr, *twst = nullptr;
+    unsigned short* x3p = nullptr;
     long long x3p_plane_elems = 0;
     uint8_t* idx0 = nullptr;
     float *GA = nullptr, *GB = nullptr, *GC = nullptr, *GD = nullptr, *GE = nullptr;
-    float *ws_stats = nullptr, *ws_part = nullptr, *ws_slab = nullptr;
+    float *ws_stats = nullptr, *ws_part = nullptr;
     // what ws_stats holds: the BN partial sums of conv `stats_conv`, `stats_tiles_n` tiles per group -- written by the conv_fwd
     // that launched the GEMM (the count depends on the kernel and on that call's operand prologue), read by the finalize
     int stats_conv = -1, stats_tiles_n = 0;
@@ -192,8 +225,6 @@ struct fm_engine {
     float* psum = nullptr;
     int64_t *pcnt = nullptr, *tcnt = nullptr;
     float* zeros = nullptr;
-    float* sk_slab = nullptr;
-    int* sk_counters = nullptr;
     int *sel_counts = nullptr, *sel_top = nullptr, *sel_bot = nullptr, *cls_dev = nullptr;
     int sel_cap = 0;
     int* tag_buf = nullptr;           // fm_select_topk_rows: [pool sizes ncls | counts 2 ncls | top ncls*cap | bot ncls*cap | rows ncls*stride]
@@ -223,16 +254,14 @@ struct fm_engine {
     PackJob* pack_jobs = nullptr;
     int n_pack_jobs = 0, n_pack_blocks = 0;
     bool wpack_dirty = true;
-    // bf16 planes of the conv weights for the split-product GEMMs (split3.h; ResNet, fp32 mode): student forward, teacher
-    // forward, student data-gradient packs; rebuilt with the packs (wpack_dirty) / the teacher shadows (twb_dirty)
-    unsigned short *wsp_f = nullptr, *twsp_f = nullptr, *wsp_d = nullptr;
+    // bf16 planes of the data-gradient packs for the split-product GEMMs (split3.h; ResNet, fp32 mode), rebuilt with the packs
+    unsigned short* wsp_d = nullptr;
     // planes mode (ResNet-18, split product forms): the 3x3 / 1x1 conv GEMMs take BOTH operands as block-major bf16 planes
     // (pconv.hip); the activation planes are written by the kernels that produce the tensors
     bool planes = false;
-    unsigned short *wbm_f = nullptr, *twbm_f = nullptr, *wbm_d = nullptr;
+    unsigned short* wbm_d = nullptr;
     SplitJobBM *bm_f = nullptr, *bm_d = nullptr;
     int n_bm_f = 0, n_bm_f_blocks = 0, n_bm_d = 0, n_bm_d_blocks = 0;
-    unsigned short *p0p = nullptr, *t_p0p = nullptr;                 // planes of the stem's pooled output
     unsigned short *GBp = nullptr, *GCp = nullptr, *GDp = nullptr;   // planes of d y2, d y_ds, d y1 (what the data gradients read)
     unsigned short *GB2p = nullptr, *GC2p = nullptr, *GD2p = nullptr;
     unsigned short* xp_scratch = nullptr;       // planes of an fp32 operand nobody produced planes for (test hooks)
@@ -251,28 +280,22 @@ struct fm_engine {
     int products = 6;                 // fm_config.reserved[2]: how the fp32 conv GEMMs form their products (0 fp32 pipe, 6 / 9 bf16 partials)
     int stream_mode = 0;              // fm_config.reserved[1]: 0 side stream for teacher + weight gradients, 1 one stream, 2 teacher only
     int dt = DT_F32;                  // storage type of activations / their gradients (DT_F32 or DT_BF16)
-    bf16 *wb = nullptr, *twb = nullptr;   // bf16 weight shadows of the student / the teacher (1x1 convs, W and W^T)
-    size_t wb_numel = 0;
+    size_t wb_numel = 0;              // elements of Weights::wb
     CastJob* cast_jobs = nullptr;
     int n_cast_jobs = 0, n_cast_blocks = 0;
-    bool wb_dirty = true, twb_dirty = true;
+    bool twb_dirty = true;            // the teacher's forward shadows are stale (the student's go with wpack_dirty)
     bool fuse_gate = false;           // squeeze-excite gate applied on the project conv's operand load (a_s never stored)
-    // stage-1 steps of EfficientNet-B0: the frozen teacher's forward is independent of the student's until the loss, so it is
-    // enqueued on a side stream with its own activation / workspace set (stream_mode 1: one stream, shared buffers)
-    hipStream_t st2 = nullptr;
+    // stage-1 steps: the frozen teacher's forward is independent of the student's until the loss, so it is enqueued on the
+    // side lane into the second activation set (side_ok; stream_mode 1: main lane, the student's set)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     bool side_ok = false;
-    float *t_a0 = nullptr, *t_Tmid = nullptr, *t_se_pool = nullptr, *t_rec = nullptr;
-    float *t_c0y = nullptr, *t_p0 = nullptr;                        // ResNet-18: stem output / pooled stem of the teacher
-    // EfficientNet backward: the weight gradients of the 1x1 and depthwise convs run on the side stream next to the
-    // data-gradient chain; the gradient tensors they read are double-buffered by block parity (stream_mode 1 or 2: inline)
+    // backward: the weight gradients run on the side lane next to the data-gradient chain; the gradient tensors they read
+    // are double-buffered by block parity (side_w; stream_mode 1 or 2: inline)
     bool side_w = false;
-    float *T_small2 = nullptr, *T_mid2 = nullptr, *T_big2 = nullptr, *ws_slab2 = nullptr;
+    float *T_small2 = nullptr, *T_mid2 = nullptr, *T_big2 = nullptr;
     float *GB2 = nullptr, *GC2 = nullptr, *GD2 = nullptr;           // ResNet-18 (stream_mode 0): the same for d y2 / d y_ds / d y1
     hipEvent_t ev_p[4][2] = {}, ev_c[4][2] = {}, ev_wdone = nullptr;    // [tensor: d y_p, d y_d, d y_e, SE vectors][block parity]
     float *se_dgp2 = nullptr, *se_drp2 = nullptr;
-    float* sk_slab2 = nullptr;                                       // stream-K fix-up workspace of igemm launches on st2
-    int* sk_counters2 = nullptr;
     float* stem_col = nullptr;        // bf16 mode: [images][hout][wout][k][4][4] bf16 im2col of the input (the stem's X operand)
 };
 static inline void soft(fm_engine* e, hipError_t rc)
@@ -288,10 +311,10 @@ static inline void soft(fm_engine* e, hipError_t rc)
         HIPCHK(hipGetLastError());                                   \
         if ((e)->host_err && *(volatile int*)(e)->host_err) {        \
             /* drain the failed step (its later kernels may report too), then clear both words: it is reported ONCE */ \
-            (void)hipStreamSynchronize((e)->st);                     \
-            if ((e)->st2) (void)hipStreamSynchronize((e)->st2);      \
+            (void)hipStreamSynchronize((e)->main.st);                \
+            if ((e)->side.st) (void)hipStreamSynchronize((e)->side.st); \
             *(volatile int*)(e)->host_err = 0;                       \
-            (void)hipMemsetAsync((e)->dev_err, 0, sizeof(int), (e)->st); \
+            (void)hipMemsetAsync((e)->dev_err, 0, sizeof(int), (e)->main.st); \
             g_err = "a stream-K part never arrived (pconv): the step's optimizer update was skipped"; \
             return FM_ERR_HIP;                                       \
         }                                                            \
@@ -309,19 +332,17 @@ int dalloc(fm_engine* e, T** p, size_t n)
     *p = reinterpret_cast<T*>(q);
     return FM_OK;
 }
-#define DALLOC(p, n)                                   \
+// pass a callee's failure on
+#define RCCHK(x)                                       \
     do {                                               \
-        int rc_ = dalloc(e, &(p), (n));                \
+        const int rc_ = (x);                           \
         if (rc_ != FM_OK) return rc_;                  \
     } while (0)
+#define DALLOC(p, n) RCCHK(dalloc(e, &(p), (n)))
 
 // activation buffer of n elements in the engine's storage type (kept behind float* handles)
 int aalloc(fm_engine* e, float** p, size_t n) { return dalloc(e, p, e->precision ? (n + 1) / 2 : n); }
-#define AALLOC(p, n)                                   \
-    do {                                               \
-        int rc_ = aalloc(e, &(p), (n));                \
-        if (rc_ != FM_OK) return rc_;                  \
-    } while (0)
+#define AALLOC(p, n) RCCHK(aalloc(e, &(p), (n)))
 
 // The engine's side stream runs at the LOWEST priority: the caller's stream carries the dependent chain (student forward,
 // BatchNorm / data-gradient chain) whose short bandwidth-bound kernels should be dispatched first; the side stream's
@@ -397,8 +418,7 @@ int build_tables(fm_engine* e)
         std::vector<int4> t(c.Kw / 4);
         if (c.stem3) {                      // chunk q = floats 4j.. of kernel row kh's window at framed pixel (2 oh + kh, 2 ow)
             for (int q = 0; q < c.Kw / 4; ++q) t[q] = make_int4(q / 6, 0, 4 * (q % 6), q < 42 ? 1 : 0);
-            int rc = upload_tab(e, t, &c.tab);
-            if (rc) return rc;
+            RCCHK(upload_tab(e, t, &c.tab));
             continue;
         }
         for (int q = 0; q < c.Kw / 4; ++q) {
@@ -407,8 +427,7 @@ int build_tables(fm_engine* e)
             const int kh = tap / c.kw_p, kw = tap % c.kw_p;
             t[q] = make_int4(kh - c.pad, kw - c.pad, ci0, kw < c.k ? 1 : 0);
         }
-        int rc = upload_tab(e, t, &c.tab);
-        if (rc) return rc;
+        RCCHK(upload_tab(e, t, &c.tab));
         if (c.cin == 3) continue;          // the stem's input gradient has its own kernels (stem_dgrad.hip)
         // data-gradient parity classes
         const int s = c.stride;
@@ -463,7 +482,7 @@ int build_tables(fm_engine* e)
         e->n_cast_jobs = (int)cj.size(); e->n_cast_blocks = cb;
         DALLOC(e->cast_jobs, cj.size());
         HIPCHK(hipMemcpy(e->cast_jobs, cj.data(), cj.size() * sizeof(CastJob), hipMemcpyHostToDevice));
-        DALLOC(e->wb, e->wb_numel); DALLOC(e->twb, e->wb_numel);
+        DALLOC(e->student.wb, e->wb_numel); DALLOC(e->teacher.wb, e->wb_numel);
     }
     e->n_pack_jobs = (int)jobs.size();
     e->n_pack_blocks = blk;
@@ -518,8 +537,8 @@ int build_tables(fm_engine* e)
             }
             float* t2 = nullptr;
             if (o_f) {
-                DALLOC(t2, (size_t)(o_f + 1) / 2); e->wbm_f = reinterpret_cast<unsigned short*>(t2);
-                DALLOC(t2, (size_t)(o_f + 1) / 2); e->twbm_f = reinterpret_cast<unsigned short*>(t2);
+                DALLOC(t2, (size_t)(o_f + 1) / 2); e->student.wbm_f = reinterpret_cast<unsigned short*>(t2);
+                DALLOC(t2, (size_t)(o_f + 1) / 2); e->teacher.wbm_f = reinterpret_cast<unsigned short*>(t2);
             }
             if (o_d) { DALLOC(t2, (size_t)(o_d + 1) / 2); e->wbm_d = reinterpret_cast<unsigned short*>(t2); }
             e->n_bm_f = (int)bf_.size(); e->n_bm_f_blocks = nbf; e->n_bm_d = (int)bd_.size(); e->n_bm_d_blocks = nbd;
@@ -534,8 +553,8 @@ int build_tables(fm_engine* e)
         }
         float* tmp = nullptr;
         if (off_f) {
-            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->wsp_f = reinterpret_cast<unsigned short*>(tmp);
-            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->twsp_f = reinterpret_cast<unsigned short*>(tmp);
+            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->student.wsp_f = reinterpret_cast<unsigned short*>(tmp);
+            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->teacher.wsp_f = reinterpret_cast<unsigned short*>(tmp);
         }
         if (off_d) { DALLOC(tmp, (size_t)(off_d + 1) / 2); e->wsp_d = reinterpret_cast<unsigned short*>(tmp); }
         e->n_split_f = (int)jf.size(); e->n_split_f_blocks = bf; e->n_split_d = (int)jd.size(); e->n_split_d_blocks = bd;
@@ -612,8 +631,8 @@ int build_resnet18(fm_engine* e)
     e->entries.push_back({1, -1, e->off_fcb, (size_t)e->C, -1});
     e->nf_sd = 0; e->ni_sd = 0;
     for (auto& en : e->entries) (en.kind == 2 ? e->ni_sd : e->nf_sd) += (int64_t)en.n;
-    e->counters.assign(e->bns.size(), 0);
-    e->tcounters = e->counters;
+    e->student.counters.assign(e->bns.size(), 0);
+    e->teacher.counters = e->student.counters;
     return FM_OK;
 }
 
@@ -724,21 +743,172 @@ int build_effnet_b0(fm_engine* e)
     e->entries.push_back({1, -1, e->off_fcb, (size_t)e->C, -1});
     e->nf_sd = 0; e->ni_sd = 0;
     for (auto& en : e->entries) (en.kind == 2 ? e->ni_sd : e->nf_sd) += (int64_t)en.n;
-    e->counters.assign(e->bns.size(), 0);
-    e->tcounters = e->counters;
+    e->student.counters.assign(e->bns.size(), 0);
+    e->teacher.counters = e->student.counters;
+    return FM_OK;
+}
+
+// planes of `elems` fp32 values: 3 x 2 B each
+int palloc(fm_engine* e, unsigned short** pp, size_t elems)
+{
+    float* t = nullptr;
+    DALLOC(t, (elems * 3 + 1) / 2);
+    *pp = reinterpret_cast<unsigned short*>(t);
+    return FM_OK;
+}
+#define PALLOC(p, n) RCCHK(palloc(e, &(p), (n)))
+
+// EfficientNet tensor sizes at max_images (elements): block input / output, d y_p, d y_d and the head, d y_e; widest ce / cs
+struct EffSizes { size_t g_io = 0, t_small = 0, t_mid = 0, t_big = 0, max_ce = 0, max_cs = 0; };
+EffSizes eff_sizes(const fm_engine* e)
+{
+    const size_t B = e->maxB;
+    const Conv& c0 = e->convs[0];
+    EffSizes z;
+    z.g_io = B * c0.hout * c0.wout * c0.cout_p;
+    for (auto& m : e->mbs) {
+        const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
+        z.g_io = std::max(z.g_io, std::max(nin * m.cin_p, nout * m.cout_p));
+        z.t_small = std::max(z.t_small, nout * m.cout_p);
+        z.t_mid = std::max(z.t_mid, nout * m.ce_p);
+        z.t_big = std::max(z.t_big, nin * m.ce_p);
+        z.max_ce = std::max<size_t>(z.max_ce, m.ce_p); z.max_cs = std::max<size_t>(z.max_cs, m.cs);
+    }
+    const Conv& chd = e->convs[e->c_head];
+    z.t_mid = std::max(z.t_mid, B * chd.hout * chd.wout * chd.cout_p);
+    return z;
+}
+
+// One activation set.  `second`: the side lane's set for the teacher's eval forward, with its own stem / downsample outputs
+// (the student's are the Conv::y the train forward writes) and pooling partials without the backward's five sums
+int alloc_acts(fm_engine* e, Acts& a, bool second)
+{
+    const size_t B = e->maxB;
+    const Conv& c0 = e->convs[0];
+    if (e->model == 0) {
+        const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
+        a.stem_y = c0.y;
+        if (second) DALLOC(a.stem_y, B * c0.hout * c0.wout * c0.cout_p);
+        DALLOC(a.p0, pooled);
+        if (e->planes) PALLOC(a.p0p, pooled);
+        a.blk.resize(e->blocks.size());
+        for (size_t i = 0; i < e->blocks.size(); ++i) {
+            const Block& blk = e->blocks[i];
+            BlockActs& ba = a.blk[i];
+            const Conv& c = e->convs[blk.c1];
+            const size_t n = B * c.hout * c.wout * c.cout;
+            DALLOC(ba.z1, n); DALLOC(ba.out, n);
+            if (blk.ds >= 0) {
+                ba.ds_y = e->convs[blk.ds].y;
+                if (second) DALLOC(ba.ds_y, n);
+            }
+            if (e->planes) { PALLOC(ba.z1p, n); PALLOC(ba.outp, n); }
+        }
+        return FM_OK;
+    }
+    const EffSizes z = eff_sizes(e);
+    AALLOC(a.a0, B * c0.hout * c0.wout * c0.cout_p);
+    a.mb.resize(e->mbs.size());
+    for (size_t i = 0; i < e->mbs.size(); ++i) {
+        const MBConv& m = e->mbs[i];
+        MBActs& ma = a.mb[i];
+        const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
+        if (m.c_exp >= 0) AALLOC(ma.a_e, nin * m.ce_p);
+        AALLOC(ma.y_d, nout * m.ce_p); AALLOC(ma.a_s, nout * m.ce_p);
+        AALLOC(ma.out, nout * m.cout_p);
+        DALLOC(ma.sq, B * m.ce_p); DALLOC(ma.rpre, B * m.cs); DALLOC(ma.gate, B * m.ce_p);
+    }
+    AALLOC(a.T_mid, z.t_mid);
+    DALLOC(a.se_pool, B * 16 * (second ? 1 : 5) * z.max_ce);       // [imgs][<=16 chunks][5 sums][C]
+    return FM_OK;
+}
+
+size_t sk_floats() { return std::max((size_t)igemm_max_blocks() * 2 * 16384, pconv_slab_floats()); }   // [blocks][2][BM*BN]
+
+// Would the side lane's buffers fit?  They roughly double the activation footprint: one stream is kept when they would not
+// fit with 4 GB to spare (fm_stream_mode() reports the mode that was actually set up).  Asked at the point of alloc_workspaces
+// where the model's second set used to be allocated, so that the answer is the one it has always been.
+bool side_fits(const fm_engine* e)
+{
+    const size_t B = e->maxB;
+    const Conv& c0 = e->convs[0];
+    size_t need = 0, spare = 0, free_b = 0, total_b = 0;
+    if (e->model == 0) {
+        // the teacher's activation set, the second gradient / slab buffers
+        const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
+        need = (B * c0.hout * c0.wout * c0.cout_p + 4 * pooled + e->slab_floats) * 4;
+        for (auto& blk : e->blocks) {
+            const Conv& c = e->convs[blk.c1];
+            need += (size_t)(blk.ds >= 0 ? 3 : 2) * B * c.hout * c.wout * c.cout * 4;
+        }
+        need += sk_floats() * 4 + ((size_t)4 << 20);
+        if (e->planes) need += need * 3 / 2;       // the planes of the teacher's activations and of the second gradient set
+        spare = (size_t)4 << 30;
+    } else {
+        // next to what is still to be allocated (slabs, statistics: < 2 GB)
+        const EffSizes z = eff_sizes(e);
+        const size_t es = e->precision ? 2 : 4;
+        for (auto& m : e->mbs) {
+            const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
+            need += ((m.c_exp >= 0 ? nin * m.ce_p : 0) + 2 * nout * m.ce_p + nout * m.cout_p) * es;
+        }
+        need += (z.t_small + 2 * z.t_mid + z.t_big) * es + 2 * ((size_t)48 << 22);
+        spare = (size_t)6 << 30;
+    }
+    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= need + spare;
+}
+
+// The side lane and what runs on it: the teacher's activation set (stream mode 0 or 2) and, in stream mode 0, the second
+// slab / gradient buffers of the weight gradients.
+// ResNet-18 (MFMA-bound, persistent 512-block kernels): 39.0 -> 37.7 ms per stage-1 step with the teacher and the weight
+// gradients on the side stream, same bits.  Co-running kernels stretch each other's launch windows, so per-kernel durations
+// (bench.py's roofline, rocprofv3) are taken from a one-stream engine (stream mode 1).
+int alloc_side(fm_engine* e)
+{
+    const size_t B = e->maxB;
+    Lane& s = e->side;
+    DALLOC(s.sk_slab, sk_floats());
+    DALLOC(s.sk_counters, (size_t)1 << 20);
+    HIPCHK(hipMemset(s.sk_counters, 0, ((size_t)1 << 20) * 4));
+    RCCHK(alloc_acts(e, e->tacts, true));
+    if (e->model == 1) DALLOC(s.rec, (size_t)16 << 20);           // pooling records of the eval depthwise forward (<= 33 MB)
+    HIPCHK(create_side_stream(&s.st));
+    HIPCHK(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&e->ev_t, hipEventDisableTiming));
+    e->side_ok = true;
+    if (e->stream_mode != 0) return FM_OK;
+    DALLOC(s.ws_slab, e->slab_floats);
+    if (e->model == 0) {
+        const Conv& c0 = e->convs[0];
+        const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
+        DALLOC(e->GB2, pooled); DALLOC(e->GC2, pooled); DALLOC(e->GD2, pooled);
+        if (e->planes) { PALLOC(e->GB2p, pooled); PALLOC(e->GC2p, pooled); PALLOC(e->GD2p, pooled); }
+    } else {
+        const EffSizes z = eff_sizes(e);
+        AALLOC(e->T_small2, z.t_small); AALLOC(e->T_mid2, z.t_mid); AALLOC(e->T_big2, z.t_big);
+        DALLOC(e->se_dgp2, B * z.max_ce); DALLOC(e->se_drp2, B * z.max_cs);
+    }
+    for (int k = 0; k < 4; ++k)
+        for (int q = 0; q < 2; ++q) {
+            HIPCHK(hipEventCreateWithFlags(&e->ev_p[k][q], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&e->ev_c[k][q], hipEventDisableTiming));
+        }
+    HIPCHK(hipEventCreateWithFlags(&e->ev_wdone, hipEventDisableTiming));
+    e->side_w = true;
     return FM_OK;
 }
 
 int alloc_workspaces(fm_engine* e)
 {
     const size_t B = e->maxB;
-    DALLOC(e->state, e->NS); DALLOC(e->tstate, e->NS);
+    for (Weights* w : {&e->student, &e->teacher}) {
+        DALLOC(w->state, e->NS);
+        HIPCHK(hipMemset(w->state, 0, e->NS * 4));
+        DALLOC(w->ev_scale, e->n_bn_ch); DALLOC(w->ev_shift, e->n_bn_ch);
+    }
     DALLOC(e->grad, e->NP); DALLOC(e->adam_m, e->NP); DALLOC(e->adam_v, e->NP);
-    HIPCHK(hipMemset(e->state, 0, e->NS * 4)); HIPCHK(hipMemset(e->tstate, 0, e->NS * 4));
     HIPCHK(hipMemset(e->grad, 0, e->NP * 4));
     HIPCHK(hipMemset(e->adam_m, 0, e->NP * 4)); HIPCHK(hipMemset(e->adam_v, 0, e->NP * 4));
-    DALLOC(e->ev_scale, e->n_bn_ch); DALLOC(e->ev_shift, e->n_bn_ch);
-    DALLOC(e->tev_scale, e->n_bn_ch); DALLOC(e->tev_shift, e->n_bn_ch);
     DALLOC(e->stage_sd, (size_t)e->nf_sd);
     DALLOC(e->x4, B * e->H * e->W * 4);
     if (e->convs[0].stem3) {
@@ -751,7 +921,7 @@ int alloc_workspaces(fm_engine* e)
         if (e->stem_rows) {
             DALLOC(e->x3p, (size_t)3 * e->x3p_plane_elems + 64);
             HIPCHK(hipMemset(e->x3p, 0, ((size_t)3 * e->x3p_plane_elems + 64) * 2));
-            DALLOC(e->wst, 7 * 3 * 64 * 32); DALLOC(e->twst, 7 * 3 * 64 * 32);
+            DALLOC(e->student.wst, 7 * 3 * 64 * 32); DALLOC(e->teacher.wst, 7 * 3 * 64 * 32);
         }
     }
     size_t max_stats = 0, max_slab = 0;
@@ -766,89 +936,27 @@ int alloc_workspaces(fm_engine* e)
     for (auto& b : e->bns) {
         DALLOC(b.mean, 2 * b.C); DALLOC(b.istd, 2 * b.C); DALLOC(b.scale, 2 * b.C); DALLOC(b.shift, 2 * b.C);
     }
+    RCCHK(alloc_acts(e, e->acts, false));
+    bool side = e->stream_mode != 1;          // fm_config.reserved[1]: 0 two streams, 1 one stream, 2 teacher only
     const Conv& c0 = e->convs[0];
     if (e->model == 0) {
         const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
-        DALLOC(e->p0, pooled); DALLOC(e->idx0, pooled);
+        DALLOC(e->idx0, pooled);
         DALLOC(e->dyh0, B * c0.hout * c0.wout * 64);
-        for (auto& blk : e->blocks) {
-            const Conv& c = e->convs[blk.c1];
-            const size_t n = B * c.hout * c.wout * c.cout;
-            DALLOC(blk.z1, n); DALLOC(blk.out, n);
-        }
         DALLOC(e->GA, pooled); DALLOC(e->GB, pooled); DALLOC(e->GC, pooled); DALLOC(e->GD, pooled); DALLOC(e->GE, pooled);
     } else {
-        size_t g_io = B * c0.hout * c0.wout * c0.cout_p, t_small = 0, t_mid = 0, t_big = 0, max_ce = 0, max_cs = 0;
-        AALLOC(e->a0, g_io);
-        for (auto& m : e->mbs) {
-            const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
-            if (m.c_exp >= 0) AALLOC(m.a_e, nin * m.ce_p);
-            AALLOC(m.y_d, nout * m.ce_p); AALLOC(m.a_s, nout * m.ce_p);
-            AALLOC(m.out, nout * m.cout_p);
-            DALLOC(m.sq, B * m.ce_p); DALLOC(m.rpre, B * m.cs); DALLOC(m.gate, B * m.ce_p);
-            g_io = std::max(g_io, std::max(nin * m.cin_p, nout * m.cout_p));
-            t_small = std::max(t_small, nout * m.cout_p);
-            t_mid = std::max(t_mid, nout * m.ce_p);
-            t_big = std::max(t_big, nin * m.ce_p);
-            max_ce = std::max<size_t>(max_ce, m.ce_p); max_cs = std::max<size_t>(max_cs, m.cs);
-        }
-        const Conv& chd = e->convs[e->c_head];
-        t_mid = std::max(t_mid, B * chd.hout * chd.wout * chd.cout_p);
-        AALLOC(e->GA, g_io); AALLOC(e->GB, g_io);
-        AALLOC(e->T_small, t_small); AALLOC(e->T_mid, t_mid); AALLOC(e->T_big, t_big);
-        DALLOC(e->se_dgp, B * max_ce); DALLOC(e->se_drp, B * max_cs); DALLOC(e->se_ds, B * max_ce);
-        DALLOC(e->se_pool, B * 16 * 5 * max_ce);       // [imgs][<=16 chunks][5 sums][C]
-        {
-            int side = e->stream_mode != 1;          // fm_config.reserved[1]: 0 two streams, 1 one stream, 2 teacher only
-            if (side) {
-                // the second buffer sets roughly double the activation footprint: keep one stream when they would not fit
-                // next to what is still to be allocated (slabs, statistics: < 2 GB) with 4 GB to spare
-                size_t need = 0, free_b = 0, total_b = 0;
-                const size_t es = e->precision ? 2 : 4;
-                for (auto& m : e->mbs) {
-                    const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
-                    need += ((m.c_exp >= 0 ? nin * m.ce_p : 0) + 2 * nout * m.ce_p + nout * m.cout_p) * es;
-                }
-                need += (t_small + 2 * t_mid + t_big) * es + 2 * ((size_t)48 << 22);
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)6 << 30)) side = 0;
-            }
-            if (side) {
-                for (auto& m : e->mbs) {
-                    const size_t nin = B * m.hin * m.win, nout = B * m.hout * m.wout;
-                    if (m.c_exp >= 0) AALLOC(m.t_a_e, nin * m.ce_p);
-                    AALLOC(m.t_y_d, nout * m.ce_p); AALLOC(m.t_a_s, nout * m.ce_p);
-                    AALLOC(m.t_out, nout * m.cout_p);
-                    DALLOC(m.t_sq, B * m.ce_p); DALLOC(m.t_rpre, B * m.cs); DALLOC(m.t_gate, B * m.ce_p);
-                }
-                AALLOC(e->t_a0, B * c0.hout * c0.wout * c0.cout_p);
-                AALLOC(e->t_Tmid, t_mid);
-                DALLOC(e->t_se_pool, B * 16 * max_ce);
-                DALLOC(e->t_rec, (size_t)16 << 20);           // pooling records of the eval depthwise forward (<= 33 MB)
-                HIPCHK(create_side_stream(&e->st2));
-                HIPCHK(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-                HIPCHK(hipEventCreateWithFlags(&e->ev_t, hipEventDisableTiming));
-                e->side_ok = true;
-                const int sidew = e->stream_mode == 0;
-                if (sidew) {
-                    AALLOC(e->T_small2, t_small); AALLOC(e->T_mid2, t_mid); AALLOC(e->T_big2, t_big);
-                    DALLOC(e->se_dgp2, B * max_ce); DALLOC(e->se_drp2, B * max_cs);
-                    for (int k = 0; k < 4; ++k)
-                        for (int q = 0; q < 2; ++q) {
-                            HIPCHK(hipEventCreateWithFlags(&e->ev_p[k][q], hipEventDisableTiming));
-                            HIPCHK(hipEventCreateWithFlags(&e->ev_c[k][q], hipEventDisableTiming));
-                        }
-                    HIPCHK(hipEventCreateWithFlags(&e->ev_wdone, hipEventDisableTiming));
-                    e->side_w = true;          // ws_slab2 is allocated with ws_slab below
-                }
-            }
-        }
+        const EffSizes z = eff_sizes(e);
+        AALLOC(e->GA, z.g_io); AALLOC(e->GB, z.g_io);
+        AALLOC(e->T_small, z.t_small); AALLOC(e->T_big, z.t_big);
+        DALLOC(e->se_dgp, B * z.max_ce); DALLOC(e->se_drp, B * z.max_cs); DALLOC(e->se_ds, B * z.max_ce);
+        side = side && side_fits(e);
         DALLOC(e->hfeat, B * e->D);
     }
     DALLOC(e->ws_stats, max_stats);
     DALLOC(e->ws_part, (size_t)2 * (1024 + 32) * 2 * e->maxC);   // per-block partials + folded partials
     e->slab_floats = std::max<size_t>(max_slab * 8, (size_t)48 << 20);   // >= 192 MB of partial slabs
-    DALLOC(e->ws_slab, e->slab_floats);
-    if (e->side_w) DALLOC(e->ws_slab2, e->slab_floats);
+    DALLOC(e->main.ws_slab, e->slab_floats);
+    e->main.rec = e->main.ws_slab;
     DALLOC(e->ca, 2 * e->maxC); DALLOC(e->cb, 2 * e->maxC); DALLOC(e->cc, 2 * e->maxC);
     DALLOC(e->feat, B * e->D); DALLOC(e->tfeat, B * e->D);
     DALLOC(e->logits, B * e->C); DALLOC(e->tlogits, B * e->C); DALLOC(e->dlogits, B * e->C);
@@ -856,20 +964,8 @@ int alloc_workspaces(fm_engine* e)
     DALLOC(e->sel_counts, 2); DALLOC(e->cls_dev, FM_MAX_CLASSES);
     DALLOC(e->zeros, 64);
     if (e->planes) {
-        auto palloc = [&](unsigned short** pp, size_t elems) -> int {       // planes of `elems` fp32 values: 3 x 2 B each
-            float* t = nullptr;
-            DALLOC(t, (elems * 3 + 1) / 2);
-            *pp = reinterpret_cast<unsigned short*>(t);
-            return FM_OK;
-        };
-        const Conv& cs = e->convs[0];
-        const size_t pooled = B * (cs.hout / 2) * (cs.wout / 2) * 64;
-        if (palloc(&e->p0p, pooled) || palloc(&e->GBp, pooled) || palloc(&e->GCp, pooled) || palloc(&e->GDp, pooled)) return FM_ERR_HIP;
-        for (auto& blk : e->blocks) {
-            const Conv& c = e->convs[blk.c1];
-            const size_t n = B * c.hout * c.wout * c.cout;
-            if (palloc(&blk.z1p, n) || palloc(&blk.outp, n)) return FM_ERR_HIP;
-        }
+        const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
+        PALLOC(e->GBp, pooled); PALLOC(e->GCp, pooled); PALLOC(e->GDp, pooled);
         // scratch planes for operands that arrive as fp32 (test hooks): the largest conv input / output-gradient tensor
         size_t mx = 0;
         for (auto& c : e->convs) {
@@ -883,90 +979,17 @@ int alloc_workspaces(fm_engine* e)
         DALLOC(t3, (e->xp_scratch_elems + 1) / 2);
         e->xp_scratch2 = reinterpret_cast<unsigned short*>(t3);
     }
-    const size_t sk_floats = std::max((size_t)igemm_max_blocks() * 2 * 16384, pconv_slab_floats());
-    DALLOC(e->sk_slab, sk_floats);   // [blocks][2][BM*BN]
+    DALLOC(e->main.sk_slab, sk_floats());
     DALLOC(e->dev_err, 16);
     HIPCHK(hipMemset(e->dev_err, 0, 16 * sizeof(int)));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->host_err), 64, hipHostMallocMapped));
     *e->host_err = 0;
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->host_err_dev), e->host_err, 0));
-    DALLOC(e->sk_counters, (size_t)1 << 20);
-    HIPCHK(hipMemset(e->sk_counters, 0, ((size_t)1 << 20) * 4));
-    {
-        int side = e->stream_mode != 1;
-        if (side && e->model == 0) {
-            // the teacher's activation set, the second gradient / slab buffers: keep one stream when they would not fit with
-            // 4 GB to spare (the EfficientNet branch above guards its own second set the same way); fm_stream_mode() reports
-            // the mode that was actually set up
-            const Conv& c0 = e->convs[0];
-            const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
-            size_t need = (B * c0.hout * c0.wout * c0.cout_p + 4 * pooled + e->slab_floats) * 4, free_b = 0, total_b = 0;
-            for (auto& blk : e->blocks) {
-                const Conv& c = e->convs[blk.c1];
-                need += (size_t)(blk.ds >= 0 ? 3 : 2) * B * c.hout * c.wout * c.cout * 4;
-            }
-            need += sk_floats * 4 + ((size_t)4 << 20);
-            if (e->planes) need += need * 3 / 2;       // the planes of the teacher's activations and of the second gradient set
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)4 << 30)) side = 0;
-        }
-        if (side) {
-            DALLOC(e->sk_slab2, sk_floats);
-            DALLOC(e->sk_counters2, (size_t)1 << 20);
-            HIPCHK(hipMemset(e->sk_counters2, 0, ((size_t)1 << 20) * 4));
-            // ResNet-18 (MFMA-bound, persistent 512-block kernels): 39.0 -> 37.7 ms per stage-1 step with the teacher and the
-            // weight gradients on the side stream, same bits.  Co-running kernels stretch each other's launch windows, so
-            // per-kernel durations (bench.py's roofline, rocprofv3) are taken from a one-stream engine (stream mode 1).
-            if (e->model == 0) {
-                const Conv& c0 = e->convs[0];
-                const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
-                DALLOC(e->t_c0y, B * c0.hout * c0.wout * c0.cout_p);
-                DALLOC(e->t_p0, pooled);
-                for (auto& blk : e->blocks) {
-                    const Conv& c = e->convs[blk.c1];
-                    const size_t n = B * c.hout * c.wout * c.cout;
-                    DALLOC(blk.t_z1, n); DALLOC(blk.t_out, n);
-                    if (blk.ds >= 0) DALLOC(blk.t_dsy, n);
-                }
-                HIPCHK(create_side_stream(&e->st2));
-                HIPCHK(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-                HIPCHK(hipEventCreateWithFlags(&e->ev_t, hipEventDisableTiming));
-                e->side_ok = true;
-                const int sidew = e->stream_mode == 0;
-                if (sidew) {
-                    DALLOC(e->GB2, pooled); DALLOC(e->GC2, pooled); DALLOC(e->GD2, pooled);
-                    DALLOC(e->ws_slab2, e->slab_floats);
-                    for (int k = 0; k < 4; ++k)
-                        for (int q = 0; q < 2; ++q) {
-                            HIPCHK(hipEventCreateWithFlags(&e->ev_p[k][q], hipEventDisableTiming));
-                            HIPCHK(hipEventCreateWithFlags(&e->ev_c[k][q], hipEventDisableTiming));
-                        }
-                    HIPCHK(hipEventCreateWithFlags(&e->ev_wdone, hipEventDisableTiming));
-                    e->side_w = true;
-                }
-            }
-        }
-    }
-    if (e->planes) {       // the side stream's sets of planes (teacher activations, second gradient buffers)
-        auto palloc = [&](unsigned short** pp, size_t elems) -> int {
-            float* t = nullptr;
-            DALLOC(t, (elems * 3 + 1) / 2);
-            *pp = reinterpret_cast<unsigned short*>(t);
-            return FM_OK;
-        };
-        const Conv& cs = e->convs[0];
-        const size_t pooled = B * (cs.hout / 2) * (cs.wout / 2) * 64;
-        if (e->side_ok) {
-            if (palloc(&e->t_p0p, pooled)) return FM_ERR_HIP;
-            for (auto& blk : e->blocks) {
-                const Conv& c = e->convs[blk.c1];
-                const size_t n = B * c.hout * c.wout * c.cout;
-                if (palloc(&blk.t_z1p, n) || palloc(&blk.t_outp, n)) return FM_ERR_HIP;
-            }
-        }
-        if (e->side_w && (palloc(&e->GB2p, pooled) || palloc(&e->GC2p, pooled) || palloc(&e->GD2p, pooled))) return FM_ERR_HIP;
-    }
+    DALLOC(e->main.sk_counters, (size_t)1 << 20);
+    HIPCHK(hipMemset(e->main.sk_counters, 0, ((size_t)1 << 20) * 4));
     HIPCHK(hipMemset(e->zeros, 0, 64 * 4));
-    return FM_OK;
+    if (e->model == 0) side = side && side_fits(e);
+    return side ? alloc_side(e) : FM_OK;
 }
 
 // ---- profiling helpers -----------------------------------------------------------
@@ -978,27 +1001,27 @@ hipEvent_t get_ev(fm_engine* e)
     return v;
 }
 struct ProfScope {
-    fm_engine* e; hipEvent_t a{}, b{}; int fam; double fl; bool on;
-    ProfScope(fm_engine* e_, int family, double flops) : e(e_), fam(family), fl(flops), on(e_->prof)
+    fm_engine* e; hipStream_t st; hipEvent_t a{}, b{}; int fam; double fl; bool on;
+    ProfScope(fm_engine* e_, const Lane& L, int family, double flops) : e(e_), st(L.st), fam(family), fl(flops), on(e_->prof)
     {
         if (on) {
             a = get_ev(e); b = get_ev(e);
             on = a && b;
-            if (on && hipEventRecord(a, e->st) != hipSuccess) { e->prof_fail = true; on = false; }
+            if (on && hipEventRecord(a, st) != hipSuccess) { e->prof_fail = true; on = false; }
         }
     }
     ~ProfScope()
     {
         if (on) {
-            if (hipEventRecord(b, e->st) != hipSuccess) e->prof_fail = true;
+            if (hipEventRecord(b, st) != hipSuccess) e->prof_fail = true;
             e->evs.push_back({a, b, fam, fl});
         }
     }
 };
 
 struct OpScope {
-    fm_engine* e; hipEvent_t a{}, b{}; int id = -1; bool on;
-    OpScope(fm_engine* e_, const char* op) : e(e_), on(e_->oprof)
+    fm_engine* e; hipStream_t st; hipEvent_t a{}, b{}; int id = -1; bool on;
+    OpScope(fm_engine* e_, const Lane& L, const char* op) : e(e_), st(L.st), on(e_->oprof)
     {
         if (!on) return;
         char lab[96];
@@ -1007,29 +1030,27 @@ struct OpScope {
             if (e->op_names[i] == lab) { id = (int)i; break; }
         if (id < 0) { id = (int)e->op_names.size(); e->op_names.push_back(lab); e->op_ms.push_back(0); e->op_n.push_back(0); }
         a = get_ev(e); b = get_ev(e);
-        on = a && b && hipEventRecord(a, e->st) == hipSuccess;
+        on = a && b && hipEventRecord(a, st) == hipSuccess;
     }
     ~OpScope()
     {
-        if (on && hipEventRecord(b, e->st) == hipSuccess) e->opevs.push_back({a, b, id});
+        if (on && hipEventRecord(b, st) == hipSuccess) e->opevs.push_back({a, b, id});
     }
 };
-#define OP(name) OpScope os_(e, name)
+#define OP(lane, name) OpScope os_(e, lane, name)
 
 // ---- layer launchers --------------------------------------------------------------
 // operand prologue of a pointwise conv (bf16 mode): Xe = swish(X*psc+psh)*gate, psc == null: X*gate
 struct Prologue { const float* psc; const float* psh; const float* gate; };
 
-const bf16* shadow_of(fm_engine* e, const float* S) { return S == e->tstate ? e->twb : e->wb; }
-
 // planes of an fp32 NHWC operand nobody produced planes for (test hooks): [C/32][3][npix][32] in the scratch buffer
-const unsigned short* scratch_planes(fm_engine* e, const float* x, long long npix, int C)
+const unsigned short* scratch_planes(fm_engine* e, Lane& L, const float* x, long long npix, int C)
 {
     if ((size_t)npix * C * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return nullptr; }
     // FM_DEBUG_REUSE_PLANES=1 (tools/probe_conv.py): time the GEMM alone -- the planes of the same operand are made once
     static const bool reuse = getenv("FM_DEBUG_REUSE_PLANES") && atoi(getenv("FM_DEBUG_REUSE_PLANES")) != 0;
     if (reuse && e->xp_scratch_src == x && e->xp_scratch_npix == npix) return e->xp_scratch;
-    k_split_planes(x, e->xp_scratch, npix, C, e->st);
+    k_split_planes(x, e->xp_scratch, npix, C, L.st);
     e->xp_scratch_src = x; e->xp_scratch_npix = npix;
     return e->xp_scratch;
 }
@@ -1051,7 +1072,7 @@ static int stats_tiles_for(fm_engine* e, const Conv& c, int imgs_per_group, int 
     return (imgs_per_group * c.hout * c.wout + bn - 1) / bn;
 }
 
-void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, int imgs, int groups,
+void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, float* y, int imgs, int groups,
               const float* scale, const float* shift, const float* res, int relu, float* stats,
               const Prologue* pro = nullptr, const unsigned short* xp = nullptr, unsigned short* yp = nullptr,
               const unsigned short* resp = nullptr)
@@ -1063,21 +1084,21 @@ void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, in
     }
     if (e->stem_rows && c.stem3) {           // `x` is ignored: the operand is the framed image's planes (to_nhwc4)
         StemRowsParams q{};
-        q.Xp = e->x3p; q.Wst = S == e->tstate ? e->twst : e->wst; q.Y = y;
+        q.Xp = e->x3p; q.Wst = W.wst; q.Y = y;
         q.scale = scale; q.shift = shift; q.stats = stats; q.relu = relu;
         q.imgs = imgs; q.imgs_per_group = imgs / groups; q.Hp = c.Hp; q.Wp = c.Wp; q.Ho = c.hout; q.Wo = c.wout;
         q.sp = e->products; q.plane_bytes = e->x3p_plane_elems * 2;
-        ProfScope ps(e, 2, 2.0 * c.macs_per_img * imgs);
-        launch_stem_rows(q, e->st);
+        ProfScope ps(e, L, 2, 2.0 * c.macs_per_img * imgs);
+        launch_stem_rows(q, L.st);
         return;
     }
     if (conv_uses_pconv(e, c, imgs)) {
         IgemmParams p{};
         p.xp_pix = (long long)imgs * c.hin * c.win;
-        p.Xp = xp ? xp : scratch_planes(e, x, p.xp_pix, c.cin_p);
-        p.Wsp = (S == e->tstate ? e->twbm_f : e->wbm_f) + c.bm_off;
+        p.Xp = xp ? xp : scratch_planes(e, L, x, p.xp_pix, c.cin_p);
+        p.Wsp = W.wbm_f + c.bm_off;
         p.Y = y; p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout;
-        p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+        p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
         p.ntaps = c.k * c.k;
         for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
         p.res = res; p.resp = resp; p.scale = scale; p.shift = shift; p.stats = stats;
@@ -1091,8 +1112,8 @@ void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, in
         p.tilesN = (p.imgs_per_group * c.hout * c.wout + pconv_tile_n(c.cout_p) - 1) / pconv_tile_n(c.cout_p);
         p.relu = relu;
         // measurement families follow the kernel symbols: 0 / 1 = pconv_kernel<4 | 2, ..., true> (tap rows shared), 6 / 7 = <..., false>
-        ProfScope ps(e, (c.cout_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs);
-        launch_pconv(p, groups, e->st);
+        ProfScope ps(e, L, (c.cout_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs);
+        launch_pconv(p, groups, L.st);
         return;
     }
     // planes mode keeps no fp32 operands for these convs (activations exist only as planes, no row-major weight planes): a shape
@@ -1102,7 +1123,7 @@ void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, in
     if (e->precision && (c.k == 1 || stem16)) {          // bf16 storage + bf16 MFMA (pwconv_bf16.hip)
         PwParams q{};
         q.zeros = e->zeros;
-        q.W = shadow_of(e, S) + c.wb_off;
+        q.W = W.wb + c.wb_off;
         q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x); q.Y = reinterpret_cast<bf16*>(y);
         q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p;
         q.npix = (imgs / groups) * c.hout * c.wout; q.groups = groups;
@@ -1110,13 +1131,13 @@ void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, in
         q.stats = stats;
         if (pro && pro->gate) { q.psc = pro->psc; q.psh = pro->psh; q.gate = pro->gate; }
         q.HW = c.hout * c.wout;
-        launch_pw_conv(q, e->st);
+        launch_pw_conv(q, L.st);
         return;
     }
     IgemmParams p{};
-    p.W = S + c.w_off; p.X = x; p.Y = y; p.zeros = e->zeros; p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
+    p.W = W.state + c.w_off; p.X = x; p.Y = y; p.zeros = e->zeros; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
     p.sp = e->products;
-    if (c.sp_off >= 0 && e->wsp_f) p.Wsp = (S == e->tstate ? e->twsp_f : e->wsp_f) + c.sp_off;
+    if (c.sp_off >= 0 && W.wsp_f) p.Wsp = W.wsp_f + c.sp_off;
     if (c.cin == 3) {
         p.stem_kw = c.k; p.stem_pad = c.pad; p.stem_h2 = c.kw_p == 8 ? 1 : 0; p.stem3 = c.stem3 ? 1 : 0;
         if (c.stem3) p.X = e->x3;               // `x` is ignored: the operand is the framed NHWC3 image
@@ -1144,34 +1165,33 @@ void conv_fwd(fm_engine* e, int ci, const float* S, const float* x, float* y, in
     const int bn = igemm_tile_n(c.cout_p, c.cin == 3);
     p.tilesN = (p.imgs_per_group * c.hout * c.wout + bn - 1) / bn;
     p.relu = relu;           // 0 none, 1 relu, 2 swish
-    ProfScope ps(e, c.cin == 3 ? 2 : (c.cout_p >= 128 ? 0 : 1), 2.0 * c.macs_per_img * imgs);
-    launch_igemm(p, groups, e->st);
+    ProfScope ps(e, L, c.cin == 3 ? 2 : (c.cout_p >= 128 ? 0 : 1), 2.0 * c.macs_per_img * imgs);
+    launch_igemm(p, groups, L.st);
 }
 
 // tiles per group of the partial sums conv ci's forward left in ws_stats (set by that conv_fwd call; asking for another conv's
 // is a graph error: the buffer holds one conv's partials at a time)
-int stats_tiles(fm_engine* e, int ci, int imgs_per_group, int groups)
+int stats_tiles(fm_engine* e, int ci)
 {
-    (void)imgs_per_group; (void)groups;
     if (e->stats_conv != ci) soft(e, hipErrorInvalidValue);
     return e->stats_tiles_n;
 }
 
 // dx[imgs][hin][win][cin] = dgrad(dy[imgs][hout][wout][cout]); res: optional residual added
 // (for stride-2 convs `acc_cls0` adds the existing dx contents for parity class (0,0))
-void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx, int imgs, const float* res,
+void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int imgs, const float* res,
                 bool acc_cls0, const unsigned short* dyp = nullptr)
 {
     Conv& c = e->convs[ci];
     if (e->planes && c.ncls > 0 && c.cls[0].bm_off >= 0 &&
         pconv_takes(c.cin_p, c.cout_p, (long long)imgs * c.hout * c.wout, c.wout)) {
         const long long xp_pix = (long long)imgs * c.hout * c.wout;
-        if (!dyp) dyp = scratch_planes(e, dy, xp_pix, c.cout_p);
+        if (!dyp) dyp = scratch_planes(e, L, dy, xp_pix, c.cout_p);
         for (int k = 0; k < c.ncls; ++k) {
             DgradClass& d = c.cls[k];
             IgemmParams p{};
             p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d + d.bm_off;
-            p.Y = dx; p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+            p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
             p.ntaps = d.taps.n;
             for (int t = 0; t < d.taps.n; ++t) { p.dh[t] = d.dh[t]; p.dw[t] = d.dw[t]; }
             p.res = res ? res : ((acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
@@ -1186,8 +1206,8 @@ void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx
             p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
             p.tilesN = (imgs * p.Hg * p.Wg + pconv_tile_n(c.cin_p) - 1) / pconv_tile_n(c.cin_p);
             p.relu = 0;
-            ProfScope ps(e, (c.cin_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
-            launch_pconv(p, 1, e->st);
+            ProfScope ps(e, L, (c.cin_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
+            launch_pconv(p, 1, L.st);
         }
         return;
     }
@@ -1195,19 +1215,19 @@ void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx
     if (e->precision && c.k == 1) {          // dX = dY W: the same streaming kernel with the transposed bf16 shadow
         PwParams q{};
         q.zeros = e->zeros;
-        q.W = shadow_of(e, S) + c.wbt_off;
+        q.W = e->student.wb + c.wbt_off;
         q.X = reinterpret_cast<const bf16*>(dy); q.Y = reinterpret_cast<bf16*>(dx);
         q.M = c.cin_p; q.K = c.cout_p;
         q.npix = imgs * c.hout * c.wout; q.groups = 1;
         q.res = reinterpret_cast<const bf16*>(res);
         q.HW = c.hout * c.wout;
-        launch_pw_conv(q, e->st);
+        launch_pw_conv(q, L.st);
         return;
     }
     for (int k = 0; k < c.ncls; ++k) {
         DgradClass& d = c.cls[k];
         IgemmParams p{};
-        p.W = d.wpack; p.X = dy; p.Y = dx; p.zeros = e->zeros; p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
+        p.W = d.wpack; p.X = dy; p.Y = dx; p.zeros = e->zeros; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
         p.sp = e->products;
         if (d.sp_off >= 0 && e->wsp_d) p.Wsp = e->wsp_d + d.sp_off;
         p.ntaps = d.taps.n;
@@ -1225,8 +1245,8 @@ void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx
         const int bn = igemm_tile_n(c.cin_p);
         p.tilesN = (imgs * p.Hg * p.Wg + bn - 1) / bn;
         p.relu = 0;
-        ProfScope ps(e, c.cin_p >= 128 ? 0 : 1, 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
-        launch_igemm(p, 1, e->st);
+        ProfScope ps(e, L, c.cin_p >= 128 ? 0 : 1, 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
+        launch_igemm(p, 1, L.st);
     }
 }
 
@@ -1235,7 +1255,7 @@ void conv_dgrad(fm_engine* e, int ci, const float* S, const float* dy, float* dx
 // 3x3's class (0,0) -- the same dy pixel -- and the same output grid: its K-steps ride behind that job's own, with dyd's planes
 // as the job's second operand.  Every element of dx is written once; nothing is read back.  false = the shapes are not of that
 // kind (or not planes mode): the caller runs the two conv_dgrad calls.
-bool block_dgrad(fm_engine* e, int c1i, int dsi, const float* dy1, const float* dyd, float* dx, int imgs,
+bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, const float* dyd, float* dx, int imgs,
                  const unsigned short* dy1p = nullptr, const unsigned short* dydp = nullptr)
 {
     Conv& c = e->convs[c1i];
@@ -1251,16 +1271,16 @@ bool block_dgrad(fm_engine* e, int c1i, int dsi, const float* dy1, const float* 
         return false;
     const DgradClass& c0 = c.cls[0];
     if (c0.ph != 0 || c0.pw != 0 || c0.taps.n != 1 || c0.dh[0] != 0 || c0.dw[0] != 0) return false;
-    if (!dy1p) dy1p = scratch_planes(e, dy1, xp_pix, c.cout_p);
+    if (!dy1p) dy1p = scratch_planes(e, L, dy1, xp_pix, c.cout_p);
     if (!dydp) {
         if ((size_t)xp_pix * d.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return true; }
-        k_split_planes(dyd, e->xp_scratch2, xp_pix, d.cout_p, e->st);
+        k_split_planes(dyd, e->xp_scratch2, xp_pix, d.cout_p, L.st);
         dydp = e->xp_scratch2;
     }
     if (!dy1p) return true;                    // (scratch_planes reported it)
     IgemmParams p{};
     p.Xp = dy1p; p.Xp2 = dydp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d;
-    p.Y = dx; p.slab = e->sk_slab; p.counters = e->sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+    p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
     p.M = c.cin_p;
     p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
     p.sg = 1;
@@ -1283,13 +1303,13 @@ bool block_dgrad(fm_engine* e, int c1i, int dsi, const float* dy1, const float* 
     p.job[0].cib += d.cout_p >> 5;
     p.job[0].wofs2 = (unsigned)(d0.bm_off * 2);
     // family 6 / 7 = pconv_kernel<4 | 2, ..., false>; the launch's algorithmic FLOPs = both convs'
-    ProfScope ps(e, (c.cin_p >= 128 ? 0 : 1) + 6, 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
-    launch_pconv(p, 1, e->st);
+    ProfScope ps(e, L, (c.cin_p >= 128 ? 0 : 1) + 6, 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
+    launch_pconv(p, 1, L.st);
     return true;
 }
 
 // xp / dyp (planes mode): block-major planes of x / dy (null = made here from the fp32 tensors: test hooks)
-void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs, const Prologue* pro = nullptr,
+void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, int imgs, const Prologue* pro = nullptr,
                 int pix_per_group = 0, const unsigned short* xp = nullptr, const unsigned short* dyp = nullptr)
 {
     const Conv& c = e->convs[ci];
@@ -1297,23 +1317,23 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
         pwgrad_takes(c.cout_p, c.cin_p, c.k, (long long)imgs * c.hout * c.wout, (long long)imgs * c.hin * c.win, c.win, c.pad)) {
         PwgradParams q{};
         q.npix = (long long)imgs * c.hout * c.wout; q.xpix = (long long)imgs * c.hin * c.win;
-        if (!xp) xp = scratch_planes(e, x, q.xpix, c.cin_p);
+        if (!xp) xp = scratch_planes(e, L, x, q.xpix, c.cin_p);
         if (!dyp) {
             if ((size_t)q.npix * c.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return; }
-            k_split_planes(dy, e->xp_scratch2, q.npix, c.cout_p, e->st);
+            k_split_planes(dy, e->xp_scratch2, q.npix, c.cout_p, L.st);
             dyp = e->xp_scratch2;
         }
-        q.dYp = dyp; q.Xp = xp; q.slab = e->ws_slab;
+        q.dYp = dyp; q.Xp = xp; q.slab = L.ws_slab;
         q.M = c.cout_p; q.Nw = c.Kw;
         q.Ho = c.hout; q.Wo = c.wout; q.Hi = c.hin; q.Wi = c.win; q.Ci = c.cin_p; q.stride = c.stride; q.pad = c.pad; q.ksz = c.k;
         q.sp = e->products;
         int sk;
         {
             const bool ring = pwgrad_ring_takes(q);
-            ProfScope ps(e, ring ? 8 : (c.cout_p >= 128 ? 3 : 4), 2.0 * c.macs_per_img * imgs);
-            sk = ring ? launch_pwgrad_ring(q, e->slab_floats, e->st) : launch_pwgrad(q, e->slab_floats, e->st);
+            ProfScope ps(e, L, ring ? 8 : (c.cout_p >= 128 ? 3 : 4), 2.0 * c.macs_per_img * imgs);
+            sk = ring ? launch_pwgrad_ring(q, e->slab_floats, L.st) : launch_pwgrad(q, e->slab_floats, L.st);
         }
-        if (sk > 0) k_reduce_slabs(e->ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, e->st);
+        if (sk > 0) k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
         else soft(e, hipErrorInvalidValue);
         return;
     }
@@ -1322,16 +1342,16 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
     if (e->precision && (c.k == 1 || stem16)) {
         PwWgradParams q{};
         q.dY = reinterpret_cast<const bf16*>(dy); q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x);
-        q.slab = e->ws_slab; q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p; q.npix = imgs * c.hout * c.wout;
+        q.slab = L.ws_slab; q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p; q.npix = imgs * c.hout * c.wout;
         if (pro && pro->gate) { q.psc = pro->psc; q.psh = pro->psh; q.gate = pro->gate; }
         q.HW = c.hout * c.wout; q.pix_per_group = pix_per_group ? pix_per_group : q.npix;
-        const int sk = launch_pw_wgrad(q, e->slab_floats, e->st);
-        if (sk > 0) k_reduce_slabs(e->ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, e->st);
+        const int sk = launch_pw_wgrad(q, e->slab_floats, L.st);
+        if (sk > 0) k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
         else g_err = "pw_wgrad: shape not handled";
         return;
     }
     WgradParams p{};
-    p.dY = dy; p.X = x; p.slab = e->ws_slab; p.tab = c.tab; p.zeros = e->zeros;
+    p.dY = dy; p.X = x; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
     p.sp = e->products;
     p.M = c.cout_p; p.Nw = c.Kw;
     p.Ho = c.hout; p.Wo = c.wout; p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p; p.stride = c.stride;
@@ -1341,11 +1361,11 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
         if (c.cin == 3) { p.gather_k = c.k; p.gather_pad = c.pad; p.gather_kw_p = c.kw_p; }
         int sk;
         {
-            ProfScope ps(e, 4, 2.0 * c.macs_per_img * imgs);
-            sk = launch_wgrad_skinny(p, e->slab_floats, e->st);
+            ProfScope ps(e, L, 4, 2.0 * c.macs_per_img * imgs);
+            sk = launch_wgrad_skinny(p, e->slab_floats, L.st);
         }
         if (sk > 0) {
-            k_reduce_slabs(e->ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, e->st);
+            k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
             return;
         }
     }
@@ -1365,34 +1385,34 @@ void conv_wgrad(fm_engine* e, int ci, const float* x, const float* dy, int imgs,
     p.pix_per_split = (((p.npix + splits - 1) / splits) + 31) & ~31;
     splits = (p.npix + p.pix_per_split - 1) / p.pix_per_split;
     {
-        ProfScope ps(e, c.cout_p >= 128 ? 3 : (c.cin == 3 ? 5 : 4), 2.0 * c.macs_per_img * imgs);
-        if (!launch_wgrad(p, splits, e->st)) soft(e, hipErrorInvalidValue);     // surfaces through STEP_DONE as FM_ERR_HIP
+        ProfScope ps(e, L, c.cout_p >= 128 ? 3 : (c.cin == 3 ? 5 : 4), 2.0 * c.macs_per_img * imgs);
+        if (!launch_wgrad(p, splits, L.st)) soft(e, hipErrorInvalidValue);     // surfaces through STEP_DONE as FM_ERR_HIP
     }
-    k_reduce_slabs(e->ws_slab, e->grad + c.w_off, splits, (int64_t)c.w_numel, e->st);
-    if (c.stem3) k_stem3_mask_grad(e->grad + c.w_off, c.cout_p, e->st);
+    k_reduce_slabs(L.ws_slab, e->grad + c.w_off, splits, (int64_t)c.w_numel, L.st);
+    if (c.stem3) k_stem3_mask_grad(e->grad + c.w_off, c.cout_p, L.st);
 }
 
 // frozen statistics: mean / istd / scale / shift of every group from the running statistics, which stay as they are
-void bn_fwd_fixed(fm_engine* e, Bn& b, int groups)
+void bn_fwd_fixed(fm_engine* e, Lane& L, Bn& b, int groups)
 {
-    k_bn_finalize_frozen(groups, b.C, e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
-                         e->state + e->off_rm + b.ch_off, e->state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale, b.shift,
-                         e->bn_eps, e->st, e->dev_err);
+    k_bn_finalize_frozen(groups, b.C, e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
+                         e->student.state + e->off_rm + b.ch_off, e->student.state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale, b.shift,
+                         e->bn_eps, L.st, e->dev_err);
 }
 
 // BN statistics of conv `ci`'s output (partials left in ws_stats by the conv epilogue)
-void bn_fwd_finalize(fm_engine* e, int ci, int groups, int imgs_per_group)
+void bn_fwd_finalize(fm_engine* e, Lane& L, int ci, int groups, int imgs_per_group, BnMode mode)
 {
     const Conv& c = e->convs[ci];
     const int bi = c.bn;
     Bn& b = e->bns[bi];
-    if (e->bn_fixed) { bn_fwd_fixed(e, b, groups); return; }
-    const bool run = !e->bn_no_update;
-    k_bn_finalize(e->ws_stats, groups, stats_tiles(e, ci, imgs_per_group, groups), b.C, imgs_per_group * c.hout * c.wout,
-                  e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
-                  run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
-                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, e->st, e->dev_err);
-    if (run) e->counters[bi] += groups;
+    if (mode == BnMode::Frozen) { bn_fwd_fixed(e, L, b, groups); return; }
+    const bool run = mode == BnMode::Batch;
+    k_bn_finalize(e->ws_stats, groups, stats_tiles(e, ci), b.C, imgs_per_group * c.hout * c.wout,
+                  e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
+                  run ? e->student.state + e->off_rm + b.ch_off : nullptr, run ? e->student.state + e->off_rv + b.ch_off : nullptr, b.mean,
+                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, L.st, e->dev_err);
+    if (run) e->student.counters[bi] += groups;
 }
 
 // backward through BN bi: dz (+ optional relu mask source z) -> dy ; optional masked grad out
@@ -1400,8 +1420,8 @@ void bn_fwd_finalize(fm_engine* e, int ci, int groups, int imgs_per_group)
 // recomputed from y, which both passes read anyway, and z is not read (FM_BN_MASK_FROM_Y=0 reads z as before)
 // dyp (planes mode): also write dy's block-major planes (what the data gradient reads)
 // zh (planes mode): z is kept only as planes: the mask is the sign of its h plane (z is then null)
-void bn_bwd(fm_engine* e, int bi, const float* dz, const float* z, float* dy, float* dyh_out, int groups,
-            int imgs_per_group, bool z_is_relu_of_bn = false, unsigned short* dyp = nullptr, const unsigned short* zh = nullptr)
+void bn_bwd(fm_engine* e, Lane& L, int bi, const float* dz, const float* z, float* dy, float* dyh_out, int groups,
+            int imgs_per_group, bool frozen, bool z_is_relu_of_bn = false, unsigned short* dyp = nullptr, const unsigned short* zh = nullptr)
 {
     const Conv& c = e->convs[bi];
     Bn& b = e->bns[bi];
@@ -1410,45 +1430,46 @@ void bn_bwd(fm_engine* e, int bi, const float* dz, const float* z, float* dy, fl
     const int from_y = fy ? atoi(fy) : 1;
     const float *msc = nullptr, *msh = nullptr;
     if (z_is_relu_of_bn && (z || zh) && (from_y || !z)) { msc = b.scale; msh = b.shift; z = nullptr; zh = nullptr; }
-    k_bn_bwd_reduce(dz, z, c.y, b.mean, b.istd, e->ws_part, groups, pix, b.C, e->st, msc, msh, zh);
-    k_bn_bwd_finalize(e->ws_part, groups, bn_bwd_blocks(pix), b.C, pix, e->state + e->off_gamma + b.ch_off, b.mean,
+    k_bn_bwd_reduce(dz, z, c.y, b.mean, b.istd, e->ws_part, groups, pix, b.C, L.st, msc, msh, zh);
+    k_bn_bwd_finalize(e->ws_part, groups, bn_bwd_blocks(pix), b.C, pix, e->student.state + e->off_gamma + b.ch_off, b.mean,
                       b.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b.ch_off,
-                      e->grad + e->off_beta + b.ch_off, e->st, e->bwd_fixed);
-    if (dyp) k_bn_bwd_apply_planes(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyp, dyh_out, groups, pix, b.C, e->st, msc, msh, zh);
-    else k_bn_bwd_apply(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyh_out, groups, pix, b.C, e->st, msc, msh);
+                      e->grad + e->off_beta + b.ch_off, L.st, frozen);
+    if (dyp) k_bn_bwd_apply_planes(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyp, dyh_out, groups, pix, b.C, L.st, msc, msh, zh);
+    else k_bn_bwd_apply(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyh_out, groups, pix, b.C, L.st, msc, msh);
 }
 
-void to_nhwc4(fm_engine* e, const float* const* xs, int groups, int B)
+void to_nhwc4(fm_engine* e, Lane& L, const float* const* xs, int groups, int B)
 {
     if (e->precision && e->model == 1) {      // bf16 EfficientNet: the stem reads an im2col matrix (teacher, student and wgrad share it)
         const Conv& c = e->convs[e->c_stem];
         for (int g = 0; g < groups; ++g)
             k_stem_im2col(xs[g], reinterpret_cast<bf16*>(e->stem_col) + (size_t)g * B * c.hout * c.wout * c.Kw, B, e->H, e->W, c.hout,
-                          c.wout, c.k, c.stride, c.pad, c.pad, e->st);
+                          c.wout, c.k, c.stride, c.pad, c.pad, L.st);
         return;
     }
     if (e->convs[0].stem3) {
         const Conv& c = e->convs[0];
         for (int g = 0; g < groups; ++g)
-            k_frame_nhwc3(xs[g], e->x3 + (size_t)g * B * c.Hp * c.Wp * 3, B, e->H, e->W, c.Hp, c.Wp, 3, 3, 0, e->st,
+            k_frame_nhwc3(xs[g], e->x3 + (size_t)g * B * c.Hp * c.Wp * 3, B, e->H, e->W, c.Hp, c.Wp, 3, 3, 0, L.st,
                           e->stem_rows ? e->x3p + (size_t)g * B * c.Hp * c.Wp * 4 : nullptr, e->x3p_plane_elems);
         return;
     }
     for (int g = 0; g < groups; ++g)
-        k_nchw_to_nhwc4(xs[g], e->x4 + (size_t)g * B * e->H * e->W * 4, B, e->H, e->W, e->st);
+        k_nchw_to_nhwc4(xs[g], e->x4 + (size_t)g * B * e->H * e->W * 4, B, e->H, e->W, L.st);
 }
 
-// train-mode forward of groups*B images already in e->x4; fills feat/logits
-void forward_train(fm_engine* e, int groups, int B)
+// train-mode forward (the student's) of groups*B images already in e->x4; fills A and feat/logits
+void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mode)
 {
     const int imgs = groups * B;
-    const float* S = e->state;
+    const Weights& W = e->student;
+    const float* S = W.state;
     Conv& c0 = e->convs[0];
-    conv_fwd(e, 0, S, e->x4, c0.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats);
-    bn_fwd_finalize(e, 0, groups, B);
+    conv_fwd(e, L, 0, W, e->x4, c0.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats);
+    bn_fwd_finalize(e, L, 0, groups, B, mode);
     const bool pm = e->planes;
-    if (pm) k_stem_pool_planes(c0.y, e->bns[0].scale, e->bns[0].shift, e->p0, e->idx0, e->p0p, groups, B, c0.hout, c0.wout, 64, e->st);
-    else k_stem_pool(c0.y, e->bns[0].scale, e->bns[0].shift, e->p0, e->idx0, groups, B, c0.hout, c0.wout, 64, e->st);
+    if (pm) k_stem_pool_planes(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, A.p0p, groups, B, c0.hout, c0.wout, 64, L.st);
+    else k_stem_pool(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, groups, B, c0.hout, c0.wout, 64, L.st);
     // BatchNorm apply.  Planes mode: the activations z1 / out exist ONLY as planes (what the conv GEMMs read; the residual add
     // and the ReLU masks of the backward re-form the fp32 value / its sign from them) -- except the last block's `out`, which
     // feeds the average pool: fp32 only
@@ -1456,120 +1477,126 @@ void forward_train(fm_engine* e, int groups, int B)
                      unsigned short* outp, int pix, int C) {
         const float *s2 = y2 ? e->bns[b2].scale : nullptr, *h2 = y2 ? e->bns[b2].shift : nullptr;
         if (pm && outp)
-            k_bn_apply_planes(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, nullptr, outp, groups, pix, C, 1, e->st, resp);
+            k_bn_apply_planes(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, nullptr, outp, groups, pix, C, 1, L.st, resp);
         else
-            k_bn_apply(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, out, groups, pix, C, 1, e->st);
+            k_bn_apply(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, out, groups, pix, C, 1, L.st);
     };
-    const float* cur = e->p0;
-    const unsigned short* curp = e->p0p;
+    const float* cur = A.p0;
+    const unsigned short* curp = A.p0p;
     bool cur_f32 = true;                 // is `cur` valid as fp32?  (p0 is written both ways)
     for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
-        Block& blk = e->blocks[bi];
+        const Block& blk = e->blocks[bi];
+        BlockActs& a = A.blk[bi];
         Conv& c1 = e->convs[blk.c1];
         Conv& c2 = e->convs[blk.c2];
         const int pix = B * c1.hout * c1.wout;
         const bool last = bi + 1 == e->blocks.size();
-        conv_fwd(e, blk.c1, S, cur, c1.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-        bn_fwd_finalize(e, blk.c1, groups, B);
-        apply(c1.y, blk.c1, nullptr, nullptr, nullptr, -1, blk.z1, blk.z1p, pix, c1.cout);
-        conv_fwd(e, blk.c2, S, blk.z1, c2.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, blk.z1p);
-        bn_fwd_finalize(e, blk.c2, groups, B);
-        unsigned short* outp = (pm && !last) ? blk.outp : nullptr;
+        conv_fwd(e, L, blk.c1, W, cur, c1.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
+        bn_fwd_finalize(e, L, blk.c1, groups, B, mode);
+        apply(c1.y, blk.c1, nullptr, nullptr, nullptr, -1, a.z1, a.z1p, pix, c1.cout);
+        conv_fwd(e, L, blk.c2, W, a.z1, c2.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, a.z1p);
+        bn_fwd_finalize(e, L, blk.c2, groups, B, mode);
+        unsigned short* outp = (pm && !last) ? a.outp : nullptr;
         if (blk.ds >= 0) {
             Conv& cd = e->convs[blk.ds];
-            conv_fwd(e, blk.ds, S, cur, cd.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-            bn_fwd_finalize(e, blk.ds, groups, B);
-            apply(c2.y, blk.c2, nullptr, nullptr, cd.y, blk.ds, blk.out, outp, pix, c2.cout);
+            conv_fwd(e, L, blk.ds, W, cur, cd.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
+            bn_fwd_finalize(e, L, blk.ds, groups, B, mode);
+            apply(c2.y, blk.c2, nullptr, nullptr, cd.y, blk.ds, a.out, outp, pix, c2.cout);
         } else if (pm && !cur_f32) {
             if (last) {      // the last block adds a planes-only residual into an fp32 output: re-form the residual first
-                k_planes_to_f32(curp, e->blocks[bi - 1].out, (long long)imgs * c1.hin * c1.win, c1.cin, e->st);
-                apply(c2.y, blk.c2, e->blocks[bi - 1].out, nullptr, nullptr, -1, blk.out, nullptr, pix, c2.cout);
+                k_planes_to_f32(curp, A.blk[bi - 1].out, (long long)imgs * c1.hin * c1.win, c1.cin, L.st);
+                apply(c2.y, blk.c2, A.blk[bi - 1].out, nullptr, nullptr, -1, a.out, nullptr, pix, c2.cout);
             } else
-                apply(c2.y, blk.c2, nullptr, curp, nullptr, -1, blk.out, outp, pix, c2.cout);
+                apply(c2.y, blk.c2, nullptr, curp, nullptr, -1, a.out, outp, pix, c2.cout);
         } else {
-            apply(c2.y, blk.c2, cur, nullptr, nullptr, -1, blk.out, outp, pix, c2.cout);
+            apply(c2.y, blk.c2, cur, nullptr, nullptr, -1, a.out, outp, pix, c2.cout);
         }
-        cur = blk.out;
-        curp = blk.outp;
+        cur = a.out;
+        curp = a.outp;
         cur_f32 = !(pm && !last);
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, e->st);
-    k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, e->st);
-    if (!e->bn_fixed) e->ev_dirty = true;      // running stats moved
+    k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
+    k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, L.st);
+    if (mode != BnMode::Frozen) e->student.ev_dirty = true;      // running stats moved
 }
 
 // eval-mode forward (BN folded into the conv epilogue) of `imgs` images in e->x4
-void forward_eval(fm_engine* e, const float* S, float* evs, float* evh, bool& dirty, int imgs, float* feat,
-                  float* logits)
+void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
-    if (dirty) {
-        k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, evs, evh, e->n_bn_ch,
-                         e->bn_eps, e->st);
-        dirty = false;
+    const float* S = W.state;
+    if (W.ev_dirty) {
+        k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, W.ev_scale, W.ev_shift, e->n_bn_ch,
+                         e->bn_eps, L.st);
+        W.ev_dirty = false;
     }
-    auto sc = [&](int bi) { return evs + e->bns[bi].ch_off; };
-    auto sh = [&](int bi) { return evh + e->bns[bi].ch_off; };
+    auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
+    auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
     Conv& c0 = e->convs[0];
-    conv_fwd(e, 0, S, e->x4, c0.y, imgs, 1, sc(0), sh(0), nullptr, 1, nullptr);
+    conv_fwd(e, L, 0, W, e->x4, A.stem_y, imgs, 1, sc(0), sh(0), nullptr, 1, nullptr);
     const bool pm = e->planes;
-    if (pm) k_stem_pool_planes(c0.y, nullptr, nullptr, e->p0, nullptr, e->p0p, 1, imgs, c0.hout, c0.wout, 64, e->st);
-    else k_stem_pool(c0.y, nullptr, nullptr, e->p0, nullptr, 1, imgs, c0.hout, c0.wout, 64, e->st);
-    const float* cur = e->p0;
-    const unsigned short* curp = e->p0p;
+    if (pm) k_stem_pool_planes(A.stem_y, nullptr, nullptr, A.p0, nullptr, A.p0p, 1, imgs, c0.hout, c0.wout, 64, L.st);
+    else k_stem_pool(A.stem_y, nullptr, nullptr, A.p0, nullptr, 1, imgs, c0.hout, c0.wout, 64, L.st);
+    const float* cur = A.p0;
+    const unsigned short* curp = A.p0p;
     bool cur_f32 = true;
     for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
-        Block& blk = e->blocks[bi];
+        const Block& blk = e->blocks[bi];
+        BlockActs& a = A.blk[bi];
         // planes mode: z1 and `out` exist only as planes (the next convs read them; the next block's residual add re-forms the fp32
         // values in the epilogue) -- except the last block's `out`, which feeds the average pool: fp32 only
         const bool last = bi + 1 == e->blocks.size();
-        conv_fwd(e, blk.c1, S, cur, pm ? nullptr : blk.z1, imgs, 1, sc(blk.c1), sh(blk.c1), nullptr, 1, nullptr, nullptr, curp,
-                 pm ? blk.z1p : nullptr);
+        conv_fwd(e, L, blk.c1, W, cur, pm ? nullptr : a.z1, imgs, 1, sc(blk.c1), sh(blk.c1), nullptr, 1, nullptr, nullptr, curp,
+                 pm ? a.z1p : nullptr);
         const float* idt = cur;
         const unsigned short* idtp = nullptr;
         if (blk.ds >= 0) {
-            Conv& cd = e->convs[blk.ds];
-            conv_fwd(e, blk.ds, S, cur, cd.y, imgs, 1, sc(blk.ds), sh(blk.ds), nullptr, 0, nullptr, nullptr, curp);
-            idt = cd.y;
+            conv_fwd(e, L, blk.ds, W, cur, a.ds_y, imgs, 1, sc(blk.ds), sh(blk.ds), nullptr, 0, nullptr, nullptr, curp);
+            idt = a.ds_y;
         } else if (!cur_f32) { idt = nullptr; idtp = curp; }
         const bool planes_only = pm && !last;
-        conv_fwd(e, blk.c2, S, blk.z1, planes_only ? nullptr : blk.out, imgs, 1, sc(blk.c2), sh(blk.c2), idt, 1, nullptr, nullptr,
-                 blk.z1p, planes_only ? blk.outp : nullptr, idtp);
-        cur = blk.out;
-        curp = blk.outp;
+        conv_fwd(e, L, blk.c2, W, a.z1, planes_only ? nullptr : a.out, imgs, 1, sc(blk.c2), sh(blk.c2), idt, 1, nullptr, nullptr,
+                 a.z1p, planes_only ? a.outp : nullptr, idtp);
+        cur = a.out;
+        curp = a.outp;
         cur_f32 = !planes_only;
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    k_avgpool(cur, DT_F32, feat, imgs, cl.hout * cl.wout, 512, e->st);
-    k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, e->st);
+    k_avgpool(cur, DT_F32, feat, imgs, cl.hout * cl.wout, 512, L.st);
+    k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, L.st);
 }
 
-// transposed weight packs of every data-gradient GEMM, all in ONE launch
+// Everything derived from the weights is (re)made on the main lane, where the weights change.
+// The student's: transposed weight packs of every data-gradient GEMM, all in ONE launch, and the forward shadows
 void ensure_packed(fm_engine* e)
 {
     if (!e->wpack_dirty) return;
+    Lane& L = e->main;
+    Weights& W = e->student;
     e->stem_dpack_stale = true;
-    if (e->precision) launch_cast_weights(e->state, e->wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, e->st);
-    else if (e->n_pack_jobs) k_pack_dgrad_all(e->state, e->pack_jobs, e->n_pack_jobs, e->n_pack_blocks, e->st);
+    if (e->precision) launch_cast_weights(W.state, W.wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, L.st);
+    else if (e->n_pack_jobs) k_pack_dgrad_all(W.state, e->pack_jobs, e->n_pack_jobs, e->n_pack_blocks, L.st);
     if (e->planes) {
-        k_split_weights_bm(e->state, e->wbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, e->st);
-        k_split_weights_bm(nullptr, e->wbm_d, e->bm_d, e->n_bm_d, e->n_bm_d_blocks, e->st);      // planes of the packs just made
-        if (e->stem_rows) k_stem_weight_planes(e->state + e->convs[0].w_off, e->wst, e->convs[0].Kw, e->st);
+        k_split_weights_bm(W.state, W.wbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, L.st);
+        k_split_weights_bm(nullptr, e->wbm_d, e->bm_d, e->n_bm_d, e->n_bm_d_blocks, L.st);      // planes of the packs just made
+        if (e->stem_rows) k_stem_weight_planes(W.state + e->convs[0].w_off, W.wst, e->convs[0].Kw, L.st);
     } else {
-        k_split_weights(e->state, e->wsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, e->st);
-        k_split_weights(nullptr, e->wsp_d, e->split_d, e->n_split_d, e->n_split_d_blocks, e->st);     // planes of the packs just made
+        k_split_weights(W.state, W.wsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, L.st);
+        k_split_weights(nullptr, e->wsp_d, e->split_d, e->n_split_d, e->n_split_d_blocks, L.st);     // planes of the packs just made
     }
     e->wpack_dirty = false;
 }
 void ensure_teacher_shadow(fm_engine* e)
 {
     if (!e->twb_dirty) return;
-    if (e->precision) launch_cast_weights(e->tstate, e->twb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, e->st);
+    Lane& L = e->main;
+    Weights& W = e->teacher;
+    if (e->precision) launch_cast_weights(W.state, W.wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, L.st);
     else if (e->planes) {
-        k_split_weights_bm(e->tstate, e->twbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, e->st);
-        if (e->stem_rows) k_stem_weight_planes(e->tstate + e->convs[0].w_off, e->twst, e->convs[0].Kw, e->st);
+        k_split_weights_bm(W.state, W.wbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, L.st);
+        if (e->stem_rows) k_stem_weight_planes(W.state + e->convs[0].w_off, W.wst, e->convs[0].Kw, L.st);
     }
-    else k_split_weights(e->tstate, e->twsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, e->st);
+    else k_split_weights(W.state, W.wsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, L.st);
     e->twb_dirty = false;
 }
 
@@ -1580,25 +1607,25 @@ int ensure_stem_dpack(fm_engine* e)
     if (e->model != 0) return FM_OK;
     const Conv& c0 = e->convs[0];
     if (!e->stem_dpack) { DALLOC(e->stem_dpack, stem_dgrad_pack_floats()); e->stem_dpack_stale = true; }
-    if (e->stem_dpack_stale) k_stem_dgrad_pack(e->state + c0.w_off, e->stem_dpack, c0.Kw, c0.kw_p, c0.cin_p, e->st);
+    if (e->stem_dpack_stale) k_stem_dgrad_pack(e->student.state + c0.w_off, e->stem_dpack, c0.Kw, c0.kw_p, c0.cin_p, e->main.st);
     e->stem_dpack_stale = false;
     return FM_OK;
 }
-void stem_dgrad(fm_engine* e, const void* dy, float* dx, int imgs, bool nhwc)
+void stem_dgrad(fm_engine* e, Lane& L, const void* dy, float* dx, int imgs, bool nhwc)
 {
     const Conv& c = e->convs[e->model == 1 ? e->c_stem : 0];
     if (e->model == 1)
-        k_eff_stem_dgrad(dy, e->dt, e->state + c.w_off, dx, imgs, c.hin, c.win, c.hout, c.wout, c.pad, c.pad, c.Kw, c.kw_p, c.cin_p,
-                         nhwc, e->st);
-    else k_stem_dgrad((const float*)dy, e->stem_dpack, dx, imgs, c.hout, c.wout, c.hin, c.win, nhwc, e->st);
+        k_eff_stem_dgrad(dy, e->dt, e->student.state + c.w_off, dx, imgs, c.hin, c.win, c.hout, c.wout, c.pad, c.pad, c.Kw, c.kw_p, c.cin_p,
+                         nhwc, L.st);
+    else k_stem_dgrad((const float*)dy, e->stem_dpack, dx, imgs, c.hout, c.wout, c.hin, c.win, nhwc, L.st);
 }
-// the views' input gradients the pending backward was asked for (fm_backward_grads_x), from the stem's complete dy
-void stem_dgrad_views(fm_engine* e, const void* dy, int groups, int B)
+// the views' input gradients the backward was asked for (fm_backward_grads_x), from the stem's complete dy
+void stem_dgrad_views(fm_engine* e, Lane& L, const void* dy, int groups, int B, float* const* dx)
 {
     const Conv& c = e->convs[e->model == 1 ? e->c_stem : 0];
     const size_t view_bytes = (size_t)B * c.hout * c.wout * c.cout_p * (e->dt == DT_BF16 ? 2 : 4);
     for (int g = 0; g < groups && g < 2; ++g)
-        if (e->dx_out[g]) stem_dgrad(e, (const char*)dy + g * view_bytes, e->dx_out[g], B, false);
+        if (dx[g]) stem_dgrad(e, L, (const char*)dy + g * view_bytes, dx[g], B, false);
 }
 
 // optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2); g = e->grad (fused steps)
@@ -1608,22 +1635,51 @@ void adam_step(fm_engine* e, const float* g)
     e->adam_t += 1;
     const double bc1 = 1.0 - pow((double)e->hp.beta1, (double)e->adam_t);
     const double bc2 = 1.0 - pow((double)e->hp.beta2, (double)e->adam_t);
-    k_adam(e->state, g, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
-           e->hp.weight_decay, (float)bc1, (float)sqrt(bc2), e->st, e->dev_err);
-    e->ev_dirty = true;
+    k_adam(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
+           e->hp.weight_decay, (float)bc1, (float)sqrt(bc2), e->main.st, e->dev_err);
+    e->student.ev_dirty = true;
     e->wpack_dirty = true;
     ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
 }
 
-// backward from e->dlogits (and e->dfeat_dev) through the graph saved by forward_train into e->grad, then Adam unless
-// step is false (fm_backward_grads)
-void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
+// Weight gradients on the side lane (side_w; otherwise everything below is a no-op that hands back the main lane).  A weight
+// gradient reads a gradient tensor the main lane's data-gradient chain has just produced, and nothing waits for it before Adam.
+// The tensors are double-buffered by block parity: side_begin records "tensor k of parity par produced" on the main lane, makes
+// the side lane wait for it and returns the lane to launch the weight gradient on; side_end records "consumed" behind it;
+// side_guard makes the main lane wait for that before it overwrites the tensor two blocks later; side_join brings every
+// weight gradient back to the main lane before the optimizer reads e->grad.
+Lane& side_begin(fm_engine* e, int k, int par)
+{
+    if (!e->side_w) return e->main;
+    soft(e, hipEventRecord(e->ev_p[k][par], e->main.st));
+    soft(e, hipStreamWaitEvent(e->side.st, e->ev_p[k][par], 0));
+    return e->side;
+}
+void side_end(fm_engine* e, int k, int par)
+{
+    if (e->side_w) soft(e, hipEventRecord(e->ev_c[k][par], e->side.st));
+}
+void side_guard(fm_engine* e, int k, int par)
+{
+    if (e->side_w) soft(e, hipStreamWaitEvent(e->main.st, e->ev_c[k][par], 0));
+}
+void side_join(fm_engine* e)
+{
+    if (!e->side_w) return;
+    soft(e, hipEventRecord(e->ev_wdone, e->side.st));
+    soft(e, hipStreamWaitEvent(e->main.st, e->ev_wdone, 0));
+}
+
+// backward from e->dlogits (and bw.dfeat) through the student's activation set, as forward_train left it, into e->grad on the
+// main lane, the weight gradients on the side lane; then Adam unless bw.step is false (fm_backward_grads)
+void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
 {
     const int imgs = groups * B;
-    const float* S = e->state;
+    Lane& L = e->main;
+    const Acts& A = e->acts;
+    const float* S = e->student.state;
     const Conv& cl = e->convs[e->blocks.back().c2];
-    // side_w (stream_mode 0): the weight gradients run on the side stream next to the BN-backward / data-gradient chain
-    // (d y2, d y_ds, d y1 double-buffered by block parity, own slab workspace) -- same scheme as eff_backward_and_step
+    // side_w (stream_mode 0): d y2, d y_ds, d y1 double-buffered by block parity for the weight gradients on the side lane
     const bool sw = e->side_w;
     float* GBp[2] = {e->GB, sw ? e->GB2 : e->GB};
     float* GCp[2] = {e->GC, sw ? e->GC2 : e->GC};
@@ -1632,65 +1688,48 @@ void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
     unsigned short* PB[2] = {e->GBp, sw ? e->GB2p : e->GBp};
     unsigned short* PC[2] = {e->GCp, sw ? e->GC2p : e->GCp};
     unsigned short* PD[2] = {e->GDp, sw ? e->GD2p : e->GDp};
-    hipStream_t main_st = e->st;
-    auto side_begin = [&](int k, int par) {
-        if (!sw) return;
-        soft(e, hipEventRecord(e->ev_p[k][par], main_st));
-        soft(e, hipStreamWaitEvent(e->st2, e->ev_p[k][par], 0));
-        e->st = e->st2;
-        std::swap(e->ws_slab, e->ws_slab2);
-    };
-    auto side_end = [&](int k, int par) {
-        if (!sw) return;
-        std::swap(e->ws_slab, e->ws_slab2);
-        soft(e, hipEventRecord(e->ev_c[k][par], e->st2));
-        e->st = main_st;
-    };
-    auto guard = [&](int k, int par) { if (sw) soft(e, hipStreamWaitEvent(main_st, e->ev_c[k][par], 0)); };
     k_fc_bwd(e->dlogits, e->feat, S + e->off_fcw, nullptr, e->grad + e->off_fcw, e->grad + e->off_fcb, e->GA, DT_F32, imgs,
-             512, e->C, cl.hout * cl.wout, e->st, e->dfeat_dev);
+             512, e->C, cl.hout * cl.wout, L.st, bw.dfeat);
     float *ga = e->GA, *ge = e->GE;
     for (int b = (int)e->blocks.size() - 1; b >= 0; --b) {
-        Block& blk = e->blocks[b];
+        const Block& blk = e->blocks[b];
+        const BlockActs& a = A.blk[b];
         const int par = b & 1;
         float *GB = GBp[par], *GC = GCp[par], *GD = GDp[par];
         unsigned short *gbp = pm ? PB[par] : nullptr, *gcp = pm ? PC[par] : nullptr, *gdp = pm ? PD[par] : nullptr;
-        const float* in = b == 0 ? e->p0 : e->blocks[b - 1].out;
+        const float* in = b == 0 ? A.p0 : A.blk[b - 1].out;
         // out = relu(bn2(y2) + identity): masked grad dyh goes to bn2 and to the identity path
         // planes mode: d y2 / d y_ds / d y1 exist only as planes (read by the data gradients and the weight gradients); the ReLU
         // mask of `out` is the sign of its h plane (the last block's `out` is fp32: it feeds the average pool)
         const bool last = b + 1 == (int)e->blocks.size();
-        guard(0, par);
-        if (pm && !last) bn_bwd(e, blk.c2, ga, nullptr, nullptr, ga, groups, B, false, gbp, blk.outp);
-        else bn_bwd(e, blk.c2, ga, blk.out, pm ? nullptr : GB, ga, groups, B, false, gbp);
-        if (blk.ds >= 0) { guard(1, par); bn_bwd(e, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, false, gcp); }
+        side_guard(e, 0, par);
+        if (pm && !last) bn_bwd(e, L, blk.c2, ga, nullptr, nullptr, ga, groups, B, bw.frozen, false, gbp, a.outp);
+        else bn_bwd(e, L, blk.c2, ga, a.out, pm ? nullptr : GB, ga, groups, B, bw.frozen, false, gbp);
+        if (blk.ds >= 0) { side_guard(e, 1, par); bn_bwd(e, L, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, bw.frozen, false, gcp); }
         // Where a weight gradient enters the side stream (round 6): behind the data gradient of the same conv, i.e. beside the
         // NEXT BatchNorm-backward passes of the main stream: a streaming kernel lives beside a GEMM's waves on a CU (the GEMMs leave
         // it the registers since their K-steps run row-major), two GEMMs do not (LDS).  Entering as soon as its dy exists put two
         // GEMMs beside each other and left the BatchNorm-backward passes that follow with nothing beside them.
-        guard(2, par);
-        conv_dgrad(e, blk.c2, S, GB, GD, imgs, nullptr, false, gbp);
-        side_begin(0, par);
-        conv_wgrad(e, blk.c2, blk.z1, GB, imgs, nullptr, 0, pm ? blk.z1p : nullptr, gbp);
-        side_end(0, par);
-        if (pm) bn_bwd(e, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, true, gdp, blk.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
-        else bn_bwd(e, blk.c1, GD, blk.z1, GD, nullptr, groups, B, true);
+        side_guard(e, 2, par);
+        conv_dgrad(e, L, blk.c2, GB, GD, imgs, nullptr, false, gbp);
+        conv_wgrad(e, side_begin(e, 0, par), blk.c2, a.z1, GB, imgs, nullptr, 0, pm ? a.z1p : nullptr, gbp);
+        side_end(e, 0, par);
+        if (pm) bn_bwd(e, L, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, bw.frozen, true, gdp, a.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
+        else bn_bwd(e, L, blk.c1, GD, a.z1, GD, nullptr, groups, B, bw.frozen, true);
         if (blk.ds >= 0) {
-            if (!block_dgrad(e, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
-                conv_dgrad(e, blk.ds, S, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
-                conv_dgrad(e, blk.c1, S, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
+            if (!block_dgrad(e, L, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
+                conv_dgrad(e, L, blk.ds, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
+                conv_dgrad(e, L, blk.c1, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
             }
         } else {
-            conv_dgrad(e, blk.c1, S, GD, ge, imgs, ga, false, gdp);
+            conv_dgrad(e, L, blk.c1, GD, ge, imgs, ga, false, gdp);
         }
-        const unsigned short* inp = pm ? (b == 0 ? e->p0p : e->blocks[b - 1].outp) : nullptr;
-        side_begin(2, par);
-        conv_wgrad(e, blk.c1, in, GD, imgs, nullptr, 0, inp, gdp);
-        side_end(2, par);
+        const unsigned short* inp = pm ? (b == 0 ? A.p0p : A.blk[b - 1].outp) : nullptr;
+        conv_wgrad(e, side_begin(e, 2, par), blk.c1, in, GD, imgs, nullptr, 0, inp, gdp);
+        side_end(e, 2, par);
         if (blk.ds >= 0) {
-            side_begin(1, par);
-            conv_wgrad(e, blk.ds, in, GC, imgs, nullptr, 0, inp, gcp);
-            side_end(1, par);
+            conv_wgrad(e, side_begin(e, 1, par), blk.ds, in, GC, imgs, nullptr, 0, inp, gcp);
+            side_end(e, 1, par);
         }
         std::swap(ga, ge);
     }
@@ -1699,20 +1738,17 @@ void backward_and_step(fm_engine* e, int groups, int B, bool step = true)
         // max-pool backward + BatchNorm backward of the stem in two passes, without the dense intermediate (elementwise.hip)
         Bn& b0 = e->bns[0];
         const int pooled_pg = B * (c0.hout / 2) * (c0.wout / 2), pix = B * c0.hout * c0.wout;
-        k_stem_pool_bn_reduce(ga, e->p0, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, e->st,
-                              e->state + e->off_gamma + b0.ch_off, e->state + e->off_beta + b0.ch_off);
-        k_bn_bwd_finalize(e->ws_part, groups, stem_pool_bn_blocks(pooled_pg), 64, pix, e->state + e->off_gamma + b0.ch_off,
+        k_stem_pool_bn_reduce(ga, A.p0, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, L.st,
+                              e->student.state + e->off_gamma + b0.ch_off, e->student.state + e->off_beta + b0.ch_off);
+        k_bn_bwd_finalize(e->ws_part, groups, stem_pool_bn_blocks(pooled_pg), 64, pix, e->student.state + e->off_gamma + b0.ch_off,
                           b0.mean, b0.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b0.ch_off,
-                          e->grad + e->off_beta + b0.ch_off, e->st, e->bwd_fixed);
-        k_stem_pool_bn_apply(ga, e->p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, e->st);
+                          e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
+        k_stem_pool_bn_apply(ga, A.p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, L.st);
     }
-    stem_dgrad_views(e, e->dyh0, groups, B);
-    conv_wgrad(e, 0, e->x4, e->dyh0, imgs);
-    if (sw) {
-        soft(e, hipEventRecord(e->ev_wdone, e->st2));
-        soft(e, hipStreamWaitEvent(main_st, e->ev_wdone, 0));
-    }
-    if (step) adam_step(e, e->grad);      // optimizer.step()
+    stem_dgrad_views(e, L, e->dyh0, groups, B, bw.dx);
+    conv_wgrad(e, L, 0, e->x4, e->dyh0, imgs);
+    side_join(e);
+    if (bw.step) adam_step(e, e->grad);      // optimizer.step()
 }
 
 // =============================== EfficientNet-B0 graph =================================
@@ -1729,24 +1765,25 @@ bool fuse_for(fm_engine* e, const MBConv& m)
 
 // BN over an arbitrary NHWC tensor (depthwise output): statistics by chan_reduce, then the same finalize
 // sums_ready: ws_part already holds dw_stats_tiles() partials per group (left by the depthwise forward)
-void bn_fwd_tensor(fm_engine* e, int bi, const float* y, int groups, int pix_per_group, int HW, bool sums_ready = false)
+void bn_fwd_tensor(fm_engine* e, Lane& L, int bi, const float* y, int groups, int pix_per_group, int HW, BnMode mode,
+                   bool sums_ready = false)
 {
     Bn& b = e->bns[bi];
-    if (e->bn_fixed) { bn_fwd_fixed(e, b, groups); return; }       // (no statistics pass either)
+    if (mode == BnMode::Frozen) { bn_fwd_fixed(e, L, b, groups); return; }       // (no statistics pass either)
     if (!sums_ready)
         k_chan_reduce(nullptr, e->dt, y, e->dt, nullptr, nullptr, nullptr, nullptr, nullptr, e->ws_part, groups, pix_per_group,
-                      HW, b.C, 0, 0, nullptr, nullptr, e->st);
-    const bool run = !e->bn_no_update;
+                      HW, b.C, 0, 0, nullptr, nullptr, L.st);
+    const bool run = mode == BnMode::Batch;
     k_bn_finalize(e->ws_part, groups, sums_ready ? dw_stats_tiles() : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
-                  e->state + e->off_gamma + b.ch_off, e->state + e->off_beta + b.ch_off,
-                  run ? e->state + e->off_rm + b.ch_off : nullptr, run ? e->state + e->off_rv + b.ch_off : nullptr, b.mean,
-                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, e->st);
-    if (run) e->counters[bi] += groups;
+                  e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
+                  run ? e->student.state + e->off_rm + b.ch_off : nullptr, run ? e->student.state + e->off_rv + b.ch_off : nullptr, b.mean,
+                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, L.st);
+    if (run) e->student.counters[bi] += groups;
 }
 
 // backward through act(bn(y))*rowscale: dz -> dy (may alias dz); writes dgamma/dbeta
-void bnact_bwd(fm_engine* e, int bi, const float* dz, const float* y, float* dy, const float* rowscale, int groups,
-               int pix_per_group, int HW, int act, const float* gate = nullptr, const float* dsv = nullptr,
+void bnact_bwd(fm_engine* e, Lane& L, int bi, const float* dz, const float* y, float* dy, const float* rowscale, int groups,
+               int pix_per_group, int HW, int act, bool frozen, const float* gate = nullptr, const float* dsv = nullptr,
                int ty = -1, int sums_ready = 0)
 {
     Bn& b = e->bns[bi];
@@ -1754,183 +1791,173 @@ void bnact_bwd(fm_engine* e, int bi, const float* dz, const float* y, float* dy,
     // sums_ready > 0: ws_part already holds the two backward sums as that many partials per group (k_se_bwd_bn1)
     if (!sums_ready)
         k_chan_reduce(dz, e->dt, y, ty, b.mean, b.istd, b.scale, b.shift, rowscale, e->ws_part, groups, pix_per_group, HW, b.C,
-                      1, act, gate, dsv, e->st);
+                      1, act, gate, dsv, L.st);
     k_bn_bwd_finalize(e->ws_part, groups, sums_ready ? sums_ready : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
-                      e->state + e->off_gamma + b.ch_off, b.mean, b.istd, e->ca, e->cb, e->cc,
-                      e->grad + e->off_gamma + b.ch_off, e->grad + e->off_beta + b.ch_off, e->st, e->bwd_fixed);
+                      e->student.state + e->off_gamma + b.ch_off, b.mean, b.istd, e->ca, e->cb, e->cc,
+                      e->grad + e->off_gamma + b.ch_off, e->grad + e->off_beta + b.ch_off, L.st, frozen);
     k_bnact_bwd_apply(dz, e->dt, y, ty, e->ca, e->cb, e->cc, b.scale, b.shift, rowscale, dy, groups, pix_per_group, HW,
-                      b.C, act, gate, dsv, e->st);
+                      b.C, act, gate, dsv, L.st);
 }
 
-void eff_forward_train(fm_engine* e, int groups, int B)
+void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mode)
 {
     const int imgs = groups * B;
-    const float* S = e->state;
+    const Weights& W = e->student;
+    const float* S = W.state;
     Conv& cs = e->convs[e->c_stem];
     e->ctx = -1;
-    { OP("conv_fwd"); conv_fwd(e, e->c_stem, S, e->x4, cs.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-    { OP("bn_fwd_finalize"); bn_fwd_finalize(e, e->c_stem, groups, B); }
+    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_stem, W, e->x4, cs.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
+    { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, e->c_stem, groups, B, mode); }
     {
         Bn& b = e->bns[e->bn_stem];
-        { OP("k_bnact_apply"); k_bnact_apply(cs.y, e->dt, b.scale, b.shift, nullptr, nullptr, e->a0, e->dt, groups, B * cs.hout * cs.wout,
-                      cs.hout * cs.wout, b.C, 2, e->st); }
+        { OP(L, "k_bnact_apply"); k_bnact_apply(cs.y, e->dt, b.scale, b.shift, nullptr, nullptr, A.a0, e->dt, groups, B * cs.hout * cs.wout,
+                      cs.hout * cs.wout, b.C, 2, L.st); }
     }
-    const float* cur = e->a0;
+    const float* cur = A.a0;
     for (size_t i = 0; i < e->mbs.size(); ++i) {
-        MBConv& m = e->mbs[i];
+        const MBConv& m = e->mbs[i];
+        MBActs& a = A.mb[i];
         e->ctx = (int)i;
         const int HWi = m.hin * m.win, HWo = m.hout * m.wout;
         const float* a_e = cur;
         if (m.c_exp >= 0) {
             Conv& ce = e->convs[m.c_exp];
-            { OP("exp_fwd"); conv_fwd(e, m.c_exp, S, cur, ce.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-            { OP("bn_fwd_finalize"); bn_fwd_finalize(e, m.c_exp, groups, B); }
+            { OP(L, "exp_fwd"); conv_fwd(e, L, m.c_exp, W, cur, ce.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
+            { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, m.c_exp, groups, B, mode); }
             Bn& b = e->bns[m.bn0];
-            { OP("k_bnact_apply"); k_bnact_apply(ce.y, e->dt, b.scale, b.shift, nullptr, nullptr, m.a_e, e->dt, groups, B * HWi, HWi, b.C, 2, e->st); }
-            a_e = m.a_e;
+            { OP(L, "k_bnact_apply"); k_bnact_apply(ce.y, e->dt, b.scale, b.shift, nullptr, nullptr, a.a_e, e->dt, groups, B * HWi, HWi, b.C, 2, L.st); }
+            a_e = a.a_e;
         }
         bool st_done;
-        { OP("k_dw_fwd"); st_done = k_dw_fwd(a_e, S + m.dw_off, m.y_d, e->dt, nullptr, nullptr, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p,
-                 m.k, m.s, m.pad_t, m.pad_l, 0, e->st, e->ws_slab, e->ws_part, groups); }   // + BN1 batch statistics
-        { OP("bn_fwd_tensor"); bn_fwd_tensor(e, m.bn1, m.y_d, groups, B * HWo, HWo, st_done); }
+        { OP(L, "k_dw_fwd"); st_done = k_dw_fwd(a_e, S + m.dw_off, a.y_d, e->dt, nullptr, nullptr, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p,
+                 m.k, m.s, m.pad_t, m.pad_l, 0, L.st, L.rec, e->ws_part, groups); }   // + BN1 batch statistics
+        { OP(L, "bn_fwd_tensor"); bn_fwd_tensor(e, L, m.bn1, a.y_d, groups, B * HWo, HWo, mode, st_done); }
         {
             // a_d = swish(bn1(y_d)) is never written: the pooling and the gating pass form it on load
             Bn& b = e->bns[m.bn1];
-            { OP("k_se_fwd"); k_se_fwd(m.y_d, e->dt, b.scale, b.shift, B, e->se_pool, S + m.w1_off, S + m.b1_off, S + m.w2_off, S + m.b2_off,
-                     m.sq, m.rpre, m.gate, imgs, HWo, m.ce_p, m.cs, e->st); }
-            if (!fuse_for(e, m)) k_se_scale(m.y_d, e->dt, b.scale, b.shift, B, m.gate, m.a_s, imgs, HWo, m.ce_p, e->st);
+            { OP(L, "k_se_fwd"); k_se_fwd(a.y_d, e->dt, b.scale, b.shift, B, A.se_pool, S + m.w1_off, S + m.b1_off, S + m.w2_off, S + m.b2_off,
+                     a.sq, a.rpre, a.gate, imgs, HWo, m.ce_p, m.cs, L.st); }
+            if (!fuse_for(e, m)) k_se_scale(a.y_d, e->dt, b.scale, b.shift, B, a.gate, a.a_s, imgs, HWo, m.ce_p, L.st);
         }
         Conv& cp = e->convs[m.c_proj];
         if (fuse_for(e, m)) {          // a_s = swish(bn1(y_d)) * gate is formed on the project conv's operand load
-            const Prologue pro{e->bns[m.bn1].scale, e->bns[m.bn1].shift, m.gate};
-            { OP("proj_fwd"); conv_fwd(e, m.c_proj, S, m.y_d, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, &pro); }
+            const Prologue pro{e->bns[m.bn1].scale, e->bns[m.bn1].shift, a.gate};
+            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.y_d, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, &pro); }
         } else
-            { OP("proj_fwd"); conv_fwd(e, m.c_proj, S, m.a_s, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-        { OP("bn_fwd_finalize"); bn_fwd_finalize(e, m.c_proj, groups, B); }
+            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.a_s, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
+        { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, m.c_proj, groups, B, mode); }
         {
             Bn& b = e->bns[m.bn2];
             const float* dc = (m.skip && e->dc_dev) ? e->dc_dev + i * (size_t)imgs : nullptr;
-            { OP("k_bnact_apply"); k_bnact_apply(cp.y, e->dt, b.scale, b.shift, m.skip ? cur : nullptr, dc, m.out, e->dt, groups, B * HWo, HWo,
-                          b.C, 0, e->st); }
+            { OP(L, "k_bnact_apply"); k_bnact_apply(cp.y, e->dt, b.scale, b.shift, m.skip ? cur : nullptr, dc, a.out, e->dt, groups, B * HWo, HWo,
+                          b.C, 0, L.st); }
         }
-        cur = m.out;
+        cur = a.out;
     }
     Conv& ch = e->convs[e->c_head];
     const int HWh = ch.hout * ch.wout;
     e->ctx = 100;
-    { OP("conv_fwd"); conv_fwd(e, e->c_head, S, cur, ch.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-    { OP("bn_fwd_finalize"); bn_fwd_finalize(e, e->c_head, groups, B); }
+    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_head, W, cur, ch.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
+    { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, e->c_head, groups, B, mode); }
     {
         Bn& b = e->bns[e->bn_head];
-        { OP("k_bnact_apply"); k_bnact_apply(ch.y, e->dt, b.scale, b.shift, nullptr, nullptr, e->T_mid, e->dt, groups, B * HWh, HWh, b.C, 2, e->st); }
+        { OP(L, "k_bnact_apply"); k_bnact_apply(ch.y, e->dt, b.scale, b.shift, nullptr, nullptr, A.T_mid, e->dt, groups, B * HWh, HWh, b.C, 2, L.st); }
     }
-    { OP("k_avgpool"); k_avgpool(e->T_mid, e->dt, e->feat, imgs, HWh, e->D, e->st); }
+    { OP(L, "k_avgpool"); k_avgpool(A.T_mid, e->dt, e->feat, imgs, HWh, e->D, L.st); }
     const float* h = e->feat;
     if (e->drop_dev) {
-        { OP("k_mul"); k_mul(e->feat, e->drop_dev, e->hfeat, (int64_t)imgs * e->D, e->st); }
+        { OP(L, "k_mul"); k_mul(e->feat, e->drop_dev, e->hfeat, (int64_t)imgs * e->D, L.st); }
         h = e->hfeat;
     }
-    { OP("k_fc_fwd"); k_fc_fwd(h, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, e->D, e->C, e->st); }
-    if (!e->bn_fixed) e->ev_dirty = true;
+    { OP(L, "k_fc_fwd"); k_fc_fwd(h, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, e->D, e->C, L.st); }
+    if (mode != BnMode::Frozen) e->student.ev_dirty = true;
 }
 
-void eff_forward_eval(fm_engine* e, const float* S, float* evs, float* evh, bool& dirty, int imgs, float* feat,
-                      float* logits)
+void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
-    if (dirty) {
-        { OP("k_bn_eval_affine"); k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, evs, evh, e->n_bn_ch,
-                         e->bn_eps, e->st); }
-        dirty = false;
+    const float* S = W.state;
+    if (W.ev_dirty) {
+        { OP(L, "k_bn_eval_affine"); k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, W.ev_scale, W.ev_shift,
+                         e->n_bn_ch, e->bn_eps, L.st); }
+        W.ev_dirty = false;
     }
-    auto sc = [&](int bi) { return evs + e->bns[bi].ch_off; };
-    auto sh = [&](int bi) { return evh + e->bns[bi].ch_off; };
-    { OP("conv_fwd"); conv_fwd(e, e->c_stem, S, e->x4, e->a0, imgs, 1, sc(e->bn_stem), sh(e->bn_stem), nullptr, 2, nullptr); }
-    const float* cur = e->a0;
-    e->ctx = 200;
-    for (auto& m : e->mbs) {
-        ++e->ctx;                                  // eval-mode ops are labelled @201..@216 (head @300)
+    auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
+    auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
+    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_stem, W, e->x4, A.a0, imgs, 1, sc(e->bn_stem), sh(e->bn_stem), nullptr, 2, nullptr); }
+    const float* cur = A.a0;
+    for (size_t i = 0; i < e->mbs.size(); ++i) {
+        const MBConv& m = e->mbs[i];
+        MBActs& a = A.mb[i];
+        e->ctx = 201 + (int)i;                     // eval-mode ops are labelled @201..@216 (head @300)
         const int HWo = m.hout * m.wout;
         const float* a_e = cur;
         if (m.c_exp >= 0) {
-            { OP("exp_fwd"); conv_fwd(e, m.c_exp, S, cur, m.a_e, imgs, 1, sc(m.bn0), sh(m.bn0), nullptr, 2, nullptr); }
-            a_e = m.a_e;
+            { OP(L, "exp_fwd"); conv_fwd(e, L, m.c_exp, W, cur, a.a_e, imgs, 1, sc(m.bn0), sh(m.bn0), nullptr, 2, nullptr); }
+            a_e = a.a_e;
         }
         bool pooled;                      // eval: y_d holds swish(bn1(.)) directly; its per-image channel sums come with it
-        { OP("k_dw_fwd"); pooled = k_dw_fwd(a_e, S + m.dw_off, m.y_d, e->dt, sc(m.bn1), sh(m.bn1), imgs, m.hin, m.win, m.hout, m.wout, m.ce_p,
-                 m.k, m.s, m.pad_t, m.pad_l, 2, e->st, e->ws_slab, nullptr, 1, e->se_pool); }
-        { OP("k_se_fwd"); k_se_fwd(m.y_d, e->dt, nullptr, nullptr, 1, e->se_pool, S + m.w1_off, S + m.b1_off, S + m.w2_off, S + m.b2_off, m.sq,
-                 m.rpre, m.gate, imgs, HWo, m.ce_p, m.cs, e->st, pooled); }
+        { OP(L, "k_dw_fwd"); pooled = k_dw_fwd(a_e, S + m.dw_off, a.y_d, e->dt, sc(m.bn1), sh(m.bn1), imgs, m.hin, m.win, m.hout, m.wout, m.ce_p,
+                 m.k, m.s, m.pad_t, m.pad_l, 2, L.st, L.rec, nullptr, 1, A.se_pool); }
+        { OP(L, "k_se_fwd"); k_se_fwd(a.y_d, e->dt, nullptr, nullptr, 1, A.se_pool, S + m.w1_off, S + m.b1_off, S + m.w2_off, S + m.b2_off, a.sq,
+                 a.rpre, a.gate, imgs, HWo, m.ce_p, m.cs, L.st, pooled); }
         // the gate multiplies the activation on the project conv's operand load: bf16 wherever the conv reads it once or twice,
         // fp32 where the conv streams through conv1x1.hip (K <= 256: the high-resolution blocks)
         const Conv& cpj = e->convs[m.c_proj];
         if (fuse_for(e, m) || (!e->precision && conv1x1_stream_takes(cpj.cin_p, cpj.cout_p, cpj.cout_p))) {
-            const Prologue pro{nullptr, nullptr, m.gate};
-            { OP("proj_fwd"); conv_fwd(e, m.c_proj, S, m.y_d, m.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr, &pro); }
+            const Prologue pro{nullptr, nullptr, a.gate};
+            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.y_d, a.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr, &pro); }
         } else {
-            { OP("k_se_scale"); k_se_scale(m.y_d, e->dt, nullptr, nullptr, 1, m.gate, m.a_s, imgs, HWo, m.ce_p, e->st); }
-            { OP("proj_fwd"); conv_fwd(e, m.c_proj, S, m.a_s, m.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr); }
+            { OP(L, "k_se_scale"); k_se_scale(a.y_d, e->dt, nullptr, nullptr, 1, a.gate, a.a_s, imgs, HWo, m.ce_p, L.st); }
+            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.a_s, a.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr); }
         }
-        cur = m.out;
+        cur = a.out;
     }
     Conv& ch = e->convs[e->c_head];
     e->ctx = 300;
-    { OP("conv_fwd"); conv_fwd(e, e->c_head, S, cur, e->T_mid, imgs, 1, sc(e->bn_head), sh(e->bn_head), nullptr, 2, nullptr); }
-    { OP("k_avgpool"); k_avgpool(e->T_mid, e->dt, feat, imgs, ch.hout * ch.wout, e->D, e->st); }
-    { OP("k_fc_fwd"); k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, e->D, e->C, e->st); }
+    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_head, W, cur, A.T_mid, imgs, 1, sc(e->bn_head), sh(e->bn_head), nullptr, 2, nullptr); }
+    { OP(L, "k_avgpool"); k_avgpool(A.T_mid, e->dt, feat, imgs, ch.hout * ch.wout, e->D, L.st); }
+    { OP(L, "k_fc_fwd"); k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, e->D, e->C, L.st); }
 }
 
 
-void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
+// same contract as backward_and_step
+void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
 {
     const int imgs = groups * B;
-    const float* S = e->state;
+    Lane& L = e->main;
+    const Acts& A = e->acts;
+    const float* S = e->student.state;
     float* G = e->grad;
     Conv& ch = e->convs[e->c_head];
     const int HWh = ch.hout * ch.wout;
     const float* h = e->drop_dev ? e->hfeat : e->feat;
-    // Weight gradients on the side stream (side_w): each reads a gradient tensor the data-gradient chain has just produced
-    // -- T_small (d y_p) for the project conv, T_mid (d y_d) for the depthwise conv, T_big (d y_e) for the expand conv --
-    // and nothing downstream waits for it before Adam.  The three tensors are double-buffered by block parity; "produced"
-    // events release the side stream, "consumed" events guard the overwrite two blocks later; the side stream has its own
-    // slab workspace.  Arithmetic and summation orders are those of the inline order: results are bit-identical.
+    // Weight gradients on the side lane (side_begin): T_small (d y_p) for the project conv, T_mid (d y_d) for the depthwise
+    // conv, T_big (d y_e) for the expand conv, the squeeze-excite vectors, each double-buffered by block parity.  Arithmetic
+    // and summation orders are those of the inline order: results are bit-identical.
     const bool sw = e->side_w;
     float* Tsm[2] = {e->T_small, sw ? e->T_small2 : e->T_small};
-    float* Tmd[2] = {e->T_mid, sw ? e->T_mid2 : e->T_mid};
+    float* Tmd[2] = {A.T_mid, sw ? e->T_mid2 : A.T_mid};
     float* Tbg[2] = {e->T_big, sw ? e->T_big2 : e->T_big};
-    hipStream_t main_st = e->st;
-    auto side_begin = [&](int k, int par) {          // main has produced tensor k of parity par
-        if (!sw) return;
-        soft(e, hipEventRecord(e->ev_p[k][par], main_st));
-        soft(e, hipStreamWaitEvent(e->st2, e->ev_p[k][par], 0));
-        e->st = e->st2;
-        std::swap(e->ws_slab, e->ws_slab2);
-    };
-    auto side_end = [&](int k, int par) {
-        if (!sw) return;
-        std::swap(e->ws_slab, e->ws_slab2);
-        soft(e, hipEventRecord(e->ev_c[k][par], e->st2));
-        e->st = main_st;
-    };
-    auto guard = [&](int k, int par) { if (sw) soft(e, hipStreamWaitEvent(main_st, e->ev_c[k][par], 0)); };
     e->ctx = 500;
-    { OP("k_fc_bwd"); k_fc_bwd(e->dlogits, h, S + e->off_fcw, e->drop_dev, G + e->off_fcw, G + e->off_fcb, e->T_mid, e->dt, imgs, e->D, e->C,
-             HWh, e->st, e->dfeat_dev); }
-    { OP("bnact_bwd"); bnact_bwd(e, e->bn_head, e->T_mid, ch.y, e->T_mid, nullptr, groups, B * HWh, HWh, 2); }
-    { OP("conv_wgrad"); conv_wgrad(e, e->c_head, e->mbs.back().out, e->T_mid, imgs); }
+    { OP(L, "k_fc_bwd"); k_fc_bwd(e->dlogits, h, S + e->off_fcw, e->drop_dev, G + e->off_fcw, G + e->off_fcb, A.T_mid, e->dt, imgs, e->D, e->C,
+             HWh, L.st, bw.dfeat); }
+    { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_head, A.T_mid, ch.y, A.T_mid, nullptr, groups, B * HWh, HWh, 2, bw.frozen); }
+    { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_head, A.mb.back().out, A.T_mid, imgs); }
     float *go = e->GA, *gi = e->GB;
-    { OP("conv_dgrad"); conv_dgrad(e, e->c_head, S, e->T_mid, go, imgs, nullptr, false); }
+    { OP(L, "conv_dgrad"); conv_dgrad(e, L, e->c_head, A.T_mid, go, imgs, nullptr, false); }
     for (int i = (int)e->mbs.size() - 1; i >= 0; --i) {
-        MBConv& m = e->mbs[i];
+        const MBConv& m = e->mbs[i];
+        const MBActs& a = A.mb[i];
         e->ctx = 400 + i;                          // backward ops @400..@415 (head @500, stem @399)
         const int par = i & 1;
         float *T_small = Tsm[par], *T_mid = Tmd[par], *T_big = Tbg[par];
-        const float* in = i == 0 ? e->a0 : e->mbs[i - 1].out;
+        const float* in = i == 0 ? A.a0 : A.mb[i - 1].out;
         const int HWi = m.hin * m.win, HWo = m.hout * m.wout;
         Conv& cp = e->convs[m.c_proj];
         const float* dc = (m.skip && e->dc_dev) ? e->dc_dev + (size_t)i * imgs : nullptr;
         // out = bn2(y_p)*dc + in
-        guard(0, par);
-        { OP("bnact_bwd"); bnact_bwd(e, m.bn2, go, cp.y, T_small, dc, groups, B * HWo, HWo, 0); }
+        side_guard(e, 0, par);
+        { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn2, go, cp.y, T_small, dc, groups, B * HWo, HWo, 0, bw.frozen); }
         Bn& b1 = e->bns[m.bn1];
         float* dgp = (sw && par) ? e->se_dgp2 : e->se_dgp;       // the squeeze-excite gradient vectors alternate too
         float* drp = (sw && par) ? e->se_drp2 : e->se_drp;
@@ -1942,37 +1969,39 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
             PwProjBwdParams q{};
             PwProjBwdF32Params qf{};
             if (e->precision) {
-                q.dYp = reinterpret_cast<const bf16*>(T_small); q.Yd = reinterpret_cast<const bf16*>(m.y_d);
-                q.Wt = shadow_of(e, S) + cp.wbt_off; q.dYd = reinterpret_cast<bf16*>(T_mid);
-                q.slab = e->ws_slab; q.pool5 = e->se_pool;
+                q.dYp = reinterpret_cast<const bf16*>(T_small); q.Yd = reinterpret_cast<const bf16*>(a.y_d);
+                q.Wt = e->student.wb + cp.wbt_off; q.dYd = reinterpret_cast<bf16*>(T_mid);
+                q.slab = L.ws_slab; q.pool5 = A.se_pool;
                 q.sc = b1.scale; q.sh = b1.shift; q.mean = b1.mean; q.istd = b1.istd; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc;
-                q.gate = m.gate; q.ds = e->se_ds;
+                q.gate = a.gate; q.ds = e->se_ds;
                 q.L = m.ce_p; q.S = cp.cout_p; q.imgs = imgs; q.HW = HWo; q.ipg = B; q.nch = nch5;
             } else {
-                qf.dYp = T_small; qf.Yd = m.y_d; qf.W = S + cp.w_off; qf.dYd = T_mid;
-                qf.slab = e->ws_slab; qf.pool5 = e->se_pool;
+                qf.dYp = T_small; qf.Yd = a.y_d; qf.W = S + cp.w_off; qf.dYd = T_mid;
+                qf.slab = L.ws_slab; qf.pool5 = A.se_pool;
                 qf.sc = b1.scale; qf.sh = b1.shift; qf.mean = b1.mean; qf.istd = b1.istd; qf.ca = e->ca; qf.cb = e->cb; qf.cc = e->cc;
-                qf.gate = m.gate; qf.ds = e->se_ds;
+                qf.gate = a.gate; qf.ds = e->se_ds;
                 qf.L = m.ce_p; qf.S = cp.cout_p; qf.imgs = imgs; qf.HW = HWo; qf.ipg = B; qf.nch = nch5;
             }
             auto launch = [&](int phase) {
-                return e->precision ? launch_pw_proj_bwd(q, phase, e->slab_floats, e->st) : launch_pw_proj_bwd_f32(qf, phase, e->slab_floats, e->st);
+                return e->precision ? launch_pw_proj_bwd(q, phase, e->slab_floats, L.st) : launch_pw_proj_bwd_f32(qf, phase, e->slab_floats, L.st);
             };
             int sk;
-            { OP("proj_bwd_sums"); sk = launch(0);
-              if (sk > 0) k_reduce_slabs(e->ws_slab, G + cp.w_off, sk, (int64_t)cp.w_numel, e->st); }
+            { OP(L, "proj_bwd_sums"); sk = launch(0);
+              if (sk > 0) k_reduce_slabs(L.ws_slab, G + cp.w_off, sk, (int64_t)cp.w_numel, L.st); }
             if (sk > 0) {
-                guard(3, par);
-                { OP("k_se_bwd"); k_se_bwd_bn1(nullptr, m.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, e->se_pool, m.gate, m.rpre,
-                             S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, e->st, nch5); }
-                side_begin(3, par);
-                { OP("k_se_wgrad"); k_se_wgrad(dgp, drp, m.rpre, m.sq, e->ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, e->st); }
-                side_end(3, par);
-                guard(1, par);
-                { OP("proj_bwd_apply");
-                  k_bn_bwd_finalize(e->ws_part, groups, se_bwd_bn1_splits(B), b1.C, B * HWo, e->state + e->off_gamma + b1.ch_off, b1.mean,
+                side_guard(e, 3, par);
+                { OP(L, "k_se_bwd"); k_se_bwd_bn1(nullptr, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
+                             S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st, nch5); }
+                {
+                    Lane& SL = side_begin(e, 3, par);
+                    { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
+                    side_end(e, 3, par);
+                }
+                side_guard(e, 1, par);
+                { OP(L, "proj_bwd_apply");
+                  k_bn_bwd_finalize(e->ws_part, groups, se_bwd_bn1_splits(B), b1.C, B * HWo, e->student.state + e->off_gamma + b1.ch_off, b1.mean,
                                     b1.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b1.ch_off, e->grad + e->off_beta + b1.ch_off,
-                                    e->st, e->bwd_fixed);
+                                    L.st, bw.frozen);
                   if (launch(1) != 1) soft(e, hipErrorInvalidValue); }      // d y_d
                 pfused = true;
             }
@@ -1980,189 +2009,172 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, bool step = true)
         if (!pfused) {
             if (!e->precision && fuse_for(e, m)) soft(e, hipErrorInvalidValue);     // fp32: a_s was not stored for this block and only
                                                                                     // the fused backward can do without it
-            side_begin(0, par);
-            if (fuse_for(e, m)) {      // the project conv's operand a_s was never stored: re-formed from y_d on load
-                const Prologue pro{b1.scale, b1.shift, m.gate};
-                { OP("proj_wgrad"); conv_wgrad(e, m.c_proj, m.y_d, T_small, imgs, &pro, B * HWo); }
-            } else
-                { OP("proj_wgrad"); conv_wgrad(e, m.c_proj, m.a_s, T_small, imgs); }
-            side_end(0, par);
-            guard(1, par);
-            { OP("proj_dgrad"); conv_dgrad(e, m.c_proj, S, T_small, T_mid, imgs, nullptr, false); }          // d a_s
+            {
+                Lane& SL = side_begin(e, 0, par);
+                if (fuse_for(e, m)) {      // the project conv's operand a_s was never stored: re-formed from y_d on load
+                    const Prologue pro{b1.scale, b1.shift, a.gate};
+                    { OP(SL, "proj_wgrad"); conv_wgrad(e, SL, m.c_proj, a.y_d, T_small, imgs, &pro, B * HWo); }
+                } else
+                    { OP(SL, "proj_wgrad"); conv_wgrad(e, SL, m.c_proj, a.a_s, T_small, imgs); }
+                side_end(e, 0, par);
+            }
+            side_guard(e, 1, par);
+            { OP(L, "proj_dgrad"); conv_dgrad(e, L, m.c_proj, T_small, T_mid, imgs, nullptr, false); }          // d a_s
             // a_s = a_d * gate(a_d)
             // ONE pass over (d a_s, y_d) yields the squeeze-excite backward's pooled sums and the BN1-backward sums
-            guard(3, par);
-            { OP("k_se_bwd"); k_se_bwd_bn1(T_mid, m.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, e->se_pool, m.gate, m.rpre,
-                         S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, e->st); }
-            side_begin(3, par);
-            { OP("k_se_wgrad"); k_se_wgrad(dgp, drp, m.rpre, m.sq, e->ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, e->st); }
-            side_end(3, par);
+            side_guard(e, 3, par);
+            { OP(L, "k_se_bwd"); k_se_bwd_bn1(T_mid, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
+                         S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st); }
+            {
+                Lane& SL = side_begin(e, 3, par);
+                { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
+                side_end(e, 3, par);
+            }
             // d a_d = d a_s * gate + ds/HW is formed on load inside the BN backward's apply pass
-            { OP("bnact_bwd"); bnact_bwd(e, m.bn1, T_mid, m.y_d, T_mid, nullptr, groups, B * HWo, HWo, 2, m.gate, e->se_ds, -1,
+            { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn1, T_mid, a.y_d, T_mid, nullptr, groups, B * HWo, HWo, 2, bw.frozen, a.gate, e->se_ds, -1,
                                          se_bwd_bn1_splits(B)); }   // d y_d
         }
-        const float* a_e = m.c_exp >= 0 ? m.a_e : in;
-        side_begin(1, par);
-        { OP("k_dw_wgrad"); k_dw_wgrad(T_mid, a_e, e->dt, e->ws_slab, G + m.dw_off, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
-                   m.pad_t, m.pad_l, e->st); }
-        side_end(1, par);
+        const float* a_e = m.c_exp >= 0 ? a.a_e : in;
+        {
+            Lane& SL = side_begin(e, 1, par);
+            { OP(SL, "k_dw_wgrad"); k_dw_wgrad(T_mid, a_e, e->dt, SL.ws_slab, G + m.dw_off, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
+                       m.pad_t, m.pad_l, SL.st); }
+            side_end(e, 1, par);
+        }
         if (m.c_exp >= 0) {
             Conv& ce = e->convs[m.c_exp];
             Bn& b0 = e->bns[m.bn0];
             bool sums;                           // d a_e, and the BN0-backward sums from the same registers
-            guard(2, par);
-            { OP("k_dw_dgrad"); sums = k_dw_dgrad(T_mid, S + m.dw_off, T_big, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
-                       m.pad_t, m.pad_l, e->st, ce.y, b0.mean, b0.istd, b0.scale, b0.shift, e->ws_slab, e->ws_part, groups); }
+            side_guard(e, 2, par);
+            { OP(L, "k_dw_dgrad"); sums = k_dw_dgrad(T_mid, S + m.dw_off, T_big, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
+                       m.pad_t, m.pad_l, L.st, ce.y, b0.mean, b0.istd, b0.scale, b0.shift, L.rec, e->ws_part, groups); }
             bool fused = false;
             if ((ce.cout_p == 96 || ce.cout_p == 144) && ce.cin_p <= 32) {
                 // early blocks (62 % of the expanded-tensor bytes): BN0-backward apply + weight gradient + data gradient of the
                 // expand conv in ONE kernel that reads d a_e and y_e once (pw_exp_bwd_kernel / pw_exp_bwd_f32_kernel) instead of
                 // five passes over them
-                OP("exp_bwd_fused");
+                OP(L, "exp_bwd_fused");
                 const int pix = B * HWi;
                 if (!sums)
                     k_chan_reduce(T_big, e->dt, ce.y, e->dt, b0.mean, b0.istd, b0.scale, b0.shift, nullptr, e->ws_part, groups, pix,
-                                  HWi, b0.C, 1, 2, nullptr, nullptr, e->st);
+                                  HWi, b0.C, 1, 2, nullptr, nullptr, L.st);
                 k_bn_bwd_finalize(e->ws_part, groups, sums ? dw_stats_tiles() : bn_bwd_blocks(pix), b0.C, pix,
-                                  e->state + e->off_gamma + b0.ch_off, b0.mean, b0.istd, e->ca, e->cb, e->cc,
-                                  e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, e->st, e->bwd_fixed);
+                                  e->student.state + e->off_gamma + b0.ch_off, b0.mean, b0.istd, e->ca, e->cb, e->cc,
+                                  e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
                 int sk;
                 if (e->precision) {
                     PwExpBwdParams q{};
                     q.dA = reinterpret_cast<const bf16*>(T_big); q.Ye = reinterpret_cast<const bf16*>(ce.y);
-                    q.X = reinterpret_cast<const bf16*>(in); q.Wt = shadow_of(e, S) + ce.wbt_off;
+                    q.X = reinterpret_cast<const bf16*>(in); q.Wt = e->student.wb + ce.wbt_off;
                     q.res = reinterpret_cast<const bf16*>(m.skip ? go : nullptr); q.dX = reinterpret_cast<bf16*>(gi);
-                    q.slab = e->ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
+                    q.slab = L.ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
                     q.L = ce.cout_p; q.S = ce.cin_p; q.npix = imgs * HWi; q.pix_per_group = pix; q.groups = groups;
-                    sk = launch_pw_exp_bwd(q, e->slab_floats, e->st);
+                    sk = launch_pw_exp_bwd(q, e->slab_floats, L.st);
                 } else {
                     PwExpBwdF32Params q{};
                     q.dA = T_big; q.Ye = ce.y; q.X = in; q.W = S + ce.w_off; q.res = m.skip ? go : nullptr; q.dX = gi;
-                    q.slab = e->ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
+                    q.slab = L.ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
                     q.L = ce.cout_p; q.S = ce.cin_p; q.npix = imgs * HWi; q.pix_per_group = pix; q.groups = groups;
-                    sk = launch_pw_exp_bwd_f32(q, e->slab_floats, e->st);
+                    sk = launch_pw_exp_bwd_f32(q, e->slab_floats, L.st);
                 }
                 if (sk > 0) {
-                    k_reduce_slabs(e->ws_slab, G + ce.w_off, sk, (int64_t)ce.w_numel, e->st);
+                    k_reduce_slabs(L.ws_slab, G + ce.w_off, sk, (int64_t)ce.w_numel, L.st);
                     fused = true;
                 }
             }
             if (!fused) {
                 // (a refused fused launch has left ca / cb / cc and the BN gradients exactly as bnact_bwd is about to)
-                { OP("bnact_bwd"); bnact_bwd(e, m.bn0, T_big, ce.y, T_big, nullptr, groups, B * HWi, HWi, 2, nullptr, nullptr, -1,
+                { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn0, T_big, ce.y, T_big, nullptr, groups, B * HWi, HWi, 2, bw.frozen, nullptr, nullptr, -1,
                                              sums ? dw_stats_tiles() : 0); }
-                side_begin(2, par);
-                { OP("exp_wgrad"); conv_wgrad(e, m.c_exp, in, T_big, imgs); }
-                side_end(2, par);
-                { OP("exp_dgrad"); conv_dgrad(e, m.c_exp, S, T_big, gi, imgs, m.skip ? go : nullptr, false); }
+                {
+                    Lane& SL = side_begin(e, 2, par);
+                    { OP(SL, "exp_wgrad"); conv_wgrad(e, SL, m.c_exp, in, T_big, imgs); }
+                    side_end(e, 2, par);
+                }
+                { OP(L, "exp_dgrad"); conv_dgrad(e, L, m.c_exp, T_big, gi, imgs, m.skip ? go : nullptr, false); }
             }
         } else {
-            { OP("k_dw_dgrad"); k_dw_dgrad(T_mid, S + m.dw_off, gi, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s, m.pad_t,
-                       m.pad_l, e->st); }
-            if (m.skip) k_add_inplace(gi, go, e->dt, (int64_t)imgs * HWi * m.cin_p, e->st);
+            { OP(L, "k_dw_dgrad"); k_dw_dgrad(T_mid, S + m.dw_off, gi, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s, m.pad_t,
+                       m.pad_l, L.st); }
+            if (m.skip) k_add_inplace(gi, go, e->dt, (int64_t)imgs * HWi * m.cin_p, L.st);
         }
         std::swap(go, gi);
     }
     Conv& cs = e->convs[e->c_stem];
     e->ctx = 399;
-    { OP("bnact_bwd"); bnact_bwd(e, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2); }
-    if (e->dx_out[0] || e->dx_out[1]) { OP("stem_dgrad"); stem_dgrad_views(e, go, groups, B); }
-    { OP("conv_wgrad"); conv_wgrad(e, e->c_stem, e->x4, go, imgs); }
-    if (sw) {                                    // every weight gradient is in G before the optimizer reads it
-        soft(e, hipEventRecord(e->ev_wdone, e->st2));
-        soft(e, hipStreamWaitEvent(main_st, e->ev_wdone, 0));
-    }
-    if (step) { OP("adam_step"); adam_step(e, e->grad); }
+    { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2, bw.frozen); }
+    if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, go, groups, B, bw.dx); }
+    { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_stem, e->x4, go, imgs); }
+    side_join(e);                                // every weight gradient is in G before the optimizer reads it
+    if (bw.step) { OP(L, "adam_step"); adam_step(e, e->grad); }
 }
 
-// model dispatch
-// update_running false (fm_forward_recompute): the same launches and saved tensors, BN running statistics and
-// num_batches_tracked counters left as they are
-// fixed_stats (fm_forward_train / fm_forward_recompute under fm_bn_freeze): every BatchNorm applies its running statistics
-void net_forward_train(fm_engine* e, int groups, int B, bool update_running = true, bool fixed_stats = false)
+// model dispatch.  The train forward and the backward are the student's: main lane, the student's activation set
+void net_forward_train(fm_engine* e, int groups, int B, BnMode mode = BnMode::Batch)
 {
     ensure_packed(e);
-    e->bn_no_update = !update_running;
-    e->bn_fixed = fixed_stats;
-    if (e->model == 1) eff_forward_train(e, groups, B);
-    else forward_train(e, groups, B);
-    e->bn_no_update = false;
-    e->bn_fixed = false;
+    if (e->model == 1) eff_forward_train(e, e->main, e->acts, groups, B, mode);
+    else forward_train(e, e->main, e->acts, groups, B, mode);
 }
-void net_forward_eval(fm_engine* e, bool teacher, int imgs)
+// W's shadows are the caller's to ensure (ensure_packed / ensure_teacher_shadow: main lane)
+void net_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
-    const float* S = teacher ? e->tstate : e->state;
-    float* evs = teacher ? e->tev_scale : e->ev_scale;
-    float* evh = teacher ? e->tev_shift : e->ev_shift;
-    bool& dirty = teacher ? e->tev_dirty : e->ev_dirty;
-    float* feat = teacher ? e->tfeat : e->feat;
-    float* logits = teacher ? e->tlogits : e->logits;
-    if (teacher) ensure_teacher_shadow(e);
-    else ensure_packed(e);
-    if (e->model == 1) eff_forward_eval(e, S, evs, evh, dirty, imgs, feat, logits);
-    else forward_eval(e, S, evs, evh, dirty, imgs, feat, logits);
+    if (e->model == 1) eff_forward_eval(e, L, W, A, imgs, feat, logits);
+    else forward_eval(e, L, W, A, imgs, feat, logits);
 }
-// teacher forward on the side stream: same code, the teacher's buffer set and stream swapped in while it is enqueued
-void swap_teacher_ws(fm_engine* e)
-{
-    for (auto& m : e->mbs) {
-        std::swap(m.a_e, m.t_a_e); std::swap(m.y_d, m.t_y_d); std::swap(m.a_s, m.t_a_s); std::swap(m.out, m.t_out);
-        std::swap(m.sq, m.t_sq); std::swap(m.rpre, m.t_rpre); std::swap(m.gate, m.t_gate);
-    }
-    std::swap(e->sk_slab, e->sk_slab2); std::swap(e->sk_counters, e->sk_counters2);
-    if (e->model == 0) {
-        std::swap(e->convs[0].y, e->t_c0y); std::swap(e->p0, e->t_p0); std::swap(e->p0p, e->t_p0p);
-        for (auto& blk : e->blocks) {
-            std::swap(blk.z1, blk.t_z1); std::swap(blk.out, blk.t_out);
-            std::swap(blk.z1p, blk.t_z1p); std::swap(blk.outp, blk.t_outp);
-            if (blk.ds >= 0) std::swap(e->convs[blk.ds].y, blk.t_dsy);
-        }
-        return;
-    }
-    std::swap(e->a0, e->t_a0); std::swap(e->T_mid, e->t_Tmid); std::swap(e->se_pool, e->t_se_pool);
-    std::swap(e->ws_slab, e->t_rec);
-}
+// the teacher's forward on the side lane, into the second activation set: the same code as on the main lane
 int teacher_forward_side(fm_engine* e, int imgs)
 {
-    ensure_teacher_shadow(e);                                   // weight shadows on the main stream, before the fork
-    HIPCHK(hipEventRecord(e->ev_in, e->st));
-    HIPCHK(hipStreamWaitEvent(e->st2, e->ev_in, 0));
-    hipStream_t main_st = e->st;
-    e->st = e->st2;
-    swap_teacher_ws(e);
-    net_forward_eval(e, true, imgs);
-    swap_teacher_ws(e);
-    e->st = main_st;
-    HIPCHK(hipEventRecord(e->ev_t, e->st2));
+    ensure_teacher_shadow(e);                                   // weight shadows on the main lane, before the fork
+    HIPCHK(hipEventRecord(e->ev_in, e->main.st));
+    HIPCHK(hipStreamWaitEvent(e->side.st, e->ev_in, 0));
+    net_forward_eval(e, e->side, e->teacher, e->tacts, imgs, e->tfeat, e->tlogits);
+    HIPCHK(hipEventRecord(e->ev_t, e->side.st));
     return FM_OK;
 }
-// fixed_stats: the backward of a forward that ran on frozen statistics (every BatchNorm-backward finalize takes its frozen form)
-void net_backward_and_step(fm_engine* e, int groups, int B, bool step = true, bool fixed_stats = false)
+void net_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw = {})
 {
     ensure_packed(e);
-    e->bwd_fixed = fixed_stats;
-    if (e->model == 1) eff_backward_and_step(e, groups, B, step);
-    else backward_and_step(e, groups, B, step);
-    e->bwd_fixed = false;
+    if (e->model == 1) eff_backward_and_step(e, groups, B, bw);
+    else backward_and_step(e, groups, B, bw);
 }
 
 // an engine-layout gradient arena (e->grad or the accumulator) -> dst in state_dict order (conv weights OIHW, BN running
-// statistics as zeros; e->nf_sd floats), enqueued on e->st
+// statistics as zeros; e->nf_sd floats), enqueued on the main lane
 int grads_to_state_dict(fm_engine* e, const float* src, float* dst)
 {
+    Lane& L = e->main;
     size_t off = 0;
     for (auto& en : e->entries) {
         if (en.kind == 0) {
-            k_ohwi_to_oihw(src + en.eng_off, dst + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->st, en.Ostride);
+            k_ohwi_to_oihw(src + en.eng_off, dst + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, L.st, en.Ostride);
             off += en.n;
         } else if (en.kind == 1) {
             if (en.eng_off < e->NP)
-                HIPCHK(hipMemcpyAsync(dst + off, src + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->st));
+                HIPCHK(hipMemcpyAsync(dst + off, src + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, L.st));
             else
-                HIPCHK(hipMemsetAsync(dst + off, 0, en.n * 4, e->st));
+                HIPCHK(hipMemsetAsync(dst + off, 0, en.n * 4, L.st));
             off += en.n;
         }
     }
+    return FM_OK;
+}
+
+// debug hooks: fold the per-tile partials conv `ci`'s forward left in ws_stats with the finalize kernel's own reduction order
+// (sum / sumsq only) into stats_dev [groups][2][cout_p]
+int debug_fold_stats(fm_engine* e, int ci, int groups, float* stats_dev)
+{
+    const int tiles = stats_tiles(e, ci), n = 2 * e->convs[ci].cout_p;
+    std::vector<float> h((size_t)groups * tiles * n), o((size_t)groups * n, 0.f);
+    HIPCHK(hipMemcpyAsync(h.data(), e->ws_stats, h.size() * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
+    for (int g = 0; g < groups; ++g)
+        for (int k = 0; k < n; ++k) {
+            double sum = 0;
+            for (int t = 0; t < tiles; ++t) sum += h[((size_t)g * tiles + t) * n + k];
+            o[(size_t)g * n + k] = (float)sum;
+        }
+    HIPCHK(hipMemcpy(stats_dev, o.data(), o.size() * 4, hipMemcpyHostToDevice));
     return FM_OK;
 }
 
@@ -2203,7 +2215,7 @@ int fm_create(const fm_config* cfg, fm_engine** out)
     e->dt = e->precision ? DT_BF16 : DT_F32;
     e->fuse_gate = e->precision && !(getenv("FM_FUSE_GATE") && atoi(getenv("FM_FUSE_GATE")) == 0);
     e->cfg = *cfg;
-    e->st = reinterpret_cast<hipStream_t>(cfg->stream);
+    e->main.st = reinterpret_cast<hipStream_t>(cfg->stream);      // the one assignment of the engine's stream
     e->C = cfg->n_classes; e->H = cfg->in_h; e->W = cfg->in_w; e->maxB = cfg->max_images;
     e->model = cfg->model;
     int rc = e->model == 1 ? build_effnet_b0(e) : build_resnet18(e);
@@ -2217,8 +2229,8 @@ int fm_create(const fm_config* cfg, fm_engine** out)
 int fm_destroy(fm_engine* e)
 {
     if (!e) return FM_OK;
-    (void)hipStreamSynchronize(e->st);
-    if (e->st2) { (void)hipStreamSynchronize(e->st2); (void)hipStreamDestroy(e->st2); }
+    (void)hipStreamSynchronize(e->main.st);
+    if (e->side.st) { (void)hipStreamSynchronize(e->side.st); (void)hipStreamDestroy(e->side.st); }
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->ev_t) (void)hipEventDestroy(e->ev_t);
     for (int k = 0; k < 4; ++k)
@@ -2239,7 +2251,7 @@ int fm_destroy(fm_engine* e)
 int fm_sync(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     STEP_DONE(e);
     return FM_OK;
 }
@@ -2255,23 +2267,23 @@ int fm_state_sizes(fm_engine* e, int64_t* n_f32, int64_t* n_i64)
 int fm_set_state(fm_engine* e, const float* host_f32, const int64_t* host_i64)
 {
     ARGCHK(e && host_f32, "null engine/state");
-    HIPCHK(hipMemcpyAsync(e->stage_sd, host_f32, (size_t)e->nf_sd * 4, hipMemcpyHostToDevice, e->st));
+    HIPCHK(hipMemcpyAsync(e->stage_sd, host_f32, (size_t)e->nf_sd * 4, hipMemcpyHostToDevice, e->main.st));
     size_t off = 0;
     int ic = 0;
     for (auto& en : e->entries) {
         if (en.kind == 0) {
-            k_oihw_to_ohwi(e->stage_sd + off, e->state + en.eng_off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->st, en.Ostride);
+            k_oihw_to_ohwi(e->stage_sd + off, e->student.state + en.eng_off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->main.st, en.Ostride);
             off += en.n;
         } else if (en.kind == 1) {
-            HIPCHK(hipMemcpyAsync(e->state + en.eng_off, e->stage_sd + off, en.n * 4, hipMemcpyDeviceToDevice, e->st));
+            HIPCHK(hipMemcpyAsync(e->student.state + en.eng_off, e->stage_sd + off, en.n * 4, hipMemcpyDeviceToDevice, e->main.st));
             off += en.n;
         } else {
-            e->counters[en.bn] = host_i64 ? host_i64[ic] : 0;
+            e->student.counters[en.bn] = host_i64 ? host_i64[ic] : 0;
             ++ic;
         }
     }
-    HIPCHK(hipStreamSynchronize(e->st));
-    e->ev_dirty = true;
+    HIPCHK(hipStreamSynchronize(e->main.st));
+    e->student.ev_dirty = true;
     e->wpack_dirty = true;
     return FM_OK;
 }
@@ -2283,27 +2295,27 @@ int fm_get_state(fm_engine* e, float* host_f32, int64_t* host_i64)
     int ic = 0;
     for (auto& en : e->entries) {
         if (en.kind == 0) {
-            k_ohwi_to_oihw(e->state + en.eng_off, e->stage_sd + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->st, en.Ostride);
+            k_ohwi_to_oihw(e->student.state + en.eng_off, e->stage_sd + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->main.st, en.Ostride);
             off += en.n;
         } else if (en.kind == 1) {
-            HIPCHK(hipMemcpyAsync(e->stage_sd + off, e->state + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->st));
+            HIPCHK(hipMemcpyAsync(e->stage_sd + off, e->student.state + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->main.st));
             off += en.n;
         } else {
-            if (host_i64) host_i64[ic] = e->counters[en.bn];
+            if (host_i64) host_i64[ic] = e->student.counters[en.bn];
             ++ic;
         }
     }
-    HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     return FM_OK;
 }
 
 int fm_state_device(fm_engine* e, float** dev_ptr, int64_t* numel)
 {
     ARGCHK(e && dev_ptr && numel, "null");
-    *dev_ptr = e->state;
+    *dev_ptr = e->student.state;
     *numel = (int64_t)e->NS;
-    e->ev_dirty = true;       // the caller is about to overwrite it (all-reduce)
+    e->student.ev_dirty = true;       // the caller is about to overwrite it (all-reduce)
     e->wpack_dirty = true;
     return FM_OK;
 }
@@ -2314,8 +2326,8 @@ int fm_counters(fm_engine* e, int64_t* host_i64, int32_t set)
     int ic = 0;
     for (auto& en : e->entries)
         if (en.kind == 2) {
-            if (set) e->counters[en.bn] = host_i64[ic];
-            else host_i64[ic] = e->counters[en.bn];
+            if (set) e->student.counters[en.bn] = host_i64[ic];
+            else host_i64[ic] = e->student.counters[en.bn];
             ++ic;
         }
     return FM_OK;
@@ -2324,8 +2336,8 @@ int fm_counters(fm_engine* e, int64_t* host_i64, int32_t set)
 int fm_state_scale(fm_engine* e, float w)
 {
     ARGCHK(e, "null engine");
-    k_scale(e->state, w, (int64_t)e->NS, e->st);
-    e->ev_dirty = true;
+    k_scale(e->student.state, w, (int64_t)e->NS, e->main.st);
+    e->student.ev_dirty = true;
     e->wpack_dirty = true;
     return FM_OK;
 }
@@ -2354,8 +2366,8 @@ int fm_fedavg_fold(fm_engine* e, const float* const* states_dev, const float* n_
         tot_d += (double)n_host[k];
     }
     tot = (float)tot_d;
-    k_fedavg_fold(a, K, tot, out_dev, (int64_t)e->NS, e->st);
-    if (out_dev == e->state) { e->ev_dirty = true; e->wpack_dirty = true; e->wb_dirty = true; }
+    k_fedavg_fold(a, K, tot, out_dev, (int64_t)e->NS, e->main.st);
+    if (out_dev == e->student.state) { e->student.ev_dirty = true; e->wpack_dirty = true; }
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -2385,7 +2397,7 @@ int fm_comm_init(fm_engine* e, const uint8_t* id128, int32_t rank, int32_t world
     if (e->comm) { COMMCHK(fmcomm_destroy(e->comm)); e->comm = nullptr; }
     COMMCHK(fmcomm_init(&e->comm, id128, rank, world));
     e->comm_rank = rank; e->comm_world = world;
-    const size_t need = std::max<size_t>((size_t)2 * e->C * e->D + 2 * e->C, e->counters.size()) + 64;
+    const size_t need = std::max<size_t>((size_t)2 * e->C * e->D + 2 * e->C, e->student.counters.size()) + 64;
     if (e->comm_buf_n < need) { DALLOC(e->comm_buf, need); e->comm_buf_n = need; }
     return FM_OK;
 }
@@ -2393,7 +2405,7 @@ int fm_comm_init(fm_engine* e, const uint8_t* id128, int32_t rank, int32_t world
 int fm_comm_destroy(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    if (e->comm) { HIPCHK(hipStreamSynchronize(e->st)); COMMCHK(fmcomm_destroy(e->comm)); }
+    if (e->comm) { HIPCHK(hipStreamSynchronize(e->main.st)); COMMCHK(fmcomm_destroy(e->comm)); }
     e->comm = nullptr; e->comm_world = 0;
     return FM_OK;
 }
@@ -2403,20 +2415,20 @@ int fm_comm_size(fm_engine* e) { return (e && e->comm) ? e->comm_world : 0; }
 int fm_fedavg_allreduce(fm_engine* e, float w)
 {
     ARGCHK(e, "null engine");
-    k_scale(e->state, w, (int64_t)e->NS, e->st);
-    e->ev_dirty = true; e->wpack_dirty = true;
+    k_scale(e->student.state, w, (int64_t)e->NS, e->main.st);
+    e->student.ev_dirty = true; e->wpack_dirty = true;
     if (!e->comm) return FM_OK;       // no communicator: a single client, FedAvg of one = w * state
     // (1) the whole fp32 arena, in place, on the engine stream: the next round's first kernels queue behind it
-    COMMCHK(fmcomm_allreduce_sum(e->comm, e->state, e->NS, false, e->st));
+    COMMCHK(fmcomm_allreduce_sum(e->comm, e->student.state, e->NS, false, e->main.st));
     // (2) num_batches_tracked: weighted mean in float64, truncated on load like utils/FedAvg.py:13 + load_state_dict
-    const size_t nb = e->counters.size();
+    const size_t nb = e->student.counters.size();
     std::vector<double> h(nb);
-    for (size_t i = 0; i < nb; ++i) h[i] = (double)w * (double)e->counters[i];
-    HIPCHK(hipMemcpyAsync(e->comm_buf, h.data(), nb * 8, hipMemcpyHostToDevice, e->st));
-    COMMCHK(fmcomm_allreduce_sum(e->comm, e->comm_buf, nb, true, e->st));
-    HIPCHK(hipMemcpyAsync(h.data(), e->comm_buf, nb * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
-    for (size_t i = 0; i < nb; ++i) e->counters[i] = (int64_t)trunc(h[i] + 1e-9);
+    for (size_t i = 0; i < nb; ++i) h[i] = (double)w * (double)e->student.counters[i];
+    HIPCHK(hipMemcpyAsync(e->comm_buf, h.data(), nb * 8, hipMemcpyHostToDevice, e->main.st));
+    COMMCHK(fmcomm_allreduce_sum(e->comm, e->comm_buf, nb, true, e->main.st));
+    HIPCHK(hipMemcpyAsync(h.data(), e->comm_buf, nb * 8, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
+    for (size_t i = 0; i < nb; ++i) e->student.counters[i] = (int64_t)trunc(h[i] + 1e-9);
     return FM_OK;
 }
 
@@ -2431,10 +2443,10 @@ int fm_fedavg_tao(fm_engine* e, const double* t_host, double n_i, const float* n
         h[C + c] = n_i * m;
     }
     if (e->comm) {
-        HIPCHK(hipMemcpyAsync(e->comm_buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, e->st));
-        COMMCHK(fmcomm_allreduce_sum(e->comm, e->comm_buf, h.size(), true, e->st));
-        HIPCHK(hipMemcpyAsync(h.data(), e->comm_buf, h.size() * 8, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
+        HIPCHK(hipMemcpyAsync(e->comm_buf, h.data(), h.size() * 8, hipMemcpyHostToDevice, e->main.st));
+        COMMCHK(fmcomm_allreduce_sum(e->comm, e->comm_buf, h.size(), true, e->main.st));
+        HIPCHK(hipMemcpyAsync(h.data(), e->comm_buf, h.size() * 8, hipMemcpyDeviceToHost, e->main.st));
+        HIPCHK(hipStreamSynchronize(e->main.st));
     }
     for (int c = 0; c < C; ++c) out_host[c] = h[C + c] == 0.0 ? 1.0 : h[c] / h[C + c];   // no active client: 1.0 (:66-67)
     return FM_OK;
@@ -2453,10 +2465,10 @@ int fm_fedavg_proto(fm_engine* e, const float* proto_host, double n_i, const flo
     }
     if (e->comm) {
         float* buf = reinterpret_cast<float*>(e->comm_buf);
-        HIPCHK(hipMemcpyAsync(buf, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->st));
-        COMMCHK(fmcomm_allreduce_sum(e->comm, buf, h.size(), false, e->st));
-        HIPCHK(hipMemcpyAsync(h.data(), buf, h.size() * 4, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
+        HIPCHK(hipMemcpyAsync(buf, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->main.st));
+        COMMCHK(fmcomm_allreduce_sum(e->comm, buf, h.size(), false, e->main.st));
+        HIPCHK(hipMemcpyAsync(h.data(), buf, h.size() * 4, hipMemcpyDeviceToHost, e->main.st));
+        HIPCHK(hipStreamSynchronize(e->main.st));
     }
     for (int r = 0; r < 2 * C; ++r)
         for (int d = 0; d < D; ++d) out_host[(size_t)r * D + d] = h[(size_t)r * D + d] / h[np + r];   // 0/0 = NaN row (:85-86)
@@ -2466,9 +2478,9 @@ int fm_fedavg_proto(fm_engine* e, const float* proto_host, double n_i, const flo
 int fm_teacher_snapshot(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    HIPCHK(hipMemcpyAsync(e->tstate, e->state, e->NS * 4, hipMemcpyDeviceToDevice, e->st));
-    e->tcounters = e->counters;
-    e->tev_dirty = true;
+    HIPCHK(hipMemcpyAsync(e->teacher.state, e->student.state, e->NS * 4, hipMemcpyDeviceToDevice, e->main.st));
+    e->teacher.counters = e->student.counters;
+    e->teacher.ev_dirty = true;
     e->twb_dirty = true;
     return FM_OK;
 }
@@ -2478,8 +2490,8 @@ int fm_adam_reset(fm_engine* e, const fm_adam* hp)
     ARGCHK(e, "null engine");
     if (hp) e->hp = *hp;
     e->adam_t = 0;
-    HIPCHK(hipMemsetAsync(e->adam_m, 0, e->NP * 4, e->st));
-    HIPCHK(hipMemsetAsync(e->adam_v, 0, e->NP * 4, e->st));
+    HIPCHK(hipMemsetAsync(e->adam_m, 0, e->NP * 4, e->main.st));
+    HIPCHK(hipMemsetAsync(e->adam_v, 0, e->NP * 4, e->main.st));
     return FM_OK;
 }
 
@@ -2489,14 +2501,14 @@ int fm_forward_eval(fm_engine* e, const float* x_dev, int32_t B, int32_t use_tea
     ARGCHK(e && x_dev, "null");
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     const float* xs[1] = {x_dev};
-    to_nhwc4(e, xs, 1, B);
-    net_forward_eval(e, use_teacher != 0, B);
-    if (feat_dev)
-        HIPCHK(hipMemcpyAsync(feat_dev, use_teacher ? e->tfeat : e->feat, (size_t)B * e->D * 4,
-                              hipMemcpyDeviceToDevice, e->st));
-    if (logits_dev)
-        HIPCHK(hipMemcpyAsync(logits_dev, use_teacher ? e->tlogits : e->logits, (size_t)B * e->C * 4,
-                              hipMemcpyDeviceToDevice, e->st));
+    to_nhwc4(e, e->main, xs, 1, B);
+    float* feat = use_teacher ? e->tfeat : e->feat;
+    float* logits = use_teacher ? e->tlogits : e->logits;
+    if (use_teacher) ensure_teacher_shadow(e);
+    else ensure_packed(e);
+    net_forward_eval(e, e->main, use_teacher ? e->teacher : e->student, e->acts, B, feat, logits);
+    if (feat_dev) HIPCHK(hipMemcpyAsync(feat_dev, feat, (size_t)B * e->D * 4, hipMemcpyDeviceToDevice, e->main.st));
+    if (logits_dev) HIPCHK(hipMemcpyAsync(logits_dev, logits, (size_t)B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -2507,10 +2519,10 @@ int fm_step_bce(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B,
     ARGCHK(e && x_dev && y_dev && pos_weight_host && loss_dev, "null");
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     const float* xs[1] = {x_dev};
-    to_nhwc4(e, xs, 1, B);
+    to_nhwc4(e, e->main, xs, 1, B);
     net_forward_train(e, 1, B);
     k_loss_bce(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, 1.f / ((float)bs_norm * (float)e->C),
-               e->dlogits, loss_dev, e->st);
+               e->dlogits, loss_dev, e->main.st);
     net_backward_and_step(e, 1, B);
     STEP_DONE(e);
     return FM_OK;
@@ -2524,21 +2536,21 @@ int fm_step_stage1(fm_engine* e, const float* x1_dev, const float* x2_dev, const
     int n_neg = 0;
     for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
     const float* xs[2] = {x1_dev, x2_dev};
-    to_nhwc4(e, xs, 2, B);
+    to_nhwc4(e, e->main, xs, 2, B);
     if (e->side_ok) {
-        // frozen teacher on the side stream (own buffers), student on the main stream; they meet at the loss
-        const int rc = teacher_forward_side(e, 2 * B);
-        if (rc != FM_OK) return rc;
+        // frozen teacher on the side lane (own activation set), student on the main lane; they meet at the loss
+        RCCHK(teacher_forward_side(e, 2 * B));
         net_forward_train(e, 2, B);
-        HIPCHK(hipStreamWaitEvent(e->st, e->ev_t, 0));
+        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
     } else {
         // frozen teacher first (eval mode; its activations may be overwritten by the student)
-        net_forward_eval(e, true, 2 * B);
+        ensure_teacher_shadow(e);
+        net_forward_eval(e, e->main, e->teacher, e->acts, 2 * B, e->tfeat, e->tlogits);
         net_forward_train(e, 2, B);
     }
     k_loss_stage1(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C,
                   1.f / ((float)bs_norm * (float)annotation_num),
-                  n_neg ? 1.f / ((float)bs_norm * (float)n_neg) : 0.f, e->dlogits, loss_dev, e->st);
+                  n_neg ? 1.f / ((float)bs_norm * (float)n_neg) : 0.f, e->dlogits, loss_dev, e->main.st);
     net_backward_and_step(e, 2, B);
     STEP_DONE(e);
     return FM_OK;
@@ -2550,9 +2562,9 @@ int fm_step_stage2(fm_engine* e, const float* x_dev, const float* y_dev, const f
     ARGCHK(e && x_dev && y_dev && distill_dev && loss_dev, "null");
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     const float* xs[1] = {x_dev};
-    to_nhwc4(e, xs, 1, B);
+    to_nhwc4(e, e->main, xs, 1, B);
     net_forward_train(e, 1, B);
-    k_loss_stage2(e->logits, y_dev, distill_dev, B, e->C, e->dlogits, loss_dev, e->st);
+    k_loss_stage2(e->logits, y_dev, distill_dev, B, e->C, e->dlogits, loss_dev, e->main.st);
     net_backward_and_step(e, 1, B);
     STEP_DONE(e);
     return FM_OK;
@@ -2568,11 +2580,11 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
     int n_neg = 0;
     for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
     const float* xs[2] = {xw_dev, xs_dev};
-    to_nhwc4(e, xs, 2, B);
+    to_nhwc4(e, e->main, xs, 2, B);
     net_forward_train(e, 2, B);
     k_loss_fixmatch(e->logits, y_dev, to_cv(pos_weight_host, e->C), to_cv(pos_weight_unk_host, e->C),
                     to_cv(active_mask_host, e->C), B, e->C, n_neg, 1.f / ((float)bs_norm * (float)annotation_num),
-                    e->C - annotation_num, e->dlogits, loss_dev, e->st);
+                    e->C - annotation_num, e->dlogits, loss_dev, e->main.st);
     net_backward_and_step(e, 2, B);
     STEP_DONE(e);
     return FM_OK;
@@ -2581,9 +2593,9 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
 int fm_proto_reset(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    HIPCHK(hipMemsetAsync(e->psum, 0, (size_t)2 * e->C * e->D * 4, e->st));
-    HIPCHK(hipMemsetAsync(e->pcnt, 0, (size_t)2 * e->C * 8, e->st));
-    HIPCHK(hipMemsetAsync(e->tcnt, 0, (size_t)e->C * 8, e->st));
+    HIPCHK(hipMemsetAsync(e->psum, 0, (size_t)2 * e->C * e->D * 4, e->main.st));
+    HIPCHK(hipMemsetAsync(e->pcnt, 0, (size_t)2 * e->C * 8, e->main.st));
+    HIPCHK(hipMemsetAsync(e->tcnt, 0, (size_t)e->C * 8, e->main.st));
     return FM_OK;
 }
 
@@ -2592,7 +2604,7 @@ int fm_proto_accumulate(fm_engine* e, const float* feat_dev, const float* logits
 {
     ARGCHK(e && feat_dev && logits_dev && labels_dev && active_mask_host && negative_mask_host, "null");
     k_proto_accumulate(feat_dev, logits_dev, labels_dev, B, e->D, e->C, to_cv(active_mask_host, e->C),
-                       to_cv(negative_mask_host, e->C), L, U, e->psum, e->pcnt, e->tcnt, e->st);
+                       to_cv(negative_mask_host, e->C), L, U, e->psum, e->pcnt, e->tcnt, e->main.st);
     return FM_OK;
 }
 
@@ -2602,10 +2614,10 @@ int fm_proto_finalize(fm_engine* e, int32_t zero_guard, int64_t n_local, const f
     ARGCHK(e && active_mask_host && proto_host && t_host, "null");
     std::vector<int64_t> pc(2 * e->C), tc(e->C);
     const int D = e->D;
-    HIPCHK(hipMemcpyAsync(proto_host, e->psum, (size_t)2 * e->C * D * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(pc.data(), e->pcnt, pc.size() * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipMemcpyAsync(tc.data(), e->tcnt, tc.size() * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipMemcpyAsync(proto_host, e->psum, (size_t)2 * e->C * D * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipMemcpyAsync(pc.data(), e->pcnt, pc.size() * 8, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipMemcpyAsync(tc.data(), e->tcnt, tc.size() * 8, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     for (int c = 0; c < e->C; ++c) {
         t_host[c] = (double)tc[c] / (double)n_local;
         if (active_mask_host[c] == 0.f) continue;
@@ -2625,8 +2637,8 @@ int fm_cos_tag(fm_engine* e, const float* feat_dev, int64_t N, const float* prot
     ARGCHK(e && feat_dev && proto_dev && classes_host && sim_dev, "null");
     ARGCHK(n_cls >= 0 && n_cls <= FM_MAX_CLASSES, "n_cls");
     if (n_cls == 0 || N == 0) return FM_OK;
-    HIPCHK(hipMemcpyAsync(e->cls_dev, classes_host, (size_t)n_cls * 4, hipMemcpyHostToDevice, e->st));
-    k_cos_tag(feat_dev, N, e->D, proto_dev, e->cls_dev, n_cls, sim_dev, e->st);
+    HIPCHK(hipMemcpyAsync(e->cls_dev, classes_host, (size_t)n_cls * 4, hipMemcpyHostToDevice, e->main.st));
+    k_cos_tag(feat_dev, N, e->D, proto_dev, e->cls_dev, n_cls, sim_dev, e->main.st);
     return FM_OK;
 }
 
@@ -2638,9 +2650,9 @@ int fm_select_topk(fm_engine* e, const float* sim_dev, int64_t N, double clean_t
     if (N == 0) return FM_OK;              // an empty pool selects nothing (sim_dev may be NULL then)
     ARGCHK(sim_dev, "null sim_dev");
     int counts[2];
-    k_count_sign(sim_dev, N, e->sel_counts, e->st);
-    HIPCHK(hipMemcpyAsync(counts, e->sel_counts, 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    k_count_sign(sim_dev, N, e->sel_counts, e->main.st);
+    HIPCHK(hipMemcpyAsync(counts, e->sel_counts, 8, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     const int kt = (int)(1 * clean_thr * counts[0]);      // int() truncation as in :1069-1070
     const int kb = (int)(1 * noise_thr * counts[1]);
     ARGCHK(kt <= cap && kb <= cap, "selection exceeds cap");
@@ -2650,10 +2662,10 @@ int fm_select_topk(fm_engine* e, const float* sim_dev, int64_t N, double clean_t
         DALLOC(e->sel_top, e->sel_cap);
         DALLOC(e->sel_bot, e->sel_cap);
     }
-    k_rank_select(sim_dev, N, kt, kb, e->sel_top, e->sel_bot, e->st);
-    if (kt) HIPCHK(hipMemcpyAsync(top_host, e->sel_top, (size_t)kt * 4, hipMemcpyDeviceToHost, e->st));
-    if (kb) HIPCHK(hipMemcpyAsync(bot_host, e->sel_bot, (size_t)kb * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    k_rank_select(sim_dev, N, kt, kb, e->sel_top, e->sel_bot, e->main.st);
+    if (kt) HIPCHK(hipMemcpyAsync(top_host, e->sel_top, (size_t)kt * 4, hipMemcpyDeviceToHost, e->main.st));
+    if (kb) HIPCHK(hipMemcpyAsync(bot_host, e->sel_bot, (size_t)kb * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     *n_top = kt; *n_bot = kb;
     return FM_OK;
 }
@@ -2682,7 +2694,7 @@ int fm_select_topk_rows(fm_engine* e, const float* sim_dev, int64_t N, int32_t n
     const size_t need = (size_t)n_cls * (3 + 2 * (size_t)cap) + rows_ints;
     if (e->tag_buf_ints < need) {
         if (e->tag_buf) {               // the outgrown buffer goes back now, not at fm_destroy (the stream may still read it)
-            HIPCHK(hipStreamSynchronize(e->st));
+            HIPCHK(hipStreamSynchronize(e->main.st));
             auto it = std::find(e->allocs.begin(), e->allocs.end(), (void*)e->tag_buf);
             if (it != e->allocs.end()) e->allocs.erase(it);
             (void)hipFree(e->tag_buf);
@@ -2697,13 +2709,13 @@ int fm_select_topk_rows(fm_engine* e, const float* sim_dev, int64_t N, int32_t n
     int* d_top = d_counts + 2 * n_cls;
     int* d_bot = d_top + (size_t)n_cls * cap;
     int* d_rows = pool_rows_host ? d_bot + (size_t)n_cls * cap : nullptr;
-    HIPCHK(hipMemcpyAsync(d_pn, pool_n_host, (size_t)n_cls * 4, hipMemcpyHostToDevice, e->st));
-    if (d_rows) HIPCHK(hipMemcpyAsync(d_rows, pool_rows_host, rows_ints * 4, hipMemcpyHostToDevice, e->st));
-    k_select_rows(sim_dev, N, n_cls, d_rows, d_pn, stride, maxn, clean_thr, noise_thr, cap, d_counts, d_top, d_bot, e->st);
+    HIPCHK(hipMemcpyAsync(d_pn, pool_n_host, (size_t)n_cls * 4, hipMemcpyHostToDevice, e->main.st));
+    if (d_rows) HIPCHK(hipMemcpyAsync(d_rows, pool_rows_host, rows_ints * 4, hipMemcpyHostToDevice, e->main.st));
+    k_select_rows(sim_dev, N, n_cls, d_rows, d_pn, stride, maxn, clean_thr, noise_thr, cap, d_counts, d_top, d_bot, e->main.st);
     // ONE device-to-host read: the counts and both pick tables
     std::vector<int> h((size_t)n_cls * (2 + 2 * (size_t)cap));
-    HIPCHK(hipMemcpyAsync(h.data(), d_counts, h.size() * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipMemcpyAsync(h.data(), d_counts, h.size() * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     for (int k = 0; k < n_cls; ++k) {
         const int kt = (int)(1 * clean_thr * h[2 * k]), kb = (int)(1 * noise_thr * h[2 * k + 1]);     // int() truncation as in :1069-1070
         ARGCHK(kt <= cap && kb <= cap, "selection exceeds cap");
@@ -2719,7 +2731,7 @@ int fm_augment(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, c
 {
     ARGCHK(e && cache_dev && idx_dev && params_dev && mean_host && std_host && out_dev && B >= 1, "null");
     k_augment(cache_dev, idx_dev, params_dev, out_dev, B, e->H, e->W, mean_host[0], mean_host[1], mean_host[2],
-              std_host[0], std_host[1], std_host[2], e->st);
+              std_host[0], std_host[1], std_host[2], e->main.st);
     return FM_OK;
 }
 
@@ -2731,7 +2743,7 @@ int fm_augment_strong(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx
     ARGCHK(e->W % 4 == 0 && e->H >= 1, "the strong view packs four pixels of a row per thread: W % 4 == 0");
     if (!e->strong_ws) DALLOC(e->strong_ws, fm_strong_ws_bytes(e->maxB, e->H, e->W));    // first use: weak-only users never pay for it
     k_augment_strong(cache_dev, idx_dev, params_dev, strong_dev, e->strong_ws, e->maxB, out_dev, B, e->H, e->W, mean_host[0],
-                     mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], e->st);
+                     mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], e->main.st);
     return FM_OK;
 }
 
@@ -2742,12 +2754,12 @@ int fm_forward_train(fm_engine* e, const float* x1_dev, const float* x2_dev, int
     const int views = x2_dev ? 2 : 1;
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
     const float* xs[2] = {x1_dev, x2_dev};
-    to_nhwc4(e, xs, views, B);
-    net_forward_train(e, views, B, true, e->bn_freeze);
+    to_nhwc4(e, e->main, xs, views, B);
+    net_forward_train(e, views, B, e->bn_freeze ? BnMode::Frozen : BnMode::Batch);
     if (feat_dev)
-        HIPCHK(hipMemcpyAsync(feat_dev, e->feat, (size_t)views * B * e->D * 4, hipMemcpyDeviceToDevice, e->st));
+        HIPCHK(hipMemcpyAsync(feat_dev, e->feat, (size_t)views * B * e->D * 4, hipMemcpyDeviceToDevice, e->main.st));
     if (logits_dev)
-        HIPCHK(hipMemcpyAsync(logits_dev, e->logits, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->st));
+        HIPCHK(hipMemcpyAsync(logits_dev, e->logits, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
     e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
     STEP_DONE(e);
     return FM_OK;
@@ -2770,8 +2782,10 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
     ARGCHK(e && dlogits_dev, "null");
     ARGCHK(e->pending_views > 0, "fm_backward_step without a preceding fm_forward_train");
     const int views = e->pending_views, B = e->pending_B;
-    HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->st));
-    net_backward_and_step(e, views, B, true, e->pending_fixed);
+    HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
+    Bwd bw;
+    bw.frozen = e->pending_fixed;
+    net_backward_and_step(e, views, B, bw);
     e->pending_views = 0;
     STEP_DONE(e);
     return FM_OK;
@@ -2789,19 +2803,16 @@ int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfe
     const int views = e->pending_views, B = e->pending_B;
     ARGCHK(views == 2 || !dx2_dev, "fm_backward_grads_x: dx2 given, but the pending forward has one view");
     if (dx1_dev || dx2_dev) {                      // first use: the stem's weights as the data gradient's B matrix
-        const int rc = ensure_stem_dpack(e);
-        if (rc != FM_OK) return rc;
+        RCCHK(ensure_stem_dpack(e));
     }
-    e->dx_out[0] = dx1_dev; e->dx_out[1] = dx2_dev;
     if (!e->gacc) DALLOC(e->gacc, e->NP);          // first use: fused-only users never pay for the accumulator
     const size_t nz = (size_t)views * B * e->C * 4;
-    if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->st));
-    else HIPCHK(hipMemsetAsync(e->dlogits, 0, nz, e->st));
-    e->dfeat_dev = dfeat_dev;
-    net_backward_and_step(e, views, B, false, e->pending_fixed);     // e->grad, every weight gradient joined to the main stream
-    e->dfeat_dev = nullptr;
-    e->dx_out[0] = e->dx_out[1] = nullptr;
-    k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->st, e->dev_err);
+    if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->main.st));
+    else HIPCHK(hipMemsetAsync(e->dlogits, 0, nz, e->main.st));
+    Bwd bw;
+    bw.frozen = e->pending_fixed; bw.dfeat = dfeat_dev; bw.dx[0] = dx1_dev; bw.dx[1] = dx2_dev; bw.step = false;
+    net_backward_and_step(e, views, B, bw);      // e->grad, every weight gradient joined to the main lane
+    k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->main.st, e->dev_err);
     e->pending_views = 0;
     STEP_DONE(e);
     e->gacc_full = true;
@@ -2814,8 +2825,8 @@ int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev,
     const int views = x2_dev ? 2 : 1;
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
     const float* xs[2] = {x1_dev, x2_dev};
-    to_nhwc4(e, xs, views, B);
-    net_forward_train(e, views, B, false, e->bn_freeze);
+    to_nhwc4(e, e->main, xs, views, B);
+    net_forward_train(e, views, B, e->bn_freeze ? BnMode::Frozen : BnMode::BatchNoUpdate);
     e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
     STEP_DONE(e);
     return FM_OK;
@@ -2841,10 +2852,9 @@ int fm_adam_step(fm_engine* e, const fm_adam* hp)
 int fm_get_grads(fm_engine* e, float* dev_out)
 {
     ARGCHK(e && dev_out, "null");
-    if (!e->gacc_full) HIPCHK(hipMemsetAsync(dev_out, 0, (size_t)e->nf_sd * 4, e->st));
+    if (!e->gacc_full) HIPCHK(hipMemsetAsync(dev_out, 0, (size_t)e->nf_sd * 4, e->main.st));
     else {
-        const int rc = grads_to_state_dict(e, e->gacc, dev_out);
-        if (rc != FM_OK) return rc;
+        RCCHK(grads_to_state_dict(e, e->gacc, dev_out));
     }
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -2853,11 +2863,11 @@ int fm_get_grads(fm_engine* e, float* dev_out)
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
 {
     ARGCHK(e, "null engine");
-    k_axpby(e->tstate, e->state, w_teacher, w_student, (int64_t)e->NS, e->st);
+    k_axpby(e->teacher.state, e->student.state, w_teacher, w_student, (int64_t)e->NS, e->main.st);
     // int64 num_batches_tracked: the float result is truncated when it is loaded back (like FedAvg, Q7)
-    for (size_t i = 0; i < e->counters.size(); ++i)
-        e->tcounters[i] = (int64_t)(w_teacher * (float)e->tcounters[i] + w_student * (float)e->counters[i]);
-    e->tev_dirty = true;
+    for (size_t i = 0; i < e->student.counters.size(); ++i)
+        e->teacher.counters[i] = (int64_t)(w_teacher * (float)e->teacher.counters[i] + w_student * (float)e->student.counters[i]);
+    e->teacher.ev_dirty = true;
     e->twb_dirty = true;
     return FM_OK;
 }
@@ -2865,12 +2875,8 @@ int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
 int fm_teacher_swap(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    std::swap(e->state, e->tstate);
-    std::swap(e->ev_scale, e->tev_scale);
-    std::swap(e->ev_shift, e->tev_shift);
-    std::swap(e->ev_dirty, e->tev_dirty);
-    std::swap(e->counters, e->tcounters);
-    e->wpack_dirty = true;
+    std::swap(e->student, e->teacher);
+    e->wpack_dirty = true;        // the shadows went along; both sets are remade all the same, as they always were
     e->twb_dirty = true;
     return FM_OK;
 }
@@ -2895,7 +2901,7 @@ int fm_profile_enable(fm_engine* e, int32_t on)
 int fm_profile_read(fm_engine* e, int32_t family, int64_t* launches, double* ms, double* flops)
 {
     ARGCHK(e && family >= 0 && family < FM_PROFILE_FAMILIES, "family");
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     if (e->prof_fail) { e->prof_fail = false; g_err = "a profiling event could not be created/recorded"; return FM_ERR_HIP; }
     for (auto& p : e->evs) {
         float t = 0.f;
@@ -2924,30 +2930,18 @@ int fm_debug_pw(fm_engine* e, int32_t op, int32_t conv, const void* x_dev, const
     const Prologue pro{psc_dev, psh_dev, gate_dev};
     if (op == 0) {
         ARGCHK(x_dev, "x");
-        conv_fwd(e, conv, e->state, reinterpret_cast<const float*>(x_dev), reinterpret_cast<float*>(out_dev), imgs, groups,
+        conv_fwd(e, e->main, conv, e->student, reinterpret_cast<const float*>(x_dev), reinterpret_cast<float*>(out_dev), imgs, groups,
                  nullptr, nullptr, nullptr, 0, stats_dev ? e->ws_stats : nullptr, gate_dev ? &pro : nullptr);
-        if (stats_dev) {
-            const int tiles = stats_tiles(e, conv, imgs / groups, groups);
-            std::vector<float> h((size_t)groups * tiles * 2 * c.cout_p), o((size_t)groups * 2 * c.cout_p, 0.f);
-            HIPCHK(hipMemcpyAsync(h.data(), e->ws_stats, h.size() * 4, hipMemcpyDeviceToHost, e->st));
-            HIPCHK(hipStreamSynchronize(e->st));
-            for (int g = 0; g < groups; ++g)
-                for (int k = 0; k < 2 * c.cout_p; ++k) {
-                    double sum = 0;
-                    for (int t = 0; t < tiles; ++t) sum += h[((size_t)g * tiles + t) * 2 * c.cout_p + k];
-                    o[(size_t)g * 2 * c.cout_p + k] = (float)sum;
-                }
-            HIPCHK(hipMemcpy(stats_dev, o.data(), o.size() * 4, hipMemcpyHostToDevice));
-        }
+        if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     } else if (op == 1) {
         ARGCHK(dy_dev, "dy");
-        conv_dgrad(e, conv, e->state, reinterpret_cast<const float*>(dy_dev), reinterpret_cast<float*>(out_dev), imgs,
+        conv_dgrad(e, e->main, conv, reinterpret_cast<const float*>(dy_dev), reinterpret_cast<float*>(out_dev), imgs,
                    reinterpret_cast<const float*>(x_dev), false);      // x_dev = optional residual [npix][cin_p] bf16
     } else if (op == 2) {
         ARGCHK(x_dev && dy_dev, "x/dy");
-        conv_wgrad(e, conv, reinterpret_cast<const float*>(x_dev), reinterpret_cast<const float*>(dy_dev), imgs,
+        conv_wgrad(e, e->main, conv, reinterpret_cast<const float*>(x_dev), reinterpret_cast<const float*>(dy_dev), imgs,
                    gate_dev ? &pro : nullptr, (imgs / groups) * c.hout * c.wout);
-        HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->st));
+        HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->main.st));
     } else {
         ARGCHK(false, "op");
     }
@@ -2972,30 +2966,30 @@ int fm_debug_proj_bwd(fm_engine* e, int32_t conv, int32_t phase, const void* dyp
     if (e->precision) {
         PwProjBwdParams q{};
         q.dYp = reinterpret_cast<const bf16*>(dyp_dev); q.Yd = reinterpret_cast<const bf16*>(yd_dev);
-        q.Wt = e->wb + c.wbt_off; q.dYd = reinterpret_cast<bf16*>(out_dev);
-        q.slab = e->ws_slab; q.pool5 = e->se_pool;
+        q.Wt = e->student.wb + c.wbt_off; q.dYd = reinterpret_cast<bf16*>(out_dev);
+        q.slab = e->main.ws_slab; q.pool5 = e->acts.se_pool;
         q.sc = bn_dev; q.sh = bn_dev + gl; q.mean = bn_dev + 2 * gl; q.istd = bn_dev + 3 * gl;
         q.ca = bn_dev + 4 * gl; q.cb = bn_dev + 5 * gl; q.cc = bn_dev + 6 * gl;
         q.gate = gate_dev; q.ds = ds_dev;
         q.L = L; q.S = c.cout_p; q.imgs = imgs; q.HW = HW; q.ipg = imgs / groups; q.nch = nch;
-        sk = launch_pw_proj_bwd(q, phase, e->slab_floats, e->st);
+        sk = launch_pw_proj_bwd(q, phase, e->slab_floats, e->main.st);
     } else {
         PwProjBwdF32Params q{};
         q.dYp = reinterpret_cast<const float*>(dyp_dev); q.Yd = reinterpret_cast<const float*>(yd_dev);
-        q.W = e->state + c.w_off; q.dYd = reinterpret_cast<float*>(out_dev);
-        q.slab = e->ws_slab; q.pool5 = e->se_pool;
+        q.W = e->student.state + c.w_off; q.dYd = reinterpret_cast<float*>(out_dev);
+        q.slab = e->main.ws_slab; q.pool5 = e->acts.se_pool;
         q.sc = bn_dev; q.sh = bn_dev + gl; q.mean = bn_dev + 2 * gl; q.istd = bn_dev + 3 * gl;
         q.ca = bn_dev + 4 * gl; q.cb = bn_dev + 5 * gl; q.cc = bn_dev + 6 * gl;
         q.gate = gate_dev; q.ds = ds_dev;
         q.L = L; q.S = c.cout_p; q.imgs = imgs; q.HW = HW; q.ipg = imgs / groups; q.nch = nch;
-        sk = launch_pw_proj_bwd_f32(q, phase, e->slab_floats, e->st);
+        sk = launch_pw_proj_bwd_f32(q, phase, e->slab_floats, e->main.st);
     }
     ARGCHK(sk > 0, "launch refused");
     if (phase == 0) {
-        k_reduce_slabs(e->ws_slab, reinterpret_cast<float*>(out_dev), sk, (int64_t)c.w_numel, e->st);
+        k_reduce_slabs(e->main.ws_slab, reinterpret_cast<float*>(out_dev), sk, (int64_t)c.w_numel, e->main.st);
         std::vector<float> h((size_t)imgs * nch * 5 * L), o((size_t)imgs * 5 * L);
-        HIPCHK(hipMemcpyAsync(h.data(), e->se_pool, h.size() * 4, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
+        HIPCHK(hipMemcpyAsync(h.data(), e->acts.se_pool, h.size() * 4, hipMemcpyDeviceToHost, e->main.st));
+        HIPCHK(hipStreamSynchronize(e->main.st));
         for (int i = 0; i < imgs; ++i)
             for (int k = 0; k < 5 * L; ++k) {
                 double sum = 0;
@@ -3022,22 +3016,22 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
     if (e->precision) {
         PwExpBwdParams q{};
         q.dA = reinterpret_cast<const bf16*>(da_dev); q.Ye = reinterpret_cast<const bf16*>(ye_dev);
-        q.X = reinterpret_cast<const bf16*>(x_dev); q.Wt = e->wb + c.wbt_off; q.res = reinterpret_cast<const bf16*>(res_dev);
-        q.dX = reinterpret_cast<bf16*>(dx_dev); q.slab = e->ws_slab;
+        q.X = reinterpret_cast<const bf16*>(x_dev); q.Wt = e->student.wb + c.wbt_off; q.res = reinterpret_cast<const bf16*>(res_dev);
+        q.dX = reinterpret_cast<bf16*>(dx_dev); q.slab = e->main.ws_slab;
         q.ca = bn_dev; q.cb = bn_dev + gl; q.cc = bn_dev + 2 * gl; q.sc = bn_dev + 3 * gl; q.sh = bn_dev + 4 * gl;
         q.L = L; q.S = S; q.npix = imgs * HW; q.pix_per_group = (imgs / groups) * HW; q.groups = groups;
-        sk = launch_pw_exp_bwd(q, e->slab_floats, e->st);
+        sk = launch_pw_exp_bwd(q, e->slab_floats, e->main.st);
     } else {
         PwExpBwdF32Params q{};
         q.dA = reinterpret_cast<const float*>(da_dev); q.Ye = reinterpret_cast<const float*>(ye_dev);
-        q.X = reinterpret_cast<const float*>(x_dev); q.W = e->state + c.w_off; q.res = reinterpret_cast<const float*>(res_dev);
-        q.dX = reinterpret_cast<float*>(dx_dev); q.slab = e->ws_slab;
+        q.X = reinterpret_cast<const float*>(x_dev); q.W = e->student.state + c.w_off; q.res = reinterpret_cast<const float*>(res_dev);
+        q.dX = reinterpret_cast<float*>(dx_dev); q.slab = e->main.ws_slab;
         q.ca = bn_dev; q.cb = bn_dev + gl; q.cc = bn_dev + 2 * gl; q.sc = bn_dev + 3 * gl; q.sh = bn_dev + 4 * gl;
         q.L = L; q.S = S; q.npix = imgs * HW; q.pix_per_group = (imgs / groups) * HW; q.groups = groups;
-        sk = launch_pw_exp_bwd_f32(q, e->slab_floats, e->st);
+        sk = launch_pw_exp_bwd_f32(q, e->slab_floats, e->main.st);
     }
     ARGCHK(sk > 0, "shape not handled by the fused expand backward");
-    k_reduce_slabs(e->ws_slab, dw_dev, sk, (int64_t)c.w_numel, e->st);
+    k_reduce_slabs(e->main.ws_slab, dw_dev, sk, (int64_t)c.w_numel, e->main.st);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -3045,17 +3039,16 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
 int fm_debug_get_grads(fm_engine* e, float* host_f32)
 {
     ARGCHK(e && host_f32, "null");
-    const int rc = grads_to_state_dict(e, e->grad, e->stage_sd);
-    if (rc != FM_OK) return rc;
-    HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipStreamSynchronize(e->st));
+    RCCHK(grads_to_state_dict(e, e->grad, e->stage_sd));
+    HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->main.st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     return FM_OK;
 }
 
 int fm_profile_ops(fm_engine* e, int32_t enable, char* buf, int32_t cap)
 {
     ARGCHK(e, "null engine");
-    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipStreamSynchronize(e->main.st));
     for (auto& p : e->opevs) {
         float t = 0.f;
         if (hipEventElapsedTime(&t, p.a, p.b) == hipSuccess) { e->op_ms[p.id] += t; e->op_n[p.id] += 1; }
@@ -3083,16 +3076,16 @@ int fm_debug_activation(fm_engine* e, int32_t kind, int32_t block, int32_t imgs,
     ARGCHK(e && dims4 && e->model == 0, "ResNet-18 engine only");
     ARGCHK(block >= 0 && block < (int)e->blocks.size() && (kind == 0 || kind == 1), "kind/block");
     ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
-    const Block& b = e->blocks[block];
-    const Conv& c = e->convs[b.c1];
+    const BlockActs& b = e->acts.blk[block];
+    const Conv& c = e->convs[e->blocks[block].c1];
     dims4[0] = imgs; dims4[1] = c.hout; dims4[2] = c.wout; dims4[3] = c.cout;
     if (host_nhwc) {
         // planes mode: z1 / out (all blocks but the last) live only as planes: re-form the fp32 values in the idle fp32 buffer
         if (e->planes && (kind == 0 || block + 1 < (int)e->blocks.size()))
-            k_planes_to_f32(kind == 0 ? b.z1p : b.outp, kind == 0 ? b.z1 : b.out, (long long)imgs * c.hout * c.wout, c.cout, e->st);
+            k_planes_to_f32(kind == 0 ? b.z1p : b.outp, kind == 0 ? b.z1 : b.out, (long long)imgs * c.hout * c.wout, c.cout, e->main.st);
         HIPCHK(hipMemcpyAsync(host_nhwc, kind == 0 ? b.z1 : b.out, (size_t)imgs * c.hout * c.wout * c.cout * 4,
-                              hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
+                              hipMemcpyDeviceToHost, e->main.st));
+        HIPCHK(hipStreamSynchronize(e->main.st));
     }
     return FM_OK;
 }
@@ -3112,15 +3105,15 @@ int fm_debug_stem_masks(fm_engine* e, int32_t imgs, int32_t groups, uint8_t* rel
     if (relu_bits_host) {
         uint8_t* bits = nullptr;
         HIPCHK(hipMalloc(&bits, (size_t)pix * 8));
-        k_stem_relu_bits(c0.y, e->bns[0].scale, e->bns[0].shift, bits, groups, pix / groups, 64, e->st);
-        hipError_t rc = hipMemcpyAsync(relu_bits_host, bits, (size_t)pix * 8, hipMemcpyDeviceToHost, e->st);
-        if (rc == hipSuccess) rc = hipStreamSynchronize(e->st);
+        k_stem_relu_bits(e->acts.stem_y, e->bns[0].scale, e->bns[0].shift, bits, groups, pix / groups, 64, e->main.st);
+        hipError_t rc = hipMemcpyAsync(relu_bits_host, bits, (size_t)pix * 8, hipMemcpyDeviceToHost, e->main.st);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(e->main.st);
         (void)hipFree(bits);
         HIPCHK(rc);
     }
     if (argmax_host) {
-        HIPCHK(hipMemcpyAsync(argmax_host, e->idx0, (size_t)imgs * (c0.hout / 2) * (c0.wout / 2) * 64, hipMemcpyDeviceToHost, e->st));
-        HIPCHK(hipStreamSynchronize(e->st));
+        HIPCHK(hipMemcpyAsync(argmax_host, e->idx0, (size_t)imgs * (c0.hout / 2) * (c0.wout / 2) * 64, hipMemcpyDeviceToHost, e->main.st));
+        HIPCHK(hipStreamSynchronize(e->main.st));
     }
     return FM_OK;
 }
@@ -3133,9 +3126,9 @@ int fm_debug_block_dgrad(fm_engine* e, int32_t block, const float* dy1_dev, cons
     ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
     ensure_packed(e);
     const Block& blk = e->blocks[block];
-    if (!block_dgrad(e, blk.c1, blk.ds, dy1_dev, dyd_dev, dx_dev, imgs)) {     // (the fp32-operand engine: its two calls)
-        conv_dgrad(e, blk.ds, e->state, dyd_dev, dx_dev, imgs, nullptr, false);
-        conv_dgrad(e, blk.c1, e->state, dy1_dev, dx_dev, imgs, nullptr, true);
+    if (!block_dgrad(e, e->main, blk.c1, blk.ds, dy1_dev, dyd_dev, dx_dev, imgs)) {     // (the fp32-operand engine: its two calls)
+        conv_dgrad(e, e->main, blk.ds, dyd_dev, dx_dev, imgs, nullptr, false);
+        conv_dgrad(e, e->main, blk.c1, dy1_dev, dx_dev, imgs, nullptr, true);
     }
     return FM_OK;
 }
@@ -3158,38 +3151,24 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
     ARGCHK(imgs >= 1 && imgs <= e->maxB && groups >= 1 && imgs % groups == 0, "imgs/groups");
     Conv& c = e->convs[conv];
     if (c.stem3 && x_dev)       // the packed stem reads the framed copy of its [imgs][H][W][3] input
-        k_frame_nhwc3(x_dev, e->x3, imgs, c.hin, c.win, c.Hp, c.Wp, 3, 3, 1, e->st, e->stem_rows ? e->x3p : nullptr, e->x3p_plane_elems);
+        k_frame_nhwc3(x_dev, e->x3, imgs, c.hin, c.win, c.Hp, c.Wp, 3, 3, 1, e->main.st, e->stem_rows ? e->x3p : nullptr, e->x3p_plane_elems);
     ensure_packed(e);           // the forward reads the weight planes, the data gradient the transposed packs
     if (op == 0) {
         ARGCHK(x_dev, "x");
-        conv_fwd(e, conv, e->state, x_dev, out_dev, imgs, groups, nullptr, nullptr, nullptr, 0,
+        conv_fwd(e, e->main, conv, e->student, x_dev, out_dev, imgs, groups, nullptr, nullptr, nullptr, 0,
                  stats_dev ? e->ws_stats : nullptr);
-        if (stats_dev) {
-            // fold the per-tile partials with the finalize kernel's own reduction order: sum/sumsq only
-            const int tiles = stats_tiles(e, conv, imgs / groups, groups);
-            std::vector<float> h((size_t)groups * tiles * 2 * c.cout_p), o((size_t)groups * 2 * c.cout_p, 0.f);
-            HIPCHK(hipMemcpyAsync(h.data(), e->ws_stats, h.size() * 4, hipMemcpyDeviceToHost, e->st));
-            HIPCHK(hipStreamSynchronize(e->st));
-            for (int g = 0; g < groups; ++g)
-                for (int k = 0; k < 2 * c.cout_p; ++k) {
-                    double s = 0;
-                    for (int t = 0; t < tiles; ++t) s += h[((size_t)g * tiles + t) * 2 * c.cout_p + k];
-                    o[(size_t)g * 2 * c.cout_p + k] = (float)s;
-                }
-            HIPCHK(hipMemcpy(stats_dev, o.data(), o.size() * 4, hipMemcpyHostToDevice));
-        }
+        if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     } else if (op == 1) {
         ARGCHK(dy_dev && (c.ncls > 0 || c.cin == 3), "dgrad unavailable for this conv");
         ensure_packed(e);
         if (c.cin == 3) {           // the stem: stem_dgrad.hip with its NHWC store, dx [imgs][hin][win][3]
-            const int rc = ensure_stem_dpack(e);
-            if (rc != FM_OK) return rc;
-            stem_dgrad(e, dy_dev, out_dev, imgs, true);
-        } else conv_dgrad(e, conv, e->state, dy_dev, out_dev, imgs, nullptr, false);
+            RCCHK(ensure_stem_dpack(e));
+            stem_dgrad(e, e->main, dy_dev, out_dev, imgs, true);
+        } else conv_dgrad(e, e->main, conv, dy_dev, out_dev, imgs, nullptr, false);
     } else if (op == 2) {
         ARGCHK(x_dev && dy_dev, "x/dy");
-        conv_wgrad(e, conv, x_dev, dy_dev, imgs);
-        HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->st));
+        conv_wgrad(e, e->main, conv, x_dev, dy_dev, imgs);
+        HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->main.st));
     } else {
         ARGCHK(false, "op");
     }

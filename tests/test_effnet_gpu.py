@@ -512,6 +512,44 @@ def test_stage1_two_stream_step_is_deterministic_and_equals_one_stream(monkeypat
         np.testing.assert_array_equal(outs[0][0], outs[k][0])
 
 
+def test_autograd_path_equals_across_stream_modes():
+    """The split path -- forward_train, backward_grads with d loss / d feature and both views' input gradients,
+    forward_recompute, a second backward_grads, adam_step -- with frozen and with batch statistics, in every stream mode:
+    the orders differ only in which stream a launch goes to, so gradients, input gradients, outputs, the state after Adam
+    and the counters are the same bits as with side stream for teacher and weight gradients (streams=0)."""
+    from fedmlp_amd.engine import Engine
+    hw, B = 64, 6
+    g = torch.Generator().manual_seed(50)
+    x1 = torch.randn((B, 3, hw, hw), generator=g).cuda(); x2 = torch.randn((B, 3, hw, hw), generator=g).cuda()
+    dlogits = torch.randn((2 * B, C_), generator=g).cuda()
+    dfeat = torch.randn((2 * B, 1280), generator=g).cuda()
+    for freeze in (False, True):
+        outs = []
+        for streams in (0, 1, 2):
+            e = Engine(M, C_, hw, hw, 4 * B, streams=streams)
+            try:
+                e.stochastic = False
+                _load(e)
+                e.teacher_snapshot()
+                e.bn_freeze(freeze)
+                feat, logits = e.forward_train(x1, x2)
+                dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
+                e.backward_grads(dlogits, dfeat, dx=(dx1, dx2))
+                e.forward_recompute(x1, x2)
+                e.backward_grads(dlogits)
+                grads = e.grads().cpu().numpy()
+                e.adam_step(LR)
+                flat, _ = e.get_state()
+                outs.append([grads, dx1.cpu().numpy(), dx2.cpu().numpy(), feat.cpu().numpy(), logits.cpu().numpy(), flat.copy(),
+                             np.asarray(e.counters()).copy()])
+            finally:
+                e.close()
+        assert np.isfinite(outs[0][0]).all() and np.abs(outs[0][1]).max() > 0
+        for k in (1, 2):
+            for want, got in zip(outs[0], outs[k]):
+                np.testing.assert_array_equal(want, got)
+
+
 def test_build_model_call_surface():
     """net = build_model(args); net.eval(); feature, logits = net(x) -- the eval-mode call of
     utils/evaluations.py:25 -- for --model Efficient_b0 (feature width 1280)."""

@@ -344,6 +344,61 @@ def test_stage1_two_stream_teacher_equals_one_stream(monkeypatch):
         np.testing.assert_array_equal(outs[0][0], outs[k][0])
 
 
+def test_autograd_path_equals_across_stream_modes():
+    """The split path -- forward_train, backward_grads with d loss / d feature and both views' input gradients,
+    forward_recompute, a second backward_grads, adam_step -- with frozen and with batch statistics, in every stream mode:
+    the orders differ only in which stream a launch goes to, so gradients, input gradients, outputs, the state after Adam
+    and the counters are the same bits as with side stream for teacher and weight gradients (streams=0)."""
+    from fedmlp_amd.engine import Engine
+    B = 3
+    (x1, x2), _ = _data(B, 46, views=2)
+    g = torch.Generator().manual_seed(47)
+    dlogits = torch.randn((2 * B, C_), generator=g).cuda()
+    dfeat = torch.randn((2 * B, 512), generator=g).cuda()
+    x1, x2 = x1.cuda(), x2.cuda()
+    for freeze in (False, True):
+        outs = []
+        for streams in (0, 1, 2):
+            e = Engine("Resnet18", C_, HW, HW, 16, streams=streams)
+            try:
+                _load(e)
+                e.teacher_snapshot()
+                e.bn_freeze(freeze)
+                feat, logits = e.forward_train(x1, x2)
+                dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
+                e.backward_grads(dlogits, dfeat, dx=(dx1, dx2))
+                e.forward_recompute(x1, x2)
+                e.backward_grads(dlogits)
+                grads = e.grads().cpu().numpy()
+                e.adam_step(LR)
+                flat, _ = e.get_state()
+                outs.append([grads, dx1.cpu().numpy(), dx2.cpu().numpy(), feat.cpu().numpy(), logits.cpu().numpy(), flat.copy(),
+                             np.asarray(e.counters()).copy()])
+            finally:
+                e.close()
+        assert np.isfinite(outs[0][0]).all() and np.abs(outs[0][1]).max() > 0
+        for k in (1, 2):
+            for want, got in zip(outs[0], outs[k]):
+                np.testing.assert_array_equal(want, got)
+
+
+def test_teacher_swap_exchanges_the_two_nets(eng):
+    """After teacher_snapshot, one training step and teacher_swap, the teacher's eval forward gives what the student's gave
+    right before the swap, bit for bit, and the other way round."""
+    (x1, x2), y = _data(6, 49, views=2)
+    _load(eng)
+    eng.teacher_snapshot()
+    lo = torch.zeros(1, device="cuda")
+    eng.step_stage1(x1.cuda(), x2.cuda(), y.cuda(), [0.0, 1.0, 0.0, 0.0, 0.0], 1, 8, lo)
+    x = x1.cuda()
+    before = {t: [v.cpu().numpy() for v in eng.forward_eval(x, teacher=t)] for t in (False, True)}
+    assert not np.array_equal(before[False][1], before[True][1])
+    eng.teacher_swap()
+    for t in (False, True):
+        for want, got in zip(before[not t], eng.forward_eval(x, teacher=t)):
+            np.testing.assert_array_equal(want, got.cpu().numpy())
+
+
 def test_relu_mask_from_conv_output_is_bit_identical(monkeypatch):
     """bn1's backward recomputes the ReLU mask from the conv output (y*scale + shift > 0, the forward's own fused
     multiply-add) instead of reading the stored activation: the same bits after three stage-1 steps as with
