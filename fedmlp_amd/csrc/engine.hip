@@ -3175,4 +3175,106 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
     return FM_OK;
 }
 
+int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)
+{
+    ARGCHK(e && p && d && sc, "null argument");
+    ARGCHK(e->model == 0 && !e->precision, "fm_debug_ew: a precision-0 ResNet-18 engine");
+    hipStream_t s = e->main.st;
+    auto F = [&](int i) { return static_cast<float*>(p[i]); };
+    auto U = [&](int i) { return static_cast<unsigned short*>(p[i]); };
+    auto B = [&](int i) { return static_cast<uint8_t*>(p[i]); };
+    auto need = [&](std::initializer_list<int> idx) { for (int i : idx) if (!p[i]) return false; return true; };
+    auto pos = [&](int n) { for (int i = 0; i < n; ++i) if (d[i] < 1) return false; return true; };
+    switch (op) {
+    case FM_EW_SPLIT_PLANES:
+    case FM_EW_PLANES_TO_F32:
+        ARGCHK(need({0, 1}) && pos(2) && d[1] % 32 == 0, "planes: C % 32");
+        if (op == FM_EW_SPLIT_PLANES) k_split_planes(F(0), U(1), d[0], d[1], s);
+        else k_planes_to_f32(U(0), F(1), d[0], d[1], s);
+        break;
+    case FM_EW_BN_FINALIZE:
+        ARGCHK(need({0, 1, 2, 5, 6, 7, 8}) && pos(4) && (!p[3] == !p[4]), "bn_finalize operands");
+        k_bn_finalize(F(0), d[0], d[1], d[2], d[3], F(1), F(2), F(3), F(4), F(5), F(6), F(7), F(8), sc[0], sc[1], s,
+                      static_cast<const int*>(p[9]));
+        break;
+    case FM_EW_BN_FINALIZE_FROZEN:
+        ARGCHK(need({0, 1, 2, 3, 4, 5, 6, 7}) && pos(2), "bn_finalize_frozen operands");
+        k_bn_finalize_frozen(d[0], d[1], F(0), F(1), F(2), F(3), F(4), F(5), F(6), F(7), sc[0], s, static_cast<const int*>(p[8]));
+        break;
+    case FM_EW_BN_EVAL_AFFINE:
+        ARGCHK(need({0, 1, 2, 3, 4, 5}) && pos(1), "bn_eval_affine operands");
+        k_bn_eval_affine(F(0), F(1), F(2), F(3), F(4), F(5), d[0], sc[0], s);
+        break;
+    case FM_EW_BN_APPLY:
+    case FM_EW_BN_APPLY_PLANES: {
+        const bool pl = op == FM_EW_BN_APPLY_PLANES;
+        ARGCHK(need({0, 1, 2}) && pos(3) && d[2] % 4 == 0, "bn_apply: C % 4");
+        ARGCHK(!p[4] || (p[5] && p[6]), "bn_apply: y2 needs scale2 / shift2");
+        if (pl) {
+            ARGCHK(d[2] % 32 == 0 && p[8] && !(p[3] && p[9]), "bn_apply_planes: C % 32, outp, one residual form");
+            k_bn_apply_planes(F(0), F(1), F(2), F(3), F(4), F(5), F(6), F(7), U(8), d[0], d[1], d[2], d[3], s, U(9));
+        } else {
+            ARGCHK(p[7], "bn_apply: out");
+            k_bn_apply(F(0), F(1), F(2), F(3), F(4), F(5), F(6), F(7), d[0], d[1], d[2], d[3], s);
+        }
+        break;
+    }
+    case FM_EW_STEM_POOL:
+    case FM_EW_STEM_POOL_PLANES: {
+        const bool pl = op == FM_EW_STEM_POOL_PLANES;
+        ARGCHK(p[0] && (!p[1] == !p[2]) && pos(5) && d[4] % 4 == 0 && d[2] % 2 == 0 && d[3] % 2 == 0, "stem_pool: C % 4, even H, W");
+        if (pl) {
+            ARGCHK(d[4] % 32 == 0 && p[5], "stem_pool_planes: C % 32, pooledp");
+            k_stem_pool_planes(F(0), F(1), F(2), F(3), B(4), U(5), d[0], d[1], d[2], d[3], d[4], s);
+        } else {
+            ARGCHK(p[3], "stem_pool: pooled");
+            k_stem_pool(F(0), F(1), F(2), F(3), B(4), d[0], d[1], d[2], d[3], d[4], s);
+        }
+        break;
+    }
+    case FM_EW_STEM_POOL_BWD:
+        ARGCHK(need({0, 1, 2, 3}) && pos(4) && d[3] % 4 == 0 && d[1] % 2 == 0 && d[2] % 2 == 0, "stem_pool_bwd: C % 4, even H, W");
+        k_stem_pool_bwd(F(0), F(1), B(2), F(3), d[0], d[1], d[2], d[3], s);
+        break;
+    case FM_EW_STEM_POOL_BN_REDUCE:
+        ARGCHK(need({0, 1, 2, 3, 4, 5, 6, 7, 8}) && pos(5) && d[4] % 4 == 0 && d[4] <= 1024 && 1024 % d[4] == 0 && d[2] % 2 == 0 &&
+                   d[3] % 2 == 0, "stem_pool_bn_reduce: C a power of two in 4 .. 1024, even H, W");
+        k_stem_pool_bn_reduce(F(0), F(1), B(2), F(3), F(4), F(5), F(6), d[0], d[1], d[2], d[3], d[4], s, F(7), F(8));
+        break;
+    case FM_EW_STEM_POOL_BN_APPLY:
+        ARGCHK(need({0, 1, 2, 3, 4, 5, 6, 7}) && pos(5) && d[4] % 4 == 0 && d[2] % 2 == 0 && d[3] % 2 == 0,
+               "stem_pool_bn_apply: C % 4, even H, W");
+        k_stem_pool_bn_apply(F(0), F(1), B(2), F(3), F(4), F(5), F(6), F(7), d[0], d[1], d[2], d[3], d[4], s);
+        break;
+    case FM_EW_BN_BWD_REDUCE:
+        ARGCHK(need({0, 2, 3, 4, 5}) && pos(3) && d[2] % 4 == 0 && d[2] <= 1024 && 1024 % d[2] == 0,
+               "bn_bwd_reduce: C a power of two in 4 .. 1024");
+        ARGCHK((!p[6] == !p[7]) && (!p[8] || d[2] % 32 == 0), "bn_bwd_reduce: mask_scale with mask_shift, zh needs C % 32");
+        k_bn_bwd_reduce(F(0), F(1), F(2), F(3), F(4), F(5), d[0], d[1], d[2], s, F(6), F(7), U(8));
+        break;
+    case FM_EW_BN_BWD_FINALIZE:
+        ARGCHK(need({0, 1, 2, 3, 4, 5, 6, 7, 8}) && pos(4), "bn_bwd_finalize operands");
+        k_bn_bwd_finalize(F(0), d[0], d[1], d[2], d[3], F(1), F(2), F(3), F(4), F(5), F(6), F(7), F(8), s, d[4] != 0);
+        break;
+    case FM_EW_BN_BWD_APPLY:
+    case FM_EW_BN_BWD_APPLY_PLANES: {
+        const bool pl = op == FM_EW_BN_BWD_APPLY_PLANES;
+        ARGCHK(need({0, 2, 3, 4, 5}) && pos(3) && d[2] % 4 == 0 && (!p[8] == !p[9]), "bn_bwd_apply: C % 4, mask_scale with mask_shift");
+        if (pl) {
+            ARGCHK(d[2] % 32 == 0 && p[10], "bn_bwd_apply_planes: C % 32, dyp");
+            k_bn_bwd_apply_planes(F(0), F(1), F(2), F(3), F(4), F(5), F(6), U(10), F(7), d[0], d[1], d[2], s, F(8), F(9), U(11));
+        } else {
+            ARGCHK(p[6], "bn_bwd_apply: dy");
+            k_bn_bwd_apply(F(0), F(1), F(2), F(3), F(4), F(5), F(6), F(7), d[0], d[1], d[2], s, F(8), F(9));
+        }
+        break;
+    }
+    default:
+        ARGCHK(false, "op");
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return FM_OK;
+}
+
 }  // extern "C"

@@ -541,6 +541,21 @@ class Engine:
         self._enqueue()
         _lib.check(self.lib.fm_debug_block_dgrad(self.h, block, _ptr(dy1), _ptr(dyd), _ptr(dx), imgs))
 
+    # op codes of fm_debug_ew (include/fedmlp_hip_debug.h), in the header's order
+    EW_OPS = ("split_planes", "planes_to_f32", "bn_finalize", "bn_finalize_frozen", "bn_eval_affine", "bn_apply",
+              "bn_apply_planes", "stem_pool", "stem_pool_planes", "stem_pool_bwd", "stem_pool_bn_reduce", "stem_pool_bn_apply",
+              "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply", "bn_bwd_apply_planes")
+
+    def debug_ew(self, op, ptrs, dims, scalars=()):
+        """one BatchNorm / stem-pool / plane-writer launcher on caller tensors (fm_debug_ew): op = a name of EW_OPS, ptrs =
+        contiguous device tensors of any dtype in the header's operand order (None = absent), dims / scalars as documented there"""
+        assert len(ptrs) <= 12 and len(dims) <= 5 and len(scalars) <= 2, (len(ptrs), len(dims), len(scalars))
+        for t in ptrs:
+            assert t is None or (t.is_cuda and t.is_contiguous()), op
+        p = (C.c_void_p * 12)(*[None if t is None else t.data_ptr() for t in ptrs])
+        d = (C.c_int32 * 5)(*[int(v) for v in dims])
+        _lib.check(self.lib.fm_debug_ew(self.h, self.EW_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (2 - len(scalars)))))
+
 
 class _CudaArrayView:
     """Minimal __cuda_array_interface__ carrier so torch can alias engine memory."""

@@ -2,8 +2,8 @@
  * fedmlp_hip_debug.h -- kernel-level test hooks of libfedmlp_hip.so (tests/ and tools/ only).
  *
  * NOT part of the drop-in surface of fedmlp_hip.h: nothing behind build_model() / LocalUpdate / FedAvg* calls these.
- * They expose single kernels (one convolution forward / data gradient / weight gradient on caller-supplied tensors),
- * the activations the last train-mode forward kept, and the gradients of the last step, so that the parity tests can
+ * They expose single kernels (one convolution forward / data gradient / weight gradient, one BatchNorm / stem-pool / plane-writer
+ * launcher on caller-supplied tensors), the activations the last train-mode forward kept, and the gradients of the last step, so that the parity tests can
  * compare each kernel with a CPU yardstick.
  */
 #ifndef FEDMLP_HIP_DEBUG_H
@@ -89,6 +89,52 @@ int fm_debug_lose_part(int32_t on);
 
 /* Gradients of the last step in state_dict order (running-stat slots are 0). */
 int fm_debug_get_grads(fm_engine* e, float* host_f32);
+
+/* One launcher of csrc/kernels.h -- the BatchNorm, stem max-pool and plane-writer kernels between ResNet-18's conv GEMMs
+ * (elementwise.hip, planes_ew.hip, the two plane converters of pconv.hip) -- on caller-supplied device tensors, on the handle's
+ * main stream, followed by a stream synchronisation.  A precision-0 ResNet-18 handle; no engine state is read or written:
+ * every operand and workspace is a caller buffer.  p[] = FM_EW_NPTR device pointers (NULL = the optional operand is absent,
+ * unused slots NULL), d[] = FM_EW_NDIM dimensions, sc[] = FM_EW_NSCAL scalars.  Arguments outside a kernel's contract (a missing
+ * required operand, a dimension < 1, C % 4 != 0, C % 32 != 0 for an op that reads or writes planes, odd H or W for the stem
+ * pool, C not a power of two for the two reduce passes) return FM_ERR_ARG before any launch.
+ *
+ * Activations are fp32 NHWC [groups * pix][C]; per-channel vectors are [groups][C] unless noted; `planes` are 16-bit words
+ * [C/32][3][P][32] over all P = groups * pix pixels (layout: the header comment of planes_ew.hip), 3 * P * C words.
+ * nblk(n) = max(1, min(1024, ceil(n / 64))) is the number of partial-sum blocks per group of a reduce pass over n pixels.
+ * A partials workspace of T tiles per group holds groups * T * 2 * C floats, and when T > 64 another groups * 32 * 2 * C floats
+ * right behind them (the fold area the finalize pass writes).
+ *
+ * FM_EW_SPLIT_PLANES        p = {x, planes};  d = {P, C}
+ * FM_EW_PLANES_TO_F32       p = {planes, x};  d = {P, C}
+ * FM_EW_BN_FINALIZE         p = {stats [groups][tiles][2][C] (+ fold area), gamma [C], beta [C], run_mean [C] | NULL, run_var [C] |
+ *                           NULL, mean, istd, scale, shift, skip (one int32) | NULL};  d = {groups, tiles, C, count};
+ *                           sc = {eps, momentum}
+ * FM_EW_BN_FINALIZE_FROZEN  p = {gamma, beta, run_mean, run_var, mean, istd, scale, shift, skip | NULL};  d = {groups, C};  sc = {eps}
+ * FM_EW_BN_EVAL_AFFINE      p = {gamma, beta, run_mean, run_var, scale, shift} all [n];  d = {n};  sc = {eps}
+ * FM_EW_BN_APPLY            p = {y, scale, shift, res | NULL, y2 | NULL, scale2 | NULL, shift2 | NULL, out};  d = {groups, pix, C, relu}
+ * FM_EW_BN_APPLY_PLANES     the same with out | NULL, and p[8] = out planes, p[9] = res planes | NULL (then res is NULL)
+ * FM_EW_STEM_POOL           p = {y [groups * ipg][H][W][C], scale | NULL, shift | NULL, pooled [..][H/2][W/2][C], idx uint8 (pooled's
+ *                           shape) | NULL};  d = {groups, ipg, H, W, C}
+ * FM_EW_STEM_POOL_PLANES    the same with pooled | NULL, and p[5] = pooled planes
+ * FM_EW_STEM_POOL_BWD       p = {dpooled, pooled, idx, dy [imgs][H][W][C]};  d = {imgs, H, W, C}
+ * FM_EW_STEM_POOL_BN_REDUCE p = {dpooled, pooled, idx, y, mean, istd, part [groups][nblk(ipg H/2 W/2)][2][C], gamma [C], beta [C]};
+ *                           d = {groups, ipg, H, W, C}
+ * FM_EW_STEM_POOL_BN_APPLY  p = {dpooled, pooled, idx, y, ca, cb, cc, dy};  d = {groups, ipg, H, W, C}
+ * FM_EW_BN_BWD_REDUCE       p = {dz, z | NULL, y, mean, istd, part [groups][nblk(pix)][2][C], mask_scale | NULL, mask_shift | NULL,
+ *                           z planes | NULL};  d = {groups, pix, C}
+ * FM_EW_BN_BWD_FINALIZE     p = {part (+ fold area), gamma [C], mean, istd, ca, cb, cc, dgamma [C], dbeta [C]};
+ *                           d = {groups, nblk, C, count, frozen}
+ * FM_EW_BN_BWD_APPLY        p = {dz, z | NULL, y, ca, cb, cc, dy, dyh_out | NULL, mask_scale | NULL, mask_shift | NULL};  d = {groups, pix, C}
+ * FM_EW_BN_BWD_APPLY_PLANES the same with dy | NULL, and p[10] = dy planes, p[11] = z planes | NULL */
+enum {
+    FM_EW_SPLIT_PLANES = 0, FM_EW_PLANES_TO_F32, FM_EW_BN_FINALIZE, FM_EW_BN_FINALIZE_FROZEN, FM_EW_BN_EVAL_AFFINE, FM_EW_BN_APPLY,
+    FM_EW_BN_APPLY_PLANES, FM_EW_STEM_POOL, FM_EW_STEM_POOL_PLANES, FM_EW_STEM_POOL_BWD, FM_EW_STEM_POOL_BN_REDUCE,
+    FM_EW_STEM_POOL_BN_APPLY, FM_EW_BN_BWD_REDUCE, FM_EW_BN_BWD_FINALIZE, FM_EW_BN_BWD_APPLY, FM_EW_BN_BWD_APPLY_PLANES
+};
+#define FM_EW_NPTR 12
+#define FM_EW_NDIM 5
+#define FM_EW_NSCAL 2
+int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc);
 
 #ifdef __cplusplus
 }
