@@ -1895,7 +1895,7 @@ void k_se_bwd_bn1(const void* dout, const void* y, int dt, const float* scale, c
     // fewer, longer pixel chunks than the forward pooling: the five-way fold at the end of a block is amortised over
     // >= 512 pixels, and imgs x nch blocks still fill the chip
     // nch_ready > 0: pool_ws already holds that many records per image (pw_proj_bwd_kernel phase 0 took the sums)
-    const int nch = nch_ready > 0 ? nch_ready : std::max(1, std::min(chan_pool_chunks(HW), std::max(HW / 512, imgs >= 512 ? 1 : 2)));
+    const int nch = nch_ready > 0 ? nch_ready : se_bwd_bn1_chunks(HW, imgs);
     const dim3 grid(nch, imgs), blk(QT * P);
     if (nch_ready > 0) {}
     else if (dt == DT_F32)
@@ -2021,3 +2021,35 @@ void k_add_inplace(void* y, const void* a, int dt, int64_t n, hipStream_t s)
     if (dt == DT_F32) hipLaunchKernelGGL((add_inplace_kernel<float>), grid, dim3(256), 0, s, mp<float>(y), cp<float>(a), n / 4);
     else hipLaunchKernelGGL((add_inplace_kernel<bf16>), grid, dim3(256), 0, s, mp<bf16>(y), cp<bf16>(a), n / 4);
 }
+
+// ------------------------------------------------------------ workspace arithmetic (fm_debug_eff_ws) ---
+// The floats each launcher above touches in its workspaces, from the host functions that size its grid.
+// Record workspace of a statistics (pool = false) or pooling request of k_dw_fwd (dgrad = false) / k_dw_dgrad; 0 = the launch
+// declines the request (generic kernels, steps that do not split into the groups, dw_stats_rowgroups() == 0) and touches nothing.
+int64_t dw_rec_floats(bool dgrad, bool pool, int imgs, int Hi, int Wi, int Ho, int Wo, int C, int K, int stride, int pad_t, int pad_l,
+                      int groups)
+{
+    if (!dw_blk_ok(K, stride, Hi, Wi, pad_t, pad_l) || (stride == 2 && !(Wi == 2 * Wo && Hi == 2 * Ho))) return 0;
+    // wave steps per image and the row the lanes cover: dw_rowu_launch / dw_rowu_s2_launch / dw_rowu_dgrad_s2_launch
+    const int spi = stride == 1 ? (Hi + 1) / 2 : (dgrad ? Hi : Ho), W = stride == 1 || dgrad ? Wi : Wo;
+    const int nchunk = (((W + 3) / 4) * (C / 4) + 63) / 64, steps = imgs * spi;
+    if (pool) return dgrad ? 0 : (int64_t)nchunk * (spi / dw_pool_rpb(spi)) * imgs * 64 * 4;
+    if (steps % groups) return 0;
+    return (int64_t)nchunk * dw_stats_rowgroups(steps / groups, nchunk, groups) * groups * 2 * 64 * 4;
+}
+// `part` of k_dw_wgrad: block records of the row-uniform kernel, or dw_wgrad_blocks() slabs of [K*K][C]
+int64_t dw_wgrad_part_floats(int dt, int imgs, int Hi, int Wi, int Ho, int Wo, int C, int K, int stride, int pad_t, int pad_l)
+{
+    if ((dt == DT_BF16 || K == 5) && dw_blk_ok(K, stride, Hi, Wi, pad_t, pad_l) && Wi == stride * Wo && Hi == stride * Ho) {
+        const int RB = stride == 1 ? 2 : 1;           // dw_rowu_wgrad_launch
+        const int nchunk = (((Wo + 3) / 4) * (C / 4) + 63) / 64, nsteps = imgs * ((Ho + RB - 1) / RB);
+        int spb = std::max(8, (int)(((int64_t)nsteps * nchunk + 2048 - 1) / 2048));
+        spb = (spb + 3) / 4 * 4;
+        return (int64_t)nchunk * ((nsteps + spb - 1) / spb) * K * K * 64 * 4;
+    }
+    return (int64_t)dw_wgrad_blocks(imgs * Ho * Wo) * K * K * C;
+}
+int se_bwd_bn1_chunks(int HW, int imgs) { return std::max(1, std::min(chan_pool_chunks(HW), std::max(HW / 512, imgs >= 512 ? 1 : 2))); }
+int64_t se_wgrad_range_floats(int C, int Cs) { return (int64_t)Cs * C + (Cs + 3) / 4 * 4 + (int64_t)C * Cs + C; }
+int se_wgrad_splits() { return SE_SPLITS; }
+int se_wgrad_max_cs() { return 4 * SE_NJ; }

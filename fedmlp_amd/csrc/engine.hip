@@ -3277,4 +3277,139 @@ int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, cons
     return FM_OK;
 }
 
+// ---- fm_debug_eff: the depthwise / squeeze-excite launchers of effnet.hip on caller tensors ---------------------------------------
+// shared argument contract of fm_debug_eff and fm_debug_eff_ws (nullptr = fine, else the complaint)
+static const char* eff_dims_bad(int32_t op, const int32_t* d)
+{
+    auto pos = [&](int a, int b) { for (int i = a; i < b; ++i) if (d[i] < 1) return false; return true; };
+    if (op == FM_EFF_DW_FWD || op == FM_EFF_DW_DGRAD || op == FM_EFF_DW_WGRAD) {
+        if (d[0] != DT_F32 && d[0] != DT_BF16) return "dt";
+        if (!pos(1, 7) || d[12] < 1) return "a dimension < 1";
+        if (d[6] % 4) return "C % 4";
+        if (d[7] != 3 && d[7] != 5) return "K is 3 or 5";
+        if (d[8] != 1 && d[8] != 2) return "stride is 1 or 2";
+        if (d[4] != (d[2] + d[8] - 1) / d[8] || d[5] != (d[3] + d[8] - 1) / d[8]) return "Ho, Wo = ceil(Hi, Wi / stride)";
+        if (d[9] < 0 || d[9] >= d[7] || d[10] < 0 || d[10] >= d[7]) return "pad_t, pad_l in 0 .. K-1";
+        if (d[11] < 0 || d[11] > 2) return "act";
+        if ((int64_t)d[1] * d[2] * d[3] * d[6] >= ((int64_t)1 << 30)) return "tensor too large";
+        return nullptr;
+    }
+    if (op == FM_EFF_SE_WGRAD) {
+        if (!pos(0, 3)) return "a dimension < 1";
+        if (d[1] % 4) return "C % 4";
+        if (d[2] > se_wgrad_max_cs()) return "Cs beyond the weight-gradient kernel's accumulators";
+        return nullptr;
+    }
+    if (op == FM_EFF_SE_FWD || op == FM_EFF_SE_SCALE || op == FM_EFF_SE_BWD_BN1) {
+        if (d[0] != DT_F32 && d[0] != DT_BF16) return "dt";
+        if (!pos(1, 6) || d[6] < 0) return "a dimension < 1";
+        if (d[3] % (d[0] == DT_BF16 ? 8 : 4)) return "C % 4 (C % 8 in bf16 storage)";
+        if (d[1] % d[5]) return "imgs % ipg";
+        if (d[3] + d[4] > 12288) return "C + Cs beyond the block's LDS";
+        if ((int64_t)d[1] * d[2] * d[3] >= ((int64_t)1 << 30)) return "tensor too large";
+        return nullptr;
+    }
+    return "op";
+}
+
+int fm_debug_eff_ws(int32_t op, const int32_t* d, int64_t* floats)
+{
+    ARGCHK(d && floats, "null argument");
+    const char* bad = eff_dims_bad(op, d);
+    ARGCHK(!bad, (bad ? bad : ""));
+    for (int i = 0; i < FM_EFF_NWS; ++i) floats[i] = 0;
+    switch (op) {
+    case FM_EFF_DW_FWD:
+    case FM_EFF_DW_DGRAD: {
+        const bool dg = op == FM_EFF_DW_DGRAD;
+        floats[0] = dw_rec_floats(dg, false, d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[12]);
+        floats[1] = (int64_t)d[12] * dw_stats_tiles() * 2 * d[6];
+        floats[2] = dw_rec_floats(dg, true, d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], 1);
+        floats[3] = dg ? 0 : (int64_t)d[1] * d[6];
+        break;
+    }
+    case FM_EFF_DW_WGRAD:
+        floats[0] = dw_wgrad_part_floats(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10]);
+        floats[1] = (int64_t)d[7] * d[7] * d[6];
+        break;
+    case FM_EFF_SE_FWD:
+        floats[0] = (int64_t)d[1] * (d[6] ? 1 : chan_pool_chunks(d[2])) * d[3];
+        break;
+    case FM_EFF_SE_SCALE:
+        break;
+    case FM_EFF_SE_BWD_BN1:
+        floats[0] = (int64_t)d[1] * (d[6] > 0 ? d[6] : se_bwd_bn1_chunks(d[2], d[1])) * 5 * d[3];
+        floats[1] = (int64_t)(d[1] / d[5]) * se_bwd_bn1_splits(d[5]) * 2 * d[3];
+        floats[2] = se_bwd_bn1_splits(d[5]);
+        break;
+    case FM_EFF_SE_WGRAD:
+        floats[1] = se_wgrad_range_floats(d[1], d[2]);
+        floats[0] = floats[1] * se_wgrad_splits();
+        break;
+    }
+    return FM_OK;
+}
+
+int fm_debug_eff(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)
+{
+    (void)sc;                           // reserved: no launcher of this family takes a scalar
+    ARGCHK(e && p && d, "null argument");
+    ARGCHK(e->model == 1, "fm_debug_eff: an EfficientNet-B0 engine");
+    const char* bad = eff_dims_bad(op, d);
+    ARGCHK(!bad, (bad ? bad : ""));
+    hipStream_t s = e->main.st;
+    auto F = [&](int i) { return static_cast<float*>(p[i]); };
+    auto need = [&](std::initializer_list<int> idx) { for (int i : idx) if (!p[i]) return false; return true; };
+    int32_t* served = static_cast<int32_t*>(p[FM_EFF_NPTR - 1]);          // HOST slot
+    bool flag = false;
+    switch (op) {
+    case FM_EFF_DW_FWD: {
+        ARGCHK(need({0, 1, 2}) && (!p[3] == !p[4]), "dw_fwd: x, w, y; scale with shift");
+        ARGCHK(p[3] || !d[11], "dw_fwd: act needs scale / shift");
+        ARGCHK(!(p[6] && p[7]) && (!p[5] == !(p[6] || p[7])), "dw_fwd: rec with exactly one of stats_out / pool_out");
+        ARGCHK(!p[5] || served, "dw_fwd: a request needs the served slot");
+        flag = k_dw_fwd(p[0], F(1), p[2], d[0], F(3), F(4), d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], s, F(5),
+                        F(6), d[12], F(7));
+        break;
+    }
+    case FM_EFF_DW_DGRAD: {
+        ARGCHK(need({0, 1, 2}), "dw_dgrad: dy, w, dx");
+        const bool any = p[3] || p[4] || p[5] || p[6] || p[7] || p[8] || p[9];
+        ARGCHK(!any || (need({3, 4, 5, 6, 7, 8, 9}) && served), "dw_dgrad: ye comes with mean, istd, scale, shift, rec, stats_out, served");
+        flag = k_dw_dgrad(p[0], F(1), p[2], d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], s, p[3], F(4), F(5), F(6),
+                          F(7), F(8), F(9), d[12]);
+        break;
+    }
+    case FM_EFF_DW_WGRAD:
+        ARGCHK(need({0, 1, 2, 3}), "dw_wgrad: dy, x, part, out");
+        k_dw_wgrad(p[0], p[1], d[0], F(2), F(3), d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], s);
+        break;
+    case FM_EFF_SE_FWD:
+        ARGCHK(need({3, 4, 5, 6, 7, 8, 9, 10}) && (!p[1] == !p[2]), "se_fwd: operands; scale with shift");
+        ARGCHK(d[6] ? !p[1] : p[0] != nullptr, "se_fwd: a unless pooled; pooled sums are of the activation (no scale / shift)");
+        k_se_fwd(p[0], d[0], F(1), F(2), d[5], F(3), F(4), F(5), F(6), F(7), F(8), F(9), F(10), d[1], d[2], d[3], d[4], s, d[6] != 0);
+        break;
+    case FM_EFF_SE_SCALE:
+        ARGCHK(need({0, 3, 4}) && (!p[1] == !p[2]), "se_scale: a, gate, out; scale with shift");
+        k_se_scale(p[0], d[0], F(1), F(2), d[5], F(3), p[4], d[1], d[2], d[3], s);
+        break;
+    case FM_EFF_SE_BWD_BN1:
+        ARGCHK(need({1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14}), "se_bwd_bn1 operands");
+        ARGCHK(p[0] || d[6] > 0, "se_bwd_bn1: dout may be absent only when pool_ws already holds nch_ready records per image");
+        k_se_bwd_bn1(p[0], p[1], d[0], F(2), F(3), F(4), F(5), d[5], F(6), F(7), F(8), F(9), F(10), F(11), F(12), F(13), F(14), d[1],
+                     d[2], d[3], d[4], s, d[6]);
+        break;
+    case FM_EFF_SE_WGRAD:
+        ARGCHK(need({0, 1, 2, 3, 4, 5}), "se_wgrad operands");
+        k_se_wgrad(F(0), F(1), F(2), F(3), F(4), F(5), d[0], d[1], d[2], s);
+        break;
+    default:
+        ARGCHK(false, "op");
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (served) *served = flag ? 1 : 0;
+    return FM_OK;
+}
+
 }  // extern "C"

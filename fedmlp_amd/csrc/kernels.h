@@ -191,6 +191,17 @@ void k_se_bwd_bn1(const void* dout, const void* y, int dt, const float* scale, c
 // dW1 = start of the contiguous [dW1 | db1 (padded to 4) | dW2 | db2] gradient range; part = workspace (16 slabs of it)
 void k_se_wgrad(const float* dgp, const float* drp, const float* rpre, const float* sq, float* part, float* dW1, int imgs, int C,
                 int Cs, hipStream_t s);
+// workspace arithmetic of the launchers above (fm_debug_eff_ws): floats of the record workspace a statistics / pooling request of
+// k_dw_fwd / k_dw_dgrad fills (0 = the launch declines the request), of k_dw_wgrad's `part`, the pixel chunks of the pooling
+// passes (k_se_fwd: chan_pool_chunks, k_se_bwd_bn1: se_bwd_bn1_chunks), and k_se_wgrad's gradient range / slab count / largest Cs
+int64_t dw_rec_floats(bool dgrad, bool pool, int imgs, int Hi, int Wi, int Ho, int Wo, int C, int K, int stride, int pad_t, int pad_l,
+                      int groups);
+int64_t dw_wgrad_part_floats(int dt, int imgs, int Hi, int Wi, int Ho, int Wo, int C, int K, int stride, int pad_t, int pad_l);
+int chan_pool_chunks(int HW);
+int se_bwd_bn1_chunks(int HW, int imgs);
+int64_t se_wgrad_range_floats(int C, int Cs);
+int se_wgrad_splits();
+int se_wgrad_max_cs();
 void k_mul(const float* a, const float* b, float* y, int64_t n, hipStream_t s);
 void k_add_inplace(void* y, const void* a, int dt, int64_t n, hipStream_t s);
 

@@ -556,6 +556,31 @@ class Engine:
         d = (C.c_int32 * 5)(*[int(v) for v in dims])
         _lib.check(self.lib.fm_debug_ew(self.h, self.EW_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (2 - len(scalars)))))
 
+    # op codes of fm_debug_eff (include/fedmlp_hip_debug.h), in the header's order
+    EFF_OPS = ("dw_fwd", "dw_dgrad", "dw_wgrad", "se_fwd", "se_scale", "se_bwd_bn1", "se_wgrad")
+
+    def debug_eff_ws(self, op, dims):
+        """floats of each workspace / result of one fm_debug_eff op at these dimensions (fm_debug_eff_ws), in the header's order"""
+        assert len(dims) <= 13, len(dims)
+        d = (C.c_int32 * 13)(*[int(v) for v in dims])
+        n = (C.c_int64 * 4)()
+        _lib.check(self.lib.fm_debug_eff_ws(self.EFF_OPS.index(op), d, n))
+        return list(n)
+
+    def debug_eff(self, op, ptrs, dims, scalars=()):
+        """one depthwise / squeeze-excite launcher of the EfficientNet-B0 path on caller tensors (fm_debug_eff): op = a name of
+        EFF_OPS, ptrs = contiguous device tensors of any dtype in the header's operand order (None = absent), dims as documented
+        there.  Returns the launcher's "request served" flag (False for the launchers that return nothing)."""
+        assert len(ptrs) <= 15 and len(dims) <= 13 and len(scalars) <= 1, (len(ptrs), len(dims), len(scalars))
+        for t in ptrs:
+            assert t is None or (t.is_cuda and t.is_contiguous()), op
+        served = C.c_int32(-1)
+        p = (C.c_void_p * 16)(*([None if t is None else t.data_ptr() for t in ptrs] + [None] * (15 - len(ptrs))
+                                + [C.addressof(served)]))
+        d = (C.c_int32 * 13)(*[int(v) for v in dims])
+        _lib.check(self.lib.fm_debug_eff(self.h, self.EFF_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (1 - len(scalars)))))
+        return served.value == 1
+
 
 class _CudaArrayView:
     """Minimal __cuda_array_interface__ carrier so torch can alias engine memory."""

@@ -3,7 +3,7 @@
  *
  * NOT part of the drop-in surface of fedmlp_hip.h: nothing behind build_model() / LocalUpdate / FedAvg* calls these.
  * They expose single kernels (one convolution forward / data gradient / weight gradient, one BatchNorm / stem-pool / plane-writer
- * launcher on caller-supplied tensors), the activations the last train-mode forward kept, and the gradients of the last step, so that the parity tests can
+ * launcher, one depthwise / squeeze-excite launcher of the EfficientNet-B0 path on caller-supplied tensors), the activations the last train-mode forward kept, and the gradients of the last step, so that the parity tests can
  * compare each kernel with a CPU yardstick.
  */
 #ifndef FEDMLP_HIP_DEBUG_H
@@ -135,6 +135,64 @@ enum {
 #define FM_EW_NDIM 5
 #define FM_EW_NSCAL 2
 int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc);
+
+/* One launcher of csrc/kernels.h -- the depthwise-convolution and squeeze-excite kernels of the EfficientNet-B0 path (effnet.hip)
+ * -- on caller-supplied device tensors, on the handle's main stream, followed by a stream synchronisation.  Any EfficientNet-B0
+ * handle, of either precision: the storage type is a dimension (dt: 0 = fp32, 1 = bf16 words), no engine state is read or
+ * written.  p[] = FM_EFF_NPTR pointers (NULL = the optional operand is absent, unused slots NULL), d[] = FM_EFF_NDIM dimensions
+ * (unused ones 0), sc = reserved (no launcher here takes a scalar; may be NULL).  Arguments outside a kernel's contract return
+ * FM_ERR_ARG before any launch: a missing required operand, a dimension < 1, C % 4 != 0 (C % 8 != 0 for the squeeze-excite
+ * ops in bf16 storage: 16-byte pieces), K outside {3, 5}, stride outside {1, 2}, Ho / Wo != ceil(Hi / stride) / ceil(Wi / stride),
+ * a padding outside 0 .. K-1, act outside 0 .. 2, imgs % ipg != 0, Cs > 48 for SE_WGRAD, a half-given optional group.
+ *
+ * p[FM_EFF_NPTR - 1] = `served`, ONE int32 in HOST memory (optional unless a request is made): for the launchers that return bool
+ * it receives 1 when the kernel served the statistics / pooling request and 0 when it declined (the caller then reduces by
+ * itself; a declined request leaves rec and stats_out / pool_out untouched).  The return value stays an error code.
+ *
+ * Tensors marked T are dt-typed (fp32, or bf16 words), everything else is fp32.  Activations are NHWC; depthwise weights
+ * w [K*K][C] (tap kh * K + kw); TF-"same" padding is (pad_t, pad_l) at the top / left, whatever remains at the bottom / right.
+ *
+ * depthwise ops: d = {dt, imgs, Hi, Wi, Ho, Wo, C, K, stride, pad_t, pad_l, act, groups}   (groups >= 1 always)
+ * FM_EFF_DW_FWD    p = {x T [imgs][Hi][Wi][C], w, y T [imgs][Ho][Wo][C], scale [C] | NULL, shift [C] | NULL, rec | NULL,
+ *                  stats_out | NULL, pool_out | NULL};  y = conv(x, w), with scale / shift: y = act(conv * scale + shift), act 0 none /
+ *                  1 relu / 2 swish.  rec + stats_out = the statistics request: when served, stats_out [groups][T][2][C], T =
+ *                  dw_stats_tiles() = 8, holds partial (sum, sum of squares) of the STORED y (bf16: of the rounded values) per group;
+ *                  their sum over T is the statistic.  A group is an equal run of the kernel's row steps: whole images whenever
+ *                  groups divides imgs.  rec + pool_out = the pooling request: pool_out [imgs][C] = per-image channel sums of the
+ *                  stored y.  Workspaces (fm_debug_eff_ws): floats[0] = rec of a statistics request, [1] = stats_out, [2] = rec of a
+ *                  pooling request, [3] = pool_out; a rec size of 0 says that the launch will decline that request.
+ * FM_EFF_DW_DGRAD  p = {dy T [imgs][Ho][Wo][C], w, dx T [imgs][Hi][Wi][C], ye T (dx's shape) | NULL, mean, istd, scale, shift (each
+ *                  [groups][C]), rec, stats_out};  dx = the data gradient.  ye (with the seven operands after it) requests the
+ *                  BN0-backward sums: stats_out [groups][8][2][C] partials of S1 = sum dx' swish'(v), S2 = sum dx' swish'(v) xhat,
+ *                  dx' = the stored dx, v = ye scale + shift, xhat = (ye - mean) istd.  Workspaces: [0] = rec, [1] = stats_out.
+ * FM_EFF_DW_WGRAD  p = {dy T, x T, part, out [K*K][C]};  out = the weight gradient.  Workspaces: [0] = part, [1] = out.
+ *
+ * squeeze-excite ops: d = {dt, imgs, HW, C, Cs, ipg, flag};  W1 [Cs][C], b1 [Cs], W2 stored transposed [Cs][C], b2 [C];  scale / shift /
+ * mean / istd [imgs / ipg][C], image i in group i / ipg (ipg = 1 and d[4] = 1 where unused)
+ * FM_EFF_SE_FWD    p = {a T [imgs][HW][C] | NULL, scale | NULL, shift | NULL, pool_ws, W1, b1, W2, b2, sq [imgs][C], rpre [imgs][Cs],
+ *                  gate [imgs][C]};  A = a, or swish(a scale + shift) with scale / shift;  sq = mean_HW A, rpre = W1 sq + b1,
+ *                  gate = sigmoid(W2^T swish(rpre) + b2).  flag = pooled: `a` is not read and pool_ws [imgs][C] holds the
+ *                  per-image channel SUMS on entry (no scale / shift then).  Workspaces: [0] = pool_ws.
+ * FM_EFF_SE_SCALE  p = {a T, scale | NULL, shift | NULL, gate [imgs][C], out T};  out = A * gate
+ * FM_EFF_SE_BWD_BN1 p = {dout T | NULL, y T, scale, shift, mean, istd, pool_ws, gate, rpre, W1, W2, dgp [imgs][C], drp [imgs][Cs],
+ *                  ds [imgs][C], bn_part};  with v = y scale + shift, A = swish(v), sg = swish'(v), xh = (y - mean) istd the pass
+ *                  leaves pool_ws [imgs][nch][5][C] = partial per-image sums of (dout A, dout sg, dout sg xh, sg, sg xh); with R, P1,
+ *                  P2, Q1, Q2 their sums over nch:  dgp = R gate (1 - gate), drp = (W2 dgp) swish'(rpre), ds = W1^T drp, and
+ *                  bn_part [imgs / ipg][splits][2][C] = partials of S1 = sum_img gate P1 + ds / HW Q1, S2 = sum_img gate P2 + ds / HW Q2.
+ *                  flag = nch_ready: > 0 says that pool_ws already holds that many records per image (the fused project-conv
+ *                  backward left them); the pooling pass is skipped and dout may be NULL.  Workspaces: [0] = pool_ws, [1] =
+ *                  bn_part, [2] = splits (a count, not a size).
+ * FM_EFF_SE_WGRAD  d = {imgs, C, Cs};  p = {dgp, drp, rpre, sq, part, dW1};  dW1 = start of the contiguous gradient range
+ *                  [dW1 [Cs][C] | db1 [Cs], padded with zeros to a multiple of 4 | dW2 (transposed) [Cs][C] | db2 [C]].
+ *                  Workspaces: [0] = part, [1] = the range. */
+enum { FM_EFF_DW_FWD = 0, FM_EFF_DW_DGRAD, FM_EFF_DW_WGRAD, FM_EFF_SE_FWD, FM_EFF_SE_SCALE, FM_EFF_SE_BWD_BN1, FM_EFF_SE_WGRAD };
+#define FM_EFF_NPTR 16
+#define FM_EFF_NDIM 13
+#define FM_EFF_NWS 4
+int fm_debug_eff(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc);
+/* floats[FM_EFF_NWS] = the number of floats each workspace / result of `op` needs for the dimensions d (listed per op above),
+ * from the host functions that size the kernels' grids.  The same FM_ERR_ARG contract on d. */
+int fm_debug_eff_ws(int32_t op, const int32_t* d, int64_t* floats);
 
 #ifdef __cplusplus
 }
