@@ -25,6 +25,11 @@ class FmAdam(C.Structure):
                 ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
+class FmSgd(C.Structure):
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float),
+                ("weight_decay", C.c_float), ("nesterov", C.c_int32)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _I32 = C.c_int32
@@ -73,6 +78,14 @@ SYMBOLS = {
     "fm_zero_grad": (C.c_int, [_P]),
     "fm_adam_step": (C.c_int, [_P, C.POINTER(FmAdam)]),
     "fm_get_grads": (C.c_int, [_P, _P]),
+    "fm_sgd_reset": (C.c_int, [_P, C.POINTER(FmSgd)]),
+    "fm_sgd_step": (C.c_int, [_P, C.POINTER(FmSgd)]),
+    "fm_adamw_step": (C.c_int, [_P, C.POINTER(FmAdam)]),
+    "fm_grad_norm": (C.c_int, [_P, _P]),
+    "fm_clip_grad_norm": (C.c_int, [_P, C.c_float, _P]),
+    "fm_clip_grad_value": (C.c_int, [_P, C.c_float]),
+    "fm_optim_get_state": (C.c_int, [_P, _P, _P, C.POINTER(_I64)]),
+    "fm_optim_set_state": (C.c_int, [_P, _P, _P, _I64]),
     "fm_bn_freeze": (C.c_int, [_P, _I32]),
     "fm_bn_frozen": (C.c_int, [_P]),
     "fm_teacher_axpby": (C.c_int, [_P, C.c_float, C.c_float]),

@@ -12,6 +12,9 @@
 //   EfficientNet-B0 (model 1): channel counts are padded to multiples of 16 inside the engine
 //   (24->32, 40->48; padded weights/gamma/beta are 0 and stay 0 under Adam, so padded channels
 //   carry exact zeros); depthwise weights are [k*k][C]; squeeze-excite W1 [Cs][C], W2 kept transposed [Cs][C].
+//   Padded slots of the gradient arenas hold exact zeros too (the stem's zero taps are masked, a padded channel's activation
+//   and gamma are 0, alignment gaps are never written), so SGD / AdamW keep the padding at 0 and the gradient norm may run over
+//   the whole arena.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -191,6 +194,10 @@ struct fm_engine {
     bool stem_dpack_stale = true;
     float* gacc = nullptr;
     bool gacc_full = false;
+    // fm_grad_norm / fm_clip_grad_norm: the per-block partial sums of squares and the norm word of a call that gives no pointer
+    // (allocated on first use)
+    double* norm_part = nullptr;
+    float* norm_word = nullptr;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
     // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read,
     // `pending_fixed` the mode of the pending forward (its backward takes the same)
@@ -1630,6 +1637,13 @@ void stem_dgrad_views(fm_engine* e, Lane& L, const void* dy, int groups, int B, 
 
 // optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2); g = e->grad (fused steps)
 // or the autograd path's accumulator (fm_adam_step)
+// what every optimizer step ends with: the student's weights moved on the main lane
+void weights_stepped(fm_engine* e)
+{
+    e->student.ev_dirty = true;
+    e->wpack_dirty = true;
+    ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
+}
 void adam_step(fm_engine* e, const float* g)
 {
     e->adam_t += 1;
@@ -1637,9 +1651,52 @@ void adam_step(fm_engine* e, const float* g)
     const double bc2 = 1.0 - pow((double)e->hp.beta2, (double)e->adam_t);
     k_adam(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
            e->hp.weight_decay, (float)bc1, (float)sqrt(bc2), e->main.st, e->dev_err);
-    e->student.ev_dirty = true;
-    e->wpack_dirty = true;
-    ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
+    weights_stepped(e);
+}
+// torch.optim.AdamW / torch.optim.SGD over the autograd path's accumulator, with the handle's moment arenas and step count
+// (optim.hip); the scalars that torch forms in double are formed in double here
+void adamw_step(fm_engine* e, const fm_adam& hp)
+{
+    e->adam_t += 1;
+    const double bc1 = 1.0 - pow((double)hp.beta1, (double)e->adam_t);
+    const double bc2 = 1.0 - pow((double)hp.beta2, (double)e->adam_t);
+    k_adamw(e->student.state, e->gacc, e->adam_m, e->adam_v, (int64_t)e->NP, (float)(1.0 - (double)hp.lr * (double)hp.weight_decay),
+            (float)((double)hp.lr / bc1), hp.beta1, hp.beta2, hp.eps, (float)sqrt(bc2), e->main.st, e->dev_err);
+    weights_stepped(e);
+}
+void sgd_step(fm_engine* e, const fm_sgd& hp)
+{
+    const bool first = e->adam_t == 0;        // torch: the momentum buffer does not exist yet
+    e->adam_t += 1;
+    k_sgd(e->student.state, e->gacc, e->adam_m, (int64_t)e->NP, hp.lr, hp.momentum, 1.0 - (double)hp.dampening,
+          hp.weight_decay, hp.nesterov != 0, first, e->main.st, e->dev_err);
+    weights_stepped(e);
+}
+// both moment arenas and the step count: a fresh optimizer of any kind
+int optim_reset(fm_engine* e)
+{
+    e->adam_t = 0;
+    HIPCHK(hipMemsetAsync(e->adam_m, 0, e->NP * 4, e->main.st));
+    HIPCHK(hipMemsetAsync(e->adam_v, 0, e->NP * 4, e->main.st));
+    return FM_OK;
+}
+const char* sgd_bad(const fm_sgd* hp)
+{
+    if (!(hp->lr >= 0.f && hp->momentum >= 0.f && hp->weight_decay >= 0.f)) return "fm_sgd: lr, momentum and weight_decay must be >= 0";
+    if (!(hp->dampening == hp->dampening)) return "fm_sgd: dampening is NaN";
+    if (hp->nesterov && !(hp->momentum > 0.f && hp->dampening == 0.f)) return "fm_sgd: nesterov needs momentum > 0 and dampening = 0";
+    return nullptr;
+}
+// the L2 norm of the accumulator into *norm (device), deterministic two-stage sum (optim.hip)
+int grad_norm(fm_engine* e, float* norm)
+{
+    if (!e->norm_part) {
+        DALLOC(e->norm_part, (size_t)grad_norm_parts((int64_t)e->NP));
+        DALLOC(e->norm_word, 4);
+        HIPCHK(hipMemsetAsync(e->norm_word, 0, 16, e->main.st));
+    }
+    k_grad_norm(e->gacc, (int64_t)e->NP, e->norm_part, norm, e->main.st, e->dev_err);
+    return FM_OK;
 }
 
 // Weight gradients on the side lane (side_w; otherwise everything below is a no-op that hands back the main lane).  A weight
@@ -2160,6 +2217,26 @@ int grads_to_state_dict(fm_engine* e, const float* src, float* dst)
     return FM_OK;
 }
 
+// the inverse: src in state_dict order (device, e->nf_sd floats) -> an engine-layout arena, enqueued on the main lane.  The
+// padding inside a conv's matrix is written as zeros; rows, tails and gaps outside it are not touched.  np_only: an arena of
+// NP floats (the moments): the BN running statistics are passed over
+int state_dict_to_arena(fm_engine* e, const float* src, float* arena, bool np_only)
+{
+    Lane& L = e->main;
+    size_t off = 0;
+    for (auto& en : e->entries) {
+        if (en.kind == 0) {
+            k_oihw_to_ohwi(src + off, arena + en.eng_off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, L.st, en.Ostride);
+            off += en.n;
+        } else if (en.kind == 1) {
+            if (!np_only || en.eng_off < e->NP)
+                HIPCHK(hipMemcpyAsync(arena + en.eng_off, src + off, en.n * 4, hipMemcpyDeviceToDevice, L.st));
+            off += en.n;
+        }
+    }
+    return FM_OK;
+}
+
 // debug hooks: fold the per-tile partials conv `ci`'s forward left in ws_stats with the finalize kernel's own reduction order
 // (sum / sumsq only) into stats_dev [groups][2][cout_p]
 int debug_fold_stats(fm_engine* e, int ci, int groups, float* stats_dev)
@@ -2268,20 +2345,13 @@ int fm_set_state(fm_engine* e, const float* host_f32, const int64_t* host_i64)
 {
     ARGCHK(e && host_f32, "null engine/state");
     HIPCHK(hipMemcpyAsync(e->stage_sd, host_f32, (size_t)e->nf_sd * 4, hipMemcpyHostToDevice, e->main.st));
-    size_t off = 0;
+    RCCHK(state_dict_to_arena(e, e->stage_sd, e->student.state, false));
     int ic = 0;
-    for (auto& en : e->entries) {
-        if (en.kind == 0) {
-            k_oihw_to_ohwi(e->stage_sd + off, e->student.state + en.eng_off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->main.st, en.Ostride);
-            off += en.n;
-        } else if (en.kind == 1) {
-            HIPCHK(hipMemcpyAsync(e->student.state + en.eng_off, e->stage_sd + off, en.n * 4, hipMemcpyDeviceToDevice, e->main.st));
-            off += en.n;
-        } else {
+    for (auto& en : e->entries)
+        if (en.kind == 2) {
             e->student.counters[en.bn] = host_i64 ? host_i64[ic] : 0;
             ++ic;
         }
-    }
     HIPCHK(hipStreamSynchronize(e->main.st));
     e->student.ev_dirty = true;
     e->wpack_dirty = true;
@@ -2489,10 +2559,7 @@ int fm_adam_reset(fm_engine* e, const fm_adam* hp)
 {
     ARGCHK(e, "null engine");
     if (hp) e->hp = *hp;
-    e->adam_t = 0;
-    HIPCHK(hipMemsetAsync(e->adam_m, 0, e->NP * 4, e->main.st));
-    HIPCHK(hipMemsetAsync(e->adam_v, 0, e->NP * 4, e->main.st));
-    return FM_OK;
+    return optim_reset(e);
 }
 
 int fm_forward_eval(fm_engine* e, const float* x_dev, int32_t B, int32_t use_teacher, float* feat_dev,
@@ -2856,6 +2923,91 @@ int fm_get_grads(fm_engine* e, float* dev_out)
     else {
         RCCHK(grads_to_state_dict(e, e->gacc, dev_out));
     }
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_sgd_reset(fm_engine* e, const fm_sgd* hp)
+{
+    ARGCHK(e, "null engine");
+    const char* bad = hp ? sgd_bad(hp) : nullptr;
+    ARGCHK(!bad, (bad ? bad : ""));
+    return optim_reset(e);
+}
+
+int fm_sgd_step(fm_engine* e, const fm_sgd* hp)
+{
+    ARGCHK(e && hp, "null");
+    const char* bad = sgd_bad(hp);
+    ARGCHK(!bad, (bad ? bad : ""));
+    if (!e->gacc_full) return FM_OK;               // torch.optim.SGD skips parameters whose .grad is None
+    sgd_step(e, *hp);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_adamw_step(fm_engine* e, const fm_adam* hp)
+{
+    ARGCHK(e && hp, "null");
+    ARGCHK(hp->lr >= 0.f && hp->eps >= 0.f && hp->weight_decay >= 0.f, "fm_adamw_step: lr, eps and weight_decay must be >= 0");
+    ARGCHK(hp->beta1 >= 0.f && hp->beta1 < 1.f && hp->beta2 >= 0.f && hp->beta2 < 1.f, "fm_adamw_step: betas must be in [0, 1)");
+    if (!e->gacc_full) return FM_OK;
+    adamw_step(e, *hp);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_grad_norm(fm_engine* e, float* norm_dev)
+{
+    ARGCHK(e && norm_dev, "null");
+    if (!e->gacc_full) HIPCHK(hipMemsetAsync(norm_dev, 0, sizeof(float), e->main.st));
+    else RCCHK(grad_norm(e, norm_dev));
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_clip_grad_norm(fm_engine* e, float max_norm, float* norm_dev)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(max_norm >= 0.f, "fm_clip_grad_norm: max_norm must be >= 0");
+    if (!e->gacc_full) {
+        if (norm_dev) HIPCHK(hipMemsetAsync(norm_dev, 0, sizeof(float), e->main.st));
+        return FM_OK;
+    }
+    RCCHK(grad_norm(e, norm_dev ? norm_dev : e->norm_word));
+    k_grad_clip_norm(e->gacc, (int64_t)e->NP, norm_dev ? norm_dev : e->norm_word, max_norm, e->main.st, e->dev_err);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_clip_grad_value(fm_engine* e, float clip)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(clip >= 0.f, "fm_clip_grad_value: clip must be >= 0");
+    if (!e->gacc_full) return FM_OK;
+    k_grad_clip_value(e->gacc, (int64_t)e->NP, clip, e->main.st, e->dev_err);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_optim_get_state(fm_engine* e, float* m_dev, float* v_dev, int64_t* step_host)
+{
+    ARGCHK(e, "null engine");
+    if (m_dev) RCCHK(grads_to_state_dict(e, e->adam_m, m_dev));
+    if (v_dev) RCCHK(grads_to_state_dict(e, e->adam_v, v_dev));
+    if (step_host) *step_host = e->adam_t;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_optim_set_state(fm_engine* e, const float* m_dev, const float* v_dev, int64_t step)
+{
+    ARGCHK(e && m_dev, "null");
+    ARGCHK(step >= 0, "fm_optim_set_state: step must be >= 0");
+    RCCHK(optim_reset(e));                         // the padding of both arenas is zero from here on
+    RCCHK(state_dict_to_arena(e, m_dev, e->adam_m, true));
+    if (v_dev) RCCHK(state_dict_to_arena(e, v_dev, e->adam_v, true));
+    e->adam_t = step;
     HIPCHK(hipGetLastError());
     return FM_OK;
 }

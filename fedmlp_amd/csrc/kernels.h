@@ -231,6 +231,24 @@ void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, f
 void k_reduce_slabs(const float* slab, float* out, int splits, int64_t n, hipStream_t s);
 // acc = g (copy) or acc += g over n floats (n a multiple of 4); *skip != 0: no update
 void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip = nullptr);
+// ---- optimizers of the autograd path (optim.hip): n floats (a multiple of 4), *skip != 0: nothing is written ----
+// torch.optim.SGD: momentum == 0 leaves buf alone; first = first step after a reset (buf = g + wd p, no dampening); the chain
+// runs in double, one rounding per stored value
+void k_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, double one_minus_damp, float wd,
+           bool nesterov, bool first, hipStream_t s, const int* skip = nullptr);
+// torch.optim.AdamW: decay = 1 - lr wd, step = lr / bc1
+void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float decay, float step, float b1, float b2, float eps,
+             float bc2_sqrt, hipStream_t s, const int* skip = nullptr);
+// *norm = sqrt(sum g^2), deterministic: every thread of stage 1 adds GRAD_NORM_F4 squares per vector component in fp32, a block
+// folds its 256 threads in a fixed tree of GRAD_NORM_TREE fp32 levels (2 over the components, 6 over the lanes, 2 over the
+// waves) into part[block] (double, grad_norm_parts(n) of them); one block sums those in double
+#define GRAD_NORM_F4 8
+#define GRAD_NORM_TREE 10
+int grad_norm_parts(int64_t n);
+void k_grad_norm(const float* g, int64_t n, double* part, float* norm, hipStream_t s, const int* skip = nullptr);
+// g *= min(1, max_norm / (*norm + 1e-6)) in fp32; g = clamp(g, -clip, clip)
+void k_grad_clip_norm(float* g, int64_t n, const float* norm, float max_norm, hipStream_t s, const int* skip = nullptr);
+void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int* skip = nullptr);
 
 // ---- prototypes / tagging ----------------------------------------------------------
 void k_proto_accumulate(const float* feat, const float* logits, const float* labels, int B, int D, int C,

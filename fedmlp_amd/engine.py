@@ -360,6 +360,73 @@ class Engine:
         _lib.check(self.lib.fm_get_grads(self.h, _ptr(out)))
         return out
 
+    # ---- SGD, AdamW, clipping, optimizer state (fedmlp_amd.optim) ----------------------------------------
+    def sgd_reset(self, lr=0.0, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        """A fresh torch.optim.SGD: the handle's moment arenas and step count zeroed (what adam_reset does)."""
+        hp = _lib.FmSgd(lr, momentum, dampening, weight_decay, int(bool(nesterov)))
+        self._enqueue()
+        _lib.check(self.lib.fm_sgd_reset(self.h, C.byref(hp)))
+
+    def sgd_step(self, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        """torch.optim.SGD over the accumulator; the momentum buffer is the engine's first moment arena."""
+        self._check_stream()
+        self._enqueue(weights=True)
+        hp = _lib.FmSgd(lr, momentum, dampening, weight_decay, int(bool(nesterov)))
+        _lib.check(self.lib.fm_sgd_step(self.h, C.byref(hp)))
+
+    def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        """torch.optim.AdamW (decoupled weight decay) over the accumulator with the engine's moments."""
+        self._check_stream()
+        self._enqueue(weights=True)
+        hp = _lib.FmAdam(lr, betas[0], betas[1], eps, weight_decay)
+        _lib.check(self.lib.fm_adamw_step(self.h, C.byref(hp)))
+
+    def grad_norm(self):
+        """L2 norm of the accumulator as a 0-dim cuda fp32 tensor (0 when it is empty); enqueued, not synchronised."""
+        self._check_stream()
+        self._enqueue()
+        out = torch.empty((), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.fm_grad_norm(self.h, _ptr(out)))
+        return out
+
+    def clip_grad_norm(self, max_norm):
+        """accumulator *= min(1, max_norm / (norm + 1e-6)); returns the norm before clipping as a 0-dim cuda tensor."""
+        self._check_stream()
+        self._enqueue()
+        out = torch.empty((), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.fm_clip_grad_norm(self.h, C.c_float(max_norm), _ptr(out)))
+        return out
+
+    def clip_grad_value(self, clip_value):
+        """accumulator = clamp(accumulator, -clip_value, clip_value)"""
+        self._check_stream()
+        self._enqueue()
+        _lib.check(self.lib.fm_clip_grad_value(self.h, C.c_float(clip_value)))
+
+    def optim_state(self):
+        """(step, m, v): the step count and the two moment arenas as flat cuda fp32 tensors in grads() layout."""
+        self._check_stream()
+        self._enqueue()
+        m = torch.empty(self.nf, device=self.device, dtype=torch.float32)
+        v = torch.empty(self.nf, device=self.device, dtype=torch.float32)
+        step = C.c_int64()
+        _lib.check(self.lib.fm_optim_get_state(self.h, _ptr(m), _ptr(v), C.byref(step)))
+        return step.value, m, v
+
+    def set_optim_state(self, step, m, v=None):
+        """The inverse of optim_state(); v None (SGD) zeroes the second arena.  m / v: nf floats in grads() layout."""
+        self._check_stream()
+        ts = []
+        for t in (m, v):
+            if t is not None:
+                t = torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous().reshape(-1)
+                if t.numel() != self.nf:
+                    raise ValueError(f"set_optim_state: a state tensor has {t.numel()} elements, the engine's layout has {self.nf}")
+            ts.append(t)
+        self._enqueue()
+        # enqueued on torch's current stream (_check_stream), so the caching allocator may take the staging tensors back at once
+        _lib.check(self.lib.fm_optim_set_state(self.h, _ptr(ts[0]), _ptr(ts[1]), int(step)))
+
     def teacher_axpby(self, w_teacher, w_student):
         self._enqueue()
         _lib.check(self.lib.fm_teacher_axpby(self.h, C.c_float(w_teacher), C.c_float(w_student)))

@@ -72,6 +72,13 @@ typedef struct fm_adam {
     float lr, beta1, beta2, eps, weight_decay;
 } fm_adam;
 
+/* torch.optim.SGD hyper-parameters (autograd path): all >= 0 except dampening; nesterov != 0 needs momentum > 0 and
+ * dampening == 0, like torch. */
+typedef struct fm_sgd {
+    float lr, momentum, dampening, weight_decay;
+    int32_t nesterov;
+} fm_sgd;
+
 const char* fm_last_error(void);
 const char* fm_version(void);
 
@@ -141,7 +148,8 @@ int fm_fedavg_proto(fm_engine* e, const float* proto_host, double n_i, const flo
  * snapshot the current state as the frozen eval-mode teacher. */
 int fm_teacher_snapshot(fm_engine* e);
 /* A fresh torch.optim.Adam every round (utils/local_training.py:912-913):
- * zero both moments and the step count. */
+ * zero both moments and the step count.  One handle holds ONE optimizer's state (two NP-float arenas and a step count,
+ * whichever optimizer steps): fm_adam_reset and fm_sgd_reset clear the same things. */
 int fm_adam_reset(fm_engine* e, const fm_adam* hp);
 
 /* ---- net(x) in eval mode: -> (feature[B,D], logits[B,C]) ----------------- */
@@ -304,6 +312,35 @@ int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev,
 int fm_zero_grad(fm_engine* e);
 int fm_adam_step(fm_engine* e, const fm_adam* hp);
 int fm_get_grads(fm_engine* e, float* dev_out);
+/* ---- more optimizers, gradient clipping and optimizer state for the autograd path ------------------
+ * Kernels over the same arenas as fm_adam_step (weights, accumulator, the handle's two moment arenas), enqueued on the
+ * engine's stream without synchronising.  The step functions behave like fm_adam_step: hp is read on every call, an empty
+ * accumulator is skipped, and the handle's step count goes up by one.  The fused steps are not affected by any of them.
+ * fm_sgd_reset: zero the moment arenas and the step count (what fm_adam_reset does; hp is validated, not kept).
+ * fm_sgd_step: torch.optim.SGD's single-tensor update: g += weight_decay p; with momentum != 0, buf = g on the first step
+ *   after a reset (no dampening, as torch), else buf = momentum buf + (1 - dampening) g; g = nesterov ? g + momentum buf :
+ *   buf; p -= lr g.  buf is the first moment arena; momentum == 0 neither reads nor writes it.
+ * fm_adamw_step: torch.optim.AdamW: p *= 1 - lr weight_decay, then Adam's update with no L2 folded into g.
+ * fm_grad_norm: the L2 norm of the accumulator as ONE float written to norm_dev (device); two launches, no atomics: the
+ *   same gradients give the same bits.  0 for an empty accumulator.  The engine's layout padding holds zeros and does not
+ *   enter.
+ * fm_clip_grad_norm: torch.nn.utils.clip_grad_norm_ (norm_type 2): accumulator *= min(1, max_norm / (norm + 1e-6)), the
+ *   coefficient formed in fp32 on the device; the multiply always happens and a non-finite norm propagates.  norm_dev
+ *   (device, may be NULL) receives the norm BEFORE clipping.  An empty accumulator: norm 0, nothing else.
+ * fm_clip_grad_value: accumulator = clamp(accumulator, -clip, clip).
+ * fm_optim_get_state / fm_optim_set_state: the two moment arenas in fm_get_grads' layout (state_dict order, conv weights
+ *   OIHW, fm_state_sizes' n_f32 floats, zeros at the BN running statistics) to / from device buffers, and the step count.
+ *   get: any pointer may be NULL.  set: the layout padding of the arenas is left zero; v_dev may be NULL (SGD: the second
+ *   arena is zeroed); step >= 0, and step == 0 makes the next fm_sgd_step a first step.
+ * Arguments: lr, weight_decay, momentum, eps, max_norm, clip >= 0; betas in [0, 1). */
+int fm_sgd_reset(fm_engine* e, const fm_sgd* hp);
+int fm_sgd_step(fm_engine* e, const fm_sgd* hp);
+int fm_adamw_step(fm_engine* e, const fm_adam* hp);
+int fm_grad_norm(fm_engine* e, float* norm_dev);
+int fm_clip_grad_norm(fm_engine* e, float max_norm, float* norm_dev);
+int fm_clip_grad_value(fm_engine* e, float clip);
+int fm_optim_get_state(fm_engine* e, float* m_dev, float* v_dev, int64_t* step_host);
+int fm_optim_set_state(fm_engine* e, const float* m_dev, const float* v_dev, int64_t step);
 /* teacher <- w_teacher*teacher + w_student*student over every state entry (train_RSCFed's EMA,
  * utils/local_training.py:751-759, weights 0.999 / 0.001). */
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student);
