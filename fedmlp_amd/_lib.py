@@ -49,6 +49,8 @@ SYMBOLS = {
     "fm_counters": (C.c_int, [_P, _P, _I32]),
     "fm_state_scale": (C.c_int, [_P, C.c_float]),
     "fm_fedavg_fold": (C.c_int, [_P, C.POINTER(_P), _F, _I32, _P]),
+    "fm_fed_w": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_double), _I32, _P]),
+    "fm_state_dist": (C.c_int, [_P, C.POINTER(_P), _I32, _P, _P, _I32]),
     "fm_stream_mode": (C.c_int, [_P]),
     "fm_mfma_products": (C.c_int, []),
     "fm_products": (C.c_int, [_P]),

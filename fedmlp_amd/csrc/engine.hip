@@ -198,6 +198,11 @@ struct fm_engine {
     // (allocated on first use)
     double* norm_part = nullptr;
     float* norm_word = nullptr;
+    // fm_state_dist: the entry / chunk table of the fp32 state entries and the per-(chunk, k) partial sums (built on first use)
+    DistEntry* dist_ent = nullptr;
+    DistChunk* dist_chunks = nullptr;
+    double* dist_part = nullptr;
+    int dist_n_ent = 0, dist_n_chunks = 0;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
     // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read,
     // `pending_fixed` the mode of the pending forward (its backward takes the same)
@@ -2255,6 +2260,56 @@ int debug_fold_stats(fm_engine* e, int ci, int groups, float* stats_dev)
     return FM_OK;
 }
 
+// fm_state_dist's table from the engine's own state entries: one DistEntry per fp32 entry in state_dict order, its arena span
+// cut into chunks of FM_DIST_CHUNK floats (a chunk never straddles an entry).  A conv weight's span is its O rows with the
+// row stride; a vector's span is its n elements.  Uploaded once per engine.
+int ensure_dist_table(fm_engine* e)
+{
+    if (e->dist_ent) return FM_OK;
+    std::vector<DistEntry> ent;
+    std::vector<DistChunk> chunks;
+    for (auto& en : e->entries) {
+        if (en.kind == 2) continue;
+        DistEntry d{};
+        d.off = (long long)en.eng_off;
+        if (en.kind == 0) {
+            d.dense = en.KH * en.Wpad * en.Ipad;
+            d.row = en.Ostride ? en.Ostride : d.dense;
+            d.len = (en.O - 1) * d.row + d.dense;          // the last row ends with its matrix
+            d.Ipad = en.Ipad; d.I = en.I; d.Wpad = en.Wpad; d.W = en.KW;
+            d.all_real = d.row == d.dense && en.Ipad == en.I && en.Wpad == en.KW;
+        } else {
+            d.len = (int)en.n; d.row = d.dense = d.len;
+            d.Ipad = d.I = d.Wpad = d.W = 1;
+            d.all_real = 1;
+        }
+        if (d.len <= 0 || d.off < 0 || (size_t)d.off + (size_t)d.len > e->NS) { g_err = "state entry outside the arena"; return FM_ERR_ARG; }
+        d.chunk0 = (int)chunks.size();
+        for (int st = 0; st < d.len; st += FM_DIST_CHUNK) chunks.push_back({(int)ent.size(), st});
+        d.nchunks = (int)chunks.size() - d.chunk0;
+        ent.push_back(d);
+    }
+    DistEntry* de = nullptr;
+    DistChunk* dc = nullptr;
+    double* dp = nullptr;
+    DALLOC(de, ent.size()); DALLOC(dc, chunks.size()); DALLOC(dp, chunks.size() * FM_FOLD_MAX);
+    HIPCHK(hipMemcpy(de, ent.data(), ent.size() * sizeof(DistEntry), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(DistChunk), hipMemcpyHostToDevice));
+    e->dist_chunks = dc; e->dist_part = dp;
+    e->dist_n_ent = (int)ent.size(); e->dist_n_chunks = (int)chunks.size();
+    e->dist_ent = de;
+    return FM_OK;
+}
+
+// the launch of fm_fedavg_fold / fm_fed_w: fp32 weights and the divisor as the caller formed them
+int fold_states(fm_engine* e, const FoldArgs& a, int K, float tot, float* out_dev)
+{
+    k_fedavg_fold(a, K, tot, out_dev, (int64_t)e->NS, e->main.st);
+    if (out_dev == e->student.state) { e->student.ev_dirty = true; e->wpack_dirty = true; }
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
 ClassVec to_cv(const float* h, int C)
 {
     ClassVec v{};
@@ -2436,8 +2491,37 @@ int fm_fedavg_fold(fm_engine* e, const float* const* states_dev, const float* n_
         tot_d += (double)n_host[k];
     }
     tot = (float)tot_d;
-    k_fedavg_fold(a, K, tot, out_dev, (int64_t)e->NS, e->main.st);
-    if (out_dev == e->student.state) { e->student.ev_dirty = true; e->wpack_dirty = true; }
+    return fold_states(e, a, K, tot, out_dev);
+}
+
+int fm_fed_w(fm_engine* e, const float* const* states_dev, const double* w_host, int32_t K, float* out_dev)
+{
+    ARGCHK(e && states_dev && w_host && out_dev, "null argument");
+    ARGCHK(K >= 1 && K <= FM_FOLD_MAX, "fm_fed_w: 1 <= K <= FM_FOLD_MAX");
+    FoldArgs a{};
+    double tot_d = 0.0;                                 // Python's sum(weight): in double, rounded to fp32 once
+    for (int k = 0; k < K; ++k) {
+        ARGCHK(states_dev[k], "fm_fed_w: null state pointer");
+        a.s[k] = states_dev[k];
+        a.n[k] = (float)w_host[k];
+        tot_d += w_host[k];
+    }
+    return fold_states(e, a, K, (float)tot_d, out_dev);
+}
+
+int fm_state_dist(fm_engine* e, const float* const* states_dev, int32_t K, const float* ref_dev, float* norms_dev, int32_t n_entries)
+{
+    ARGCHK(e && states_dev && norms_dev, "null argument");
+    ARGCHK(K >= 1 && K <= FM_FOLD_MAX, "fm_state_dist: 1 <= K <= FM_FOLD_MAX");
+    RCCHK(ensure_dist_table(e));
+    ARGCHK(n_entries == e->dist_n_ent, "fm_state_dist: n_entries is not the engine's number of fp32 state_dict entries");
+    FoldArgs a{};
+    for (int k = 0; k < K; ++k) {
+        ARGCHK(states_dev[k], "fm_state_dist: null state pointer");
+        a.s[k] = states_dev[k];
+    }
+    k_state_dist(a, K, ref_dev, e->dist_ent, e->dist_n_ent, e->dist_chunks, e->dist_n_chunks, (int64_t)e->NS, e->dist_part, norms_dev,
+                 e->main.st);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }

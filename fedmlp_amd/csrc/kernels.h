@@ -60,6 +60,16 @@ void k_scale(float* x, float w, int64_t n, hipStream_t s);
 struct FoldArgs { const float* s[FM_FOLD_MAX]; float n[FM_FOLD_MAX]; };
 void k_fedavg_fold(const FoldArgs& a, int K, float tot, float* out, int64_t n, hipStream_t s);
 void k_axpby(float* y, const float* x, float a, float b, int64_t n, hipStream_t s);   // y = a*y + b*x
+// agg.hip: norms[k][entry] = || s_k - ref || over the real elements of every fp32 state_dict entry (ref null: the states'
+// unweighted Fed_w mean, formed in registers), fp64 sums in a fixed order.  One DistEntry per fp32 entry: the arena span
+// [off, off + len), rows of `row` floats of which the first `dense` are [..][Wpad][Ipad] with wp < W, ip < I real (all_real:
+// every element of the span is); its chunks are chunk0 .. chunk0 + nchunks - 1, FM_DIST_CHUNK floats of the span each.
+// part: n_chunks * K doubles.
+#define FM_DIST_CHUNK 8192
+struct DistEntry { long long off; int len, row, dense, Ipad, I, Wpad, W, chunk0, nchunks, all_real; };
+struct DistChunk { int entry, start; };
+void k_state_dist(const FoldArgs& a, int K, const float* ref, const DistEntry* ent, int n_entries, const DistChunk* chunks,
+                  int n_chunks, int64_t NS, double* part, float* norms, hipStream_t s);
 
 // ---- input pipeline: uint8 HBM cache -> augmented, normalised fp32 NCHW batch.
 // params[b] = {c0, c1, c2, c3, c4, c5 (Pillow's 16.16 fixed-point inverse affine), flip, unused}; nearest sampling,

@@ -162,6 +162,51 @@ class Engine:
         _lib.check(self.lib.fm_fedavg_fold(self.h, ptrs, _lib.fvec(dict_len, K), K, _ptr(dst)))
         return dst
 
+    def _state_ptrs(self, states):
+        K = len(states)
+        assert K >= 1
+        if getattr(self, "_ns", None) is None:
+            self._ns = self.state_tensor().numel()
+        for t in states:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self._ns
+        return (C.c_void_p * K)(*[t.data_ptr() for t in states])
+
+    def fed_w(self, states, weights, out=None):
+        """Fed_w (utils/FedAvg.py:16-23) of K engine-layout device states: the fold with Python-float weights, each rounded
+        to fp32 once, divided by float32(sum of the double weights).  out: destination (default: the engine's own state)."""
+        K = len(states)
+        assert K == len(weights)
+        ptrs = self._state_ptrs(states)
+        dst = self.state_tensor() if out is None else out
+        assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() == states[0].numel()
+        self._check_stream()
+        self._enqueue(weights=True)
+        w = (C.c_double * K)(*[float(v) for v in weights])
+        _lib.check(self.lib.fm_fed_w(self.h, ptrs, w, K, _ptr(dst)))
+        return dst
+
+    @property
+    def n_float_entries(self):
+        """fp32 entries of the state_dict (the columns of state_dist)."""
+        if getattr(self, "_nfe", None) is None:
+            self._nfe = sum(1 for _, _, dt in spec.entries(self.model, self.n_classes) if dt == "f32")
+        return self._nfe
+
+    def state_dist(self, states, ref=None, n_entries=None):
+        """The terms of model_dist (utils/FedAvg.py:43-49) on the device: a cuda fp32 tensor [K, n_float_entries] of the L2
+        norms of (states[k] - ref) per fp32 state_dict entry, in state_dict order, over the real elements of the engine
+        layout only.  ref None: the states' own Fed_w(states, [1]*K) mean, formed in registers."""
+        K = len(states)
+        ptrs = self._state_ptrs(states)
+        if ref is not None:
+            assert ref.is_cuda and ref.dtype == torch.float32 and ref.is_contiguous() and ref.numel() == states[0].numel()
+        ne = self.n_float_entries if n_entries is None else int(n_entries)
+        norms = torch.empty((K, ne), device=self.device, dtype=torch.float32)
+        self._check_stream()
+        self._enqueue()
+        _lib.check(self.lib.fm_state_dist(self.h, ptrs, K, _ptr(ref), _ptr(norms), ne))
+        return norms
+
     def _check_stream(self):
         """The engine enqueues on the stream that was torch's current one when it was built (fm_config.stream is fixed for
         the handle's life: its workspaces are ordered on that stream).  A call made under another torch.cuda.stream(...)

@@ -5,6 +5,9 @@ Two forms of the same arithmetic:
     (utils/FedAvg.py:7-14, 51-70, 72-93) for a single-process driver that holds
     every client's state_dict on the host, as main.py:216-234 does.  Host glue:
     left-to-right weighted mean, same order as the reference.
+  * Fed_w / model_dist / RSCFed -- the `--exp RSCFed` aggregation (utils/FedAvg.py:16-49, main.py:213-214): host drop-ins
+    with the reference's signatures and roundings, and rscfed_device, the same aggregation over engine-layout device
+    states (fm_state_dist + fm_fed_w), which RSCFed itself takes when it is handed DeviceState clients.
   * fedavg_allreduce / tao_allreduce / proto_allreduce -- one client per GPU:
     each rank pre-scales its device-resident state by n_i/sum(n) (HIP kernel) and
     the sum is an RCCL all-reduce over xGMI (torch.distributed backend "nccl");
@@ -12,6 +15,7 @@ Two forms of the same arithmetic:
 """
 import copy
 import logging
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -37,6 +41,137 @@ def FedAvg(w, dict_len):
             acc = (acc / np.float32(sum(dict_len))).astype(np.float32)
         out[k] = torch.from_numpy(np.ascontiguousarray(acc))
     return out
+
+
+def _is_int(a):
+    return np.issubdtype(np.asarray(a).dtype, np.integer)
+
+
+def Fed_w(w, weight):
+    """utils/FedAvg.py:16-23: ((w0*wt0 + w1*wt1) + ...) / sum(weight), left to right in fp32.  A Python-float weight is
+    rounded to fp32 once (torch's tensor * scalar), every product and sum is rounded separately, and the divisor is
+    float32(sum(weight)) with Python's sum (in double for float weights).  An int64 entry (num_batches_tracked) stays
+    integer under int weights until the true division makes it fp32, and is fp32 from the first product under float ones."""
+    ints = all(isinstance(x, (int, np.integer)) for x in weight)
+    tot = np.float32(sum(weight))
+    out = OrderedDict()
+    for k in w[0].keys():
+        vs = [_np(wi[k]) for wi in w]
+        if _is_int(vs[0]) and ints:
+            acc = vs[0] * int(weight[0])
+            for i in range(1, len(w)):
+                acc = acc + vs[i] * int(weight[i])
+            acc = acc.astype(np.float32)
+        else:
+            acc = vs[0].astype(np.float32) * np.float32(weight[0])
+            for i in range(1, len(w)):
+                acc = acc + vs[i].astype(np.float32) * np.float32(weight[i])
+        out[k] = torch.from_numpy(np.ascontiguousarray((acc / tot).astype(np.float32)))
+    return out
+
+
+def _entry_norm(a, b):
+    """|| a - b ||_2 as fm_state_dist forms it: the difference in fp32 (torch's), squares and sum in fp64, one rounding."""
+    d = (np.asarray(a).astype(np.float32) - np.asarray(b).astype(np.float32)).astype(np.float64).reshape(-1)
+    return np.float32(np.sqrt(np.dot(d, d)))
+
+
+def _dist_sum(terms):
+    """model_dist's accumulation: dist_total is an fp32 tensor, every term is added in turn."""
+    tot = np.float32(0.0)
+    for t in terms:
+        tot = np.float32(tot + np.float32(t))
+    return float(tot)
+
+
+def _dist_rows(terms):
+    """_dist_sum of every row of an fp32 [rows, terms] array: add.accumulate is r[i] = r[i - 1] + t[i], each sum rounded to
+    fp32, the same left-to-right chain."""
+    return [float(v) for v in np.add.accumulate(np.asarray(terms, dtype=np.float32), axis=1, dtype=np.float32)[:, -1]]
+
+
+def model_dist(w_1, w_2):
+    """utils/FedAvg.py:43-49: the fp32 sum over keys, in key order, of norm(w_1[k] - w_2[k]); int64 entries take part as
+    fp32 values.  (torch.norm sums its squares in fp32 in an order of its own; here they are summed in fp64, so the two
+    agree to fp32 rounding, not bit for bit.)"""
+    assert w_1.keys() == w_2.keys(), "Error: cannot compute distance between dict with different keys"
+    return _dist_sum(_entry_norm(_np(w_1[k]), _np(w_2[k])) for k in w_1)
+
+
+def _rscfed_weights(ids, dict_len, dists):
+    """utils/FedAvg.py:29-38 in double: a = n_id / N_group, b = exp(-0.01 * dist / n_id)."""
+    n_total = 0
+    for i in ids:
+        n_total += dict_len[i]
+    return [dict_len[i] / n_total * math.exp((-0.01) * (d / dict_len[i])) for i, d in zip(ids, dists)]
+
+
+class DeviceState:
+    """One client's result kept on the GPU: the engine-layout state (`engine.state_tensor().clone()`) and its
+    num_batches_tracked counters.  RSCFed takes the device path when every client is one of these."""
+
+    def __init__(self, engine, tensor, counters):
+        self.engine, self.tensor = engine, tensor
+        self.counters = np.asarray(counters)
+
+    @classmethod
+    def capture(cls, engine):
+        return cls(engine, engine.state_tensor().clone(), engine.counters())
+
+
+def rscfed_device(engine, states, counters, DMA, dict_len):
+    """RSCFed (utils/FedAvg.py:25-41) over engine-layout device states, one tensor per client, and their [n_clients, ni]
+    int64 counters.  Per group: one fm_state_dist against the group's own mean (never stored), ONE device-to-host read (the
+    [K, n_entries] norms), the weights on the host in double -- each distance the fp32 sum, in key order, of a row of norms
+    and of the counters' terms |float32(nbt_id) - mean_nbt| -- and one fm_fed_w; then a final fm_fed_w with [1]*M.
+    Returns (device state, float counters [ni]); the counters are truncated on load as for FedAvg."""
+    from . import spec
+    M = len(DMA)
+    assert 1 <= M <= 16, "rscfed_device: the final fold takes at most FM_FOLD_MAX = 16 groups"
+    counters = np.asarray(counters)
+    is_f32 = np.array([dt == "f32" for _, _, dt in spec.entries(engine.model, engine.n_classes)])
+    subs = [torch.empty_like(states[0]) for _ in range(M)]
+    sub_cnt = []
+    for g, group in enumerate(DMA):
+        ids = list(group)
+        K = len(ids)
+        sel = [states[i] for i in ids]
+        cnt = counters[ids].astype(np.int64)                              # [K, ni]
+        mean_cnt = cnt.sum(axis=0).astype(np.float32) / np.float32(K)     # Fed_w(.., [1]*K) of an int64 entry
+        terms = np.empty((K, is_f32.size), np.float32)                    # model_dist's terms in key order
+        terms[:, ~is_f32] = np.abs(cnt.astype(np.float32) - mean_cnt[None, :])
+        terms[:, is_f32] = engine.state_dist(sel).cpu().numpy()           # the group's one device-to-host read
+        dists = _dist_rows(terms)
+        wts = _rscfed_weights(ids, dict_len, dists)
+        engine.fed_w(sel, wts, subs[g])
+        acc = cnt[0].astype(np.float32) * np.float32(wts[0])
+        for r in range(1, K):
+            acc = acc + cnt[r].astype(np.float32) * np.float32(wts[r])
+        sub_cnt.append((acc / np.float32(sum(wts))).astype(np.float32))
+    out = torch.empty_like(states[0])
+    engine.fed_w(subs, [1] * M, out)
+    acc = sub_cnt[0] * np.float32(1)
+    for g in range(1, M):
+        acc = acc + sub_cnt[g] * np.float32(1)
+    return out, (acc / np.float32(M)).astype(np.float32)
+
+
+def RSCFed(DMA, w_locals, K, dict_len, M):
+    """utils/FedAvg.py:25-41 (main.py:213-214).  state_dicts: the host path, the reference's arithmetic.  DeviceState
+    clients of one engine: rscfed_device, and the result is a DeviceState with float counters."""
+    if len(w_locals) and all(isinstance(w, DeviceState) for w in w_locals):
+        eng = w_locals[0].engine
+        assert all(w.engine is eng for w in w_locals), "RSCFed: the device states belong to different engines"
+        assert all(len(g) == K for g in DMA) and len(DMA) == M
+        st, cnt = rscfed_device(eng, [w.tensor for w in w_locals], np.stack([w.counters for w in w_locals]), DMA, dict_len)
+        return DeviceState(eng, st, cnt)
+    w_sub = []
+    for group in DMA:
+        w_select = [w_locals[i] for i in group]
+        w_avg = Fed_w(w_select, [1] * K)
+        dists = [model_dist(w_locals[i], w_avg) for i in group]
+        w_sub.append(Fed_w(w_select, _rscfed_weights(group, dict_len, dists)))
+    return Fed_w(w_sub, [1] * M)
 
 
 def FedAvg_tao(t, weight, class_active_client_list=None):

@@ -112,6 +112,22 @@ int fm_state_scale(fm_engine* e, float w);
  * be fm_state_device()'s buffer itself or any of the inputs.  The num_batches_tracked counters stay with the caller
  * (fm_counters). */
 int fm_fedavg_fold(fm_engine* e, const float* const* states_dev, const float* n_host, int32_t K, float* out_dev);
+/* ---- RSCFed aggregation (utils/FedAvg.py:16-49) over client states that share ONE GPU ------
+ * Fed_w (:16-23): the fold above with the reference's Python-float weights: every weight is rounded to fp32 once and the
+ * divisor is (float)(sum of the DOUBLE weights), which can differ in the last bit from the fold's sum of rounded weights when
+ * the weights are not integers.  Same kernels, K limit, aliasing rule (out_dev may be an input or the engine's state) and
+ * roundings as the fold: bit-identical on fp32 entries to Fed_w on CPU tensors. */
+int fm_fed_w(fm_engine* e, const float* const* states_dev, const double* w_host, int32_t K, float* out_dev);
+/* The per-entry terms of model_dist (:43-49): norms_dev[k * n_entries + j] = || entry j of states_dev[k] - entry j of ref_dev ||_2
+ * for every fp32 state_dict entry j in state_dict order (n_entries of them: 102 for ResNet-18; the int64 counters stay with
+ * the caller).  ref_dev NULL: the reference is the states' own unweighted mean Fed_w(states, [1]*K), formed element by element
+ * in registers with the fold's roundings and never stored, so each state is read once.  Only state_dict elements count: the
+ * padding of the engine layout and the gaps between its matrices may hold anything.  The difference is formed in fp32 as
+ * torch does, squares and sums in fp64 in a fixed order (no atomics: two calls give the same bits), so each norm is the
+ * correctly rounded norm of the fp32 differences to within one fp32 ulp.  model_dist is the fp32 sum of a row, in order, with
+ * the counters' terms at their places.  K <= 16; device norms_dev of K * n_entries floats; enqueued on the engine's stream. */
+int fm_state_dist(fm_engine* e, const float* const* states_dev, int32_t K, const float* ref_dev, float* norms_dev,
+                  int32_t n_entries);
 /* ---- FedAvg across ranks as RCCL calls inside the library (one client per GPU) --------------
  * utils/FedAvg.py:7-14 (FedAvg), :51-70 (FedAvg_tao), :72-93 (FedAvg_proto) walk a Python list of
  * client results in one process.  With one process per GPU the same weighted sums are
