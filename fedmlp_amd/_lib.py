@@ -120,6 +120,7 @@ SYMBOLS = {
     "fm_debug_ew": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
     "fm_debug_eff": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
     "fm_debug_eff_ws": (C.c_int, [_I32, C.POINTER(_I32), C.POINTER(C.c_int64)]),
+    "fm_debug_head": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
 }
 
 _lib = None

@@ -3545,6 +3545,18 @@ static const char* eff_dims_bad(int32_t op, const int32_t* d)
         if ((int64_t)d[1] * d[2] * d[3] >= ((int64_t)1 << 30)) return "tensor too large";
         return nullptr;
     }
+    if (op == FM_EFF_BNACT_APPLY || op == FM_EFF_CHAN_REDUCE || op == FM_EFF_BNACT_BWD_APPLY) {
+        // d = {ty, ta, groups, pix_per_group, HW, C, mode, act}
+        if ((d[0] != DT_F32 && d[0] != DT_BF16) || (d[1] != DT_F32 && d[1] != DT_BF16)) return "ty / ta";
+        if (d[0] == DT_BF16 && d[1] == DT_F32) return "(ty, ta) is (f32, f32), (f32, bf16) or (bf16, bf16)";
+        if (!pos(2, 6)) return "a dimension < 1";
+        if (d[5] % ((d[0] == DT_BF16 && d[1] == DT_BF16) ? 8 : 4)) return "C % 4 (C % 8 when both types are bf16)";
+        if (d[3] % d[4]) return "pix_per_group % HW";
+        if (op == FM_EFF_CHAN_REDUCE ? (d[6] != 0 && d[6] != 1) : d[6] != 0) return "mode";
+        if (op == FM_EFF_BNACT_APPLY ? (d[7] < 0 || d[7] > 2) : (d[7] != 0 && d[7] != 2)) return "act";
+        if ((int64_t)d[2] * d[3] * d[5] >= ((int64_t)1 << 30)) return "tensor too large";
+        return nullptr;
+    }
     return "op";
 }
 
@@ -3581,6 +3593,12 @@ int fm_debug_eff_ws(int32_t op, const int32_t* d, int64_t* floats)
     case FM_EFF_SE_WGRAD:
         floats[1] = se_wgrad_range_floats(d[1], d[2]);
         floats[0] = floats[1] * se_wgrad_splits();
+        break;
+    case FM_EFF_CHAN_REDUCE:
+        floats[0] = (int64_t)d[2] * bn_bwd_blocks(d[3]) * 2 * d[5];
+        break;
+    case FM_EFF_BNACT_APPLY:
+    case FM_EFF_BNACT_BWD_APPLY:
         break;
     }
     return FM_OK;
@@ -3639,12 +3657,87 @@ int fm_debug_eff(fm_engine* e, int32_t op, void* const* p, const int32_t* d, con
         ARGCHK(need({0, 1, 2, 3, 4, 5}), "se_wgrad operands");
         k_se_wgrad(F(0), F(1), F(2), F(3), F(4), F(5), d[0], d[1], d[2], s);
         break;
+    case FM_EFF_BNACT_APPLY:
+        ARGCHK(need({0, 1, 2, 5}), "bnact_apply: y, scale, shift, out");
+        k_bnact_apply(p[0], d[0], F(1), F(2), p[3], F(4), p[5], d[1], d[2], d[3], d[4], d[5], d[7], s);
+        break;
+    case FM_EFF_CHAN_REDUCE:
+        ARGCHK(need({1, 7}), "chan_reduce: y, part");
+        ARGCHK(d[6] == 0 || need({0, 2, 3}), "chan_reduce mode 1: a, mean, istd");
+        ARGCHK(d[7] != 2 || (p[4] && p[5]), "chan_reduce: act 2 needs scale / shift");
+        ARGCHK(!p[8] == !p[9], "chan_reduce: gate with dsv");
+        k_chan_reduce(p[0], d[1], p[1], d[0], F(2), F(3), F(4), F(5), F(6), F(7), d[2], d[3], d[4], d[5], d[6], d[7], F(8), F(9), s);
+        break;
+    case FM_EFF_BNACT_BWD_APPLY:
+        ARGCHK(need({0, 1, 2, 3, 4, 8}), "bnact_bwd_apply: dz, y, ca, cb, cc, dy");
+        ARGCHK(d[7] != 2 || (p[5] && p[6]), "bnact_bwd_apply: act 2 needs scale / shift");
+        ARGCHK(!p[9] == !p[10], "bnact_bwd_apply: gate with dsv");
+        k_bnact_bwd_apply(p[0], d[1], p[1], d[0], F(2), F(3), F(4), F(5), F(6), F(7), p[8], d[2], d[3], d[4], d[5], d[7], F(9), F(10), s);
+        break;
     default:
         ARGCHK(false, "op");
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     if (served) *served = flag ? 1 : 0;
+    return FM_OK;
+}
+
+// ---- fm_debug_head: the classifier-head and loss launchers of heads.hip on caller tensors ------------------------------------------
+int fm_debug_head(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)
+{
+    ARGCHK(e && p && d && sc, "null argument");
+    hipStream_t s = e->main.st;
+    auto F = [&](int i) { return static_cast<float*>(p[i]); };
+    auto need = [&](int n) { for (int i = 0; i < n; ++i) if (!p[i]) return false; return true; };
+    auto pos = [&](int a, int b) { for (int i = a; i < b; ++i) if (d[i] < 1) return false; return true; };
+    auto small = [&](int64_t n) { return n < ((int64_t)1 << 30); };
+    switch (op) {
+    case FM_HD_AVGPOOL:
+        ARGCHK(d[0] == DT_F32 || d[0] == DT_BF16, "avgpool: dt");
+        ARGCHK(need(2) && pos(1, 4) && small((int64_t)d[1] * d[2] * d[3]), "avgpool: x, feat; imgs, HW, C >= 1");
+        k_avgpool(p[0], d[0], F(1), d[1], d[2], d[3], s);
+        break;
+    case FM_HD_FC_FWD:
+        ARGCHK(need(4) && pos(0, 3) && d[2] <= FM_MAXC && small((int64_t)d[0] * d[1]), "fc_fwd: feat, W, b, logits; imgs, D >= 1, C in 1 .. 32");
+        k_fc_fwd(F(0), F(1), F(2), F(3), d[0], d[1], d[2], s);
+        break;
+    case FM_HD_FC_BWD:
+        ARGCHK(d[0] == DT_F32 || d[0] == DT_BF16, "fc_bwd: dt");
+        ARGCHK(need(3) && p[4] && p[5] && p[6], "fc_bwd: dz, feat, W, dW, db, dout");
+        ARGCHK(pos(1, 5) && d[3] <= FM_MAXC && small((int64_t)d[1] * d[2] * d[4]), "fc_bwd: imgs, D, HW >= 1, C in 1 .. 32");
+        k_fc_bwd(F(0), F(1), F(2), F(3), F(4), F(5), p[6], d[0], d[1], d[2], d[3], d[4], s, F(7));
+        break;
+    case FM_HD_LOSS_BCE:
+        ARGCHK(need(5) && pos(0, 2) && d[1] <= FM_MAXC && small((int64_t)d[0] * d[1]), "loss_bce: z, y, pos_w, dz, loss; B >= 1, C in 1 .. 32");
+        k_loss_bce(F(0), F(1), to_cv(F(2), d[1]), d[0], d[1], sc[0], F(3), F(4), s);
+        break;
+    case FM_HD_LOSS_STAGE1:
+        ARGCHK(need(6) && pos(0, 2) && d[1] <= FM_MAXC && small((int64_t)d[0] * d[1]),
+               "loss_stage1: z, g, y, active, dz, loss; B >= 1, C in 1 .. 32");
+        k_loss_stage1(F(0), F(1), F(2), to_cv(F(3), d[1]), d[0], d[1], sc[0], sc[1], F(4), F(5), s);
+        break;
+    case FM_HD_LOSS_STAGE2:
+        ARGCHK(need(5) && pos(0, 2) && d[1] <= FM_MAXC && small((int64_t)d[0] * d[1]),
+               "loss_stage2: z, y, distill, dz, loss; B >= 1, C in 1 .. 32");
+        k_loss_stage2(F(0), F(1), F(2), d[0], d[1], F(3), F(4), s);
+        break;
+    case FM_HD_LOSS_FIXMATCH: {
+        ARGCHK(need(7) && pos(0, 2) && d[1] <= FM_MAXC && d[2] >= 0 && small((int64_t)d[0] * d[1]),
+               "loss_fixmatch: z, y, pos_w, pos_wu, active, dz, loss; B >= 1, C in 1 .. 32");
+        ARGCHK(d[0] <= 2048, "loss_fixmatch: B <= 2048 (the confident-row table)");
+        int n_neg = 0;
+        for (int c = 0; c < d[1]; ++c) n_neg += F(4)[c] == 0.f;
+        ARGCHK(n_neg == 0 || d[2] >= 1, "loss_fixmatch: cls_minus_ann >= 1 when a class is missing (the kernel divides by it)");
+        k_loss_fixmatch(F(0), F(1), to_cv(F(2), d[1]), to_cv(F(3), d[1]), to_cv(F(4), d[1]), d[0], d[1], n_neg, sc[0], d[2], F(5),
+                        F(6), s);
+        break;
+    }
+    default:
+        ARGCHK(false, "op");
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
     return FM_OK;
 }
 

@@ -669,7 +669,8 @@ class Engine:
         _lib.check(self.lib.fm_debug_ew(self.h, self.EW_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (2 - len(scalars)))))
 
     # op codes of fm_debug_eff (include/fedmlp_hip_debug.h), in the header's order
-    EFF_OPS = ("dw_fwd", "dw_dgrad", "dw_wgrad", "se_fwd", "se_scale", "se_bwd_bn1", "se_wgrad")
+    EFF_OPS = ("dw_fwd", "dw_dgrad", "dw_wgrad", "se_fwd", "se_scale", "se_bwd_bn1", "se_wgrad", "bnact_apply", "chan_reduce",
+               "bnact_bwd_apply")
 
     def debug_eff_ws(self, op, dims):
         """floats of each workspace / result of one fm_debug_eff op at these dimensions (fm_debug_eff_ws), in the header's order"""
@@ -680,7 +681,7 @@ class Engine:
         return list(n)
 
     def debug_eff(self, op, ptrs, dims, scalars=()):
-        """one depthwise / squeeze-excite launcher of the EfficientNet-B0 path on caller tensors (fm_debug_eff): op = a name of
+        """one depthwise / squeeze-excite / BN+activation launcher of the EfficientNet-B0 path on caller tensors (fm_debug_eff): op = a name of
         EFF_OPS, ptrs = contiguous device tensors of any dtype in the header's operand order (None = absent), dims as documented
         there.  Returns the launcher's "request served" flag (False for the launchers that return nothing)."""
         assert len(ptrs) <= 15 and len(dims) <= 13 and len(scalars) <= 1, (len(ptrs), len(dims), len(scalars))
@@ -692,6 +693,28 @@ class Engine:
         d = (C.c_int32 * 13)(*[int(v) for v in dims])
         _lib.check(self.lib.fm_debug_eff(self.h, self.EFF_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (1 - len(scalars)))))
         return served.value == 1
+
+    # op codes of fm_debug_head (include/fedmlp_hip_debug.h), in the header's order
+    HEAD_OPS = ("avgpool", "fc_fwd", "fc_bwd", "loss_bce", "loss_stage1", "loss_stage2", "loss_fixmatch")
+
+    def debug_head(self, op, ptrs, dims, scalars=()):
+        """one classifier-head / loss launcher on caller tensors (fm_debug_head): op = a name of HEAD_OPS, ptrs = contiguous device
+        tensors in the header's operand order (None = absent); a per-class HOST vector (pos_w, pos_wu, active) is given as a list
+        of floats.  dims / scalars as documented there."""
+        assert len(ptrs) <= 8 and len(dims) <= 5 and len(scalars) <= 2, (len(ptrs), len(dims), len(scalars))
+        keep, raw = [], []
+        for t in ptrs:
+            if t is None:
+                raw.append(None)
+            elif isinstance(t, (list, tuple)):
+                keep.append(_lib.fvec(t))
+                raw.append(C.addressof(keep[-1]))
+            else:
+                assert t.is_cuda and t.is_contiguous(), op
+                raw.append(t.data_ptr())
+        p = (C.c_void_p * 8)(*(raw + [None] * (8 - len(raw))))
+        d = (C.c_int32 * 5)(*[int(v) for v in dims])
+        _lib.check(self.lib.fm_debug_head(self.h, self.HEAD_OPS.index(op), p, d, _lib.fvec(list(scalars) + [0.0] * (2 - len(scalars)))))
 
 
 class _CudaArrayView:

@@ -3,8 +3,9 @@
  *
  * NOT part of the drop-in surface of fedmlp_hip.h: nothing behind build_model() / LocalUpdate / FedAvg* calls these.
  * They expose single kernels (one convolution forward / data gradient / weight gradient, one BatchNorm / stem-pool / plane-writer
- * launcher, one depthwise / squeeze-excite launcher of the EfficientNet-B0 path on caller-supplied tensors), the activations the last train-mode forward kept, and the gradients of the last step, so that the parity tests can
- * compare each kernel with a CPU yardstick.
+ * launcher, one depthwise / squeeze-excite / BN+activation launcher of the EfficientNet-B0 path, one classifier-head or loss launcher
+ * on caller-supplied tensors), the activations the last train-mode forward kept, and the gradients of the last step, so that the
+ * parity tests can compare each kernel with a CPU yardstick.
  */
 #ifndef FEDMLP_HIP_DEBUG_H
 #define FEDMLP_HIP_DEBUG_H
@@ -136,14 +137,15 @@ enum {
 #define FM_EW_NSCAL 2
 int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc);
 
-/* One launcher of csrc/kernels.h -- the depthwise-convolution and squeeze-excite kernels of the EfficientNet-B0 path (effnet.hip)
- * -- on caller-supplied device tensors, on the handle's main stream, followed by a stream synchronisation.  Any EfficientNet-B0
+/* One launcher of csrc/kernels.h -- the depthwise-convolution, squeeze-excite and BN+activation kernels of the EfficientNet-B0 path
+ * (effnet.hip) -- on caller-supplied device tensors, on the handle's main stream, followed by a stream synchronisation.  Any EfficientNet-B0
  * handle, of either precision: the storage type is a dimension (dt: 0 = fp32, 1 = bf16 words), no engine state is read or
  * written.  p[] = FM_EFF_NPTR pointers (NULL = the optional operand is absent, unused slots NULL), d[] = FM_EFF_NDIM dimensions
  * (unused ones 0), sc = reserved (no launcher here takes a scalar; may be NULL).  Arguments outside a kernel's contract return
  * FM_ERR_ARG before any launch: a missing required operand, a dimension < 1, C % 4 != 0 (C % 8 != 0 for the squeeze-excite
  * ops in bf16 storage: 16-byte pieces), K outside {3, 5}, stride outside {1, 2}, Ho / Wo != ceil(Hi / stride) / ceil(Wi / stride),
- * a padding outside 0 .. K-1, act outside 0 .. 2, imgs % ipg != 0, Cs > 48 for SE_WGRAD, a half-given optional group.
+ * a padding outside 0 .. K-1, act outside 0 .. 2, imgs % ipg != 0, Cs > 48 for SE_WGRAD, a half-given optional group, and what the
+ * BN+activation passes list below.
  *
  * p[FM_EFF_NPTR - 1] = `served`, ONE int32 in HOST memory (optional unless a request is made): for the launchers that return bool
  * it receives 1 when the kernel served the statistics / pooling request and 0 when it declined (the caller then reduces by
@@ -184,8 +186,24 @@ int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, cons
  *                  bn_part, [2] = splits (a count, not a size).
  * FM_EFF_SE_WGRAD  d = {imgs, C, Cs};  p = {dgp, drp, rpre, sq, part, dW1};  dW1 = start of the contiguous gradient range
  *                  [dW1 [Cs][C] | db1 [Cs], padded with zeros to a multiple of 4 | dW2 (transposed) [Cs][C] | db2 [C]].
- *                  Workspaces: [0] = part, [1] = the range. */
-enum { FM_EFF_DW_FWD = 0, FM_EFF_DW_DGRAD, FM_EFF_DW_WGRAD, FM_EFF_SE_FWD, FM_EFF_SE_SCALE, FM_EFF_SE_BWD_BN1, FM_EFF_SE_WGRAD };
+ *                  Workspaces: [0] = part, [1] = the range.
+ *
+ * BN+activation passes: d = {ty, ta, groups, pix_per_group, HW, C, mode, act}.  ty = storage type of the raw convolution output (y, dy),
+ * ta = that of the activations and their gradients (res, out, a, dz); (ty, ta) is one of (fp32, fp32), (fp32, bf16), (bf16, bf16).
+ * Tensors are [groups * pix_per_group][C], an image is HW consecutive pixels (pix_per_group % HW == 0), per-channel vectors are
+ * [groups][C], per-image ones (rowscale [imgs], gate / dsv [imgs][C]) count images over all groups.  C % 4 == 0, C % 8 == 0 when
+ * both types are bf16 (16-byte pieces); gate and dsv come together; mode and act are 0 where unused.
+ * FM_EFF_BNACT_APPLY     p = {y TY, scale, shift, res TA | NULL, rowscale | NULL, out TA};  out = act(y scale + shift) * rowscale[img]
+ *                  + res, act 0 none / 1 relu / 2 swish
+ * FM_EFF_CHAN_REDUCE     p = {a TA | NULL, y TY, mean | NULL, istd | NULL, scale | NULL, shift | NULL, rowscale | NULL, part, gate |
+ *                  NULL, dsv | NULL};  part [groups][nblk][2][C], nblk = bn_bwd_blocks(pix_per_group); its sum over nblk is, mode 0:
+ *                  (sum y, sum y^2) -- only y and part are read; mode 1: (sum dyh, sum dyh xhat) with d = a (with gate: a gate[img] +
+ *                  dsv[img] / HW), dyh = d act'(y scale + shift) rowscale[img], xhat = (y - mean) istd.  Mode 1 needs a, mean, istd;
+ *                  act is 0 or 2, and 2 needs scale and shift.  Workspaces: [0] = part.
+ * FM_EFF_BNACT_BWD_APPLY p = {dz TA, y TY, ca, cb, cc, scale | NULL, shift | NULL, rowscale | NULL, dy TY, gate | NULL, dsv | NULL};
+ *                  dy = ca dyh + cb y + cc with dyh as above from d = dz; act is 0 or 2, and 2 needs scale and shift. */
+enum { FM_EFF_DW_FWD = 0, FM_EFF_DW_DGRAD, FM_EFF_DW_WGRAD, FM_EFF_SE_FWD, FM_EFF_SE_SCALE, FM_EFF_SE_BWD_BN1, FM_EFF_SE_WGRAD,
+       FM_EFF_BNACT_APPLY, FM_EFF_CHAN_REDUCE, FM_EFF_BNACT_BWD_APPLY };
 #define FM_EFF_NPTR 16
 #define FM_EFF_NDIM 13
 #define FM_EFF_NWS 4
@@ -193,6 +211,36 @@ int fm_debug_eff(fm_engine* e, int32_t op, void* const* p, const int32_t* d, con
 /* floats[FM_EFF_NWS] = the number of floats each workspace / result of `op` needs for the dimensions d (listed per op above),
  * from the host functions that size the kernels' grids.  The same FM_ERR_ARG contract on d. */
 int fm_debug_eff_ws(int32_t op, const int32_t* d, int64_t* floats);
+
+/* One launcher of csrc/kernels.h -- the classifier head and the loss heads (heads.hip) -- on caller-supplied tensors, on the
+ * handle's main stream, followed by a stream synchronisation.  Any handle; no engine state is read or written.  p[] = FM_HD_NPTR
+ * pointers (NULL = the optional operand is absent, unused slots NULL), d[] = FM_HD_NDIM dimensions (unused ones 0), sc[] =
+ * FM_HD_NSCAL scalars.  Pointers marked HOST are float[C] arrays in host memory, as fm_step_* take them; everything else is fp32
+ * on the device unless marked T (dt-typed: 0 = fp32, 1 = bf16 words).  Arguments outside a kernel's contract return FM_ERR_ARG
+ * before any launch: a missing required operand, a dimension < 1, a class count C > FM_MAX_CLASSES (the by-value class vectors; the
+ * channel count of AVGPOOL is not a class count), B > 2048 for FIXMATCH (its confident-row table in LDS), a dt outside {0, 1}.
+ *
+ * FM_HD_AVGPOOL       p = {x T [imgs][HW][C], feat [imgs][C]};  d = {dt, imgs, HW, C};  feat = mean over HW
+ * FM_HD_FC_FWD        p = {feat [imgs][D], W [C][D], b [C], logits [imgs][C]};  d = {imgs, D, C};  logits = feat W^T + b
+ * FM_HD_FC_BWD        p = {dz [imgs][C], feat [imgs][D], W [C][D], mask [imgs][D] | NULL, dW [C][D], db [C], dout T [imgs][HW][D],
+ *                     dfeat [imgs][D] | NULL};  d = {dt, imgs, D, C, HW};  dW = dz^T feat, db = sum_img dz, and every pixel p < HW of
+ *                     dout[img][p] = ((dz W) mask + dfeat) / HW  (without dfeat: ((dz W) / HW) mask; mask, dfeat absent = 1, 0)
+ * FM_HD_LOSS_BCE      p = {z [B][C], y [B][C], pos_w HOST, dz [B][C], loss (1 float)};  d = {B, C};  sc = {inv_norm};
+ *                     loss = inv_norm sum BCEWithLogits(z, y; pos_w), dz = d loss / d z
+ * FM_HD_LOSS_STAGE1   p = {z [2B][C], g [2B][C], y [B][C], active HOST, dz [2B][C], loss};  d = {B, C};  sc = {inv_sup, inv_dis};
+ *                     rows r and r + B are the two views of sample r; active classes: inv_sup sum BCE(sigmoid z, y) / 2, the others:
+ *                     inv_dis sum (sigmoid z - sigmoid g)^2 / 2
+ * FM_HD_LOSS_STAGE2   p = {z [B][C], y [B][C], distill [B][C], dz [B][C], loss};  d = {B, C};  BCE(sigmoid z, y) over the elements with
+ *                     distill == 0, divided by their number (none: 0 / 0)
+ * FM_HD_LOSS_FIXMATCH p = {z [2B][C] (weak rows, then strong rows), y [B][C], pos_w HOST, pos_wu HOST, active HOST, dz [2B][C], loss};
+ *                     d = {B, C, cls_minus_ann (>= 0)};  sc = {inv_sup};  n_neg = the number of classes with active == 0, counted here
+ *                     as fm_step_fixmatch does; with n_neg > 0 the kernel divides by n_conf cls_minus_ann, so cls_minus_ann = 0 is
+ *                     then FM_ERR_ARG */
+enum { FM_HD_AVGPOOL = 0, FM_HD_FC_FWD, FM_HD_FC_BWD, FM_HD_LOSS_BCE, FM_HD_LOSS_STAGE1, FM_HD_LOSS_STAGE2, FM_HD_LOSS_FIXMATCH };
+#define FM_HD_NPTR 8
+#define FM_HD_NDIM 5
+#define FM_HD_NSCAL 2
+int fm_debug_head(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""float64 restatements of the EfficientNet-B0 depthwise and squeeze-excite kernels (csrc/effnet.hip) in the kernels' own layouts:
+"""float64 restatements of the EfficientNet-B0 depthwise, squeeze-excite and BN+activation kernels (csrc/effnet.hip) in the kernels' own layouts:
 NHWC activations, depthwise weights [K*K][C] (tap kh * K + kw), TF-"same" padding given as (pad_t, pad_l) with the remainder at
 the bottom / right, W2 stored transposed [Cs][C], the five per-image sums of k_se_bwd_bn1, the contiguous squeeze-excite gradient
 range.  tests/test_eff_ref_cpu.py pins every function to torch float64 autograd; tests/test_eff_kernels_gpu.py holds the kernels
@@ -209,3 +209,59 @@ def se_wgrad(dgp, drp, rpre, sq):
     out[o_w2:o_b2] = (swish(rpre).T @ dgp).reshape(-1)       # dW2^T[j][c] = sum_img swish(rpre[img][j]) dgp[img][c]
     out[o_b2:] = dgp.sum(0)
     return out
+
+
+# ---- BN + activation passes --------------------------------------------------------------------------------------------------------
+# y, a, dz, res [groups][pix][C]; per-channel vectors [groups][C]; an image is HW consecutive pixels of a group; per-image operands
+# rowscale [groups][pix / HW], gate / dsv [groups][pix / HW][C]
+def _per_pixel(v, HW):
+    """per-image operand -> per pixel: [groups][imgs] -> [groups][pix][1], [groups][imgs][C] -> [groups][pix][C]"""
+    v = np.asarray(v, np.float64)
+    return np.repeat(v, HW, axis=1)[..., None] if v.ndim == 2 else np.repeat(v, HW, axis=1)
+
+
+def bnact_apply(y, scale, shift, HW, a, res=None, rowscale=None):
+    """out = act(y scale + shift) * rowscale[img] + res   (k_bnact_apply)"""
+    y, sc, sh = np.asarray(y, np.float64), np.asarray(scale, np.float64)[:, None, :], np.asarray(shift, np.float64)[:, None, :]
+    out = act(y * sc + sh, a)
+    if rowscale is not None:
+        out = out * _per_pixel(rowscale, HW)
+    return out if res is None else out + np.asarray(res, np.float64)
+
+
+def bnact_dyh(d, y, HW, a, scale=None, shift=None, rowscale=None, gate=None, dsv=None):
+    """the gradient reaching v = y scale + shift: d (with gate: d gate[img] + dsv[img] / HW, the squeeze-excite backward folded in)
+    times act'(v) (act 0: 1, act 2: swish') times rowscale[img]"""
+    d, y = np.asarray(d, np.float64), np.asarray(y, np.float64)
+    if gate is not None:
+        d = d * _per_pixel(gate, HW) + _per_pixel(dsv, HW) / HW
+    if a == 2:
+        d = d * swish_grad(y * np.asarray(scale, np.float64)[:, None, :] + np.asarray(shift, np.float64)[:, None, :])
+    else:
+        assert a == 0
+    return d if rowscale is None else d * _per_pixel(rowscale, HW)
+
+
+def chan_reduce(y, mode, HW=1, a=0, d=None, mean=None, istd=None, **kw):
+    """[groups][2][C].  mode 0: (sum y, sum y^2); mode 1: (sum dyh, sum dyh xhat), xhat = (y - mean) istd   (k_chan_reduce)"""
+    y = np.asarray(y, np.float64)
+    if mode == 0:
+        return np.stack([y.sum(1), (y * y).sum(1)], 1)
+    dyh = bnact_dyh(d, y, HW, a, **kw)
+    xh = (y - np.asarray(mean, np.float64)[:, None, :]) * np.asarray(istd, np.float64)[:, None, :]
+    return np.stack([dyh.sum(1), (dyh * xh).sum(1)], 1)
+
+
+def bnact_bwd_apply(dz, y, ca, cb, cc, HW, a, **kw):
+    """dy = ca dyh + cb y + cc   (k_bnact_bwd_apply)"""
+    ca, cb, cc = (np.asarray(t, np.float64)[:, None, :] for t in (ca, cb, cc))
+    return ca * bnact_dyh(dz, y, HW, a, **kw) + cb * np.asarray(y, np.float64) + cc
+
+
+def bn_bwd_coefficients(sums, gamma, mean, istd, n):
+    """(ca, cb, cc) [groups][C] of the train-mode BatchNorm backward from the mode-1 sums (S1, S2) over n pixels per group:
+    dy = gamma istd (dyh - S1 / n - xhat S2 / n)"""
+    sums, gamma, mean, istd = (np.asarray(t, np.float64) for t in (sums, gamma, mean, istd))
+    ca = gamma * istd
+    cb = -ca * istd * sums[:, 1] / n
+    return ca, cb, -ca * sums[:, 0] / n - cb * mean

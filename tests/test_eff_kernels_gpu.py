@@ -92,51 +92,53 @@ def _canaries(pool, name):
         b.check(f"{name}[buffer {i}]")
 
 
-def _dump():
-    _dump_report(REPORT, "eff_parity.json")
+def _parity(report, path):
+    """(_bits, _within, _check) recording into `report`, which is written to `path` beside the other parity reports after every
+    check (tests/test_head_kernels_gpu.py keeps a report of its own through the same three)"""
+
+    def _rec(key, err, bound):
+        ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))))
+        r = report.setdefault(key, {})
+        r["max_abs_err"] = max(r.get("max_abs_err", 0.0), float(err.max()))
+        r["worst_err_over_bound"] = max(r.get("worst_err_over_bound", 0.0), ratio)
+        _dump_report(report, path)
+        return ratio
+
+    def _bits(name, got, want64):
+        got64, want64 = np.asarray(got).astype(np.float64), np.asarray(want64, np.float64)
+        got, want = got64.astype(np.float32), want64.astype(np.float32)
+        assert np.array_equal(got.astype(np.float64), got64, equal_nan=True)
+        assert np.array_equal(want.astype(np.float64), want64), f"{name}: the dyadic case is not exact in fp32"
+        assert got.shape == want.shape, (name, got.shape, want.shape)
+        bad = (got.view(np.uint32) != want.view(np.uint32)) & ~((got == 0) & (want == 0))
+        assert not bad.any(), f"{name}: {bad.sum()} of {bad.size} differ, first at {np.argwhere(bad)[0]}: " \
+                              f"{got[bad][0]!r} vs {want[bad][0]!r}"
+        r = report.setdefault(name.split(" ")[0] + "/dyadic", {})
+        r["bit_exact_checks"] = r.get("bit_exact_checks", 0) + 1
+        _dump_report(report, path)
+
+    def _within(name, got, want64, bound, family="random"):
+        got = np.asarray(got).astype(np.float64)
+        want64 = np.asarray(want64, np.float64)
+        bound = np.broadcast_to(np.asarray(bound, np.float64), want64.shape)
+        assert got.shape == want64.shape, (name, got.shape, want64.shape)
+        assert not np.isnan(got).any(), f"{name}: NaN (an element was not written)"
+        err = np.abs(got - want64)
+        ratio = _rec(name.split(" ")[0] + "/" + family, err, bound)
+        print(f"{name}: max|err| {err.max():.3e}, worst err/bound {ratio:.3f}")
+        assert not (err > bound).any(), f"{name}: {(err > bound).sum()} of {err.size} beyond the bound, worst err/bound {ratio:.3f}"
+
+    def _check(family, name, got, want64, bound, bf=False):
+        """bf: `got` was stored as bf16 -- the dyadic reference is rounded to nearest even, the random bound gains half a bf16 ulp"""
+        if family == "dyadic":
+            _bits(name, got, R.store(want64, bf))
+        else:
+            _within(name, got, want64, bound + (R.half_ulp_bf16(np.abs(want64) + bound) if bf else 0.0))
+
+    return _bits, _within, _check
 
 
-def _rec(key, err, bound):
-    ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))))
-    r = REPORT.setdefault(key, {})
-    r["max_abs_err"] = max(r.get("max_abs_err", 0.0), float(err.max()))
-    r["worst_err_over_bound"] = max(r.get("worst_err_over_bound", 0.0), ratio)
-    _dump()
-    return ratio
-
-
-def _bits(name, got, want64):
-    got64, want64 = np.asarray(got).astype(np.float64), np.asarray(want64, np.float64)
-    got, want = got64.astype(np.float32), want64.astype(np.float32)
-    assert np.array_equal(got.astype(np.float64), got64, equal_nan=True)
-    assert np.array_equal(want.astype(np.float64), want64), f"{name}: the dyadic case is not exact in fp32"
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~((got == 0) & (want == 0))
-    assert not bad.any(), f"{name}: {bad.sum()} of {bad.size} differ, first at {np.argwhere(bad)[0]}: " \
-                          f"{got[bad][0]!r} vs {want[bad][0]!r}"
-    r = REPORT.setdefault(name.split(" ")[0] + "/dyadic", {})
-    r["bit_exact_checks"] = r.get("bit_exact_checks", 0) + 1
-    _dump()
-
-
-def _within(name, got, want64, bound, family="random"):
-    got = np.asarray(got).astype(np.float64)
-    want64 = np.asarray(want64, np.float64)
-    bound = np.broadcast_to(np.asarray(bound, np.float64), want64.shape)
-    assert got.shape == want64.shape, (name, got.shape, want64.shape)
-    assert not np.isnan(got).any(), f"{name}: NaN (an element was not written)"
-    err = np.abs(got - want64)
-    ratio = _rec(name.split(" ")[0] + "/" + family, err, bound)
-    print(f"{name}: max|err| {err.max():.3e}, worst err/bound {ratio:.3f}")
-    assert not (err > bound).any(), f"{name}: {(err > bound).sum()} of {err.size} beyond the bound, worst err/bound {ratio:.3f}"
-
-
-def _check(family, name, got, want64, bound, bf=False):
-    """bf: `got` was stored as bf16 -- the dyadic reference is rounded to nearest even, the random bound gains half a bf16 ulp"""
-    if family == "dyadic":
-        _bits(name, got, R.store(want64, bf))
-    else:
-        _within(name, got, want64, bound + (R.half_ulp_bf16(np.abs(want64) + bound) if bf else 0.0))
+_bits, _within, _check = _parity(REPORT, "eff_parity.json")
 
 
 def _exact(terms, unit):
@@ -690,6 +692,247 @@ def test_se_wgrad(eng, shape, family):
     assert pad.size == (-Cs) % 4 and not pad.view(np.uint32).any(), "pad slots after db1 are not +0"
 
 
+# ---- BN + activation passes --------------------------------------------------------------------------------------------------------
+# (groups, images per group, HW, C) -- Q = C / (4 NV) 16-byte pieces per pixel, NV = 2 when both types are bf16, else 1:
+#  (2, 3, 6, 16)    Q = 4 / 2: tiny, two groups, HW = 6 divides nothing else
+#  (1, 2, 49, 100)  fp32 only (C % 8 != 0).  Q = 25: the rows form runs T = 250 threads (6 idle) and a block covers 4 rows = 1000
+#                   pieces.  2450 pieces = 2 blocks + 450: the last block's first row is full and its second ends at thread 200
+#  (1, 3, 49, 100)  3675 pieces = 3 blocks + 675: ends inside the THIRD row (thread 175): the tail breaks at k = 3
+#  (1, 4, 49, 100)  4900 pieces = 4 blocks + 900: ends inside the FOURTH row (thread 150): no row is skipped, the last is partial
+#  (1, 5, 9, 24)    bf16 only: Q = 3, T = 255, a block covers 1020 pieces; 135 pieces end inside the first row
+#  (1, 19, 9, 24)   bf16 only: 513 pieces end inside the third row (thread 3);  (1, 29, 9, 24): 783 pieces, the fourth (thread 18)
+#                   (`_arm_asserts` holds each of these rows with `_tail_row`)
+#  (3, 1, 5, 672)   Q = 168 > 128 (84 in bf16): one pixel row per block in the rows form and in chan_reduce, 88 idle threads
+#  (1, 2, 4, 1152)  fp32 Q = 288 > 256: the rows form is declined and chan_reduce's threads 0 .. 31 make a second trip over the
+#                   channel pieces; bf16 Q = 144
+#  (2, 4, 64, 32)   256 pixels per group: 4 chan_reduce blocks per group, pixel tiles dealt round-robin
+BN_SHAPES = [(2, 3, 6, 16), (1, 2, 49, 100), (1, 3, 49, 100), (1, 4, 49, 100), (1, 5, 9, 24), (1, 19, 9, 24), (1, 29, 9, 24),
+             (3, 1, 5, 672), (1, 2, 4, 1152), (2, 4, 64, 32)]
+# row of the rows form's last block in which the piece count ends (0 = first), for the shapes whose Q does not divide 256
+TAIL_ROWS = {(1, 2, 49, 100): (25, 1), (1, 3, 49, 100): (25, 2), (1, 4, 49, 100): (25, 3),
+             (1, 5, 9, 24): (3, 0), (1, 19, 9, 24): (3, 2), (1, 29, 9, 24): (3, 3)}
+BN_TYPES = [(F32, F32), (BF16, BF16), (F32, BF16)]
+EW_R = 4
+
+
+def _bn_cases():
+    for k, sh in enumerate(BN_SHAPES):
+        for ty, ta in BN_TYPES:
+            if (ty, ta) == (F32, F32) and sh[3] == 24:
+                continue
+            if (ty, ta) == (BF16, BF16) and sh[3] % 8:
+                continue
+            if (ty, ta) == (F32, BF16) and k not in (0, len(BN_SHAPES) - 1):
+                continue
+            yield pytest.param(sh, ty, ta, id=f"{sh}-{'f32' if ty == F32 else 'bf16'}.{'f32' if ta == F32 else 'bf16'}")
+
+
+def _rows_on(C, ty, ta, mode, bit):
+    """ew_rows_on of effnet.hip restated: the rows form runs when the pass's bit is set in FM_EW_ROWS (both types bf16) /
+    FM_EW_ROWS_F32 (otherwise) and a pixel has 1 .. 256 pieces"""
+    nv = 2 if (ty == BF16 and ta == BF16) else 1
+    Q = C // (4 * nv)
+    return bool(int(mode) & bit) and 1 <= Q <= 256, Q
+
+
+def _tail_row(pix, Q):
+    """row (0 .. EW_R - 1) of the rows form's last block in which the last piece lies, and whether it fills that row"""
+    T = (256 // Q) * Q
+    rem = (pix * Q - 1) % (EW_R * T) + 1
+    return (rem - 1) // T, rem % T == 0
+
+
+def _set_rows(monkeypatch, mode):
+    monkeypatch.setenv("FM_EW_ROWS", mode)
+    monkeypatch.setenv("FM_EW_ROWS_F32", mode)
+
+
+def _arm_asserts(shape, ty, ta, mode, bit):
+    G, ipg, HW, C = shape
+    on, Q = _rows_on(C, ty, ta, mode, bit)
+    assert on == (mode == "3" and Q <= 256)
+    if shape == (1, 2, 4, 1152):
+        assert (Q, on) == ((288, False) if ta == F32 else (144, mode == "3"))
+    if shape in TAIL_ROWS:
+        assert ty == ta and 256 % Q and (Q, _tail_row(ipg * HW, Q)) == (TAIL_ROWS[shape][0], (TAIL_ROWS[shape][1], False))   # ends INSIDE that row
+    if shape == (3, 1, 5, 672) and ta == F32:
+        assert Q == 168 and 256 // Q == 1
+    return on
+
+
+def _bn_operands(family, rs, shape, ty, ta, backward):
+    G, ipg, HW, C = shape
+    n = ipg * HW
+    dy = family == "dyadic"
+    o = {"y": _vals(family, rs, (G, n, C), ty == BF16), "x": _vals(family, rs, (G, n, C), ta == BF16)}       # x: res, or a / dz
+    o["scale"], o["shift"] = _coef(family, rs, (G, C)), _coef(family, rs, (G, C))
+    o["rowscale"] = rs.choice([0.0, 2.0] if dy else [0.0, 1.25], (G, ipg))              # stochastic depth: 0 or 1 / keep
+    if backward:
+        o["mean"], o["istd"] = _coef(family, rs, (G, C)), _coef(family, rs, (G, C), pos=True)
+        o["ca"], o["cb"], o["cc"] = (_coef(family, rs, (G, C)) for _ in range(3))
+        if dy:
+            o["gate"] = np.abs(rs.choice(DYC, (G, ipg, C)))
+            # dsv / HW must be exact: HW a power of two and dsv a multiple of HW / 16; otherwise 0
+            o["dsv"] = rs.choice(DYC, (G, ipg, C)) * HW / 4 if HW & (HW - 1) == 0 else np.zeros((G, ipg, C))
+        else:
+            o["gate"] = R.sigmoid(rs.standard_normal((G, ipg, C))).astype(np.float32).astype(np.float64)
+            o["dsv"] = rs.standard_normal((G, ipg, C)).astype(np.float32).astype(np.float64)
+    return o
+
+
+def _dyh_terms(family, o, shape, a, rowscaled, gated):
+    """(kw of the reference, dyh, its absolute error bound) for the operands o.  d = x gate + dsv (1 / HW): roundings of 1 / HW, the
+    two products and the sum; times swish'(v) (`_swish_grad_err`, v within `_affine_err`), times rowscale: one rounding each"""
+    G, ipg, HW, C = shape
+    sc, sh = (o["scale"], o["shift"]) if not (family == "dyadic" and a == 2) else (np.zeros((G, C)), np.zeros((G, C)))
+    kw = dict(scale=sc, shift=sh, rowscale=o["rowscale"] if rowscaled else None, gate=o["gate"] if gated else None,
+              dsv=o["dsv"] if gated else None)
+    d, e = o["x"], np.zeros_like(o["x"])
+    if gated:
+        g, dv = R._per_pixel(o["gate"], HW), R._per_pixel(o["dsv"], HW) / HW
+        d = o["x"] * g + dv
+        e = U * np.abs(o["x"] * g) + 2 * U * np.abs(dv) + U * np.abs(d)
+    if a == 2:
+        v = o["y"] * sc[:, None, :] + sh[:, None, :]
+        sg = R.swish_grad(v)
+        e = np.abs(sg) * e + np.abs(d) * _swish_grad_err(v, _affine_err(o["y"], sc[:, None, :], sh[:, None, :])) + U * np.abs(d * sg)
+        d = d * sg
+    if rowscaled:
+        r = R._per_pixel(o["rowscale"], HW)
+        d, e = d * r, r * e + U * np.abs(d * r)
+    return kw, sc, sh, d, e
+
+
+@pytest.mark.parametrize("family", ["dyadic", "random"])
+@pytest.mark.parametrize("mode", ["0", "3"], ids=["piece", "rows"])
+@pytest.mark.parametrize("shape,ty,ta", _bn_cases())
+def test_bnact_apply(eng, monkeypatch, shape, ty, ta, mode, family):
+    """out = act(y scale + shift) rowscale[img] + res through k_bnact_apply in the one-piece form (FM_EW_ROWS = FM_EW_ROWS_F32 = 0) and
+    the rows form (3), with and without res and rowscale (0 or 1 / keep), act 0 / 1 / 2 (dyadic: 0 and 1, the affine is exact).
+    Random bound: v within `_affine_err`, swish within `_swish_err`, one rounding for the rowscale product and one for the residual
+    sum (+ half a bf16 ulp for a bf16 out).  Worst ratios: eff_parity.json (bnact_apply/random)."""
+    G, ipg, HW, C = shape
+    _set_rows(monkeypatch, mode)
+    on = _arm_asserts(shape, ty, ta, mode, 1)
+    rs = np.random.RandomState(1000 + C + HW)
+    o = _bn_operands(family, rs, shape, ty, ta, False)
+    d = [ty, ta, G, ipg * HW, HW, C, 0, 0]
+    assert eng.debug_eff_ws("bnact_apply", d) == [0, 0, 0, 0]
+    for a in ((0, 1) if family == "dyadic" else (0, 1, 2)):
+        for with_res, with_rs in ((False, False), (True, False), (False, True), (True, True)):
+            name = f"bnact_apply {shape}{ty}{ta}{'rows' if on else 'piece'} act{a}{'+res' if with_res else ''}{'*rs' if with_rs else ''}"
+            pool = []
+            yb = Buf(eng, o["y"].size, ty == BF16, o["y"], pool)
+            scb, shb = Buf(eng, G * C, False, o["scale"], pool), Buf(eng, G * C, False, o["shift"], pool)
+            rb = Buf(eng, o["x"].size, ta == BF16, o["x"], pool) if with_res else None
+            rsb = Buf(eng, G * ipg, False, o["rowscale"], pool) if with_rs else None
+            ob = Buf(eng, o["y"].size, ta == BF16, pool=pool)
+            d[7] = a
+            eng.debug_eff("bnact_apply", [yb.t, scb.t, shb.t, rb and rb.t, rsb and rsb.t, ob.t], d)
+            _canaries(pool, name)
+            sc, sh = o["scale"][:, None, :], o["shift"][:, None, :]
+            v = o["y"] * sc + sh
+            want = R.bnact_apply(o["y"], o["scale"], o["shift"], HW, a, o["x"] if with_res else None, o["rowscale"] if with_rs else None)
+            dv = _affine_err(o["y"], sc, sh)
+            bound = _swish_err(v, dv) if a == 2 else dv
+            if with_rs:
+                r = R._per_pixel(o["rowscale"], HW)
+                bound = r * bound + U * np.abs(R.act(v, a) * r)
+            if with_res:
+                bound = bound + U * np.abs(want)
+            if family == "dyadic":
+                _exact(np.abs(o["y"]).max() * np.abs(o["scale"]) * 2 + 4, 1 / 16)
+            _check(family, name, ob.np((G, ipg * HW, C)), want, bound, ta == BF16)
+
+
+@pytest.mark.parametrize("family", ["dyadic", "random"])
+@pytest.mark.parametrize("shape,ty,ta", _bn_cases())
+def test_chan_reduce(eng, shape, ty, ta, family):
+    """k_chan_reduce, `part` summed over its bn_bwd_blocks(pix) blocks in float64.  Mode 0: (sum y, sum y^2) over n = pix values: n u
+    sum|y| and (n + 1) u sum y^2.  Mode 1: (sum dyh, sum dyh xhat) with act 0 / 2, with and without rowscale and gate + dsv: n u sum|t|
+    + sum of the terms' errors (`_dyh_terms`; xhat = (y - mean) istd within 2 u |xhat|, the product one more rounding).  Dyadic:
+    act 2 enters with scale = shift = 0 (swish' = 1/2 exactly), dsv only where HW is a power of two.  The size of `part` comes from
+    fm_debug_eff_ws and is asserted against the launch arithmetic.  Worst ratios: eff_parity.json (chan_reduce/random)."""
+    G, ipg, HW, C = shape
+    n = ipg * HW
+    nblk = max(1, min(1024, -(-n // 64)))
+    rs = np.random.RandomState(1100 + C + HW)
+    o = _bn_operands(family, rs, shape, ty, ta, True)
+    d = [ty, ta, G, n, HW, C, 0, 0]
+    ws = eng.debug_eff_ws("chan_reduce", d)
+    assert ws == [G * nblk * 2 * C, 0, 0, 0]
+    tag = f"chan_reduce {shape}{ty}{ta}"
+    pool = []
+    yb = Buf(eng, o["y"].size, ty == BF16, o["y"], pool)
+    pb = Buf(eng, ws[0], pool=pool)
+    eng.debug_eff("chan_reduce", [None, yb.t, None, None, None, None, None, pb.t], d)
+    _canaries(pool, tag)
+    got = pb.np((G, nblk, 2, C)).astype(np.float64).sum(1)
+    ref = R.chan_reduce(o["y"], 0)
+    ay = np.abs(o["y"])
+    if family == "dyadic":
+        _exact(o["y"][0] ** 2, 1 / 4)
+    _check(family, tag + " sum", got[:, 0], ref[:, 0], n * U * ay.sum(1))
+    _check(family, tag + " sumsq", got[:, 1], ref[:, 1], (n + 1) * U * (ay * ay).sum(1))
+    ab = Buf(eng, o["x"].size, ta == BF16, o["x"], pool)
+    vb = {k: Buf(eng, o[k].size, False, o[k], pool) for k in ("mean", "istd", "rowscale", "gate", "dsv")}
+    xh = (o["y"] - o["mean"][:, None, :]) * o["istd"][:, None, :]
+    for a in (0, 2):
+        for rowscaled, gated in ((False, False), (True, False), (False, True), (True, True)):
+            name = f"{tag} act{a}{'*rs' if rowscaled else ''}{'+se' if gated else ''}"
+            kw, sc, sh, t1, e1 = _dyh_terms(family, o, shape, a, rowscaled, gated)
+            scb, shb = Buf(eng, G * C, False, sc, pool), Buf(eng, G * C, False, sh, pool)
+            pb = Buf(eng, ws[0], pool=pool)
+            d[6], d[7] = 1, a
+            eng.debug_eff("chan_reduce", [ab.t, yb.t, vb["mean"].t, vb["istd"].t, scb.t if a == 2 else None, shb.t if a == 2 else None,
+                                          vb["rowscale"].t if rowscaled else None, pb.t, vb["gate"].t if gated else None,
+                                          vb["dsv"].t if gated else None], d)
+            _canaries(pool, name)
+            got = pb.np((G, nblk, 2, C)).astype(np.float64).sum(1)
+            ref = R.chan_reduce(o["y"], 1, HW, a, d=o["x"], mean=o["mean"], istd=o["istd"], **kw)
+            e2 = np.abs(xh) * e1 + np.abs(t1) * 2 * U * np.abs(xh) + U * np.abs(t1 * xh)
+            if family == "dyadic":
+                _exact(t1[0] * np.abs(xh[0]).max(), 2.0 ** -10)
+            _check(family, name + " S1", got[:, 0], ref[:, 0], n * U * np.abs(t1).sum(1) + e1.sum(1))
+            _check(family, name + " S2", got[:, 1], ref[:, 1], n * U * np.abs(t1 * xh).sum(1) + e2.sum(1))
+
+
+@pytest.mark.parametrize("family", ["dyadic", "random"])
+@pytest.mark.parametrize("mode", ["0", "3"], ids=["piece", "rows"])
+@pytest.mark.parametrize("shape,ty,ta", _bn_cases())
+def test_bnact_bwd_apply(eng, monkeypatch, shape, ty, ta, mode, family):
+    """dy = ca dyh + cb y + cc through k_bnact_bwd_apply in both forms, act 0 / 2, with and without rowscale and gate + dsv; dz is
+    stored as the activations are (ta), y and dy as the raw convolution output (ty).  Random bound: |ca| times the error of dyh
+    (`_dyh_terms`) plus 3 u (|ca dyh| + |cb y| + |cc|) for the two products and two sums (+ half a bf16 ulp for a bf16 dy).
+    Worst ratios: eff_parity.json (bnact_bwd_apply/random)."""
+    G, ipg, HW, C = shape
+    _set_rows(monkeypatch, mode)
+    on = _arm_asserts(shape, ty, ta, mode, 2)
+    rs = np.random.RandomState(1200 + C + HW)
+    o = _bn_operands(family, rs, shape, ty, ta, True)
+    d = [ty, ta, G, ipg * HW, HW, C, 0, 0]
+    pool = []
+    zb, yb = Buf(eng, o["x"].size, ta == BF16, o["x"], pool), Buf(eng, o["y"].size, ty == BF16, o["y"], pool)
+    vb = {k: Buf(eng, o[k].size, False, o[k], pool) for k in ("ca", "cb", "cc", "rowscale", "gate", "dsv")}
+    ca, cb, cc = (o[k][:, None, :] for k in ("ca", "cb", "cc"))
+    for a in (0, 2):
+        for rowscaled, gated in ((False, False), (True, False), (False, True), (True, True)):
+            name = f"bnact_bwd_apply {shape}{ty}{ta}{'rows' if on else 'piece'} act{a}{'*rs' if rowscaled else ''}{'+se' if gated else ''}"
+            kw, sc, sh, t1, e1 = _dyh_terms(family, o, shape, a, rowscaled, gated)
+            scb, shb = Buf(eng, G * C, False, sc, pool), Buf(eng, G * C, False, sh, pool)
+            ob = Buf(eng, o["y"].size, ty == BF16, pool=pool)
+            d[7] = a
+            eng.debug_eff("bnact_bwd_apply", [zb.t, yb.t, vb["ca"].t, vb["cb"].t, vb["cc"].t, scb.t if a == 2 else None,
+                                              shb.t if a == 2 else None, vb["rowscale"].t if rowscaled else None, ob.t,
+                                              vb["gate"].t if gated else None, vb["dsv"].t if gated else None], d)
+            _canaries(pool, name)
+            want = R.bnact_bwd_apply(o["x"], o["y"], o["ca"], o["cb"], o["cc"], HW, a, **kw)
+            bound = np.abs(ca) * e1 + 3 * U * (np.abs(ca * t1) + np.abs(cb * o["y"]) + np.abs(cc))
+            if family == "dyadic":
+                _exact(np.abs(ca * t1)[0] + np.abs(cb * o["y"])[0] + np.abs(cc)[0], 2.0 ** -12)
+            _check(family, name, ob.np((G, ipg * HW, C)), want, bound, ty == BF16)
+
+
 # ---- contract -----------------------------------------------------------------------------------------------------------------------
 def test_contract_errors(eng):
     """arguments outside a kernel's contract return FM_ERR_ARG before any launch: the outputs keep their NaN fill"""
@@ -728,7 +971,27 @@ def test_contract_errors(eng):
              ("se_scale", [x.t, None, None, None, y.t], [F32, 1, 4, 8, 1, 1, 0]),
              ("se_bwd_bn1", [None] + [x.t] * 5 + [rec.t] + [x.t] * 4 + [y.t, y.t, y.t, st.t], [F32, 1, 4, 8, 2, 1, 0]),  # dout, no records
              ("se_wgrad", [x.t, x.t, x.t, x.t, rec.t, y.t], [1, 8, 49]),                                              # Cs > 48
-             ("se_wgrad", [x.t, x.t, x.t, x.t, rec.t, None], [1, 8, 2])]
+             ("se_wgrad", [x.t, x.t, x.t, x.t, rec.t, None], [1, 8, 2]),
+             # BN + activation passes: d = {ty, ta, groups, pix_per_group, HW, C, mode, act}; x: 128 elements = 1 x 16 x 8
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [F32, F32, 1, 16, 4, 6, 0, 0]),                          # C % 4
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [BF16, BF16, 1, 8, 4, 12, 0, 0]),                        # both bf16: C % 8
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [F32, F32, 1, 16, 3, 8, 0, 0]),                          # pix % HW
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [BF16, F32, 1, 16, 4, 8, 0, 0]),                         # (bf16, f32)
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [F32, 2, 1, 16, 4, 8, 0, 0]),                            # unknown type
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [F32, F32, 1, 16, 4, 8, 0, 3]),                          # act
+             ("bnact_apply", [x.t, w.t, w.t, None, None, y.t], [F32, F32, 0, 16, 4, 8, 0, 0]),                          # a dimension < 1
+             ("bnact_apply", [x.t, w.t, None, None, None, y.t], [F32, F32, 1, 16, 4, 8, 0, 0]),                         # shift missing
+             ("bnact_apply", [x.t, w.t, w.t, None, None, None], [F32, F32, 1, 16, 4, 8, 0, 0]),                         # out missing
+             ("chan_reduce", [None, x.t, None, None, None, None, None, None], [F32, F32, 1, 16, 4, 8, 0, 0]),           # part missing
+             ("chan_reduce", [None, x.t, w.t, w.t, None, None, None, st.t], [F32, F32, 1, 16, 4, 8, 1, 0]),             # mode 1 without a
+             ("chan_reduce", [x.t, x.t, w.t, w.t, None, None, None, st.t], [F32, F32, 1, 16, 4, 8, 1, 2]),              # act 2, no scale / shift
+             ("chan_reduce", [x.t, x.t, w.t, w.t, None, None, None, st.t], [F32, F32, 1, 16, 4, 8, 1, 1]),              # act 1 in a backward pass
+             ("chan_reduce", [x.t, x.t, w.t, w.t, None, None, None, st.t, x.t, None], [F32, F32, 1, 16, 4, 8, 1, 0]),   # gate without dsv
+             ("chan_reduce", [None, x.t, None, None, None, None, None, st.t], [F32, F32, 1, 16, 4, 8, 2, 0]),           # mode
+             ("bnact_bwd_apply", [x.t, x.t, w.t, w.t, w.t, None, None, None, y.t, None, x.t], [F32, F32, 1, 16, 4, 8, 0, 0]),   # dsv without gate
+             ("bnact_bwd_apply", [x.t, x.t, w.t, w.t, w.t, w.t, None, None, y.t], [F32, F32, 1, 16, 4, 8, 0, 2]),       # act 2, no shift
+             ("bnact_bwd_apply", [x.t, x.t, w.t, w.t, None, None, None, None, y.t], [F32, F32, 1, 16, 4, 8, 0, 0]),     # cc missing
+             ("bnact_bwd_apply", [x.t, x.t, w.t, w.t, w.t, None, None, None, None], [F32, F32, 1, 16, 4, 8, 0, 0])]     # dy missing
     for op, ptrs, d in cases:
         with pytest.raises(FmError, match="bad argument"):
             eng.debug_eff(op, ptrs, d)
@@ -736,6 +999,8 @@ def test_contract_errors(eng):
         eng.debug_eff_ws("dw_wgrad", bad_dims(d7=4))
     with pytest.raises(FmError, match="bad argument"):
         eng.debug_eff_ws("se_fwd", [F32, 1, 0, 8, 2, 1, 0])
+    with pytest.raises(FmError, match="bad argument"):
+        eng.debug_eff_ws("chan_reduce", [F32, F32, 1, 16, 3, 8, 0, 0])
     for b in (y, rec, st):
         assert np.isnan(b.np()).all(), "a refused call launched something"
     _canaries(pool, "contract")

@@ -140,3 +140,68 @@ def test_bf16_helpers():
     assert np.array_equal(R.bf16_round(x), want)                            # ties to even both ways, above a tie, sign, zero
     assert np.array_equal(R.bf16_decode(R.bf16_words(want)).astype(np.float64), want)
     assert R.half_ulp_bf16(1.5) == 2.0 ** -8 and R.half_ulp_bf16(-4.0) == 2.0 ** -6
+
+
+@pytest.mark.parametrize("a", [0, 1, 2])
+@pytest.mark.parametrize("gated", [False, True])
+@pytest.mark.parametrize("rowscaled", [False, True])
+def test_bnact_passes_against_autograd(rowscaled, gated, a):
+    """out = act(bn(y)) rowscale + res with train-mode statistics per group, in float64.  Forward: chan_reduce mode 0 gives the
+    statistics, bnact_apply the output.  Backward: the upstream gradient of out = act(bn(y)) rowscale is `up`; with gate / dsv the
+    loss is sum up (out gate(mean_HW out)) through a small squeeze-excite, gate its forward value and dsv autograd's gradient at the
+    squeeze, and d loss / d y comes from differentiating all of it at once; chan_reduce mode 1
+    gives (S1, S2), bn_bwd_coefficients the (ca, cb, cc) of BatchNorm's backward, bnact_bwd_apply d loss / d y.  The backward passes
+    serve act 0 and 2 only."""
+    G, ipg, HW, C, eps = 2, 3, 5, 8, 1e-3
+    n = ipg * HW
+    rs = np.random.RandomState(40 + a)
+    y, res, up = (rs.standard_normal((G, n, C)) for _ in range(3))
+    gamma, beta = rs.standard_normal(C), rs.standard_normal(C)
+    rowscale = rs.choice([0.0, 1.25], (G, ipg)) if rowscaled else None
+    gate = dsv = None
+    st = R.chan_reduce(y, 0)
+    mean = st[:, 0] / n
+    var = st[:, 1] / n - mean ** 2
+    yt = torch.tensor(y, requires_grad=True)
+    _close("mean", mean, yt.detach().mean(1).numpy())
+    _close("var", var, yt.detach().var(1, unbiased=False).numpy())
+    istd = 1.0 / np.sqrt(var + eps)
+    scale = gamma * istd
+    shift = beta - mean * scale
+    v = (yt - yt.mean(1, keepdim=True)) / torch.sqrt(yt.var(1, unbiased=False, keepdim=True) + eps) * torch.tensor(gamma) + torch.tensor(beta)
+    o = v if a == 0 else (torch.relu(v) if a == 1 else O.swish(v))
+    rs_t = torch.tensor(np.repeat(rowscale, HW, 1)[..., None]) if rowscaled else 1.0
+    out = o * rs_t + torch.tensor(res)
+    _close("apply", R.bnact_apply(y, scale, shift, HW, a, res, rowscale), out.detach().numpy())
+    _close("apply plain", R.bnact_apply(y, scale, shift, HW, a), o.detach().numpy())
+    if a == 1:
+        return
+    d = torch.tensor(up)
+    if gated:
+        # a squeeze-excite forward on out = act(bn(y)) rowscale, differentiated as a whole: gate is its forward value and dsv is
+        # autograd's d loss / d squeeze (the gate path alone, out held constant) -- the fold d gate + dsv / HW is nowhere restated
+        Cs = 3
+        W1, b1, W2t, b2 = (torch.tensor(rs.standard_normal(sh)) for sh in ((Cs, C), (Cs,), (Cs, C), (C,)))
+        gate_of = lambda sq: torch.sigmoid(O.swish(sq @ W1.t() + b1) @ W2t + b2)
+        o_rs = o * rs_t
+        o_img, up_img = o_rs.reshape(G, ipg, HW, C), d.reshape(G, ipg, HW, C)
+        loss = (o_img * gate_of(o_img.mean(2))[:, :, None, :] * up_img).sum()
+        gy, d = torch.autograd.grad(loss, [yt, o_rs])                        # d: the gradient reaching out, both branches
+        sq = o_img.detach().mean(2).requires_grad_(True)
+        dsv, = torch.autograd.grad((o_img.detach() * gate_of(sq)[:, :, None, :] * up_img).sum(), sq)
+        gate, dsv = gate_of(sq).detach().numpy(), dsv.numpy()
+        assert dsv.any() and (gate > 0).all() and (gate < 1).all()
+        yt.grad = gy
+    else:
+        ((o * rs_t) * d).sum().backward()
+    kw = dict(scale=scale, shift=shift, rowscale=rowscale, gate=gate, dsv=dsv)
+    sums = R.chan_reduce(y, 1, HW, a, d=up, mean=mean, istd=istd, **kw)
+    ca, cb, cc = R.bn_bwd_coefficients(sums, np.broadcast_to(gamma, (G, C)), mean, istd, n)
+    _close("bwd_apply", R.bnact_bwd_apply(up, y, ca, cb, cc, HW, a, **kw), yt.grad.numpy())
+    # the sums themselves: d loss / d beta and d loss / d gamma per group
+    vt = v.detach().requires_grad_(True)
+    o2 = vt if a == 0 else O.swish(vt)
+    ((o2 * rs_t) * d).sum().backward()
+    xh = (y - mean[:, None]) * istd[:, None]
+    _close("S1", sums[:, 0], vt.grad.numpy().sum(1))
+    _close("S2", sums[:, 1], (vt.grad.numpy() * xh).sum(1))
