@@ -3411,6 +3411,44 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
     return FM_OK;
 }
 
+int fm_debug_conv_fwd(fm_engine* e, int32_t conv, const float* x_dev, float* out_dev, int32_t imgs, int32_t groups,
+                      const float* scale_dev, const float* shift_dev, const float* res_dev, int32_t act, const float* psc_dev,
+                      const float* psh_dev, const float* gate_dev, float* stats_dev)
+{
+    ARGCHK(e && x_dev && out_dev && conv >= 0 && conv < (int)e->convs.size(), "conv index");
+    ARGCHK(!e->precision, "fm_debug_conv_fwd works on fp32 tensors: create the engine with precision 0");
+    ARGCHK(imgs >= 1 && imgs <= e->maxB && groups >= 1 && imgs % groups == 0, "imgs/groups");
+    ARGCHK(act >= 0 && act <= 2, "act");
+    Conv& c = e->convs[conv];
+    // the three forms the engine's graphs use; everything else would end in conv_fwd's deferred-error branches or in a kernel
+    // instantiation that does not exist
+    ARGCHK(!scale_dev == !shift_dev, "scale and shift come together");
+    ARGCHK(!psc_dev == !psh_dev, "psc and psh come together");
+    const bool epi = scale_dev != nullptr, pro = gate_dev != nullptr;
+    ARGCHK(epi || (!res_dev && act == 0), "res / act belong to the eval epilogue: give scale and shift");
+    ARGCHK(!epi || (!stats_dev && groups == 1), "the eval epilogue runs without statistics on one group");
+    ARGCHK(!(c.cin == 3 && res_dev), "no graph hands a stem a residual (the stem_rows kernel has no such operand)");
+    ARGCHK(pro || !psc_dev, "psc / psh without a gate");
+    if (pro) {
+        ARGCHK(e->model == 1 && c.k == 1 && c.stride == 1 && conv1x1_stream_takes(c.cin_p, c.cout_p, c.cout_p),
+               "an operand prologue needs a 1x1 convolution of an EfficientNet handle that streams through conv1x1.hip");
+        ARGCHK(psc_dev ? (stats_dev && !epi) : !stats_dev,
+               "prologue forms: gate alone without statistics, or psc + psh + gate with statistics and no epilogue");
+    }
+    if (e->planes && c.cin != 3)        // planes mode: the per-tap planes kernel with the operand's planes in the scratch buffer
+        ARGCHK(conv_uses_pconv(e, c, imgs) && (size_t)imgs * c.hin * c.win * c.cin_p * 3 <= e->xp_scratch_elems,
+               "shape outside the planes kernel");
+    if (c.stem3)                // the packed stem reads the framed copy of its [imgs][H][W][3] input
+        k_frame_nhwc3(x_dev, e->x3, imgs, c.hin, c.win, c.Hp, c.Wp, 3, 3, 1, e->main.st, e->stem_rows ? e->x3p : nullptr, e->x3p_plane_elems);
+    ensure_packed(e);
+    const Prologue pr{psc_dev, psh_dev, gate_dev};
+    conv_fwd(e, e->main, conv, e->student, x_dev, out_dev, imgs, groups, scale_dev, shift_dev, res_dev, act,
+             stats_dev ? e->ws_stats : nullptr, pro ? &pr : nullptr);
+    if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
 int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)
 {
     ARGCHK(e && p && d && sc, "null argument");

@@ -648,6 +648,14 @@ class Engine:
         _lib.check(self.lib.fm_debug_conv(self.h, op, conv, _ptr(x), _ptr(dy), _ptr(out), imgs, groups,
                                           _ptr(stats)))
 
+    def debug_conv_fwd(self, conv, x, out, imgs, groups=1, scale=None, shift=None, res=None, act=0, psc=None, psh=None,
+                       gate=None, stats=None):
+        """one convolution forward with the eval epilogue (scale, shift, res, act), the operand prologue of the streaming 1x1
+        kernel (gate, psc, psh) or the train statistics (fm_debug_conv_fwd: the three forms the engine's graphs use)"""
+        self._enqueue()
+        _lib.check(self.lib.fm_debug_conv_fwd(self.h, conv, _ptr(x), _ptr(out), imgs, groups, _ptr(scale), _ptr(shift),
+                                              _ptr(res), int(act), _ptr(psc), _ptr(psh), _ptr(gate), _ptr(stats)))
+
     def debug_block_dgrad(self, block, dy1, dyd, dx, imgs):
         """input gradient of stride-2 basic block `block` from the gradients of its conv1 / downsample outputs (fp32 NHWC)"""
         self._enqueue()

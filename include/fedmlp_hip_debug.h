@@ -32,6 +32,26 @@ int fm_debug_num_convs(fm_engine* e);
 int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, const float* dy_dev,
                   float* out_dev, int32_t imgs, int32_t groups, float* stats_dev);
 
+/* The forward of one convolution with the optional operands the engine's graphs hand to it (a precision-0 handle of either model;
+ * weights are the engine's current state): x[imgs,hin,win,cin_p] -> out[imgs,hout,wout,cout_p].  On an EfficientNet-B0 handle out
+ * (and the dy of fm_debug_conv) carries cout_p channels, the pad channels included; on a ResNet-18 handle cout_p = cout, and the
+ * packed stem is framed as fm_debug_conv frames it.
+ *   epilogue: scale, shift [cout_p], res [imgs,hout,wout,cout_p] | NULL, act 0 none / 1 relu / 2 swish:
+ *             out = act(conv * scale + shift + res)
+ *   prologue: gate [imgs][cin_p], psc, psh [groups][cin_p] | NULL: the operand is x * gate[img], with psc / psh
+ *             swish(x * psc[g] + psh[g]) * gate[img]
+ *   stats:    per-group per-channel (sum, sumsq) [groups][2][cout_p] of the raw convolution, folded as by fm_debug_conv
+ * Exactly the three forms the graphs use are taken:
+ *   plain / train  no epilogue, no prologue, stats optional;
+ *   eval           scale + shift (+ res, act), no stats, groups = 1; may carry the gate-only prologue; no res on a stem;
+ *   prologue       gate alone without stats, or psc + psh + gate with stats and without an epilogue -- on a 1x1 stride-1
+ *                  convolution of an EfficientNet-B0 handle that streams through conv1x1.hip (cin_p <= 256) only.
+ * Anything else (half a pair, res or act without scale / shift, res on a stem, groups > 1 or stats with an epilogue, a prologue on
+ * another conv or on a ResNet-18 handle) returns FM_ERR_ARG before any launch and leaves the handle usable. */
+int fm_debug_conv_fwd(fm_engine* e, int32_t conv, const float* x_dev, float* out_dev, int32_t imgs, int32_t groups,
+                      const float* scale_dev, const float* shift_dev, const float* res_dev, int32_t act, const float* psc_dev,
+                      const float* psh_dev, const float* gate_dev, float* stats_dev);
+
 /* Input gradient of a stride-2 residual block of ResNet-18 (block = index of the basic block: 2, 4, 6), as backward_and_step
  * runs it: dx[imgs,hin,win,cin] = dgrad(conv1; dy1) + dgrad(downsample; dyd), dy1 / dyd [imgs,hout,wout,cout] fp32 NHWC on
  * device.  Planes mode: ONE grouped launch of the per-tap planes kernel (the planes of dy1 / dyd are made inside); every
