@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FEDMLP_HIP_LIB") or os.path.join(_HERE, "libfedmlp_hip.so")
 
 FM_MAX_CLASSES = 32
+FM_MAX_GROUPS = 8
 FM_COMM_ID_BYTES = 128
 
 
@@ -83,6 +84,12 @@ SYMBOLS = {
     "fm_sgd_reset": (C.c_int, [_P, C.POINTER(FmSgd)]),
     "fm_sgd_step": (C.c_int, [_P, C.POINTER(FmSgd)]),
     "fm_adamw_step": (C.c_int, [_P, C.POINTER(FmAdam)]),
+    "fm_set_trainable": (C.c_int, [_P, _P, _I32]),
+    "fm_get_trainable": (C.c_int, [_P, _P, _I32]),
+    "fm_optim_groups": (C.c_int, [_P, _P, _I32, _I32]),
+    "fm_adam_step_groups": (C.c_int, [_P, C.POINTER(FmAdam), _I32]),
+    "fm_adamw_step_groups": (C.c_int, [_P, C.POINTER(FmAdam), _I32]),
+    "fm_sgd_step_groups": (C.c_int, [_P, C.POINTER(FmSgd), _I32]),
     "fm_grad_norm": (C.c_int, [_P, _P]),
     "fm_clip_grad_norm": (C.c_int, [_P, C.c_float, _P]),
     "fm_clip_grad_value": (C.c_int, [_P, C.c_float]),
@@ -115,6 +122,8 @@ SYMBOLS = {
     "fm_debug_proj_bwd": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "fm_debug_exp_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "fm_debug_get_grads": (C.c_int, [_P, _P]),
+    "fm_debug_optim_arena": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I64)]),
+    "fm_debug_entry_spans": (C.c_int, [_P, _P, _I32]),
     "fm_debug_activation": (C.c_int, [_P, _I32, _I32, _I32, _P, C.POINTER(_I32)]),
     "fm_debug_stem_masks": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "fm_debug_lose_part": (C.c_int, [_I32]),

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/fedmlp_hip.h"
@@ -153,6 +154,11 @@ struct Bwd {
     const float* dfeat = nullptr;     // d loss / d feature (caller-owned, or null)
     float* dx[2] = {nullptr, nullptr};    // where d loss / d image of the views goes (null = not wanted: no launch)
     bool step = true;                 // optimizer.step() at the end
+    // per-layer requires_grad (fm_set_trainable): one flag per state entry in reference key order, null = every parameter.
+    // The backward stops behind the first unit (forward order) that has a trainable parameter unless dx is wanted, and inside
+    // the part that runs a frozen conv's weight gradient is not launched where it is a launch of its own.  e->grad then holds
+    // stale values at the frozen entries: the caller masks them (fm_backward_grads_x: k_grad_accumulate_masked)
+    const int32_t* train = nullptr;
 };
 
 struct StateEntry {           // one state_dict entry, in reference key order
@@ -207,6 +213,18 @@ struct fm_engine {
     // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read,
     // `pending_fixed` the mode of the pending forward (its backward takes the same)
     bool bn_freeze = false, pending_fixed = false;
+    // per-layer requires_grad and optimizer parameter groups (autograd path only).  `trainable`: one flag per state entry,
+    // EMPTY = the default mask (every parameter trainable: every code path is then the one it was before masks existed);
+    // `pending_trainable` the mask of the pending forward (its backward takes that one, like pending_fixed).  `group_of`: the
+    // parameter group of each state entry, -1 = not optimized (fm_optim_groups; empty = no table).  The entry / chunk table
+    // of the trainable arena behind both (ensure_opt_table): opt_ent maps a state entry to its index in the table's entry
+    // list (-1: running statistic or counter), ent_at an arena offset to the state entry that starts there
+    std::vector<int32_t> trainable, pending_trainable, group_of;
+    int n_groups = 0;
+    OptChunk* opt_chunks = nullptr;
+    int n_opt_chunks = 0;
+    std::vector<int> opt_ent;
+    std::unordered_map<size_t, int> ent_at;
     std::vector<StateEntry> entries;
     int n_bn_ch = 0;
     size_t NP = 0, NS = 0;            // trainable floats (padded to 4), whole state floats
@@ -1704,6 +1722,130 @@ int grad_norm(fm_engine* e, float* norm)
     return FM_OK;
 }
 
+// ---- per-layer requires_grad, parameter groups ----------------------------------------------------------------------
+// a state entry is a PARAMETER if it is a float entry inside the trainable arena (running statistics and counters are buffers)
+inline bool is_param(const fm_engine* e, const StateEntry& en) { return en.kind != 2 && en.eng_off < e->NP; }
+// The entry / chunk table of the trainable arena: ensure_dist_table's construction restricted to the parameters -- one table
+// entry per parameter in state_dict order, its arena span (a conv weight: its O rows with the row stride, the packed stem's row
+// tails included) cut into chunks of FM_DIST_CHUNK floats, so a chunk never straddles an entry.  Built and uploaded once per
+// engine, at the first fm_set_trainable / fm_optim_groups; plain host code up to the upload.
+int build_opt_table(const std::vector<StateEntry>& entries, size_t NP, std::vector<OptChunk>& chunks, std::vector<int>& opt_ent,
+                    std::unordered_map<size_t, int>& ent_at)
+{
+    chunks.clear(); ent_at.clear();
+    opt_ent.assign(entries.size(), -1);
+    int n_ent = 0;
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const StateEntry& en = entries[i];
+        if (en.kind == 2 || en.eng_off >= NP) continue;
+        long long len = (long long)en.n;
+        if (en.kind == 0) {
+            const long long dense = (long long)en.KH * en.Wpad * en.Ipad, row = en.Ostride ? en.Ostride : dense;
+            len = (en.O - 1) * row + dense;
+        }
+        if (len <= 0 || en.eng_off + (size_t)len > NP) return -1;
+        opt_ent[i] = n_ent;
+        ent_at[en.eng_off] = (int)i;
+        for (long long st = 0; st < len; st += FM_DIST_CHUNK)
+            chunks.push_back({(long long)en.eng_off + st, (int)std::min<long long>(FM_DIST_CHUNK, len - st), n_ent});
+        ++n_ent;
+    }
+    return n_ent;
+}
+int ensure_opt_table(fm_engine* e)
+{
+    if (e->opt_chunks) return FM_OK;
+    std::vector<OptChunk> chunks;
+    const int n_ent = build_opt_table(e->entries, e->NP, chunks, e->opt_ent, e->ent_at);
+    if (n_ent < 0) { g_err = "a parameter entry lies outside the trainable arena"; return FM_ERR_ARG; }
+    if (n_ent > OPT_MAX_ENT) { g_err = "more parameter entries than the optimizer table holds"; return FM_ERR_ARG; }
+    // every offset the backward asks ent_on() about must start a table entry: a layout change fails here, not by quietly
+    // switching truncation and the skipped weight gradients off (checked before anything is allocated)
+    std::vector<size_t> offs = {e->off_fcw, e->off_fcb};
+    for (auto& c : e->convs) offs.push_back(c.w_off);
+    for (auto& b : e->bns) { offs.push_back(e->off_gamma + b.ch_off); offs.push_back(e->off_beta + b.ch_off); }
+    for (auto& m : e->mbs) { offs.push_back(m.dw_off); offs.push_back(m.w1_off); offs.push_back(m.b1_off); offs.push_back(m.w2_off); offs.push_back(m.b2_off); }
+    for (size_t o : offs)
+        if (!e->ent_at.count(o)) { g_err = "a layer's arena offset starts no state entry (optimizer entry table)"; return FM_ERR_ARG; }
+    OptChunk* dc = nullptr;
+    DALLOC(dc, chunks.size());
+    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(OptChunk), hipMemcpyHostToDevice));
+    e->n_opt_chunks = (int)chunks.size();
+    e->opt_chunks = dc;
+    return FM_OK;
+}
+// is the parameter that starts at arena offset `off` trainable under the mask `tr` (null: yes)
+inline bool ent_on(const fm_engine* e, const int32_t* tr, size_t off)
+{
+    if (!tr) return true;
+    const auto it = e->ent_at.find(off);             // (ensure_opt_table checked that every offset asked about resolves)
+    return it == e->ent_at.end() || tr[it->second] != 0;
+}
+inline bool conv_on(const fm_engine* e, const int32_t* tr, int ci) { return ent_on(e, tr, e->convs[ci].w_off); }
+inline bool bn_on(const fm_engine* e, const int32_t* tr, int bi)
+{
+    return ent_on(e, tr, e->off_gamma + e->bns[bi].ch_off) || ent_on(e, tr, e->off_beta + e->bns[bi].ch_off);
+}
+// the launch's selector: the parameter group of every table entry, OPT_SKIP where nobody steps it (no group, or frozen)
+OptSel group_sel(const fm_engine* e)
+{
+    OptSel sel{};
+    for (size_t i = 0; i < e->entries.size(); ++i) {
+        const int t = e->opt_ent[i];
+        if (t < 0) continue;
+        const int g = e->group_of[i];
+        const bool on = g >= 0 && (e->trainable.empty() || e->trainable[i] != 0);
+        opt_sel_set(sel, t, on ? (unsigned)g : OPT_SKIP);
+    }
+    return sel;
+}
+// ... and the masked accumulate's: 0 = trainable, 1 = frozen
+OptSel mask_sel(const fm_engine* e, const int32_t* tr)
+{
+    OptSel sel{};
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        if (e->opt_ent[i] >= 0) opt_sel_set(sel, e->opt_ent[i], tr[i] != 0 ? 0u : 1u);
+    return sel;
+}
+// The grouped steps: hp[i] belongs to group i of fm_optim_groups' table; the scalars torch forms in double are formed per group
+// exactly as adam_step / adamw_step / sgd_step form them.  One step count per engine, as there.
+void adam_step_groups(fm_engine* e, const fm_adam* hp, int n)
+{
+    e->adam_t += 1;
+    OptAdamArgs a{};
+    for (int i = 0; i < n; ++i) {
+        const double bc1 = 1.0 - pow((double)hp[i].beta1, (double)e->adam_t);
+        const double bc2 = 1.0 - pow((double)hp[i].beta2, (double)e->adam_t);
+        a.hp[i] = {hp[i].lr, hp[i].beta1, hp[i].beta2, hp[i].eps, hp[i].weight_decay, (float)bc1, (float)sqrt(bc2)};
+    }
+    k_adam_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    weights_stepped(e);
+}
+void adamw_step_groups(fm_engine* e, const fm_adam* hp, int n)
+{
+    e->adam_t += 1;
+    OptAdamWArgs a{};
+    for (int i = 0; i < n; ++i) {
+        const double bc1 = 1.0 - pow((double)hp[i].beta1, (double)e->adam_t);
+        const double bc2 = 1.0 - pow((double)hp[i].beta2, (double)e->adam_t);
+        a.hp[i] = {(float)(1.0 - (double)hp[i].lr * (double)hp[i].weight_decay), (float)((double)hp[i].lr / bc1), hp[i].beta2, hp[i].eps,
+                   (float)sqrt(bc2), 1.0 - (double)hp[i].beta1};
+    }
+    k_adamw_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    weights_stepped(e);
+}
+void sgd_step_groups(fm_engine* e, const fm_sgd* hp, int n)
+{
+    const bool first = e->adam_t == 0;
+    e->adam_t += 1;
+    OptSgdArgs a{};
+    for (int i = 0; i < n; ++i)
+        a.hp[i] = {(double)hp[i].lr, (double)hp[i].momentum, 1.0 - (double)hp[i].dampening, (double)hp[i].weight_decay,
+                   (hp[i].momentum != 0.f && hp[i].nesterov != 0) ? 1 : 0, hp[i].momentum == 0.f ? 0 : (first ? 1 : 2)};
+    k_sgd_groups(e->student.state, e->gacc, e->adam_m, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    weights_stepped(e);
+}
+
 // Weight gradients on the side lane (side_w; otherwise everything below is a no-op that hands back the main lane).  A weight
 // gradient reads a gradient tensor the main lane's data-gradient chain has just produced, and nothing waits for it before Adam.
 // The tensors are double-buffered by block parity: side_begin records "tensor k of parity par produced" on the main lane, makes
@@ -1750,11 +1892,34 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     unsigned short* PB[2] = {e->GBp, sw ? e->GB2p : e->GBp};
     unsigned short* PC[2] = {e->GCp, sw ? e->GC2p : e->GCp};
     unsigned short* PD[2] = {e->GDp, sw ? e->GD2p : e->GDp};
-    k_fc_bwd(e->dlogits, e->feat, S + e->off_fcw, nullptr, e->grad + e->off_fcw, e->grad + e->off_fcb, e->GA, DT_F32, imgs,
-             512, e->C, cl.hout * cl.wout, L.st, bw.dfeat);
+    // Under a mask (bw.train): units in forward order are the stem (0), the BasicBlocks (1 + b) and fc (nb + 1); `first` is the
+    // first one with a trainable parameter.  Without a wanted dx nothing of a unit before it is enqueued, and a frozen conv's
+    // weight gradient is not launched (nor its side-lane fork opened).  No mask: first = 0, every flag true, the list below
+    // is the one it always was.
+    const int32_t* tr = bw.train;
+    const int nb = (int)e->blocks.size();
+    int first = 0;
+    if (tr && !(bw.dx[0] || bw.dx[1])) {
+        auto blk_live = [&](const Block& k) {
+            return conv_on(e, tr, k.c1) || bn_on(e, tr, k.c1) || conv_on(e, tr, k.c2) || bn_on(e, tr, k.c2) ||
+                   (k.ds >= 0 && (conv_on(e, tr, k.ds) || bn_on(e, tr, k.ds)));
+        };
+        first = nb + 2;
+        if (ent_on(e, tr, e->off_fcw) || ent_on(e, tr, e->off_fcb)) first = nb + 1;
+        for (int b = nb - 1; b >= 0; --b)
+            if (blk_live(e->blocks[b])) first = 1 + b;
+        if (conv_on(e, tr, 0) || bn_on(e, tr, 0)) first = 0;
+    }
+    bool forked = false;               // a weight gradient went to the side lane: join it at the end
+    auto side = [&](int k, int par) -> Lane& { forked = true; return side_begin(e, k, par); };
+    if (first > nb + 1) return;        // nothing is trainable and no dx is wanted
+    e->ctx = 500;
+    { OP(L, "k_fc_bwd"); k_fc_bwd(e->dlogits, e->feat, S + e->off_fcw, nullptr, e->grad + e->off_fcw, e->grad + e->off_fcb, e->GA, DT_F32, imgs,
+             512, e->C, cl.hout * cl.wout, L.st, bw.dfeat); }
     float *ga = e->GA, *ge = e->GE;
-    for (int b = (int)e->blocks.size() - 1; b >= 0; --b) {
+    for (int b = nb - 1; b >= 0 && 1 + b >= first; --b) {
         const Block& blk = e->blocks[b];
+        e->ctx = 400 + b;                          // backward ops @400..@407 (fc @500, stem @399), like EfficientNet's
         const BlockActs& a = A.blk[b];
         const int par = b & 1;
         float *GB = GBp[par], *GC = GCp[par], *GD = GDp[par];
@@ -1765,39 +1930,52 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         // mask of `out` is the sign of its h plane (the last block's `out` is fp32: it feeds the average pool)
         const bool last = b + 1 == (int)e->blocks.size();
         side_guard(e, 0, par);
-        if (pm && !last) bn_bwd(e, L, blk.c2, ga, nullptr, nullptr, ga, groups, B, bw.frozen, false, gbp, a.outp);
-        else bn_bwd(e, L, blk.c2, ga, a.out, pm ? nullptr : GB, ga, groups, B, bw.frozen, false, gbp);
-        if (blk.ds >= 0) { side_guard(e, 1, par); bn_bwd(e, L, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, bw.frozen, false, gcp); }
+        { OP(L, "bn_bwd");
+          if (pm && !last) bn_bwd(e, L, blk.c2, ga, nullptr, nullptr, ga, groups, B, bw.frozen, false, gbp, a.outp);
+          else bn_bwd(e, L, blk.c2, ga, a.out, pm ? nullptr : GB, ga, groups, B, bw.frozen, false, gbp); }
+        if (blk.ds >= 0) { side_guard(e, 1, par); OP(L, "bn_bwd"); bn_bwd(e, L, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, bw.frozen, false, gcp); }
         // Where a weight gradient enters the side stream (round 6): behind the data gradient of the same conv, i.e. beside the
         // NEXT BatchNorm-backward passes of the main stream: a streaming kernel lives beside a GEMM's waves on a CU (the GEMMs leave
         // it the registers since their K-steps run row-major), two GEMMs do not (LDS).  Entering as soon as its dy exists put two
         // GEMMs beside each other and left the BatchNorm-backward passes that follow with nothing beside them.
         side_guard(e, 2, par);
-        conv_dgrad(e, L, blk.c2, GB, GD, imgs, nullptr, false, gbp);
-        conv_wgrad(e, side_begin(e, 0, par), blk.c2, a.z1, GB, imgs, nullptr, 0, pm ? a.z1p : nullptr, gbp);
-        side_end(e, 0, par);
-        if (pm) bn_bwd(e, L, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, bw.frozen, true, gdp, a.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
-        else bn_bwd(e, L, blk.c1, GD, a.z1, GD, nullptr, groups, B, bw.frozen, true);
-        if (blk.ds >= 0) {
-            if (!block_dgrad(e, L, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
-                conv_dgrad(e, L, blk.ds, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
-                conv_dgrad(e, L, blk.c1, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
-            }
-        } else {
-            conv_dgrad(e, L, blk.c1, GD, ge, imgs, ga, false, gdp);
+        { OP(L, "conv_dgrad"); conv_dgrad(e, L, blk.c2, GB, GD, imgs, nullptr, false, gbp); }
+        if (conv_on(e, tr, blk.c2)) {
+            Lane& SL = side(0, par);
+            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.c2, a.z1, GB, imgs, nullptr, 0, pm ? a.z1p : nullptr, gbp); }
+            side_end(e, 0, par);
         }
+        { OP(L, "bn_bwd");
+          if (pm) bn_bwd(e, L, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, bw.frozen, true, gdp, a.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
+          else bn_bwd(e, L, blk.c1, GD, a.z1, GD, nullptr, groups, B, bw.frozen, true); }
+        // (the block the backward stops behind keeps its own data gradient: a unit runs whole or not at all)
+        { OP(L, "conv_dgrad");
+          if (blk.ds >= 0) {
+              if (!block_dgrad(e, L, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
+                  conv_dgrad(e, L, blk.ds, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
+                  conv_dgrad(e, L, blk.c1, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
+              }
+          } else {
+              conv_dgrad(e, L, blk.c1, GD, ge, imgs, ga, false, gdp);
+          } }
         const unsigned short* inp = pm ? (b == 0 ? A.p0p : A.blk[b - 1].outp) : nullptr;
-        conv_wgrad(e, side_begin(e, 2, par), blk.c1, in, GD, imgs, nullptr, 0, inp, gdp);
-        side_end(e, 2, par);
-        if (blk.ds >= 0) {
-            conv_wgrad(e, side_begin(e, 1, par), blk.ds, in, GC, imgs, nullptr, 0, inp, gcp);
+        if (conv_on(e, tr, blk.c1)) {
+            Lane& SL = side(2, par);
+            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.c1, in, GD, imgs, nullptr, 0, inp, gdp); }
+            side_end(e, 2, par);
+        }
+        if (blk.ds >= 0 && conv_on(e, tr, blk.ds)) {
+            Lane& SL = side(1, par);
+            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.ds, in, GC, imgs, nullptr, 0, inp, gcp); }
             side_end(e, 1, par);
         }
         std::swap(ga, ge);
     }
     const Conv& c0 = e->convs[0];
-    {
+    e->ctx = 399;
+    if (first == 0) {
         // max-pool backward + BatchNorm backward of the stem in two passes, without the dense intermediate (elementwise.hip)
+        OP(L, "stem_pool_bn_bwd");
         Bn& b0 = e->bns[0];
         const int pooled_pg = B * (c0.hout / 2) * (c0.wout / 2), pix = B * c0.hout * c0.wout;
         k_stem_pool_bn_reduce(ga, A.p0, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, L.st,
@@ -1807,9 +1985,11 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                           e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
         k_stem_pool_bn_apply(ga, A.p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, L.st);
     }
-    stem_dgrad_views(e, L, e->dyh0, groups, B, bw.dx);
-    conv_wgrad(e, L, 0, e->x4, e->dyh0, imgs);
-    side_join(e);
+    if (first == 0) {
+        if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, e->dyh0, groups, B, bw.dx); }
+        if (conv_on(e, tr, 0)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, 0, e->x4, e->dyh0, imgs); }
+    }
+    if (forked) side_join(e);
     if (bw.step) adam_step(e, e->grad);      // optimizer.step()
 }
 
@@ -2000,14 +2180,39 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     float* Tsm[2] = {e->T_small, sw ? e->T_small2 : e->T_small};
     float* Tmd[2] = {A.T_mid, sw ? e->T_mid2 : A.T_mid};
     float* Tbg[2] = {e->T_big, sw ? e->T_big2 : e->T_big};
+    // Under a mask (bw.train; backward_and_step's note): units in forward order are the stem (0), the MBConv blocks (1 + i), the
+    // head (nm + 1) and _fc (nm + 2).  Weight gradients that are launches of their own -- the pointwise and depthwise ones -- are
+    // skipped for a frozen weight; those that come out of a kernel the data gradient needs (the fused expand / project backward,
+    // BatchNorm's dgamma / dbeta, the squeeze-excite backward) are computed as ever and masked by the caller.
+    const int32_t* tr = bw.train;
+    const int nm = (int)e->mbs.size();
+    int first = 0;
+    if (tr && !(bw.dx[0] || bw.dx[1])) {
+        auto mb_live = [&](const MBConv& m) {
+            return (m.c_exp >= 0 && (conv_on(e, tr, m.c_exp) || bn_on(e, tr, m.bn0))) || ent_on(e, tr, m.dw_off) || bn_on(e, tr, m.bn1) ||
+                   ent_on(e, tr, m.w1_off) || ent_on(e, tr, m.b1_off) || ent_on(e, tr, m.w2_off) || ent_on(e, tr, m.b2_off) ||
+                   conv_on(e, tr, m.c_proj) || bn_on(e, tr, m.bn2);
+        };
+        first = nm + 3;
+        if (ent_on(e, tr, e->off_fcw) || ent_on(e, tr, e->off_fcb)) first = nm + 2;
+        if (conv_on(e, tr, e->c_head) || bn_on(e, tr, e->bn_head)) first = nm + 1;
+        for (int i = nm - 1; i >= 0; --i)
+            if (mb_live(e->mbs[i])) first = 1 + i;
+        if (conv_on(e, tr, e->c_stem) || bn_on(e, tr, e->bn_stem)) first = 0;
+    }
+    bool forked = false;
+    auto side = [&](int k, int par) -> Lane& { forked = true; return side_begin(e, k, par); };
+    if (first > nm + 2) return;        // nothing is trainable and no dx is wanted
     e->ctx = 500;
     { OP(L, "k_fc_bwd"); k_fc_bwd(e->dlogits, h, S + e->off_fcw, e->drop_dev, G + e->off_fcw, G + e->off_fcb, A.T_mid, e->dt, imgs, e->D, e->C,
              HWh, L.st, bw.dfeat); }
+    if (first > nm + 1) return;        // head-only training: _fc's backward and nothing else
     { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_head, A.T_mid, ch.y, A.T_mid, nullptr, groups, B * HWh, HWh, 2, bw.frozen); }
-    { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_head, A.mb.back().out, A.T_mid, imgs); }
+    if (conv_on(e, tr, e->c_head)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_head, A.mb.back().out, A.T_mid, imgs); }
+    if (first > nm) return;
     float *go = e->GA, *gi = e->GB;
     { OP(L, "conv_dgrad"); conv_dgrad(e, L, e->c_head, A.T_mid, go, imgs, nullptr, false); }
-    for (int i = (int)e->mbs.size() - 1; i >= 0; --i) {
+    for (int i = nm - 1; i >= 0 && 1 + i >= first; --i) {
         const MBConv& m = e->mbs[i];
         const MBActs& a = A.mb[i];
         e->ctx = 400 + i;                          // backward ops @400..@415 (head @500, stem @399)
@@ -2055,7 +2260,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                 { OP(L, "k_se_bwd"); k_se_bwd_bn1(nullptr, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
                              S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st, nch5); }
                 {
-                    Lane& SL = side_begin(e, 3, par);
+                    Lane& SL = side(3, par);
                     { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
                     side_end(e, 3, par);
                 }
@@ -2071,8 +2276,8 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         if (!pfused) {
             if (!e->precision && fuse_for(e, m)) soft(e, hipErrorInvalidValue);     // fp32: a_s was not stored for this block and only
                                                                                     // the fused backward can do without it
-            {
-                Lane& SL = side_begin(e, 0, par);
+            if (conv_on(e, tr, m.c_proj)) {
+                Lane& SL = side(0, par);
                 if (fuse_for(e, m)) {      // the project conv's operand a_s was never stored: re-formed from y_d on load
                     const Prologue pro{b1.scale, b1.shift, a.gate};
                     { OP(SL, "proj_wgrad"); conv_wgrad(e, SL, m.c_proj, a.y_d, T_small, imgs, &pro, B * HWo); }
@@ -2088,7 +2293,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
             { OP(L, "k_se_bwd"); k_se_bwd_bn1(T_mid, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
                          S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st); }
             {
-                Lane& SL = side_begin(e, 3, par);
+                Lane& SL = side(3, par);
                 { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
                 side_end(e, 3, par);
             }
@@ -2097,8 +2302,8 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                                          se_bwd_bn1_splits(B)); }   // d y_d
         }
         const float* a_e = m.c_exp >= 0 ? a.a_e : in;
-        {
-            Lane& SL = side_begin(e, 1, par);
+        if (ent_on(e, tr, m.dw_off)) {
+            Lane& SL = side(1, par);
             { OP(SL, "k_dw_wgrad"); k_dw_wgrad(T_mid, a_e, e->dt, SL.ws_slab, G + m.dw_off, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
                        m.pad_t, m.pad_l, SL.st); }
             side_end(e, 1, par);
@@ -2148,8 +2353,8 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                 // (a refused fused launch has left ca / cb / cc and the BN gradients exactly as bnact_bwd is about to)
                 { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn0, T_big, ce.y, T_big, nullptr, groups, B * HWi, HWi, 2, bw.frozen, nullptr, nullptr, -1,
                                              sums ? dw_stats_tiles() : 0); }
-                {
-                    Lane& SL = side_begin(e, 2, par);
+                if (conv_on(e, tr, m.c_exp)) {
+                    Lane& SL = side(2, par);
                     { OP(SL, "exp_wgrad"); conv_wgrad(e, SL, m.c_exp, in, T_big, imgs); }
                     side_end(e, 2, par);
                 }
@@ -2164,10 +2369,12 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     }
     Conv& cs = e->convs[e->c_stem];
     e->ctx = 399;
-    { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2, bw.frozen); }
-    if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, go, groups, B, bw.dx); }
-    { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_stem, e->x4, go, imgs); }
-    side_join(e);                                // every weight gradient is in G before the optimizer reads it
+    if (first == 0) {
+        { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2, bw.frozen); }
+        if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, go, groups, B, bw.dx); }
+        if (conv_on(e, tr, e->c_stem)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_stem, e->x4, go, imgs); }
+    }
+    if (forked) side_join(e);                    // every weight gradient is in G before the optimizer reads it
     if (bw.step) { OP(L, "adam_step"); adam_step(e, e->grad); }
 }
 
@@ -2318,6 +2525,12 @@ ClassVec to_cv(const float* h, int C)
 }
 
 }  // namespace
+
+// what the fused steps answer under a non-default requires_grad mask
+static const char* const kMaskRefusal =
+    "a requires_grad mask is installed and the fused steps train every layer: use the autograd path (fm_forward_train, "
+    "fm_backward_grads, fm_adam_step_groups / fm_adamw_step_groups / fm_sgd_step_groups), or restore the default mask with "
+    "fm_set_trainable";
 
 // =============================== C ABI =======================================
 extern "C" {
@@ -2668,6 +2881,7 @@ int fm_step_bce(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B,
                 int32_t bs_norm, float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && pos_weight_host && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     const float* xs[1] = {x_dev};
     to_nhwc4(e, e->main, xs, 1, B);
@@ -2683,6 +2897,7 @@ int fm_step_stage1(fm_engine* e, const float* x1_dev, const float* x2_dev, const
                    const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, float* loss_dev)
 {
     ARGCHK(e && x1_dev && x2_dev && y_dev && active_mask_host && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
     ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
     int n_neg = 0;
     for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
@@ -2711,6 +2926,7 @@ int fm_step_stage2(fm_engine* e, const float* x_dev, const float* y_dev, const f
                    float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && distill_dev && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     const float* xs[1] = {x_dev};
     to_nhwc4(e, e->main, xs, 1, B);
@@ -2727,6 +2943,7 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
 {
     ARGCHK(e && xw_dev && xs_dev && y_dev && pos_weight_host && pos_weight_unk_host && active_mask_host && loss_dev,
            "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
     ARGCHK(B >= 1 && 2 * B <= e->maxB && B <= 2048, "2*B exceeds max_images");
     int n_neg = 0;
     for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
@@ -2912,6 +3129,7 @@ int fm_forward_train(fm_engine* e, const float* x1_dev, const float* x2_dev, int
     if (logits_dev)
         HIPCHK(hipMemcpyAsync(logits_dev, e->logits, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
     e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
+    e->pending_trainable = e->trainable;
     STEP_DONE(e);
     return FM_OK;
 }
@@ -2932,6 +3150,7 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
 {
     ARGCHK(e && dlogits_dev, "null");
     ARGCHK(e->pending_views > 0, "fm_backward_step without a preceding fm_forward_train");
+    ARGCHK(e->trainable.empty() && e->pending_trainable.empty(), kMaskRefusal);      // the current mask and the pending forward's
     const int views = e->pending_views, B = e->pending_B;
     HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
     Bwd bw;
@@ -2956,14 +3175,25 @@ int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfe
     if (dx1_dev || dx2_dev) {                      // first use: the stem's weights as the data gradient's B matrix
         RCCHK(ensure_stem_dpack(e));
     }
-    if (!e->gacc) DALLOC(e->gacc, e->NP);          // first use: fused-only users never pay for the accumulator
+    if (!e->gacc) {                                // first use: fused-only users never pay for the accumulator
+        DALLOC(e->gacc, e->NP);
+        HIPCHK(hipMemsetAsync(e->gacc, 0, e->NP * 4, e->main.st));     // zeroed at allocation like every arena (padding)
+    }
     const size_t nz = (size_t)views * B * e->C * 4;
     if (dlogits_dev) HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, nz, hipMemcpyDeviceToDevice, e->main.st));
     else HIPCHK(hipMemsetAsync(e->dlogits, 0, nz, e->main.st));
     Bwd bw;
     bw.frozen = e->pending_fixed; bw.dfeat = dfeat_dev; bw.dx[0] = dx1_dev; bw.dx[1] = dx2_dev; bw.step = false;
+    // the mask the pending forward ran under (empty = every parameter: the flat pass, as ever)
+    const bool masked = !e->pending_trainable.empty();
+    if (masked) bw.train = e->pending_trainable.data();
     net_backward_and_step(e, views, B, bw);      // e->grad, every weight gradient joined to the main lane
-    k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->main.st, e->dev_err);
+    // Masking happens IN the copy / accumulate pass: its table-driven form copies or adds the trainable entries' spans, writes
+    // zeros over the frozen ones (stale in e->grad where a launch was skipped) and touches nothing outside the entries (zero
+    // since the accumulator was allocated)
+    if (!masked) k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->main.st, e->dev_err);
+    else k_grad_accumulate_masked(e->gacc, e->grad, e->opt_chunks, e->n_opt_chunks, mask_sel(e, bw.train), !e->gacc_full, e->main.st,
+                                  e->dev_err);
     e->pending_views = 0;
     STEP_DONE(e);
     e->gacc_full = true;
@@ -2979,6 +3209,7 @@ int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev,
     to_nhwc4(e, e->main, xs, views, B);
     net_forward_train(e, views, B, e->bn_freeze ? BnMode::Frozen : BnMode::BatchNoUpdate);
     e->pending_views = views; e->pending_B = B; e->pending_fixed = e->bn_freeze;
+    e->pending_trainable = e->trainable;
     STEP_DONE(e);
     return FM_OK;
 }
@@ -3037,6 +3268,90 @@ int fm_adamw_step(fm_engine* e, const fm_adam* hp)
     ARGCHK(hp->beta1 >= 0.f && hp->beta1 < 1.f && hp->beta2 >= 0.f && hp->beta2 < 1.f, "fm_adamw_step: betas must be in [0, 1)");
     if (!e->gacc_full) return FM_OK;
     adamw_step(e, *hp);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_set_trainable(fm_engine* e, const int32_t* flags, int32_t n_entries)
+{
+    ARGCHK(e && flags, "null");
+    ARGCHK(n_entries == (int32_t)e->entries.size(), "fm_set_trainable: one flag per state entry (fm_state_sizes' entry count)");
+    RCCHK(ensure_opt_table(e));
+    bool all = true;
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        if (is_param(e, e->entries[i]) && !flags[i]) all = false;
+    e->trainable.clear();                          // the default mask is the EMPTY one: nothing then differs from a handle without masks
+    if (!all) {
+        e->trainable.assign(e->entries.size(), 0);
+        for (size_t i = 0; i < e->entries.size(); ++i) e->trainable[i] = is_param(e, e->entries[i]) && flags[i] ? 1 : 0;
+    }
+    return FM_OK;
+}
+
+int fm_get_trainable(fm_engine* e, int32_t* flags, int32_t n_entries)
+{
+    ARGCHK(e && flags, "null");
+    ARGCHK(n_entries == (int32_t)e->entries.size(), "fm_get_trainable: one flag per state entry");
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        flags[i] = is_param(e, e->entries[i]) && (e->trainable.empty() || e->trainable[i]) ? 1 : 0;
+    return FM_OK;
+}
+
+int fm_optim_groups(fm_engine* e, const int32_t* group_of_entry, int32_t n_entries, int32_t n_groups)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(n_groups >= 0 && n_groups <= FM_MAX_GROUPS, "fm_optim_groups: n_groups must be in 0 .. FM_MAX_GROUPS");
+    if (n_groups == 0) { e->group_of.clear(); e->n_groups = 0; return FM_OK; }
+    ARGCHK(group_of_entry && n_entries == (int32_t)e->entries.size(), "fm_optim_groups: one group per state entry");
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        ARGCHK(!is_param(e, e->entries[i]) || (group_of_entry[i] >= -1 && group_of_entry[i] < n_groups),
+               "fm_optim_groups: a group index outside -1 .. n_groups - 1");
+    RCCHK(ensure_opt_table(e));
+    e->group_of.assign(e->entries.size(), -1);
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        if (is_param(e, e->entries[i])) e->group_of[i] = group_of_entry[i];
+    e->n_groups = n_groups;
+    return FM_OK;
+}
+
+int fm_adam_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
+{
+    ARGCHK(e && hp, "null");
+    ARGCHK(n >= 1 && n == e->n_groups, "fm_adam_step_groups: n must be the group count of the installed fm_optim_groups table");
+    for (int i = 0; i < n; ++i) {
+        ARGCHK(hp[i].lr >= 0.f && hp[i].eps >= 0.f && hp[i].weight_decay >= 0.f, "fm_adam_step_groups: lr, eps and weight_decay must be >= 0");
+        ARGCHK(hp[i].beta1 >= 0.f && hp[i].beta1 < 1.f && hp[i].beta2 >= 0.f && hp[i].beta2 < 1.f, "fm_adam_step_groups: betas must be in [0, 1)");
+    }
+    if (!e->gacc_full) return FM_OK;
+    adam_step_groups(e, hp, n);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_adamw_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
+{
+    ARGCHK(e && hp, "null");
+    ARGCHK(n >= 1 && n == e->n_groups, "fm_adamw_step_groups: n must be the group count of the installed fm_optim_groups table");
+    for (int i = 0; i < n; ++i) {
+        ARGCHK(hp[i].lr >= 0.f && hp[i].eps >= 0.f && hp[i].weight_decay >= 0.f, "fm_adamw_step_groups: lr, eps and weight_decay must be >= 0");
+        ARGCHK(hp[i].beta1 >= 0.f && hp[i].beta1 < 1.f && hp[i].beta2 >= 0.f && hp[i].beta2 < 1.f, "fm_adamw_step_groups: betas must be in [0, 1)");
+    }
+    if (!e->gacc_full) return FM_OK;
+    adamw_step_groups(e, hp, n);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_sgd_step_groups(fm_engine* e, const fm_sgd* hp, int32_t n)
+{
+    ARGCHK(e && hp, "null");
+    ARGCHK(n >= 1 && n == e->n_groups, "fm_sgd_step_groups: n must be the group count of the installed fm_optim_groups table");
+    for (int i = 0; i < n; ++i) {
+        const char* bad = sgd_bad(&hp[i]);
+        ARGCHK(!bad, (bad ? bad : ""));
+    }
+    if (!e->gacc_full) return FM_OK;
+    sgd_step_groups(e, hp, n);
     STEP_DONE(e);
     return FM_OK;
 }
@@ -3269,6 +3584,38 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
     ARGCHK(sk > 0, "shape not handled by the fused expand backward");
     k_reduce_slabs(e->main.ws_slab, dw_dev, sk, (int64_t)c.w_numel, e->main.st);
     HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_debug_optim_arena(fm_engine* e, int32_t which, float** dev_ptr, int64_t* numel)
+{
+    ARGCHK(e && dev_ptr && numel && which >= 0 && which <= 2, "null / which");
+    if (which == 2 && !e->gacc) {
+        DALLOC(e->gacc, e->NP);
+        HIPCHK(hipMemsetAsync(e->gacc, 0, e->NP * 4, e->main.st));
+    }
+    *dev_ptr = which == 0 ? e->adam_m : (which == 1 ? e->adam_v : e->gacc);
+    *numel = (int64_t)e->NP;
+    return FM_OK;
+}
+
+int fm_debug_entry_spans(fm_engine* e, int64_t* off_len, int32_t n_entries)
+{
+    ARGCHK(e && off_len && n_entries == (int32_t)e->entries.size(), "null / entry count");
+    RCCHK(ensure_opt_table(e));
+    std::vector<OptChunk> chunks;
+    std::vector<int> ent;
+    std::unordered_map<size_t, int> at;
+    build_opt_table(e->entries, e->NP, chunks, ent, at);
+    for (int32_t i = 0; i < n_entries; ++i) { off_len[2 * i] = -1; off_len[2 * i + 1] = 0; }
+    std::vector<int> of_table(chunks.empty() ? 0 : chunks.back().ent + 1, -1);
+    for (int32_t i = 0; i < n_entries; ++i)
+        if (ent[i] >= 0) of_table[ent[i]] = i;
+    for (const OptChunk& c : chunks) {
+        const int i = of_table[c.ent];
+        if (off_len[2 * i] < 0) off_len[2 * i] = c.begin;
+        off_len[2 * i + 1] += c.len;
+    }
     return FM_OK;
 }
 

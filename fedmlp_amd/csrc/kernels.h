@@ -259,6 +259,33 @@ void k_grad_norm(const float* g, int64_t n, double* part, float* norm, hipStream
 // g *= min(1, max_norm / (*norm + 1e-6)) in fp32; g = clamp(g, -clip, clip)
 void k_grad_clip_norm(float* g, int64_t n, const float* norm, float max_norm, hipStream_t s, const int* skip = nullptr);
 void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int* skip = nullptr);
+// ---- parameter groups and frozen entries (optim.hip): one block per chunk of the trainable arena's entry table -------------
+// OptChunk: <= FM_DIST_CHUNK consecutive arena floats of ONE trainable state entry (index `ent` into the table's entry list).
+// OptSel: four bits per table entry, by value with the launch (no device table to keep in step): the entry's parameter group
+// 0 .. FM_MAX_GROUPS - 1, or OPT_SKIP = nobody steps it (no group, or frozen).  For the masked accumulate: 0 = trainable.
+#define OPT_MAX_ENT 512
+#define OPT_MAX_GROUPS 8
+#define OPT_SKIP 15u
+struct OptChunk { long long begin; int len; int ent; };
+struct OptSel { unsigned w[OPT_MAX_ENT / 8]; };
+static inline void opt_sel_set(OptSel& t, int ent, unsigned v) { t.w[ent >> 3] = (t.w[ent >> 3] & ~(15u << ((ent & 7) * 4))) | (v << ((ent & 7) * 4)); }
+// per-group scalars as the single-group launchers pass them (k_adam / k_adamw / k_sgd's arguments)
+struct OptAdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
+struct OptAdamWHp { float decay, step, b2, eps, bc2_sqrt; double one_minus_b1; };
+struct OptSgdHp { double lr, momentum, one_minus_damp, wd; int nesterov, mode; };     // mode: sgd_kernel's MODE
+struct OptAdamArgs { OptAdamHp hp[OPT_MAX_GROUPS]; };
+struct OptAdamWArgs { OptAdamWHp hp[OPT_MAX_GROUPS]; };
+struct OptSgdArgs { OptSgdHp hp[OPT_MAX_GROUPS]; };
+void k_adam_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                   const OptAdamArgs& a, hipStream_t s, const int* skip);
+void k_adamw_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                    const OptAdamWArgs& a, hipStream_t s, const int* skip);
+void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                  const OptSgdArgs& a, hipStream_t s, const int* skip);
+// the accumulate pass under a mask: a trainable entry's span is copied / added like k_grad_accumulate, a frozen entry's span is
+// written as zeros; floats outside every entry are not touched
+void k_grad_accumulate_masked(float* acc, const float* g, const OptChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
+                              hipStream_t s, const int* skip);
 
 // ---- prototypes / tagging ----------------------------------------------------------
 void k_proto_accumulate(const float* feat, const float* logits, const float* labels, int B, int D, int C,

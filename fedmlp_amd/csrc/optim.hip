@@ -183,3 +183,246 @@ void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int
     const int64_t n4 = n / 4;
     hipLaunchKernelGGL(grad_clip_value_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, g, n4, clip, skip);
 }
+
+// ------------------------------------------- parameter groups, frozen entries --------
+// The three steps again, over the entry table of the trainable arena (engine.hip: ensure_opt_table) instead of the flat arena:
+// one block of 256 threads per chunk of <= FM_DIST_CHUNK floats of ONE state entry, whose parameter group the block fetches
+// once from the launch's own argument block (OptSel: four bits per entry).  An entry nobody steps -- in no group, or frozen --
+// costs its blocks one kernel-argument read: they return before any load.  The hyper-parameters are an argument array of
+// OPT_MAX_GROUPS structs holding what the single-group launchers pass to their kernels, formed the same way on the host.
+//
+// An entry begins at any element offset, so a chunk's first quad starts at the 16-byte boundary at or below `begin`
+// (state_dist_kernel's rule) and that quad -- like the last one -- may hold floats of the neighbouring entry, which belongs to
+// another block and possibly to another group or to nobody.  A block therefore WRITES only its own floats: the first and the
+// last quad of a chunk are stored lane by lane (4-byte stores of the lanes inside [begin, end)), interior quads as 16 bytes.  It
+// still reads and computes whole quads: the neighbour's lanes are computed and dropped.  Floats outside every entry (the gaps
+// between matrices and vectors, a padded BatchNorm vector's tail) are touched by nobody and stay zero; padding inside an entry's
+// span (padded input channels and taps, the packed stem's row tails) is stepped with its entry and stays zero under all three
+// rules (zero weight, zero gradient: DESIGN.md section 1's padding note).
+//
+// The arithmetic per element is adam_kernel's (elementwise.hip), adamw_kernel's and sgd_kernel<MODE>'s above, restated: Adam
+// and SGD on the same expressions, which the compiler contracts alike in both kernels; AdamW with its contraction spelled out
+// (AdamWRule).  tests/test_param_groups_gpu.py compares the bits of every pair.
+// A thread holds OPT_QPT quads of every operand: all its 16-byte loads are in flight before the first use.  A full chunk that
+// starts off a 16-byte boundary has one quad more (2049): thread 0 takes it after the others.
+#define OPT_QPT (FM_DIST_CHUNK / 4 / 256)
+
+__device__ __forceinline__ unsigned opt_sel_get(const OptSel& t, int ent) { return (t.w[ent >> 3] >> ((ent & 7) * 4)) & 15u; }
+
+__device__ __forceinline__ void store_own(float* __restrict__ a, int64_t o, int64_t begin, int64_t end, const f32x4 v)
+{
+    if (o >= begin && o + 4 <= end) {
+        *reinterpret_cast<f32x4*>(a + o) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (o + k >= begin && o + k < end) a[o + k] = v[k];
+    }
+}
+
+struct AdamRule {
+    float* p; const float* g; float* m; float* v;
+    OptAdamArgs a;
+    struct Quad { f32x4 p, g, m, v; };
+    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
+    {
+        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
+        q.m = *reinterpret_cast<const f32x4*>(m + o); q.v = *reinterpret_cast<const f32x4*>(v + o);
+    }
+    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
+    {
+        const float lr = a.hp[gi].lr, b1 = a.hp[gi].b1, b2 = a.hp[gi].b2, eps = a.hp[gi].eps, wd = a.hp[gi].wd;
+        const float bc1 = a.hp[gi].bc1, bc2_sqrt = a.hp[gi].bc2_sqrt;
+        const float step = lr / bc1;
+        f32x4 pp = q.p;
+        f32x4 gg = q.g + wd * pp;
+        f32x4 mm = q.m;
+        f32x4 vv = q.v;
+        mm = mm + (1.f - b1) * (gg - mm);
+        vv = vv * b2 + (1.f - b2) * gg * gg;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
+            pp[k] = pp[k] - step * (mm[k] / den);
+        }
+        q.p = pp; q.m = mm; q.v = vv;
+    }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
+    {
+        store_own(p, o, begin, end, q.p); store_own(m, o, begin, end, q.m); store_own(v, o, begin, end, q.v);
+    }
+};
+
+struct AdamWRule {
+    float* p; const float* g; float* m; float* v;
+    OptAdamWArgs a;
+    struct Quad { f32x4 p, g, m, v; };
+    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
+    {
+        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
+        q.m = *reinterpret_cast<const f32x4*>(m + o); q.v = *reinterpret_cast<const f32x4*>(v + o);
+    }
+    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
+    {
+#pragma clang fp contract(off)
+        const float decay = a.hp[gi].decay, step = a.hp[gi].step, b2 = a.hp[gi].b2, eps = a.hp[gi].eps;
+        const float bc2_sqrt = a.hp[gi].bc2_sqrt;
+        const double one_minus_b1 = a.hp[gi].one_minus_b1;
+        // adamw_kernel's expressions leave the compiler three choices of what to contract (which product of the exp_avg_sq
+        // update joins the addition, and whether p * decay or step * (m / denom) joins the subtraction), and it does not make them
+        // alike in two kernels.  So the choices adamw_kernel's code object holds are spelled out here with contraction off:
+        //   exp_avg_sq = fma(g, (1 - beta2) g, exp_avg_sq beta2);   p = fma(decay, p, -(step (exp_avg / denom)))
+        // and the lerp as there, one fma in double.  tests/test_param_groups_gpu.py holds the two kernels to the same bits.
+        f32x4 pp = q.p;
+        const f32x4 gg = q.g;
+        f32x4 mm = q.m;
+        f32x4 vv = q.v;
+        const float one_minus_b2 = 1.f - b2, nstep = -step;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            vv[k] = __builtin_fmaf(gg[k], one_minus_b2 * gg[k], vv[k] * b2);
+            mm[k] = (float)__builtin_fma(one_minus_b1, (double)gg[k] - (double)mm[k], (double)mm[k]);
+            const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
+            pp[k] = __builtin_fmaf(decay, pp[k], nstep * (mm[k] / den));       // (-step) x = -(step x), signed zeros included
+        }
+        q.p = pp; q.m = mm; q.v = vv;
+    }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
+    {
+        store_own(p, o, begin, end, q.p); store_own(m, o, begin, end, q.m); store_own(v, o, begin, end, q.v);
+    }
+};
+
+template <int MODE>
+__device__ __forceinline__ void sgd_quad(f32x4& pp, const f32x4 gg, f32x4& bb, double lr, double momentum, double one_minus_damp,
+                                         double wd, int nesterov)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double d = (double)gg[k] + wd * (double)pp[k];
+        if (MODE != 0) {
+            const double b = MODE == 1 ? d : momentum * (double)bb[k] + one_minus_damp * d;
+            bb[k] = (float)b;
+            d = nesterov ? d + momentum * b : b;
+        }
+        pp[k] = (float)((double)pp[k] - lr * d);
+    }
+}
+// MODE is a template argument here too: one instantiation of the whole chunk loop per MODE, chosen by the block from its group's
+// mode, so that each keeps sgd_kernel<MODE>'s expression tree (a run-time MODE inside the loop lets the compiler merge the three)
+template <int MODE>
+struct SgdRule {
+    float* p; const float* g; float* buf;
+    const OptSgdArgs& a;
+    struct Quad { f32x4 p, g, b; };
+    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
+    {
+        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
+        q.b = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (MODE == 2) q.b = *reinterpret_cast<const f32x4*>(buf + o);
+    }
+    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
+    {
+        sgd_quad<MODE>(q.p, q.g, q.b, a.hp[gi].lr, a.hp[gi].momentum, a.hp[gi].one_minus_damp, a.hp[gi].wd, a.hp[gi].nesterov);
+    }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
+    {
+        if (MODE != 0) store_own(buf, o, begin, end, q.b);
+        store_own(p, o, begin, end, q.p);
+    }
+};
+
+template <class R>
+__device__ __forceinline__ void opt_chunk(const R& r, const OptChunk ch, unsigned gi)
+{
+    const int64_t begin = ch.begin, end = begin + ch.len;
+    const int64_t o0 = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x;
+    typename R::Quad q[OPT_QPT];
+#pragma unroll
+    for (int j = 0; j < OPT_QPT; ++j) {
+        const int64_t o = o0 + (int64_t)j * 1024;
+        if (o < end) r.load(q[j], o, gi);
+    }
+#pragma unroll
+    for (int j = 0; j < OPT_QPT; ++j) {
+        const int64_t o = o0 + (int64_t)j * 1024;
+        if (o < end) {
+            r.update(q[j], gi);
+            r.store(q[j], o, begin, end, gi);
+        }
+    }
+    const int64_t o = o0 + (int64_t)OPT_QPT * 1024;
+    if (o < end) {
+        typename R::Quad t;
+        r.load(t, o, gi);
+        r.update(t, gi);
+        r.store(t, o, begin, end, gi);
+    }
+}
+template <class R>
+__global__ void __launch_bounds__(256) opt_groups_kernel(const R r, const OptChunk* __restrict__ chunks, const OptSel sel,
+                                                         const int* __restrict__ skip)
+{
+    if (skip && *skip) return;
+    const OptChunk ch = chunks[blockIdx.x];
+    const unsigned gi = opt_sel_get(sel, ch.ent);
+    if (gi >= OPT_MAX_GROUPS) return;             // in no group, or frozen: before any load
+    opt_chunk(r, ch, gi);
+}
+__global__ void __launch_bounds__(256) sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                         const OptSgdArgs a, const OptChunk* __restrict__ chunks, const OptSel sel,
+                                                         const int* __restrict__ skip)
+{
+    if (skip && *skip) return;
+    const OptChunk ch = chunks[blockIdx.x];
+    const unsigned gi = opt_sel_get(sel, ch.ent);
+    if (gi >= OPT_MAX_GROUPS) return;
+    const int mode = a.hp[gi].mode;
+    if (mode == 0) opt_chunk(SgdRule<0>{p, g, buf, a}, ch, gi);
+    else if (mode == 1) opt_chunk(SgdRule<1>{p, g, buf, a}, ch, gi);
+    else opt_chunk(SgdRule<2>{p, g, buf, a}, ch, gi);
+}
+
+void k_adam_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                   const OptAdamArgs& a, hipStream_t s, const int* skip)
+{
+    const AdamRule r{p, g, m, v, a};
+    hipLaunchKernelGGL(opt_groups_kernel<AdamRule>, dim3(n_chunks), dim3(256), 0, s, r, chunks, sel, skip);
+}
+void k_adamw_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                    const OptAdamWArgs& a, hipStream_t s, const int* skip)
+{
+    const AdamWRule r{p, g, m, v, a};
+    hipLaunchKernelGGL(opt_groups_kernel<AdamWRule>, dim3(n_chunks), dim3(256), 0, s, r, chunks, sel, skip);
+}
+void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+                  const OptSgdArgs& a, hipStream_t s, const int* skip)
+{
+    hipLaunchKernelGGL(sgd_groups_kernel, dim3(n_chunks), dim3(256), 0, s, p, g, buf, a, chunks, sel, skip);
+}
+
+// k_grad_accumulate under a mask, over the same table with the same boundary rule: sel = 0 marks a trainable entry (acc = g or
+// acc += g, the flat kernel's one addition), anything else a frozen one, whose span becomes exact zeros in both forms -- whatever
+// e->grad holds there (a skipped weight gradient leaves it stale).
+__global__ void __launch_bounds__(256) grad_accumulate_masked_kernel(float* __restrict__ acc, const float* __restrict__ g,
+                                                                     const OptChunk* __restrict__ chunks, const OptSel sel, int copy,
+                                                                     const int* __restrict__ skip)
+{
+    if (skip && *skip) return;
+    const OptChunk ch = chunks[blockIdx.x];
+    const bool frozen = opt_sel_get(sel, ch.ent) != 0u;
+    const int64_t begin = ch.begin, end = begin + ch.len;
+    for (int64_t o = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x; o < end; o += 1024) {
+        f32x4 r = {0.f, 0.f, 0.f, 0.f};
+        if (!frozen) {
+            const f32x4 gg = *reinterpret_cast<const f32x4*>(g + o);
+            r = copy ? gg : *reinterpret_cast<const f32x4*>(acc + o) + gg;
+        }
+        store_own(acc, o, begin, end, r);
+    }
+}
+void k_grad_accumulate_masked(float* acc, const float* g, const OptChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
+                              hipStream_t s, const int* skip)
+{
+    hipLaunchKernelGGL(grad_accumulate_masked_kernel, dim3(n_chunks), dim3(256), 0, s, acc, g, chunks, sel, copy ? 1 : 0, skip);
+}

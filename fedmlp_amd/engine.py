@@ -426,6 +426,52 @@ class Engine:
         hp = _lib.FmAdam(lr, betas[0], betas[1], eps, weight_decay)
         _lib.check(self.lib.fm_adamw_step(self.h, C.byref(hp)))
 
+    # ---- per-layer requires_grad, optimizer parameter groups (model.HipNet.requires_grad_, fedmlp_amd.optim) --------------
+    def _entry_array(self, values, what):
+        a = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+        n = len(spec.entries(self.model, self.n_classes))
+        if a.size != n:
+            raise ValueError(f"{what}: {a.size} values, the state has {n} entries")
+        return a, n
+
+    def set_trainable(self, flags):
+        """requires_grad of every parameter: one flag per state_dict entry in spec.entries order (buffers' slots are ignored).
+        Read by the NEXT forward_train / forward_recompute -- a backward runs under the mask of the forward it belongs to --
+        and by the grouped optimizer steps.  Under a non-default mask the fused step_* raise."""
+        a, n = self._entry_array(flags, "set_trainable")
+        _lib.check(self.lib.fm_set_trainable(self.h, a.ctypes.data_as(C.c_void_p), n))
+
+    def get_trainable(self):
+        n = len(spec.entries(self.model, self.n_classes))
+        a = np.empty(n, np.int32)
+        _lib.check(self.lib.fm_get_trainable(self.h, a.ctypes.data_as(C.c_void_p), n))
+        return a
+
+    def optim_groups(self, group_of_entry, n_groups):
+        """The parameter group (0 .. n_groups - 1, -1 = not optimized) of every state_dict entry; n_groups = 0 clears the table."""
+        if not n_groups:
+            _lib.check(self.lib.fm_optim_groups(self.h, None, 0, 0))
+            return
+        a, n = self._entry_array(group_of_entry, "optim_groups")
+        _lib.check(self.lib.fm_optim_groups(self.h, a.ctypes.data_as(C.c_void_p), n, int(n_groups)))
+
+    def _step_groups(self, fn, struct, rows):
+        self._check_stream()
+        self._enqueue(weights=True)
+        hp = (struct * len(rows))(*[struct(*r) for r in rows])
+        _lib.check(fn(self.h, hp, len(rows)))
+
+    def adam_step_groups(self, hps):
+        """adam_step with one (lr, betas, eps, weight_decay) per group of the installed optim_groups table."""
+        self._step_groups(self.lib.fm_adam_step_groups, _lib.FmAdam, [(lr, b[0], b[1], eps, wd) for lr, b, eps, wd in hps])
+
+    def adamw_step_groups(self, hps):
+        self._step_groups(self.lib.fm_adamw_step_groups, _lib.FmAdam, [(lr, b[0], b[1], eps, wd) for lr, b, eps, wd in hps])
+
+    def sgd_step_groups(self, hps):
+        """sgd_step with one (lr, momentum, dampening, weight_decay, nesterov) per group."""
+        self._step_groups(self.lib.fm_sgd_step_groups, _lib.FmSgd, [(lr, m, d, wd, int(bool(n))) for lr, m, d, wd, n in hps])
+
     def grad_norm(self):
         """L2 norm of the accumulator as a 0-dim cuda fp32 tensor (0 when it is empty); enqueued, not synchronised."""
         self._check_stream()
@@ -616,6 +662,19 @@ class Engine:
         flat = np.empty(self.nf, np.float32)
         _lib.check(self.lib.fm_debug_get_grads(self.h, flat.ctypes.data_as(C.c_void_p)))
         return flat
+
+    def debug_optim_arena(self, which):
+        """torch view of a raw engine-layout arena of the optimizers: 0 / 1 the moments, 2 the gradient accumulator."""
+        p, n = C.c_void_p(), C.c_int64()
+        _lib.check(self.lib.fm_debug_optim_arena(self.h, int(which), C.byref(p), C.byref(n)))
+        return _device_view(p.value, n.value, self.device)
+
+    def debug_entry_spans(self):
+        """int64 [n_entries, 2]: (arena offset, span floats) of every state_dict entry, (-1, 0) for buffers."""
+        n = len(spec.entries(self.model, self.n_classes))
+        a = np.empty((n, 2), np.int64)
+        _lib.check(self.lib.fm_debug_entry_spans(self.h, a.ctypes.data_as(C.c_void_p), n))
+        return a
 
     def debug_pw(self, op, conv, x, dy, out, imgs, groups=1, psc=None, psh=None, gate=None, stats=None):
         self._enqueue()

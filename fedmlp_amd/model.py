@@ -55,6 +55,7 @@ class _TrainCall(torch.autograd.Function):
     def forward(ctx, anchor, xin, net, eng, x, max_images):
         feat, logits = net._forward_train(eng, x)
         ctx.frozen, ctx.stats_ver = net.bn_frozen, net._stats_ver
+        ctx.mask = net._frozen                   # the requires_grad mask the forward ran under: its backward's, whatever the net says by then
         ctx.set_materialize_grads(False)
         ctx.net, ctx.eng, ctx.x, ctx.max_images = net, eng, x, max_images
         ctx.serial, ctx.key = eng.serial, net._weights_key()
@@ -84,11 +85,13 @@ class _TrainCall(torch.autograd.Function):
                 was = bool(getattr(eng, "bn_frozen", False))
                 if was != ctx.frozen:
                     eng.bn_freeze(ctx.frozen)
+                net._install_mask(eng, ctx.mask)
                 try:
                     eng.forward_recompute(ctx.x)
                 finally:
                     if was != ctx.frozen:
                         eng.bn_freeze(was)
+                    net._install_mask(eng)
             if dx is None:
                 eng.backward_grads(dlogits, dfeat)
             else:
@@ -128,6 +131,7 @@ class HipNet:
         self.precision = "fp32"        # activation storage of the engine this net binds to
         self.bn_frozen = False         # freeze_bn(): train-mode calls apply the BatchNorm running statistics
         self._stats_ver = 0            # bumped by every call that moves the running statistics alone (a batch-statistics net(x))
+        self._frozen = frozenset()     # requires_grad_(False, ...): the frozen parameters' keys (empty = the default mask)
 
     # ---- nn.Module-like surface ----------------------------------------------------------
     def train(self, mode=True):
@@ -144,6 +148,51 @@ class HipNet:
         steps (LocalUpdate.train*, Engine.step_*) are not affected."""
         self.bn_frozen = bool(mode)
         return self
+
+    # ---- per-layer requires_grad -------------------------------------------------------------------
+    def _param_keys(self):
+        """The trainable keys in state_dict order (running statistics and counters are buffers)."""
+        return [k for k, _, _ in spec.entries(self.model, self.n_classes) if spec.is_trainable(k)]
+
+    def _resolve(self, names, what):
+        """Trainable keys named by `names`: state_dict keys or dotted prefixes ("fc", "layer4", "layer3.1.bn2", "_blocks.15");
+        a prefix matches a key equal to it or starting with it + ".".  A name that matches no trainable key raises."""
+        keys = self._param_keys()
+        if isinstance(names, str):
+            names = [names]
+        out = []
+        for name in names:
+            hit = [k for k in keys if k == name or k.startswith(name + ".")]
+            if not hit:
+                raise ValueError(f"{what}: {name!r} names no trainable parameter of {self.model} (buffers -- running statistics and "
+                                 "counters -- are not parameters)")
+            out += [k for k in hit if k not in out]
+        return out
+
+    def requires_grad_(self, flag=True, names=None):
+        """torch's `p.requires_grad_(flag)` for the parameters named by `names` (state_dict keys or dotted prefixes; None =
+        every parameter).  A frozen parameter gets no gradient (net.grads() reports exact zeros) and no optimizer touches it;
+        the backward stops behind the first layer that has a trainable parameter unless x.grad is wanted.  The mask is read
+        by the next train-mode net(x); a pending forward's backward uses the mask it ran under.  BatchNorm running statistics
+        of a frozen layer still move in a batch-statistics forward, as in torch: freeze_bn() is the switch for that."""
+        hit = self._param_keys() if names is None else self._resolve(names, "requires_grad_")
+        self._frozen = frozenset(self._frozen - set(hit) if flag else self._frozen | set(hit))
+        return self
+
+    def trainable(self):
+        """OrderedDict key -> requires_grad over the trainable keys in state_dict order."""
+        return OrderedDict((k, k not in self._frozen) for k in self._param_keys())
+
+    def _entry_flags(self, frozen):
+        return [int(spec.is_trainable(k) and k not in frozen) for k, _, _ in spec.entries(self.model, self.n_classes)]
+
+    def _install_mask(self, eng, frozen=None):
+        """Make `frozen` (default: this net's mask) the engine's requires_grad mask; an engine that never saw a mask is not
+        called while the mask is the default one."""
+        want = self._frozen if frozen is None else frozen
+        if getattr(eng, "_frozen_keys", frozenset()) != want:
+            eng.set_trainable(self._entry_flags(want))
+            eng._frozen_keys = want
 
     def to(self, *a, **k):
         return self
@@ -198,6 +247,7 @@ class HipNet:
         c.default_max_images = self.default_max_images
         c.precision = self.precision
         c.bn_frozen = self.bn_frozen
+        c._frozen = self._frozen
         return c
 
     def __call__(self, x):
@@ -227,6 +277,7 @@ class HipNet:
         was = bool(getattr(eng, "bn_frozen", False))
         if was != self.bn_frozen:
             eng.bn_freeze(self.bn_frozen)
+        self._install_mask(eng)
         try:
             out = eng.forward_train(x)
         finally:
@@ -291,6 +342,7 @@ class HipNet:
             eng.set_state(self.flat, self.counters)
             eng._owner, eng._owner_version, eng._dirty = self, self._version, False
             self._engine = eng
+        self._install_mask(eng)            # the mask belongs to the net, like the state (the fused steps refuse a non-default one)
         return eng
 
     def _pull(self):
@@ -326,12 +378,14 @@ class ResidentNet(HipNet):
         self.precision = engine.precision
         self.bn_frozen = False
         self._stats_ver = 0
+        self._frozen = frozenset()
         self.resident = True
 
     def bind(self, in_h, in_w, max_images, device=None):
         eng = self._engine
         assert (in_h, in_w) == (eng.in_h, eng.in_w) and max_images <= eng.max_images, \
             "resident engine was created for another input size / batch"
+        self._install_mask(eng)
         return eng
 
     def _pull(self):

@@ -14,21 +14,46 @@ Arithmetic: torch's single-tensor updates -- Adam with coupled L2 weight decay (
 torch.nn.utils (fm_clip_grad_norm, fm_clip_grad_value).  One engine holds ONE optimizer's state: a second optimizer on the same
 net resets it at its first step.  state_dict() / load_state_dict() move the moments as flat CUDA tensors in ``net.grads()``
 layout (state_dict order, conv weights OIHW, zeros at the BatchNorm running statistics).
+
+Parameter groups and frozen layers (fine-tuning a pretrained backbone):
+
+    net.requires_grad_(False).requires_grad_(True, ["layer4", "fc"])
+    opt = AdamW(net, lr=1e-3, groups=[{"params": ["fc"]}, {"params": ["layer4"], "lr": 1e-4}])
+
+``groups`` is a list of at most 8 dicts ``{"params": [state_dict keys or dotted prefixes], <overrides of the defaults>}``; a
+parameter named by two groups raises, one named by none is not optimized (both as in torch).  ``param_groups[i]`` is the merged
+dict with "params" resolved to the key list, read on every step.  A frozen parameter (``net.requires_grad_(False, ...)``) is
+skipped by every optimizer -- no update, no weight decay, moments untouched: torch's ``grad is None`` rule -- and its slots of
+the gradient accumulator are exact zeros, so the clips' norm is the norm over the trainable parameters.  With ``groups=None``
+and no frozen parameter the engine calls are the single-group ones (fm_adam_step / fm_adamw_step / fm_sgd_step); otherwise one
+grouped launch (fm_*_step_groups), under a mask with ``groups=None`` over one group of the trainable parameters.
+
+Deviations from torch: the step count stays ONE per engine, not per parameter (a parameter that joins later -- unfrozen, or
+a momentum buffer torch would create at its first gradient -- takes the bias corrections / the later-step SGD form of the
+engine's count); ``requires_grad=False`` does not stop a batch-statistics BatchNorm from updating its running statistics
+(torch's behaviour too): ``net.freeze_bn()`` is the switch for that.
 """
 import torch
 
 
 class _EngineOptimizer:
     """What every optimizer here does around the engine: the bound-engine check, the reset on first use or when the net is
-    bound to another engine, the gradient-owner check, ``param_groups[0]`` read on every step, ``mark_trained``."""
+    bound to another engine, the gradient-owner check, ``param_groups`` read on every step, ``mark_trained``; parameter groups and the
+    frozen-parameter rule (the module docstring)."""
 
     _state_keys = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, net, defaults):
+    MAX_GROUPS = 8                   # FM_MAX_GROUPS
+
+    def __init__(self, net, defaults, groups=None):
         self.net = net
         self.defaults = defaults
         # read on every step, so a caller may change lr between steps (param_groups[0]["lr"] = ...)
-        self.param_groups = [dict(self.defaults)]
+        if groups is None:
+            self.param_groups = [dict(self.defaults)]
+        else:
+            self.param_groups = self._make_groups(groups)
+        self._grouped = groups is not None
         # a fresh torch optimizer: zero moments and step count.  The moments belong to the engine; a net that is not bound
         # yet gets them reset at its first step
         self._engine = None
@@ -36,6 +61,43 @@ class _EngineOptimizer:
         eng = net._bound_engine()
         if eng is not None:
             self._reset(eng)
+
+    def _make_groups(self, groups):
+        name = type(self).__name__
+        groups = list(groups)
+        if not 1 <= len(groups) <= self.MAX_GROUPS:
+            raise ValueError(f"{name}: 1 to {self.MAX_GROUPS} parameter groups are supported, got {len(groups)}")
+        out, seen = [], set()
+        for i, g in enumerate(groups):
+            if not isinstance(g, dict) or "params" not in g:
+                raise ValueError(f"{name}: parameter group {i} must be a dict with a 'params' list of keys or prefixes")
+            unknown = set(g) - set(self.defaults) - {"params"}
+            if unknown:
+                raise ValueError(f"{name}: parameter group {i} has unknown options {sorted(unknown)}")
+            keys = self.net._resolve(g["params"], f"{name} parameter group {i}")
+            twice = [k for k in keys if k in seen]
+            if twice:
+                raise ValueError(f"{name}: some parameters appear in more than one parameter group: {twice[:4]}")
+            seen.update(keys)
+            merged = dict(self.defaults)
+            merged.update({k: v for k, v in g.items() if k != "params"})
+            if "betas" in merged:
+                merged["betas"] = tuple(merged["betas"])
+            merged["params"] = keys
+            self._check(merged)
+            out.append(merged)
+        return out
+
+    def _group_of_entry(self):
+        """(group of every state_dict entry: -1 = not optimized, group count).  groups=None under a mask: one group whose
+        members are the trainable parameters."""
+        from . import spec
+        keys = [k for k, _, _ in spec.entries(self.net.model, self.net.n_classes)]
+        if not self._grouped:
+            frozen = self.net._frozen
+            return tuple(0 if spec.is_trainable(k) and k not in frozen else -1 for k in keys), 1
+        of = {k: i for i, g in enumerate(self.param_groups) for k in g["params"]}
+        return tuple(of.get(k, -1) for k in keys), len(self.param_groups)
 
     def _reset(self, eng):
         self._engine_reset(eng, self.param_groups[0])
@@ -62,7 +124,17 @@ class _EngineOptimizer:
         eng = self._bound("step")
         if getattr(eng, "_grad_owner", None) is not self.net:
             return                      # no gradients: torch skips parameters whose .grad is None
-        self._engine_step(eng, self.param_groups[0])
+        self.net._install_mask(eng)       # a frozen parameter is skipped: the grouped steps read the engine's mask
+        if not self._grouped and not self.net._frozen:
+            self._engine_step(eng, self.param_groups[0])
+        else:
+            table = self._group_of_entry()
+            if getattr(eng, "_groups_key", None) != table:
+                eng.optim_groups(*table)
+                eng._groups_key = table
+            for g in self.param_groups:
+                self._check(g)
+            self._engine_step_groups(eng, self.param_groups)
         self.net.mark_trained()
 
     def state_dict(self):
@@ -91,9 +163,14 @@ class _EngineOptimizer:
             tensors.append(t.clone())
         groups = sd.get("param_groups")
         if groups:
-            if len(groups) != 1:
-                raise ValueError(f"{type(self).__name__}.load_state_dict: one parameter group is supported, got {len(groups)}")
-            self.param_groups = [dict(groups[0])]
+            if len(groups) != len(self.param_groups):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: the state has {len(groups)} parameter groups, this "
+                                 f"optimizer has {len(self.param_groups)}")
+            for i, (g, mine) in enumerate(zip(groups, self.param_groups)):
+                if list(g.get("params", ())) != list(mine.get("params", ())):
+                    raise ValueError(f"{type(self).__name__}.load_state_dict: parameter group {i} names other parameters than "
+                                     "this optimizer's")
+            self.param_groups = [dict(g) for g in groups]
         # installed when the engine holds the net (now, or at the next step)
         self._pending_state = (int(state["step"]), tuple(tensors))
         if self.net._bound_engine() is not None:
@@ -101,10 +178,15 @@ class _EngineOptimizer:
 
 
 class Adam(_EngineOptimizer):
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"Adam: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
-        super().__init__(net, {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay})
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, groups=None):
+        defaults = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay}
+        self._check(defaults)
+        _EngineOptimizer.__init__(self, net, defaults, groups)
+
+    def _check(self, g):
+        lr, betas, eps, wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        if lr < 0.0 or eps < 0.0 or wd < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"{type(self).__name__}: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={wd}")
 
     def _engine_reset(self, eng, g):
         eng.adam_reset(g["lr"], g["betas"], g["eps"], g["weight_decay"])
@@ -112,17 +194,21 @@ class Adam(_EngineOptimizer):
     def _engine_step(self, eng, g):
         eng.adam_step(g["lr"], g["betas"], g["eps"], g["weight_decay"])
 
+    def _engine_step_groups(self, eng, groups):
+        eng.adam_step_groups([(g["lr"], g["betas"], g["eps"], g["weight_decay"]) for g in groups])
+
 
 class AdamW(Adam):
     """torch.optim.AdamW: p *= 1 - lr * weight_decay, then Adam's update with no L2 term in the gradient."""
 
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"AdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
-        _EngineOptimizer.__init__(self, net, {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay})
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None):
+        Adam.__init__(self, net, lr, betas, eps, weight_decay, groups)
 
     def _engine_step(self, eng, g):
         eng.adamw_step(g["lr"], g["betas"], g["eps"], g["weight_decay"])
+
+    def _engine_step_groups(self, eng, groups):
+        eng.adamw_step_groups([(g["lr"], g["betas"], g["eps"], g["weight_decay"]) for g in groups])
 
 
 class SGD(_EngineOptimizer):
@@ -130,19 +216,26 @@ class SGD(_EngineOptimizer):
 
     _state_keys = ("momentum_buffer",)
 
-    def __init__(self, net, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False):
+    def __init__(self, net, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, groups=None):
+        defaults = {"lr": lr, "momentum": momentum, "dampening": dampening, "weight_decay": weight_decay, "nesterov": bool(nesterov)}
+        self._check(defaults)
+        super().__init__(net, defaults, groups)
+
+    def _check(self, g):
+        lr, momentum, weight_decay = g["lr"], g["momentum"], g["weight_decay"]
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError(f"SGD: invalid hyper-parameters lr={lr} momentum={momentum} weight_decay={weight_decay}")
-        if nesterov and (momentum <= 0 or dampening != 0):
+        if g["nesterov"] and (momentum <= 0 or g["dampening"] != 0):
             raise ValueError("SGD: Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(net, {"lr": lr, "momentum": momentum, "dampening": dampening, "weight_decay": weight_decay,
-                               "nesterov": bool(nesterov)})
 
     def _engine_reset(self, eng, g):
         eng.sgd_reset(g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"])
 
     def _engine_step(self, eng, g):
         eng.sgd_step(g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"])
+
+    def _engine_step_groups(self, eng, groups):
+        eng.sgd_step_groups([(g["lr"], g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"]) for g in groups])
 
 
 def _grad_engine(net):

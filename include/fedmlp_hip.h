@@ -357,6 +357,35 @@ int fm_clip_grad_norm(fm_engine* e, float max_norm, float* norm_dev);
 int fm_clip_grad_value(fm_engine* e, float clip);
 int fm_optim_get_state(fm_engine* e, float* m_dev, float* v_dev, int64_t* step_host);
 int fm_optim_set_state(fm_engine* e, const float* m_dev, const float* v_dev, int64_t step);
+/* ---- per-layer requires_grad and optimizer parameter groups (autograd path) ------------------------------
+ * One int32 per STATE ENTRY in reference key order (the order of fm_get_state / the state_dict: conv and linear weights,
+ * biases, BatchNorm weight / bias / running_mean / running_var / num_batches_tracked); entries that are running
+ * statistics or counters are buffers and their slots are ignored.  n_entries must be the entry count.
+ * fm_set_trainable / fm_get_trainable: the requires_grad flag of every parameter (default: all ones).  The pending forward
+ *   remembers the mask it ran under, like the BatchNorm mode.  Under a non-default mask fm_backward_grads(_x):
+ *   - leave exact zeros at the frozen parameters' spans of the accumulator (copy and add form alike), and the same bits
+ *     as an all-trainable backward at the trainable ones;
+ *   - with no dx wanted, stop behind the first unit in forward order that has a trainable parameter (ResNet-18: stem,
+ *     layer1.0 .. layer4.1, fc; EfficientNet-B0: stem, _blocks.0 .. _blocks.15, head, _fc): nothing of an earlier unit is
+ *     enqueued, and head-only training is the classifier's backward alone;
+ *   - do not launch a frozen convolution's weight gradient where it is a launch of its own.
+ *   The fused fm_step_* and fm_backward_step train every layer: under a non-default mask they return FM_ERR_ARG.  With the
+ *   default mask everything is launch for launch what it is without these calls.
+ *   A frozen parameter still sees its BatchNorm running statistics move in a batch-statistics forward (torch's behaviour):
+ *   fm_bn_freeze is the switch for that.
+ * fm_optim_groups: the parameter group of every parameter, 0 .. n_groups - 1, or -1 = not optimized; n_groups <=
+ *   FM_MAX_GROUPS; n_groups = 0 clears the table.
+ * fm_adam_step_groups / fm_adamw_step_groups / fm_sgd_step_groups: fm_adam_step / fm_adamw_step / fm_sgd_step with hp[i] the
+ *   hyper-parameters of group i (n = the table's group count): one launch over the parameters' entry table, the same
+ *   arithmetic per element to the bit.  A parameter in no group or frozen is not touched: no update, no weight decay,
+ *   moments as they were (torch: .grad is None).  One step count per handle, whatever the groups. */
+#define FM_MAX_GROUPS 8
+int fm_set_trainable(fm_engine* e, const int32_t* flags, int32_t n_entries);
+int fm_get_trainable(fm_engine* e, int32_t* flags, int32_t n_entries);
+int fm_optim_groups(fm_engine* e, const int32_t* group_of_entry, int32_t n_entries, int32_t n_groups);
+int fm_adam_step_groups(fm_engine* e, const fm_adam* hp, int32_t n);
+int fm_adamw_step_groups(fm_engine* e, const fm_adam* hp, int32_t n);
+int fm_sgd_step_groups(fm_engine* e, const fm_sgd* hp, int32_t n);
 /* teacher <- w_teacher*teacher + w_student*student over every state entry (train_RSCFed's EMA,
  * utils/local_training.py:751-759, weights 0.999 / 0.001). */
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student);

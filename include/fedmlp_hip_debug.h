@@ -110,6 +110,13 @@ int fm_debug_lose_part(int32_t on);
 
 /* Gradients of the last step in state_dict order (running-stat slots are 0). */
 int fm_debug_get_grads(fm_engine* e, float* host_f32);
+/* The raw engine-layout arenas behind the optimizers (NP floats each, layout padding included; the trainable part of
+ * fm_state_device's layout): which = 0 first moment, 1 second moment, 2 the gradient accumulator (allocated if it was not). */
+int fm_debug_optim_arena(fm_engine* e, int32_t which, float** dev_ptr, int64_t* numel);
+/* The entry table of the grouped optimizer steps and the masked accumulate: off_len[2 i] = arena offset, off_len[2 i + 1] =
+ * span length in floats of state entry i (reference key order), summed over its chunks; -1 / 0 for running statistics and
+ * counters.  Floats of the trainable arena outside every span are layout gaps nobody writes. */
+int fm_debug_entry_spans(fm_engine* e, int64_t* off_len, int32_t n_entries);
 
 /* One launcher of csrc/kernels.h -- the BatchNorm, stem max-pool and plane-writer kernels between ResNet-18's conv GEMMs
  * (elementwise.hip, planes_ew.hip, the two plane converters of pconv.hip) -- on caller-supplied device tensors, on the handle's
