@@ -73,6 +73,7 @@ SYMBOLS = {
                                       C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "fm_augment": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, _P]),
     "fm_augment_strong": (C.c_int, [_P, _P, _P, _P, _P, _I32, _F, _F, _P]),
+    "fm_eval_metrics": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_float, _P, _P, _P]),
     "fm_forward_train": (C.c_int, [_P, _P, _P, _I32, _P, _P]),
     "fm_backward_step": (C.c_int, [_P, _P]),
     "fm_backward_grads": (C.c_int, [_P, _P, _P]),

@@ -210,6 +210,8 @@ struct fm_engine {
     double* dist_part = nullptr;
     int dist_n_ent = 0, dist_n_chunks = 0;
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
+    uint8_t* metrics_ws = nullptr;    // fm_eval_metrics' workspace (class-major scores, chunk counts, partials): grows on demand
+    size_t metrics_ws_bytes = 0;
     // frozen BatchNorm statistics (fm_bn_freeze): `bn_freeze` is the handle flag fm_forward_train / fm_forward_recompute read,
     // `pending_fixed` the mode of the pending forward (its backward takes the same)
     bool bn_freeze = false, pending_fixed = false;
@@ -3112,6 +3114,30 @@ int fm_augment_strong(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx
     if (!e->strong_ws) DALLOC(e->strong_ws, fm_strong_ws_bytes(e->maxB, e->H, e->W));    // first use: weak-only users never pay for it
     k_augment_strong(cache_dev, idx_dev, params_dev, strong_dev, e->strong_ws, e->maxB, out_dev, B, e->H, e->W, mean_host[0],
                      mean_host[1], mean_host[2], std_host[0], std_host[1], std_host[2], e->main.st);
+    return FM_OK;
+}
+
+int fm_eval_metrics(fm_engine* e, const float* scores_dev, const float* labels_dev, int64_t N, int32_t C, float threshold,
+                    double* ap_dev, double* auc_dev, int64_t* counts_dev)
+{
+    ARGCHK(e && scores_dev && labels_dev, "null argument");
+    ARGCHK(C >= 1 && C <= FM_MAX_CLASSES, "fm_eval_metrics: 1 <= C <= FM_MAX_CLASSES");
+    ARGCHK(N >= 1 && N <= ((int64_t)1 << 22), "fm_eval_metrics: 1 <= N <= 2^22");
+    if (!ap_dev && !auc_dev && !counts_dev) return FM_OK;
+    const size_t need = fm_metrics_ws_bytes(N, C);
+    if (e->metrics_ws_bytes < need) {
+        if (e->metrics_ws) {            // the outgrown workspace goes back now (the stream may still read it)
+            HIPCHK(hipStreamSynchronize(e->main.st));
+            auto it = std::find(e->allocs.begin(), e->allocs.end(), (void*)e->metrics_ws);
+            if (it != e->allocs.end()) e->allocs.erase(it);
+            (void)hipFree(e->metrics_ws);
+            e->metrics_ws = nullptr; e->metrics_ws_bytes = 0;
+        }
+        DALLOC(e->metrics_ws, need);
+        e->metrics_ws_bytes = need;
+    }
+    k_eval_metrics(scores_dev, labels_dev, N, C, threshold, e->metrics_ws, ap_dev, auc_dev, counts_dev, e->main.st);
+    HIPCHK(hipGetLastError());
     return FM_OK;
 }
 

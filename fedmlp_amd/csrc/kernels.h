@@ -71,6 +71,15 @@ struct DistChunk { int entry, start; };
 void k_state_dist(const FoldArgs& a, int K, const float* ref, const DistEntry* ent, int n_entries, const DistChunk* chunks,
                   int n_chunks, int64_t NS, double* part, float* norms, hipStream_t s);
 
+// metrics.hip: globaltest's per-class metrics of fp32 [N][C] scores / labels (include/fedmlp_hip.h, fm_eval_metrics).
+// ws = fm_metrics_ws_bytes(N, C) bytes, 16-byte aligned; rank = false forms the counts only (ap / auc are then ignored).
+#define FM_METRICS_ROWS 64       // rows of one count / scatter chunk: one wave
+#define FM_METRICS_BP 256        // positives of one pair-pass block: one per thread
+#define FM_METRICS_TILE 2048     // scores of one LDS tile of the pair pass
+size_t fm_metrics_ws_bytes(int64_t N, int C);
+void k_eval_metrics(const float* scores, const float* labels, int64_t N, int C, float threshold, void* ws, double* ap, double* auc,
+                    int64_t* counts, hipStream_t s);
+
 // ---- input pipeline: uint8 HBM cache -> augmented, normalised fp32 NCHW batch.
 // params[b] = {c0, c1, c2, c3, c4, c5 (Pillow's 16.16 fixed-point inverse affine), flip, unused}; nearest sampling,
 // fill 0, then horizontal flip, /255, (v-mean)/std   (dataset/dataset.py:40-53 pipeline)

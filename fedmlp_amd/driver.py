@@ -50,6 +50,10 @@ def args_parser():
     p.add_argument("--augment", type=int, default=0,
                    help="1: uint8 HBM cache + per-sample RandomAffine/HFlip/Normalize kernel (dataset/dataset.py:40-53); "
                         "2: the same with the FixMatch pair (:63-77): image_aug_2 is weak + RandAugmentMC(2, 10) + cutout")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="globaltest of the new global model every K rounds (main.py:322-357 uses 10), the forward dealt over "
+                        "the ranks and the metrics from fm_eval_metrics; 0 = never")
+    p.add_argument("--n_test", type=int, default=1024, help="samples of the synthetic test set (--eval_every)")
     return p.parse_args()
 
 
@@ -81,6 +85,54 @@ class DeviceDataset:
 
     def device_views(self, device):
         return self._v
+
+
+class ShardedTestSet:
+    """The synthetic test set of --eval_every: generated in fixed blocks of `bs` rows, block b from the seed (seed, b), so
+    the data does not depend on the world size; the labels of every block are kept on the host (they are small), the images
+    of the blocks b % world == rank in HBM.  With world = 1 it is a whole dataset (globaltest takes it)."""
+
+    def __init__(self, n, C, hw, seed, bs, rank, world, device, p_pos=0.3):
+        self.bs, self.rank, self.world = int(bs), rank, world
+        self.blocks, targets = {}, []
+        for b, i in enumerate(range(0, n, self.bs)):
+            rows = min(self.bs, n - i)
+            g = torch.Generator().manual_seed(int(seed) * 1000003 + b)
+            targets.append((torch.rand((rows, C), generator=g) < p_pos).float().numpy())
+            if b % world == rank:
+                gd = torch.Generator(device=device).manual_seed(int(seed) * 1000003 + b)
+                self.blocks[b] = torch.randn((rows, 3, hw, hw), device=device, generator=gd)
+        self.targets = np.concatenate(targets, 0)
+
+    def __len__(self):
+        return len(self.targets)
+
+    def block_of(self, rows):
+        """the images of the consecutive rows `rows`, which are one of this rank's blocks"""
+        x = self.blocks[rows[0] // self.bs]
+        assert rows[0] % self.bs == 0 and len(rows) == x.shape[0]
+        return x
+
+    def __getitem__(self, i):
+        return {"image": self.blocks[i // self.bs][i % self.bs], "target": self.targets[i].copy(), "index": i}
+
+    def device_views(self, device):
+        assert self.world == 1, "a shard is not a whole dataset"
+        if getattr(self, "_v", None) is None:
+            self._v = {"image": torch.cat([self.blocks[b] for b in sorted(self.blocks)], 0)}
+        return self._v
+
+
+def evaluate_sharded(net, eng, test, C, rank, world, dev):
+    """globaltest of the engine's resident model on a ShardedTestSet: every rank forwards its blocks, one all-reduce
+    completes the [n, C] probabilities, fm_eval_metrics ranks them -> main.py:326-331's seven numbers as floats."""
+    from fedmlp_amd.evaluations import multilabel_metrics_device, sharded_probs
+    was = net.training
+    net.eval()
+    probs = sharded_probs(lambda rows: net(test.block_of(rows))[1], len(test), C, rank, world, test.bs, dev)
+    net.train(was)
+    targets = torch.from_numpy(np.ascontiguousarray(test.targets, dtype=np.float32)).to(dev)
+    return {k: float(v) for k, v in multilabel_metrics_device(eng, targets, probs).items()}
 
 
 class RoundAccumulator:
@@ -186,6 +238,9 @@ def main():
         pos = [np.where(ds.targets[:, k] == 1)[0] for k in range(C)]
         a = argparse.Namespace(**vars(args))
         clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C])
+    test = None
+    if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
+        test = ShardedTestSet(args.n_test, C, args.hw, args.seed + 500, 4 * args.batch_size, rank, world, dev)
     tao, Prototype = [0] * C, None
     log = []
     for rnd in range(args.rounds_warmup):
@@ -212,10 +267,19 @@ def main():
         glob.copy_(eng.state_tensor())
         if tao_new is not None:
             tao, Prototype = tao_new, proto_new
+        metrics = None
+        if test is not None and (rnd + 1) % args.eval_every == 0:     # globaltest of the new netglob (main.py:322-331)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            metrics = evaluate_sharded(net, eng, test, C, rank, world, dev)
+            eval_sec = time.perf_counter() - t1
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"round": rnd, "sec": round(dt, 3), "mean_loss": float(np.mean(losses)) if losses else None,
                "samples_per_sec_per_gpu": round(len(mine) * args.n_local / dt, 1)}
+        if metrics is not None:
+            rec["test"] = metrics
+            rec["eval_sec"] = round(eval_sec, 3)
         if rank == 0:
             print(json.dumps(rec), flush=True)
             if args.save_every and (rnd + 1) % args.save_every == 0:     # torch.save(netglob.state_dict(), ...) main.py:237

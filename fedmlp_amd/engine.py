@@ -379,6 +379,30 @@ class Engine:
     def zero_grad(self):
         _lib.check(self.lib.fm_zero_grad(self.h))
 
+    def eval_metrics(self, scores, labels, threshold=0.5, ap=True, auc=True, counts=True):
+        """globaltest's per-class metrics on the device (fm_eval_metrics): scores, labels contiguous fp32 [N, C] device
+        tensors -> (ap [C] fp64, auc [C] fp64, counts [C, 4] int64 {tp, npos, npred, tn} with pred = score > threshold) as
+        device tensors; enqueued, not synchronised.  ap / auc / counts False: that output is not computed and comes back as
+        None (counts alone skips the ranking passes)."""
+        for name, t in (("scores", scores), ("labels", labels)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
+                    or t.device.index != torch.cuda.current_device() or t.dim() != 2):
+                raise ValueError(f"eval_metrics: {name} must be a contiguous fp32 [N, C] tensor on {self.device}")
+        if scores.shape != labels.shape:
+            raise ValueError(f"eval_metrics: scores {tuple(scores.shape)} and labels {tuple(labels.shape)} differ")
+        N, Cn = int(scores.shape[0]), int(scores.shape[1])
+        if not (1 <= Cn <= _lib.FM_MAX_CLASSES and 1 <= N <= 1 << 22):
+            raise ValueError(f"eval_metrics: N = {N}, C = {Cn}: 1 <= C <= {_lib.FM_MAX_CLASSES}, 1 <= N <= 2^22")
+        self._check_stream()
+        self._enqueue()
+        o_ap = torch.empty(Cn, device=self.device, dtype=torch.float64) if ap else None
+        o_auc = torch.empty(Cn, device=self.device, dtype=torch.float64) if auc else None
+        o_cnt = torch.empty((Cn, 4), device=self.device, dtype=torch.int64) if counts else None
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+        _lib.check(self.lib.fm_eval_metrics(self.h, vp(scores), vp(labels), N, Cn, float(threshold), vp(o_ap), vp(o_auc),
+                                            vp(o_cnt)))
+        return o_ap, o_auc, o_cnt
+
     def bn_freeze(self, on=True):
         """Frozen BatchNorm statistics for the NEXT forward_train / forward_recompute (kept until changed): every BatchNorm
         applies its running statistics, which -- like the num_batches_tracked counters -- stay as they are.  A backward runs

@@ -276,6 +276,21 @@ int fm_augment(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, c
 int fm_augment_strong(fm_engine* e, const uint8_t* cache_dev, const int32_t* idx_dev, const int32_t* params_dev,
                       const int32_t* strong_dev, int32_t B, const float* mean_host, const float* std_host, float* out_dev);
 
+/* ---- evaluation metrics on the device ----------------------------------------------------- */
+/* globaltest's metrics (utils/evaluations.py:41-66, utils/multilabel_metrixs.py) on device tensors.
+ * scores_dev, labels_dev: fp32 [N][C] row-major, contiguous; a label is positive iff != 0.
+ * ap_dev[C], auc_dev[C]: fp64; counts_dev[C][4]: int64 {tp, npos, npred, tn} with pred = score > threshold.
+ * Any output pointer may be NULL (that part is skipped).  Enqueued on the engine's stream, no host
+ * synchronisation, no atomics, bit-identical from run to run.  1 <= C <= FM_MAX_CLASSES, 1 <= N <= 2^22.
+ * Workspace belongs to the handle and grows on demand (like fm_augment_strong's).
+ * Per class, with P positives and Nn = N - P negatives, and IEEE fp32 compares on the scores:
+ *   AP  = ( sum over positives i of (double)#{j positive : s_j >= s_i} / (double)#{j : s_j >= s_i} ) / P
+ *   AUC = (double)( sum over positives i of 2 #{j negative : s_j < s_i} + #{j negative : s_j == s_i} ) / (2.0 P Nn)
+ * which are sklearn's average_precision_score and auc(roc_curve(...)) with every tie grouped.  P = 0: AP = AUC = NaN;
+ * Nn = 0: AUC = NaN, AP = 1 (fedmlp_amd/evaluations.py's host functions).  NaN scores are outside the contract. */
+int fm_eval_metrics(fm_engine* e, const float* scores_dev, const float* labels_dev, int64_t N, int32_t C,
+                    float threshold, double* ap_dev, double* auc_dev, int64_t* counts_dev);
+
 /* ---- generic train step (the other baselines of main.py's --exp switch) -----
  * train_RSCFed (utils/local_training.py:705-769), train_FedNoRo (:115-234) and train_CBAFed
  * (:236-342) differ from the steps above only in the loss head on the [B,C] logits.  The split
