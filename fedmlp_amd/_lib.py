@@ -63,6 +63,10 @@ SYMBOLS = {
     "fm_step_stage1": (C.c_int, [_P, _P, _P, _P, _I32, _F, _I32, _I32, _P]),
     "fm_step_stage2": (C.c_int, [_P, _P, _P, _P, _I32, _P]),
     "fm_step_fixmatch": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, _F, _I32, _I32, _P]),
+    "fm_loss_fedlsr": (C.c_int, [_P, _P, _P, _F, C.c_float, C.c_float, _I32, _P, _P]),
+    "fm_loss_fedirm_sup": (C.c_int, [_P, _P, _P, _F, _F, _I32, _I32, _I32, _P, _P, _P]),
+    "fm_loss_fedirm_rel": (C.c_int, [_P, _P, _P, _P, _F, _F, _I32, _I32, C.c_float, _P, _I32, _P, _P, _P]),
+    "fm_step_fedlsr": (C.c_int, [_P, _P, _P, _P, _I32, _F, C.c_float, C.c_float, _P]),
     "fm_proto_reset": (C.c_int, [_P]),
     "fm_proto_accumulate": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, C.c_float, C.c_float]),
     "fm_proto_finalize": (C.c_int, [_P, _I32, _I64, _F, _P, _P]),
@@ -99,6 +103,7 @@ SYMBOLS = {
     "fm_bn_freeze": (C.c_int, [_P, _I32]),
     "fm_bn_frozen": (C.c_int, [_P]),
     "fm_teacher_axpby": (C.c_int, [_P, C.c_float, C.c_float]),
+    "fm_teacher_ema_params": (C.c_int, [_P, C.c_double]),
     "fm_teacher_swap": (C.c_int, [_P]),
     "fm_set_stochastic": (C.c_int, [_P, _P, _P]),
     "fm_feature_dim": (C.c_int, [_P]),

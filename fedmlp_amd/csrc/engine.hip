@@ -2960,6 +2960,64 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
     return FM_OK;
 }
 
+// ---- FedLSR / FedIRM: the heads alone on caller tensors, and the fused FedLSR step ----
+int fm_loss_fedlsr(fm_engine* e, const float* z_dev, const float* y_dev, const float* pos_weight_host, float mix1, float beta,
+                   int32_t B, float* dz_dev, float* loss_dev)
+{
+    ARGCHK(e && z_dev && y_dev && pos_weight_host && dz_dev && loss_dev, "null");
+    ARGCHK(B >= 1, "B >= 1");
+    ARGCHK(mix1 >= 0.f && mix1 <= 1.f, "fm_loss_fedlsr: mix1 in [0, 1]");
+    k_loss_fedlsr(z_dev, y_dev, to_cv(pos_weight_host, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, dz_dev, loss_dev,
+                  e->main.st);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_loss_fedirm_sup(fm_engine* e, const float* z_dev, const float* y_dev, const float* pos_weight_host,
+                       const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, int32_t B, float* rel_acc_dev,
+                       float* dz_dev, float* loss_dev)
+{
+    ARGCHK(e && z_dev && y_dev && pos_weight_host && active_mask_host && dz_dev && loss_dev, "null");
+    ARGCHK(B >= 1 && annotation_num >= 1 && bs_norm >= 1 && (int64_t)bs_norm * annotation_num < (1 << 24),
+           "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24");
+    k_loss_fedirm_sup(z_dev, y_dev, to_cv(pos_weight_host, e->C), to_cv(active_mask_host, e->C), B, e->C,
+                      (float)bs_norm * (float)annotation_num, rel_acc_dev, dz_dev, loss_dev, e->main.st);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_loss_fedirm_rel(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* pos_weight_host,
+                       const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, float cw, const float* target_dev,
+                       int32_t B, float* rel_acc_dev, float* dz_dev, float* loss_dev)
+{
+    ARGCHK(e && z_dev && zt_dev && y_dev && pos_weight_host && active_mask_host && target_dev && dz_dev && loss_dev, "null");
+    ARGCHK(B >= 1 && annotation_num >= 1 && bs_norm >= 1 && (int64_t)bs_norm * annotation_num < (1 << 24),
+           "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24");
+    ARGCHK(B <= 2048, "fm_loss_fedirm_rel: B <= 2048 (the selected-row table)");
+    k_loss_fedirm_rel(z_dev, zt_dev, y_dev, to_cv(pos_weight_host, e->C), to_cv(active_mask_host, e->C), B, e->C,
+                      (float)bs_norm * (float)annotation_num, (float)bs_norm, cw, target_dev, rel_acc_dev, dz_dev,
+                      loss_dev, e->main.st);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_step_fedlsr(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
+                   const float* pos_weight_host, float mix1, float beta, float* loss_dev)
+{
+    ARGCHK(e && x1_dev && x2_dev && y_dev && pos_weight_host && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
+    ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
+    ARGCHK(mix1 >= 0.f && mix1 <= 1.f, "fm_step_fedlsr: mix1 in [0, 1]");
+    const float* xs[2] = {x1_dev, x2_dev};
+    to_nhwc4(e, e->main, xs, 2, B);
+    net_forward_train(e, 2, B);
+    k_loss_fedlsr(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, e->dlogits,
+                  loss_dev, e->main.st);
+    net_backward_and_step(e, 2, B);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
 int fm_proto_reset(fm_engine* e)
 {
     ARGCHK(e, "null engine");
@@ -3446,6 +3504,18 @@ int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
         e->teacher.counters[i] = (int64_t)(w_teacher * (float)e->teacher.counters[i] + w_student * (float)e->student.counters[i]);
     e->teacher.ev_dirty = true;
     e->twb_dirty = true;
+    return FM_OK;
+}
+
+int fm_teacher_ema_params(fm_engine* e, double alpha)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(alpha >= 0.0 && alpha <= 1.0, "fm_teacher_ema_params: alpha in [0, 1]");
+    // the trainable part of the arena only: running statistics (behind NP) and the counters stay as they are
+    k_axpby(e->teacher.state, e->student.state, (float)alpha, (float)(1.0 - alpha), (int64_t)e->NP, e->main.st);
+    e->teacher.ev_dirty = true;
+    e->twb_dirty = true;
+    HIPCHK(hipGetLastError());
     return FM_OK;
 }
 

@@ -7,6 +7,8 @@
 //   stage-1 BCE-on-probabilities(active) + MSE-to-teacher(missing)    (:937-963, FedNoRo.py:22)
 //   stage-2 masked BCE-on-probabilities                               (:1183-1188)
 //   FixMatch weak/strong loss                                         (:797-815)
+//   FedLSR mixed-prediction BCE + beta JS, two views                  (:1258-1269, 1294-1314)
+//   FedIRM supervised / relation-phase heads, relation matrices       (:73-113, 370-376, 421-452)
 //   prototype masked sums + confident-count t                         (:985-994, 1229-1238)
 //   CosineSimilarityFast difference                                   (:1417-1435, 1056-1057)
 //   stable top-k / bottom-k                                           (utils/utils.py:24-35)
@@ -275,6 +277,245 @@ void k_loss_fixmatch(const float* z, const float* y, ClassVec pos_w, ClassVec po
 {
     hipLaunchKernelGGL(loss_fixmatch_kernel, dim3(1), dim3(256), 0, s, z, y, pos_w, pos_wu, active, B, C, n_neg,
                        inv_sup, n_cls_minus_ann, dz, loss);
+}
+
+// ------------------------------------------------------------ FedLSR / FedIRM heads ---
+// Two-view heads of train_FedLSR (utils/local_training.py:1294-1314) and train_FedIRM (:370-376, 421-452).  z [2B][C]: view 1
+// rows, then view 2 rows (fm_forward_train's layout); every element of dz [2B][C] is written.  One block, no atomics.  The
+// gradients are fp32 like every head's.  The loss VALUE is formed and summed in double (per thread, then a fixed tree) and
+// rounded once: it costs a few microseconds of a step and makes the reported scalar the correctly rounded one.  The C x C
+// relation sums are fp32, folded in LDS in a fixed order; the quotient and sigmoid on top of them (C x C values) are double.
+__device__ __forceinline__ double sigmoid_d(double z) { return 1.0 / (1.0 + exp(-z)); }
+// value of BCEWithLogits(pos_weight) in double (bce_logits' formula)
+__device__ __forceinline__ double bce_logits_d(double z, float y, float pw)
+{
+    const double lw = 1.0 + ((double)pw - 1.0) * (double)y;
+    return (1.0 - (double)y) * z + lw * (log1p(exp(-fabs(z))) + fmax(-z, 0.0));
+}
+__device__ __forceinline__ double block_sum_d(double v, double* sh /*[4]*/)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// FedLSR: mean BCEWithLogits(pos_weight)(pred_mix, y) + beta JS(q1, q2), both means over the B C elements.
+//   p = mix1 s1 + mix2 s2, pred_mix = sigmoid(2 log(p / (1 - p))) = p^2 / (p^2 + (1 - p)^2), fed to the criterion as a LOGIT
+//   (the reference does); d pred_mix / dp = 2 p (1 - p) / (p^2 + (1 - p)^2)^2.
+//   q_v = clamp(sigmoid(3 z_v), 1e-6, 1), m = (q1 + q2) / 2, JS element = (q1 log(q1 / m) + q2 log(q2 / m)) / 2,
+//   d / d q_v = log(q_v / m) / 2 (the m terms cancel); the clamp passes no gradient below 1e-6.
+// The one deviation from torch's fp32 autograd: the rational form of pred_mix, with 1 - p formed as mix1 sigmoid(-z1) +
+// mix2 sigmoid(-z2), stays finite where p rounds to 1 (torch forms 0 * inf in log(p / (1 - p)) and returns NaN); the derivative
+// tends to 0 there.
+__global__ void loss_fedlsr_kernel(const float* __restrict__ z, const float* __restrict__ y, ClassVec pw, int B, int C,
+                                   float mix1, float mix2, float beta, float* __restrict__ dz, float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    const int n = B * C;
+    const float inv_n = 1.f / (float)n;
+    double ce = 0.0, js = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float z1 = z[i], z2 = z[n + i];
+        const float s1 = sigmoidf_(z1), s2 = sigmoidf_(z2), o1 = sigmoidf_(-z1), o2 = sigmoidf_(-z2);
+        const float p = mix1 * s1 + mix2 * s2, q = mix1 * o1 + mix2 * o2;      // q = 1 - p without the cancellation
+        const float den = p * p + q * q;                                       // >= 1/2 up to rounding: never 0
+        const float pm = p * p / den;
+        float g;
+        bce_logits(pm, y[i], pw.v[i % C], &g);
+        const float dp = g * (2.f * p * q / (den * den)) * inv_n;
+        const float a1 = sigmoidf_(3.f * z1), a2 = sigmoidf_(3.f * z2);
+        const float c1 = fmaxf(a1, 1e-6f), c2 = fmaxf(a2, 1e-6f);              // the upper clamp at 1 never binds
+        const float m = 0.5f * (c1 + c2);
+        const float l1 = logf(c1 / m), l2 = logf(c2 / m);
+        {                                                                      // the value, in double
+            const double S1 = sigmoid_d(z1), S2 = sigmoid_d(z2);
+            const double P = (double)mix1 * S1 + (double)mix2 * S2, Q = (double)mix1 * (1.0 - S1) + (double)mix2 * (1.0 - S2);
+            ce += bce_logits_d(P * P / (P * P + Q * Q), y[i], pw.v[i % C]);
+            const double C1 = fmax(sigmoid_d(3.0 * z1), 1e-6), C2 = fmax(sigmoid_d(3.0 * z2), 1e-6), M = 0.5 * (C1 + C2);
+            js += 0.5 * (C1 * log(C1 / M) + C2 * log(C2 / M));
+        }
+        const float k = 0.5f * beta * inv_n;
+        const float d1 = a1 >= 1e-6f ? k * l1 * 3.f * a1 * sigmoidf_(-3.f * z1) : 0.f;
+        const float d2 = a2 >= 1e-6f ? k * l2 * 3.f * a2 * sigmoidf_(-3.f * z2) : 0.f;
+        dz[i] = dp * mix1 * s1 * o1 + d1;
+        dz[n + i] = dp * mix2 * s2 * o2 + d2;
+    }
+    const double t1 = block_sum_d(ce, shd);
+    const double t2 = block_sum_d(js, shd);
+    if (threadIdx.x == 0) *loss = (float)((t1 + (double)beta * t2) / (double)n);
+}
+void k_loss_fedlsr(const float* z, const float* y, ClassVec pos_w, int B, int C, float mix1, float mix2, float beta, float* dz,
+                   float* loss, hipStream_t s)
+{
+    hipLaunchKernelGGL(loss_fedlsr_kernel, dim3(1), dim3(256), 0, s, z, y, pos_w, B, C, mix1, mix2, beta, dz, loss);
+}
+
+// get_confuse_matrix (:73-81) for C classes (the reference hard-codes 8: identical at C = 8): row i, column j of the matrix is
+// sigmoid((sum_b z1[b][j] lab[b][i]) / (sum_b lab[b][i] + 1e-8) / 2).  PSEUDO: lab[b][i] = sel[b] && sigmoid(z1[b][i]) > 0.5
+// (the relation phase's pseudo-labels over the selected rows), else lab = y.  The 256 threads take min(C C, 256) pairs at a
+// time; with fewer pairs than threads the rows b are dealt to 256 / pairs lanes and folded in lane order through LDS.
+// emit(pair, sum, count) runs in one thread per pair.  Block-uniform control flow (barriers inside).
+// one element of the relation matrix from its fp32 sums: the denominator is the fp32 sum + 1e-8 as the reference forms it
+__device__ __forceinline__ float relation_prob(float S, float N) { return (float)sigmoid_d((double)S / (double)(N + 1e-8f) / 2.0); }
+
+template <bool PSEUDO, typename Emit>
+__device__ __forceinline__ void relation_sums(const float* __restrict__ z1, const float* __restrict__ y,
+                                              const unsigned char* sel, int B, int C, float* red_s, float* red_n, Emit emit)
+{
+    const int P = C * C, Pc = P < 256 ? P : 256, L = 256 / Pc;
+    const int pl = threadIdx.x % Pc, bl = threadIdx.x / Pc;
+    for (int pair0 = 0; pair0 < P; pair0 += Pc) {
+        const int pair = pair0 + pl;
+        float s = 0.f, n = 0.f;
+        if (bl < L && pair < P) {
+            const int i = pair / C, j = pair % C;
+            for (int b = bl; b < B; b += L) {
+                float lab;
+                if (PSEUDO) lab = (sel[b] && sigmoidf_(z1[b * C + i]) > 0.5f) ? 1.f : 0.f;
+                else lab = y[b * C + i];
+                s += z1[b * C + j] * lab;
+                n += lab;
+            }
+        }
+        red_s[threadIdx.x] = s;
+        red_n[threadIdx.x] = n;
+        __syncthreads();
+        if (bl == 0 && pair < P) {
+            float S = red_s[pl], N = red_n[pl];
+            for (int l = 1; l < L; ++l) { S += red_s[l * Pc + pl]; N += red_n[l * Pc + pl]; }
+            emit(pair, S, N);
+        }
+        __syncthreads();
+    }
+}
+
+// FedIRM, supervised phase: sum over both views and the active classes of BCEWithLogits(pos_weight)(z_v, y) / sup_norm;
+// rel_acc (may be null) += get_confuse_matrix(z_1, y), which carries no gradient
+__global__ void loss_fedirm_sup_kernel(const float* __restrict__ z, const float* __restrict__ y, ClassVec pw, ClassVec active,
+                                       int B, int C, float sup_norm, float* __restrict__ rel_acc, float* __restrict__ dz,
+                                       float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    __shared__ float red_s[256], red_n[256];
+    const float inv_sup = 1.f / sup_norm;               // sup_norm = bs_norm annotation_num, an integer held exactly
+    double sup = 0.0;
+    for (int i = threadIdx.x; i < 2 * B * C; i += 256) {
+        const int c = i % C, row = i / C;
+        const int yr = row < B ? row : row - B;
+        float d = 0.f;
+        if (active.v[c] != 0.f) {
+            bce_logits(z[i], y[yr * C + c], pw.v[c], &d);
+            sup += bce_logits_d(z[i], y[yr * C + c], pw.v[c]);
+            d *= inv_sup;
+        }
+        dz[i] = d;
+    }
+    if (rel_acc)
+        relation_sums<false>(z, y, nullptr, B, C, red_s, red_n,
+                             [&](int pair, float S, float N) { rel_acc[pair] += relation_prob(S, N); });
+    const double tot = block_sum_d(sup, shd);
+    if (threadIdx.x == 0) *loss = (float)(tot / (double)sup_norm);
+}
+void k_loss_fedirm_sup(const float* z, const float* y, ClassVec pos_w, ClassVec active, int B, int C, float sup_norm,
+                       float* rel_acc, float* dz, float* loss, hipStream_t s)
+{
+    hipLaunchKernelGGL(loss_fedirm_sup_kernel, dim3(1), dim3(256), 0, s, z, y, pos_w, active, B, C, sup_norm, rel_acc, dz, loss);
+}
+
+// FedIRM, relation phase: the supervised term + cw sum (sigmoid z_1 - sigmoid z_t)^2 / bs_norm + cw kd(Q, T).
+//   selected rows (:426-433): every probability of the row > 0.7 or < 0.3, and -sum_c (p log(p + 1e-6) + (1 - p) log(1 - p + 1e-6)) < 2;
+//   Q = get_confuse_matrix(z_1[selected], sigmoid(z_1)[selected] > 0.5); no row selected: Q = 0.5 and no kd gradient
+//   (decided here, on the device); kd (:109-113) = sum_ij (T - Q)(log T - log Q) / (2 C), both kl_div terms 'batchmean' over C rows;
+//   d kd / d Q = (log(Q / T) + 1 - T / Q) / (2 C), d Q_ij / d z_1[b][j] = Q (1 - Q) / 2 lab[b][i] / (n_i + 1e-8).
+// The selection and the pseudo-labels carry no gradient; zt [B][C] gets none.  rel_acc (may be null) += get_confuse_matrix(z_1, y).
+__global__ void loss_fedirm_rel_kernel(const float* __restrict__ z, const float* __restrict__ zt, const float* __restrict__ y,
+                                       ClassVec pw, ClassVec active, int B, int C, float sup_norm, float bs_norm, float cw,
+                                       const float* __restrict__ target, float* __restrict__ rel_acc, float* __restrict__ dz,
+                                       float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    __shared__ float sh[4];
+    __shared__ float red_s[256], red_n[256];
+    __shared__ float G[FM_MAXC * FM_MAXC];      // d kd / d (the relation sum of pair (i, j))
+    __shared__ unsigned char sel[2048];
+    const float inv_sup = 1.f / sup_norm, inv_bs = 1.f / bs_norm;       // integers held exactly: the loss divides by them in double
+    float nsel = 0.f;
+    for (int r = threadIdx.x; r < B; r += 256) {
+        bool ok = true;
+        float unc = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float p = sigmoidf_(z[r * C + c]);
+            ok = ok && (p > 0.7f || p < 0.3f);
+            unc += p * logf(p + 1e-6f) + (1.f - p) * logf(1.f - p + 1e-6f);
+        }
+        ok = ok && (-unc < 2.0f);
+        sel[r] = ok;
+        nsel += ok ? 1.f : 0.f;
+    }
+    const bool any = block_sum(nsel, sh) > 0.f;             // also makes sel[] visible; block-uniform
+    if (rel_acc)
+        relation_sums<false>(z, y, nullptr, B, C, red_s, red_n,
+                             [&](int pair, float S, float N) { rel_acc[pair] += relation_prob(S, N); });
+    double kd = 0.0;
+    const float inv_2c = 0.5f / (float)C;
+    if (any) {
+        relation_sums<true>(z, y, sel, B, C, red_s, red_n, [&](int pair, float S, float N) {
+            const float den = N + 1e-8f;
+            const double a = (double)S / (double)den / 2.0, Q = sigmoid_d(a), T = target[pair];
+            kd += (Q - T) * log(Q / T);
+            const float q = (float)Q, t = target[pair];
+            G[pair] = (logf(q / t) + 1.f - t / q) * inv_2c * (q * (float)sigmoid_d(-a) * 0.5f) / den;
+        });
+    } else {
+        for (int pair = threadIdx.x; pair < C * C; pair += 256) {
+            const double T = target[pair];
+            kd += (0.5 - T) * log(0.5 / T);
+            G[pair] = 0.f;
+        }
+    }
+    __syncthreads();
+    double sup = 0.0, con = 0.0;
+    for (int i = threadIdx.x; i < B * C; i += 256) {
+        const int j = i % C, b = i / C;
+        float d1 = 0.f, d2 = 0.f, d;
+        if (active.v[j] != 0.f) {
+            const float yy = y[i];
+            bce_logits(z[i], yy, pw.v[j], &d);
+            d1 = d * inv_sup;
+            bce_logits(z[B * C + i], yy, pw.v[j], &d);
+            d2 = d * inv_sup;
+            sup += bce_logits_d(z[i], yy, pw.v[j]) + bce_logits_d(z[B * C + i], yy, pw.v[j]);
+        }
+        const float p = sigmoidf_(z[i]), e = p - sigmoidf_(zt[i]);
+        {
+            const double E = sigmoid_d(z[i]) - sigmoid_d(zt[i]);
+            con += E * E;
+        }
+        d1 += cw * inv_bs * 2.f * e * p * sigmoidf_(-z[i]);
+        if (any && sel[b]) {
+            float g = 0.f;
+            for (int k = 0; k < C; ++k)
+                if (sigmoidf_(z[b * C + k]) > 0.5f) g += G[k * C + j];
+            d1 += cw * g;
+        }
+        dz[i] = d1;
+        dz[B * C + i] = d2;
+    }
+    const double t1 = block_sum_d(sup, shd);
+    const double t2 = block_sum_d(con, shd);
+    const double t3 = block_sum_d(kd, shd);
+    if (threadIdx.x == 0)
+        *loss = (float)(t1 / (double)sup_norm + (double)cw * (t2 / (double)bs_norm + t3 / (2.0 * (double)C)));
+}
+void k_loss_fedirm_rel(const float* z, const float* zt, const float* y, ClassVec pos_w, ClassVec active, int B, int C,
+                       float sup_norm, float bs_norm, float cw, const float* target, float* rel_acc, float* dz, float* loss,
+                       hipStream_t s)
+{
+    hipLaunchKernelGGL(loss_fedirm_rel_kernel, dim3(1), dim3(256), 0, s, z, zt, y, pos_w, active, B, C, sup_norm, bs_norm, cw,
+                       target, rel_acc, dz, loss);
 }
 
 // ------------------------------------------------------------ prototypes -------

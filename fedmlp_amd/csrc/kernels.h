@@ -243,6 +243,15 @@ void k_loss_stage2(const float* z, const float* y, const float* distill, int B, 
 void k_loss_fixmatch(const float* z, const float* y, ClassVec pos_w, ClassVec pos_wu, ClassVec active,
                      int B, int C, int n_neg, float inv_sup, int n_cls_minus_ann, float* dz, float* loss,
                      hipStream_t s);
+// FedLSR / FedIRM two-view heads: z, dz [2B][C] view-major, y [B][C]; the loss is summed in double, relation sums in fp32 in LDS.
+// sup_norm = bs_norm annotation_num and bs_norm: the integer divisors as floats.  rel_acc [C][C] (may be null) += get_confuse_matrix(z_1, y); zt [B][C] teacher logits; target [C][C]; B <= 2048 for the rel head
+void k_loss_fedlsr(const float* z, const float* y, ClassVec pos_w, int B, int C, float mix1, float mix2, float beta, float* dz,
+                   float* loss, hipStream_t s);
+void k_loss_fedirm_sup(const float* z, const float* y, ClassVec pos_w, ClassVec active, int B, int C, float sup_norm,
+                       float* rel_acc, float* dz, float* loss, hipStream_t s);
+void k_loss_fedirm_rel(const float* z, const float* zt, const float* y, ClassVec pos_w, ClassVec active, int B, int C,
+                       float sup_norm, float bs_norm, float cw, const float* target, float* rel_acc, float* dz, float* loss,
+                       hipStream_t s);
 
 // ---- optimiser -------------------------------------------------------------------
 void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,

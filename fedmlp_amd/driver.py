@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Thin FL driver: the FedMLP / FedAVG / FedAVG+FixMatch rows of the reference's main.py
-(main.py:106-237, with the 'FeMLP' typos normalised) on the HIP engine, one process
+"""Thin FL driver: the FedMLP / FedAVG / FedAVG+FixMatch / FedLSR / FedIRM rows of the reference's main.py
+(main.py:106-252, with the 'FeMLP' typos normalised) on the HIP engine, one process
 per GPU, clients dealt round-robin over the ranks, aggregation as RCCL all-reduces
 (fedmlp_amd/fedavg.py).  Data is synthetic and HBM-resident (the reference's datasets and
 ImageNet weights are not available offline).
 
   python -m fedmlp_amd.driver --gpus 8 --exp FedMLP --n_clients 8 --rounds_warmup 4 --rounds_FedMLP_stage1 2
+  python -m fedmlp_amd.driver --exp FedIRM --rounds_warmup 4 --rounds_FedIRM_sup 2
 (with --gpus N > 1 and no torchrun environment the driver starts its N ranks itself, fedmlp_amd/launch.py)
 """
 import argparse
@@ -17,9 +18,9 @@ import numpy as np
 import torch
 
 
-def args_parser():
+def args_parser(argv=None):
     p = argparse.ArgumentParser()      # flag names/defaults follow utils/options.py:4-81
-    p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch"])
+    p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch", "FedLSR", "FedIRM"])
     p.add_argument("--model", default="Resnet18")
     p.add_argument("--seed", type=int, default=1037)
     p.add_argument("--batch_size", type=int, default=32)
@@ -30,6 +31,11 @@ def args_parser():
     p.add_argument("--local_ep", type=int, default=1)
     p.add_argument("--rounds_warmup", type=int, default=500)      # utils/options.py:42
     p.add_argument("--rounds_FedMLP_stage1", type=int, default=50)    # utils/options.py:46
+    p.add_argument("--t_w", type=int, default=40)                 # utils/options.py:67 (FedLSR: rounds of the beta warm-up)
+    p.add_argument("--rounds_FedIRM_sup", type=int, default=20)   # utils/options.py:69
+    p.add_argument("--consistency", type=float, default=1)        # utils/options.py:70
+    p.add_argument("--consistency_rampup", type=float, default=30)    # utils/options.py:71
+    p.add_argument("--ema_decay", type=float, default=0.99)       # utils/options.py:72
     p.add_argument("--U", type=float, default=0.7)
     p.add_argument("--L", type=float, default=0.3)
     p.add_argument("--clean_threshold", type=float, default=0.005)
@@ -54,7 +60,7 @@ def args_parser():
                    help="globaltest of the new global model every K rounds (main.py:322-357 uses 10), the forward dealt over "
                         "the ranks and the metrics from fm_eval_metrics; 0 = never")
     p.add_argument("--n_test", type=int, default=1024, help="samples of the synthetic test set (--eval_every)")
-    return p.parse_args()
+    return p.parse_args(argv)
 
 
 def AugmentedDeviceDataset(n, C, hw, seed, device, strong=False):
@@ -237,16 +243,22 @@ def main():
             ds = DeviceDataset(args.n_local, C, args.hw, args.seed + 1000 * c, dev)
         pos = [np.where(ds.targets[:, k] == 1)[0] for k in range(C)]
         a = argparse.Namespace(**vars(args))
-        clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C])
+        # FedIRM: every client keeps its own EMA model (main.py hands LocalUpdate a teacher_neg; :31, 393-395)
+        ema = build_model(args) if args.exp == "FedIRM" else None
+        clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C], teacher_neg=ema)
     test = None
     if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
         test = ShardedTestSet(args.n_test, C, args.hw, args.seed + 500, 4 * args.batch_size, rank, world, dev)
     tao, Prototype = [0] * C, None
+    SI = args.rounds_FedIRM_sup
+    # main.py:200-208: class k is annotated by the clients c with c mod C == k (every rank knows the whole assignment)
+    class_active_client_list = [[c for c in range(args.n_clients) if c % C == k] for k in range(C)]
     log = []
     for rnd in range(args.rounds_warmup):
         t0 = time.perf_counter()
         acc = RoundAccumulator(glob, len(glob_cnt), C, args.feature_dim, float(sum(n_all)))
         losses = []
+        relas = {}                                        # FedIRM: client -> its relation matrix (host), main.py:192-193
         for c in mine:
             loc = clients[c]
             eng.state_tensor().copy_(glob)                # net = deepcopy(netglob)  (main.py:181-184)
@@ -255,6 +267,14 @@ def main():
                 ret = loc.train(rnd, net, None)
             elif args.exp == "FedAVG+FixMatch":
                 ret = loc.train_FixMatch(rnd, net)
+            elif args.exp == "FedLSR":
+                ret = loc.train_FedLSR(rnd, net)          # main.py:161-163
+            elif args.exp == "FedIRM":                    # main.py:169-177
+                if rnd < SI - 1:
+                    ret = loc.train_FedIRM(rnd, Prototype, None, None, None, net=net)
+                else:
+                    ret = loc.train_FedIRM(rnd, Prototype, None, loc.negative_class_list, loc.active_class_list, net=net)
+                    relas[c] = ret[6].detach().cpu()
             elif rnd < S1 - 1:
                 ret = loc.train_FedMLP(rnd, tao, Prototype, None, None, None, net=net)
             else:
@@ -267,6 +287,18 @@ def main():
         glob.copy_(eng.state_tensor())
         if tao_new is not None:
             tao, Prototype = tao_new, proto_new
+        if args.exp == "FedIRM" and rnd >= SI - 1:        # main.py:245-251: FedAvg above, then FedAvg_rela with lam = 1
+            from fedmlp_amd.fedavg import FedAvg_rela
+            if dist is not None:                          # C x C floats per client: gathered as objects, folded on every rank alike
+                parts = [None] * world
+                dist.all_gather_object(parts, relas)
+                relas = {k: v for part in parts for k, v in part.items()}
+            rela = FedAvg_rela([relas[c] for c in range(args.n_clients)], n_all, class_active_client_list)
+            if rnd == SI - 1:
+                Prototype = rela
+            else:
+                lam = 1.0
+                Prototype = (1 - lam) * Prototype + lam * rela
         metrics = None
         if test is not None and (rnd + 1) % args.eval_every == 0:     # globaltest of the new netglob (main.py:322-331)
             torch.cuda.synchronize()

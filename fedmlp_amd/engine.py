@@ -320,6 +320,66 @@ class Engine:
             _lib.fvec(pos_weight_unk, n), _lib.fvec(active_mask, n), int(annotation_num),
             int(bs_norm), _ptr(loss_out)))
 
+    def step_fedlsr(self, x1, x2, y, pos_weight, mix1, beta, loss_out):
+        """train_FedLSR's step (utils/local_training.py:1294-1319) fused: two-view forward, loss_fedlsr's head, backward, Adam"""
+        self._check_stream()
+        self._enqueue(weights=True)
+        self._draw(2 * x1.shape[0])
+        _lib.check(self.lib.fm_step_fedlsr(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0],
+                                           _lib.fvec(pos_weight, self.n_classes), C.c_float(mix1), C.c_float(beta),
+                                           _ptr(loss_out)))
+
+    # ---- FedLSR / FedIRM loss heads on two-view logits z [2B,C] (forward_train's layout): -> (dz [2B,C], loss [1]) ----------
+    def _head_out(self, z, y):
+        B = y.shape[0]
+        if tuple(z.shape) != (2 * B, self.n_classes) or tuple(y.shape) != (B, self.n_classes):
+            raise ValueError(f"two-view head: z must be [2B, C] and y [B, C], got {tuple(z.shape)} and {tuple(y.shape)}")
+        for t in (z, y):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("two-view head: contiguous float32 tensors are required")
+        return B, torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
+
+    def _rel_arg(self, t, what):
+        if t is None:
+            return None
+        n = self.n_classes
+        if tuple(t.shape) != (n, n) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 [{n}, {n}] device tensor")
+        return t
+
+    def loss_fedlsr(self, z, y, pos_weight, mix1, beta):
+        self._check_stream()
+        self._enqueue()
+        B, dz, loss = self._head_out(z, y)
+        _lib.check(self.lib.fm_loss_fedlsr(self.h, _ptr(z), _ptr(y), _lib.fvec(pos_weight, self.n_classes), C.c_float(mix1),
+                                           C.c_float(beta), B, _ptr(dz), _ptr(loss)))
+        return dz, loss
+
+    def loss_fedirm_sup(self, z, y, pos_weight, active_mask, annotation_num, bs_norm, rel_acc=None):
+        """rel_acc [C,C] (optional) += get_confuse_matrix(z[:B], y)"""
+        self._check_stream()
+        self._enqueue()
+        n = self.n_classes
+        B, dz, loss = self._head_out(z, y)
+        _lib.check(self.lib.fm_loss_fedirm_sup(self.h, _ptr(z), _ptr(y), _lib.fvec(pos_weight, n), _lib.fvec(active_mask, n),
+                                               int(annotation_num), int(bs_norm), B, _ptr(self._rel_arg(rel_acc, "rel_acc")),
+                                               _ptr(dz), _ptr(loss)))
+        return dz, loss
+
+    def loss_fedirm_rel(self, z, zt, y, pos_weight, active_mask, annotation_num, bs_norm, cw, target, rel_acc=None):
+        """zt [B,C]: the EMA model's logits on view 2; target [C,C]: the aggregated relation matrix (device)"""
+        self._check_stream()
+        self._enqueue()
+        n = self.n_classes
+        B, dz, loss = self._head_out(z, y)
+        if tuple(zt.shape) != (B, n) or zt.dtype != torch.float32 or not zt.is_contiguous():
+            raise ValueError(f"loss_fedirm_rel: zt must be a contiguous float32 [{B}, {n}] tensor")
+        _lib.check(self.lib.fm_loss_fedirm_rel(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(pos_weight, n),
+                                               _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(cw),
+                                               _ptr(self._rel_arg(target, "target")), B,
+                                               _ptr(self._rel_arg(rel_acc, "rel_acc")), _ptr(dz), _ptr(loss)))
+        return dz, loss
+
     # ---- prototypes / tagging ------------------------------------------------------
     # ---- generic split step (rank-4 baselines: loss head computed by the host mirror) -----------
     def forward_train(self, x1, x2=None):
@@ -545,6 +605,11 @@ class Engine:
     def teacher_axpby(self, w_teacher, w_student):
         self._enqueue()
         _lib.check(self.lib.fm_teacher_axpby(self.h, C.c_float(w_teacher), C.c_float(w_student)))
+
+    def teacher_ema_params(self, alpha):
+        """update_ema_variables (utils/local_training.py:62-65) over the parameters only: running statistics and counters stay"""
+        self._enqueue()
+        _lib.check(self.lib.fm_teacher_ema_params(self.h, C.c_double(float(alpha))))
 
     def teacher_swap(self):
         self._enqueue(weights=True)

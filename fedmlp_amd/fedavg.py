@@ -1,8 +1,8 @@
 """Aggregation: the reference's utils/FedAvg.py surface + its RCCL form.
 
 Two forms of the same arithmetic:
-  * FedAvg / FedAvg_tao / FedAvg_proto -- drop-ins with the reference signatures
-    (utils/FedAvg.py:7-14, 51-70, 72-93) for a single-process driver that holds
+  * FedAvg / FedAvg_tao / FedAvg_proto / FedAvg_rela -- drop-ins with the reference signatures
+    (utils/FedAvg.py:7-14, 51-70, 72-93, 95-103) for a single-process driver that holds
     every client's state_dict on the host, as main.py:216-234 does.  Host glue:
     left-to-right weighted mean, same order as the reference.
   * Fed_w / model_dist / RSCFed -- the `--exp RSCFed` aggregation (utils/FedAvg.py:16-49, main.py:213-214): host drop-ins
@@ -208,6 +208,22 @@ def FedAvg_proto(Prototypes, weight, class_active_client_list):
         den = np.sum(np.array(weight)[clients])
         out[2 * cls] = a0 / den
         out[2 * cls + 1] = a1 / den
+    return out
+
+
+def FedAvg_rela(Prototypes, weight, class_active_client_list):
+    """utils/FedAvg.py:95-103 (main.py:247, 251): row cls of the result is the weighted mean of the clients' relation-matrix
+    rows over the clients that annotate cls, accumulated in the listed order as `row * weight + acc` in fp32 and divided by
+    numpy's sum of their weights: the reference's operations on host tensors, bit for bit.  A class nobody annotates yields a
+    NaN row (0 / 0) as there."""
+    P = [torch.as_tensor(_np(p)) for p in Prototypes]
+    out = torch.zeros((len(P[0]), len(P[0][0])))
+    for cls, clients in enumerate(class_active_client_list):
+        acc = torch.zeros_like(P[0][0])
+        for cid in clients:
+            acc = P[cid][cls] * weight[cid] + acc
+        acc = acc / np.sum(np.array(weight)[clients])
+        out[cls] = acc
     return out
 
 

@@ -1,6 +1,6 @@
 """LocalUpdate drop-in: the reference's per-client trainer surface
 (utils/local_training.py:26-55 ctor, :628-703 train, :771-825 train_FixMatch,
-:904-1256 train_FedMLP) driven through the HIP engine.
+:904-1256 train_FedMLP, :1270-1326 train_FedLSR, :344-464 train_FedIRM) driven through the HIP engine.
 
 Same constructor and method signatures, same return tuples (positions 3-4 are
 the reference's junk `_` placeholders -> None), same persistent per-client
@@ -98,6 +98,7 @@ class LocalUpdate(object):
         self.lr = args.base_lr
         self.traindata_idx = []
         self.idxss = []
+        self.flag = True                    # :54: the first relation-phase call of train_FedIRM loads the EMA model from net
         self._dev = {}
 
     # ---- data plumbing -------------------------------------------------------------------
@@ -247,6 +248,117 @@ class LocalUpdate(object):
         eng.teacher_swap()
         net.mark_trained()
         return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act
+
+    # ---- LocalUpdate.train_FedLSR (:1270-1326) --------------------------------------------------------
+    def train_FedLSR(self, rnd, net):
+        a = self.args
+        eng = self._bind(net, "image_aug_1")
+        eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        y = self._labels_dev(eng, self._y_masked, "y_masked")
+        n = len(self.idxs)
+        betaa = 0.4                                                 # :1309-1311
+        if rnd < a.t_w:
+            betaa = 0.4 * rnd / a.t_w
+        epoch_loss = []
+        for _ in range(a.local_ep):
+            batches = _batches(self._order(n), a.batch_size)
+            losses = torch.zeros(len(batches), device=eng.device)
+            for k, pos in enumerate(batches):
+                mix_1 = np.random.beta(1, 1)                        # :1296: one draw per step from numpy's global RNG
+                eng.step_fedlsr(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
+                                self._rows(y, pos, eng), self.loss_w, mix_1, betaa, losses[k:k + 1])
+                self.iter_num += 1                                  # :1321
+            self.epoch += 1
+            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
+        net.mark_trained()
+        return self._sd(net), np.array(epoch_loss).mean(), None, None, \
+            list(self.negative_class_list), list(self.active_class_list)
+
+    # ---- LocalUpdate.train_FedIRM (:344-464) -----------------------------------------------------------
+    @staticmethod
+    def sigmoid_rampup(current, rampup_length):
+        """:83-90"""
+        if rampup_length == 0:
+            return 1.0
+        current = np.clip(current, 0.0, rampup_length)
+        phase = 1.0 - current / rampup_length
+        return float(np.exp(-5.0 * phase * phase))
+
+    @staticmethod
+    def ema_alpha(global_step, ema_decay):
+        """update_ema_variables' alpha (:63)"""
+        return min(1 - 1 / (global_step + 1), ema_decay)
+
+    def train_FedIRM(self, rnd, target_matrix, writer1, negetive_class_list, active_class_list_client_i, net):
+        a = self.args
+        C = a.n_classes
+        eng = self._bind(net, "image_aug_1")
+        y = self._labels_dev(eng, self._y_masked, "y_masked")
+        n = len(self.idxs)
+        act, neg = list(self.active_class_list), list(self.negative_class_list)
+        amask = self._mask(act)
+        rel = torch.zeros((C, C), device=eng.device)                # self.confuse_matrix (:352, 403), C x C for the reference's 8 x 8
+        epoch_loss = []
+        if rnd < a.rounds_FedIRM_sup:
+            eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+            first_rel = rnd == a.rounds_FedIRM_sup - 1              # :372: the first relation matrix
+            for _ in range(a.local_ep):
+                batches = _batches(self._order(n), a.batch_size)
+                losses = torch.zeros(len(batches), device=eng.device)
+                for k, pos in enumerate(batches):
+                    _, z = eng.forward_train(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos))
+                    dz, loss = eng.loss_fedirm_sup(z, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
+                                                   a.batch_size, rel if first_rel else None)
+                    eng.backward_step(dz)
+                    losses[k:k + 1] = loss
+                self.epoch += 1
+                epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
+            net.mark_trained()
+            if first_rel:
+                rel = rel / (1.0 * a.local_ep * len(batches))       # :385, once, after the epochs (j + 1 = batches per epoch)
+                return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, rel
+            return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act
+
+        # ---- inter-client relation matching (:392-464) ----
+        assert isinstance(self.teacher_neg, HipNet), "LocalUpdate(teacher_neg=build_model(...)) is required"
+        # the EMA model lives in the engine's teacher slot for the duration of the call (as in train_RSCFed)
+        if self.flag:                                               # :393-395: ema_model.load_state_dict(net.state_dict())
+            eng.teacher_snapshot()
+            self.flag = False
+        else:
+            self.teacher_neg._pull()
+            eng.teacher_swap()
+            eng.set_state(self.teacher_neg.flat, self.teacher_neg.counters)
+            eng.teacher_swap()
+        eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        target = torch.as_tensor(target_matrix, dtype=torch.float32).to(eng.device).contiguous()
+        cw = a.consistency * self.sigmoid_rampup(rnd, a.consistency_rampup)     # :91-92, 442
+        for _ in range(a.local_ep):
+            batches = _batches(self._order(n), a.batch_size)
+            losses = torch.zeros(len(batches), device=eng.device)
+            for k, pos in enumerate(batches):
+                x1, x2 = self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos)
+                # :422-423: the reference never puts the EMA model in eval mode, so its no-grad forward is a TRAIN-mode
+                # forward: batch statistics, and its running statistics and counters move
+                eng.teacher_swap()
+                _, zt = eng.forward_train(x2)
+                eng.teacher_swap()
+                _, z = eng.forward_train(x1, x2)
+                dz, loss = eng.loss_fedirm_rel(z, zt, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
+                                               a.batch_size, cw, target, rel)
+                eng.backward_step(dz)
+                eng.teacher_ema_params(self.ema_alpha(self.iter_num, a.ema_decay))       # :456, parameters only
+                losses[k:k + 1] = loss
+                self.iter_num += 1                                  # :458: persists across rounds
+            self.epoch += 1
+            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
+            rel = rel / (1.0 * a.local_ep * len(batches))           # :461-462: INSIDE the epoch loop, as the reference has it
+        eng.teacher_swap()
+        self.teacher_neg.flat, self.teacher_neg.counters = eng.get_state()
+        self.teacher_neg._version += 1
+        eng.teacher_swap()
+        net.mark_trained()
+        return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, rel
 
     # ---- LocalUpdate.train_FedNoRo (:115-234) ----------------------------------------------------------
     def train_FedNoRo(self, id, rnd, net, writer1=None, weight_kd=None, clean_clients=None, noisy_clients=None):

@@ -205,6 +205,44 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
                      const float* active_mask_host, int32_t annotation_num, int32_t bs_norm,
                      float* loss_dev);
 
+/* ---- FedLSR and FedIRM (utils/local_training.py:1270-1326, 344-464) ---------
+ * Three loss heads on TWO-VIEW logits z_dev [2B][C] (view 1 rows, then view 2 rows: fm_forward_train's layout), y_dev [B][C].
+ * Each is one launch on the engine's stream with no synchronisation, writes every element of dz_dev [2B][C] and the scalar
+ * *loss_dev, uses no atomics and gives the same bits from run to run; usable between fm_forward_train and fm_backward_step.
+ *
+ * fm_loss_fedlsr (:1294-1314): s_v = sigmoid(z_v), p = mix1 s_1 + (1 - mix1) s_2, pred_mix = sigmoid(2 log(p / (1 - p)));
+ *   loss = mean over the B C elements of BCEWithLogits(pos_weight)(pred_mix, y) -- the reference feeds the probability in as
+ *   a logit, and so does this -- + beta JS(q_1, q_2), q_v = clamp(sigmoid(3 z_v), 1e-6, 1), JS of :1258-1266 with
+ *   KLDivLoss(reduction='mean'), i.e. the mean over all B C elements.  The means are over the actual B.  The clamp passes no
+ *   gradient where it binds.  mix1 in [0, 1] is the caller's draw (np.random.beta(1, 1), one per step); beta is 0.4, or
+ *   0.4 rnd / t_w while rnd < t_w.
+ *   The one deviation: pred_mix is formed as p^2 / (p^2 + (1 - p)^2) with 1 - p = mix1 sigmoid(-z_1) + (1 - mix1) sigmoid(-z_2).
+ *   torch's fp32 autograd of the logarithm returns NaN once p rounds to 1 (0 * inf); this form stays finite there and its
+ *   derivative tends to 0.
+ * fm_loss_fedirm_sup (:370-376): sum over both views and the active classes of BCEWithLogits(pos_weight)(z_v, y) /
+ *   (bs_norm annotation_num).  rel_acc_dev [C][C] (NULL = skipped) += get_confuse_matrix(z_1, y) (:73-81): row i is
+ *   sigmoid((sum_b z_1[b][:] y[b][i]) / (sum_b y[b][i] + 1e-8) / 2).  The reference hard-codes 8 classes there (range(8), tile 8);
+ *   this is built for C and identical to the reference at C = 8.
+ * fm_loss_fedirm_rel (:421-452): the supervised term + cw sum (sigmoid z_1 - sigmoid zt)^2 / bs_norm + cw kd(Q, target), where
+ *   zt_dev [B][C] is the EMA model's logits on view 2 (no gradient), target_dev [C][C] the aggregated relation matrix,
+ *   kd the symmetric kl_div(..., 'batchmean') of :109-113, Q = get_confuse_matrix(z_1[sel], sigmoid(z_1)[sel] > 0.5) over the rows
+ *   whose every probability is > 0.7 or < 0.3 and whose uncertainty (:426-427) is < 2.  The selection and the pseudo-labels
+ *   carry no gradient; kd's gradient reaches z_1 through Q.  With no row selected Q is the constant 0.5 matrix and kd has no
+ *   gradient: decided on the device, no host read.  rel_acc_dev as above (NULL = skipped).  B <= 2048.
+ * fm_step_fedlsr: the fused step like fm_step_fixmatch: two-view train-mode forward (BN statistics per view, running
+ *   statistics updated view 1 then view 2), fm_loss_fedlsr's head, backward, Adam.  FM_ERR_ARG under a requires_grad mask.
+ * FedIRM runs on the split step: fm_forward_train(x1, x2) -> fm_loss_fedirm_* -> fm_backward_step(dz). */
+int fm_loss_fedlsr(fm_engine* e, const float* z_dev, const float* y_dev, const float* pos_weight_host, float mix1, float beta,
+                   int32_t B, float* dz_dev, float* loss_dev);
+int fm_loss_fedirm_sup(fm_engine* e, const float* z_dev, const float* y_dev, const float* pos_weight_host,
+                       const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, int32_t B, float* rel_acc_dev,
+                       float* dz_dev, float* loss_dev);
+int fm_loss_fedirm_rel(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* pos_weight_host,
+                       const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, float cw, const float* target_dev,
+                       int32_t B, float* rel_acc_dev, float* dz_dev, float* loss_dev);
+int fm_step_fedlsr(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
+                   const float* pos_weight_host, float mix1, float beta, float* loss_dev);
+
 /* ---- prototype + t pass (utils/local_training.py:971-1002, 1208-1250) ---- */
 /* Accumulators live in the engine: proto sums [2C,D], counts [2C], t counts [C]. */
 int fm_proto_reset(fm_engine* e);
@@ -404,6 +442,10 @@ int fm_sgd_step_groups(fm_engine* e, const fm_sgd* hp, int32_t n);
 /* teacher <- w_teacher*teacher + w_student*student over every state entry (train_RSCFed's EMA,
  * utils/local_training.py:751-759, weights 0.999 / 0.001). */
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student);
+/* teacher <- alpha*teacher + (1-alpha)*student over the PARAMETERS only (update_ema_variables,
+ * utils/local_training.py:62-65; the caller forms alpha = min(1 - 1/(step+1), ema_decay)): BatchNorm running
+ * statistics and num_batches_tracked of the teacher stay untouched.  Both weights are rounded to fp32 once. */
+int fm_teacher_ema_params(fm_engine* e, double alpha);
 /* exchange the student and teacher slots (so fm_set_state / fm_get_state reach the teacher) */
 int fm_teacher_swap(fm_engine* e);
 
