@@ -285,6 +285,7 @@ bool launch_wgrad(const WgradParams& p, int splits, hipStream_t s);    // false 
 int wgrad_tile_n(int M, int Nw);
 // 1x1 stride-1 convs with min(M, Nw) <= 128: returns the splits written to p.slab, 0 = not handled
 int launch_wgrad_skinny(const WgradParams& p, size_t slab_floats, hipStream_t s);
+bool wgrad_skinny_takes(const WgradParams& p);     // will launch_wgrad_skinny handle this shape?
 int igemm_tile_n(int M, bool stem = false);   // pixel-tile width the igemm uses for this M (the stem kernels: 256)
 int igemm_tile_m(int M);
 

@@ -1091,6 +1091,54 @@ bool conv_uses_pconv(const fm_engine* e, const Conv& c, int imgs)
     return e->planes && c.bm_off >= 0 && pconv_takes(c.cout_p, c.cin_p, (long long)imgs * c.hin * c.win, c.win);
 }
 
+// the GEMM geometry of the planes kernel's launches -- taps, operand map, output grid: what pconv_uses_ts decides on.  conv_fwd /
+// conv_dgrad build their parameters from these, and fm_debug_conv_arm asks the same predicate about the same fields.
+static void pconv_fwd_geometry(const Conv& c, IgemmParams& p)
+{
+    p.ntaps = c.k * c.k;
+    for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
+    p.M = c.cout_p;
+    p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p;
+    p.Hg = c.hout; p.Wg = c.wout; p.sg = c.stride;
+}
+static void pconv_dgrad_geometry(const Conv& c, const DgradClass& d, IgemmParams& p)
+{
+    p.ntaps = d.taps.n;
+    for (int t = 0; t < d.taps.n; ++t) { p.dh[t] = d.dh[t]; p.dw[t] = d.dw[t]; }
+    p.M = c.cin_p;
+    p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
+    p.Hg = (c.hin - d.ph + c.stride - 1) / c.stride;
+    p.Wg = (c.win - d.pw + c.stride - 1) / c.stride;
+    p.sg = 1;
+}
+static bool dgrad_uses_pconv(const fm_engine* e, const Conv& c, int imgs)
+{
+    return e->planes && c.ncls > 0 && c.cls[0].bm_off >= 0 && pconv_takes(c.cin_p, c.cout_p, (long long)imgs * c.hout * c.wout, c.wout);
+}
+// the operand shapes of the planes weight gradient: what pwgrad_takes admitted and pwgrad_ring_takes decides on
+static bool wgrad_uses_pwgrad(const fm_engine* e, const Conv& c, int imgs)
+{
+    return e->planes && c.cin != 3 &&
+           pwgrad_takes(c.cout_p, c.cin_p, c.k, (long long)imgs * c.hout * c.wout, (long long)imgs * c.hin * c.win, c.win, c.pad);
+}
+static void pwgrad_geometry(const fm_engine* e, const Conv& c, int imgs, PwgradParams& q)
+{
+    q.npix = (long long)imgs * c.hout * c.wout; q.xpix = (long long)imgs * c.hin * c.win;
+    q.M = c.cout_p; q.Nw = c.Kw;
+    q.Ho = c.hout; q.Wo = c.wout; q.Hi = c.hin; q.Wi = c.win; q.Ci = c.cin_p; q.stride = c.stride; q.pad = c.pad; q.ksz = c.k;
+    q.sp = e->products;
+}
+// the shape fields of the fp32-operand weight gradient (wgrad.hip); the gather form of EfficientNet-B0's stem for the skinny kernels
+static void wgrad_geometry(const fm_engine* e, const Conv& c, int imgs, WgradParams& p)
+{
+    p.sp = e->products;
+    p.M = c.cout_p; p.Nw = c.Kw;
+    p.Ho = c.hout; p.Wo = c.wout; p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p; p.stride = c.stride;
+    if (c.stem3) { p.Hi = c.Hp; p.Wi = c.Wp; }      // gather table of build_tables: framed rows, no bounds
+    p.npix = imgs * c.hout * c.wout;
+    if (e->model == 1 && c.cin == 3) { p.gather_k = c.k; p.gather_pad = c.pad; p.gather_kw_p = c.kw_p; }
+}
+
 // xp: the input's block-major planes (planes mode; null = made here from x); yp: also / only write the output's planes
 // (eval epilogue; y may then be null)
 // partial-sum tiles per group the forward GEMM of conv c leaves in `stats` (pro_gate: this call carries an operand prologue)
@@ -1131,12 +1179,8 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
         p.Wsp = W.wbm_f + c.bm_off;
         p.Y = y; p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout;
         p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
-        p.ntaps = c.k * c.k;
-        for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
+        pconv_fwd_geometry(c, p);
         p.res = res; p.resp = resp; p.scale = scale; p.shift = shift; p.stats = stats;
-        p.M = c.cout_p;
-        p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p;
-        p.Hg = c.hout; p.Wg = c.wout; p.sg = c.stride;
         p.Ho = c.hout; p.Wo = c.wout; p.Co = c.cout_p;
         p.os = 1; p.oh0 = 0; p.ow0 = 0;
         p.imgs_per_group = imgs / groups;
@@ -1215,8 +1259,7 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
                 bool acc_cls0, const unsigned short* dyp = nullptr)
 {
     Conv& c = e->convs[ci];
-    if (e->planes && c.ncls > 0 && c.cls[0].bm_off >= 0 &&
-        pconv_takes(c.cin_p, c.cout_p, (long long)imgs * c.hout * c.wout, c.wout)) {
+    if (dgrad_uses_pconv(e, c, imgs)) {
         const long long xp_pix = (long long)imgs * c.hout * c.wout;
         if (!dyp) dyp = scratch_planes(e, L, dy, xp_pix, c.cout_p);
         for (int k = 0; k < c.ncls; ++k) {
@@ -1224,14 +1267,8 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
             IgemmParams p{};
             p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d + d.bm_off;
             p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
-            p.ntaps = d.taps.n;
-            for (int t = 0; t < d.taps.n; ++t) { p.dh[t] = d.dh[t]; p.dw[t] = d.dw[t]; }
+            pconv_dgrad_geometry(c, d, p);
             p.res = res ? res : ((acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
-            p.M = c.cin_p;
-            p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
-            p.Hg = (c.hin - d.ph + c.stride - 1) / c.stride;
-            p.Wg = (c.win - d.pw + c.stride - 1) / c.stride;
-            p.sg = 1;
             p.Ho = c.hin; p.Wo = c.win; p.Co = c.cin_p;
             p.os = c.stride; p.oh0 = d.ph; p.ow0 = d.pw;
             p.imgs_per_group = imgs;
@@ -1345,10 +1382,9 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
                 int pix_per_group = 0, const unsigned short* xp = nullptr, const unsigned short* dyp = nullptr)
 {
     const Conv& c = e->convs[ci];
-    if (e->planes && c.cin != 3 &&
-        pwgrad_takes(c.cout_p, c.cin_p, c.k, (long long)imgs * c.hout * c.wout, (long long)imgs * c.hin * c.win, c.win, c.pad)) {
+    if (wgrad_uses_pwgrad(e, c, imgs)) {
         PwgradParams q{};
-        q.npix = (long long)imgs * c.hout * c.wout; q.xpix = (long long)imgs * c.hin * c.win;
+        pwgrad_geometry(e, c, imgs, q);
         if (!xp) xp = scratch_planes(e, L, x, q.xpix, c.cin_p);
         if (!dyp) {
             if ((size_t)q.npix * c.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return; }
@@ -1356,9 +1392,6 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
             dyp = e->xp_scratch2;
         }
         q.dYp = dyp; q.Xp = xp; q.slab = L.ws_slab;
-        q.M = c.cout_p; q.Nw = c.Kw;
-        q.Ho = c.hout; q.Wo = c.wout; q.Hi = c.hin; q.Wi = c.win; q.Ci = c.cin_p; q.stride = c.stride; q.pad = c.pad; q.ksz = c.k;
-        q.sp = e->products;
         int sk;
         {
             const bool ring = pwgrad_ring_takes(q);
@@ -1384,13 +1417,9 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
     }
     WgradParams p{};
     p.dY = dy; p.X = x; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
-    p.sp = e->products;
-    p.M = c.cout_p; p.Nw = c.Kw;
-    p.Ho = c.hout; p.Wo = c.wout; p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p; p.stride = c.stride;
-    if (c.stem3) { p.X = e->x3; p.Hi = c.Hp; p.Wi = c.Wp; }      // gather table of build_tables: framed rows, no bounds
-    p.npix = imgs * c.hout * c.wout;
+    wgrad_geometry(e, c, imgs, p);
+    if (c.stem3) p.X = e->x3;
     if (e->model == 1 && (c.k == 1 || c.cin == 3)) {
-        if (c.cin == 3) { p.gather_k = c.k; p.gather_pad = c.pad; p.gather_kw_p = c.kw_p; }
         int sk;
         {
             ProfScope ps(e, L, 4, 2.0 * c.macs_per_img * imgs);
@@ -3890,6 +3919,71 @@ int fm_debug_conv_fwd(fm_engine* e, int32_t conv, const float* x_dev, float* out
     if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     HIPCHK(hipGetLastError());
     return FM_OK;
+}
+
+int fm_debug_conv_planes(fm_engine* e, int32_t conv, const uint16_t* xp_dev, int32_t imgs, const float* scale_dev,
+                         const float* shift_dev, const float* res_dev, const uint16_t* resp_dev, int32_t relu, float* out_dev,
+                         uint16_t* outp_dev)
+{
+    ARGCHK(e && xp_dev && conv >= 0 && conv < (int)e->convs.size(), "conv index");
+    ARGCHK(e->model == 0 && !e->precision && e->planes, "fm_debug_conv_planes: a planes-mode precision-0 ResNet-18 engine");
+    ARGCHK(scale_dev && shift_dev, "the eval epilogue needs scale and shift");
+    ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
+    ARGCHK(relu == 0 || relu == 1, "relu");
+    ARGCHK(!(res_dev && resp_dev), "one residual form: fp32 or planes");
+    ARGCHK(out_dev || outp_dev, "an output: fp32, planes or both");
+    Conv& c = e->convs[conv];
+    ARGCHK(c.cin != 3 && conv_uses_pconv(e, c, imgs), "a convolution the planes kernel runs (not the stem)");
+    ensure_packed(e);
+    // as forward_eval: the operand's planes, one group, no statistics, the output and the residual in either form
+    conv_fwd(e, e->main, conv, e->student, nullptr, out_dev, imgs, 1, scale_dev, shift_dev, res_dev, relu, nullptr, nullptr, xp_dev,
+             outp_dev, resp_dev);
+    HIPCHK(hipStreamSynchronize(e->main.st));
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_debug_conv_arm(fm_engine* e, int32_t op, int32_t conv, int32_t imgs)
+{
+    ARGCHK(e && conv >= 0 && conv < (int)e->convs.size(), "conv index");
+    ARGCHK(!e->precision, "fm_debug_conv_arm: a precision-0 engine");
+    ARGCHK(imgs >= 1 && imgs <= e->maxB && op >= 0 && op <= 2, "imgs / op");
+    const Conv& c = e->convs[conv];
+    if (op == 0) {                      // conv_fwd
+        if (e->stem_rows && c.stem3) return FM_ARM_STEM_ROWS;
+        if (conv_uses_pconv(e, c, imgs)) {
+            IgemmParams p{};
+            pconv_fwd_geometry(c, p);
+            return pconv_uses_ts(p) ? FM_ARM_PCONV_TS : FM_ARM_PCONV_TAP;
+        }
+        ARGCHK(!(e->planes && c.cin != 3), "conv_fwd has no kernel for this shape in planes mode");
+        return c.cin == 3 ? FM_ARM_IGEMM_STEM : FM_ARM_IGEMM;
+    }
+    if (op == 1) {                      // fm_debug_conv's data gradient: the stem's kernel, else conv_dgrad
+        if (c.cin == 3) return FM_ARM_STEM_DGRAD;
+        ARGCHK(c.ncls > 0, "dgrad unavailable for this conv");
+        if (dgrad_uses_pconv(e, c, imgs)) {
+            bool ts = true;
+            for (int k = 0; k < c.ncls; ++k) {
+                IgemmParams p{};
+                pconv_dgrad_geometry(c, c.cls[k], p);
+                ts = ts && pconv_uses_ts(p);
+            }
+            return ts ? FM_ARM_PCONV_TS : FM_ARM_PCONV_TAP;
+        }
+        ARGCHK(!e->planes, "conv_dgrad has no kernel for this shape in planes mode");
+        return FM_ARM_IGEMM;
+    }
+    if (wgrad_uses_pwgrad(e, c, imgs)) {        // conv_wgrad
+        PwgradParams q{};
+        pwgrad_geometry(e, c, imgs, q);
+        return pwgrad_ring_takes(q) ? FM_ARM_PWGRAD_RING : FM_ARM_PWGRAD;
+    }
+    ARGCHK(!(e->planes && c.cin != 3), "conv_wgrad has no kernel for this shape in planes mode");
+    WgradParams p{};
+    wgrad_geometry(e, c, imgs, p);
+    if (e->model == 1 && (c.k == 1 || c.cin == 3) && wgrad_skinny_takes(p)) return FM_ARM_WGRAD_SKINNY;
+    return FM_ARM_WGRAD_GENERIC;
 }
 
 int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)

@@ -595,13 +595,20 @@ __global__ __launch_bounds__(256) void wgrad_skinny_split_kernel(const SkinnyPar
 #endif
 }
 
+// the shapes the skinny kernels handle: min(M, Nw) <= 128, and a 1x1 stride-1 convolution or the gathered stem
+bool wgrad_skinny_takes(const WgradParams& w)
+{
+    const bool stem = w.Ci == 4 && w.gather_k > 0;
+    if (std::min(w.M, w.Nw) > 128) return false;
+    return stem || !(w.stride != 1 || w.Ci != w.Nw || w.Ho != w.Hi || w.Wo != w.Wi);
+}
+
 // returns the number of splits used, or 0 if the shape is not handled (caller falls back)
 int launch_wgrad_skinny(const WgradParams& w, size_t slab_floats, hipStream_t s)
 {
     const int S = std::min(w.M, w.Nw), L = std::max(w.M, w.Nw);
     const bool stem = w.Ci == 4 && w.gather_k > 0;
-    if (S > 128) return 0;
-    if (!stem && (w.stride != 1 || w.Ci != w.Nw || w.Ho != w.Hi || w.Wo != w.Wi)) return 0;
+    if (!wgrad_skinny_takes(w)) return 0;
     SkinnyParams p{};
     if (stem) {
         p.gather = 1; p.Hi = w.Hi; p.Wi = w.Wi; p.Ho = w.Ho; p.Wo = w.Wo; p.stride = w.stride;

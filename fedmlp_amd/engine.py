@@ -804,6 +804,27 @@ class Engine:
         _lib.check(self.lib.fm_debug_conv_fwd(self.h, conv, _ptr(x), _ptr(out), imgs, groups, _ptr(scale), _ptr(shift),
                                               _ptr(res), int(act), _ptr(psc), _ptr(psh), _ptr(gate), _ptr(stats)))
 
+    def debug_conv_planes(self, conv, xp, imgs, scale, shift, res=None, resp=None, relu=0, out=None, outp=None):
+        """one convolution as forward_eval runs it in planes mode (fm_debug_conv_planes): operand, residual and output as
+        block-major bf16 planes (int16 device tensors) and / or fp32"""
+        def words(t):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.int16), "planes are int16 device tensors"
+            return None if t is None else C.c_void_p(t.data_ptr())
+        self._enqueue()
+        _lib.check(self.lib.fm_debug_conv_planes(self.h, conv, words(xp), imgs, _ptr(scale), _ptr(shift), _ptr(res), words(resp),
+                                                 int(relu), _ptr(out), words(outp)))
+
+    # arm codes of fm_debug_conv_arm (include/fedmlp_hip_debug.h), in the header's order
+    CONV_ARMS = ("igemm", "igemm_stem", "stem_rows", "pconv_ts", "pconv_tap", "pwgrad", "pwgrad_ring", "wgrad_generic",
+                 "wgrad_skinny", "stem_dgrad")
+
+    def debug_conv_arm(self, op, conv, imgs):
+        """the launcher fm_debug_conv(op, conv) takes for `imgs` images: a name of CONV_ARMS (host-side query, no launch)"""
+        rc = self.lib.fm_debug_conv_arm(self.h, op, conv, imgs)
+        if rc < 0:
+            _lib.check(rc)
+        return self.CONV_ARMS[rc]
+
     def debug_block_dgrad(self, block, dy1, dyd, dx, imgs):
         """input gradient of stride-2 basic block `block` from the gradients of its conv1 / downsample outputs (fp32 NHWC)"""
         self._enqueue()

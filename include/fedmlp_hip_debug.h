@@ -52,6 +52,26 @@ int fm_debug_conv_fwd(fm_engine* e, int32_t conv, const float* x_dev, float* out
                       const float* scale_dev, const float* shift_dev, const float* res_dev, int32_t act, const float* psc_dev,
                       const float* psh_dev, const float* gate_dev, float* stats_dev);
 
+/* One convolution of forward_eval in planes mode (a planes-mode precision-0 ResNet-18 handle, a non-stem conv; weights are the
+ * engine's current state), called as forward_eval calls conv_fwd: the operand is xp = the block-major bf16 planes of
+ * x[imgs,hin,win,cin] ([cin/32][3][imgs*hin*win][32] 16-bit words: the header comment of planes_ew.hip), one group, no statistics:
+ *   v = relu?(conv * scale + shift + residual), scale / shift [cout] required, relu 0 / 1,
+ *   residual = res fp32 [imgs,hout,wout,cout] | resp, the same tensor as planes | neither (never both),
+ *   v goes to out fp32 [imgs,hout,wout,cout] and / or to outp as planes (at least one of them).
+ * imgs <= max_images.  Anything else returns FM_ERR_ARG before any launch and leaves the handle usable.  The call synchronises the
+ * stream and returns a deferred launch error, if there is one. */
+int fm_debug_conv_planes(fm_engine* e, int32_t conv, const uint16_t* xp_dev, int32_t imgs, const float* scale_dev,
+                         const float* shift_dev, const float* res_dev, const uint16_t* resp_dev, int32_t relu, float* out_dev,
+                         uint16_t* outp_dev);
+
+/* Which launcher fm_debug_conv's op (0 forward = conv_fwd, 1 data gradient, 2 weight gradient = conv_wgrad) takes for `imgs` images
+ * on this handle (precision 0): a host-side query, nothing is launched.  It evaluates the predicates those functions branch on, on
+ * the parameters they build.  A data gradient of several parity classes reports FM_ARM_PCONV_TAP if any class runs per tap.
+ * Returns an FM_ARM_* code (>= 0) or a negative error code. */
+enum { FM_ARM_IGEMM = 0, FM_ARM_IGEMM_STEM, FM_ARM_STEM_ROWS, FM_ARM_PCONV_TS, FM_ARM_PCONV_TAP, FM_ARM_PWGRAD, FM_ARM_PWGRAD_RING,
+       FM_ARM_WGRAD_GENERIC, FM_ARM_WGRAD_SKINNY, FM_ARM_STEM_DGRAD };
+int fm_debug_conv_arm(fm_engine* e, int32_t op, int32_t conv, int32_t imgs);
+
 /* Input gradient of a stride-2 residual block of ResNet-18 (block = index of the basic block: 2, 4, 6), as backward_and_step
  * runs it: dx[imgs,hin,win,cin] = dgrad(conv1; dy1) + dgrad(downsample; dyd), dy1 / dyd [imgs,hout,wout,cout] fp32 NHWC on
  * device.  Planes mode: ONE grouped launch of the per-tap planes kernel (the planes of dy1 / dyd are made inside); every
