@@ -127,6 +127,7 @@ SYMBOLS = {
     "fm_debug_conv_planes": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P]),
     "fm_debug_conv_arm": (C.c_int, [_P, _I32, _I32, _I32]),
     "fm_debug_pw": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "fm_debug_pw_fwd": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_debug_proj_bwd": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "fm_debug_exp_bwd": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "fm_debug_get_grads": (C.c_int, [_P, _P]),

@@ -3594,15 +3594,27 @@ int fm_profile_read(fm_engine* e, int32_t family, int64_t* launches, double* ms,
     return FM_OK;
 }
 
+// the bf16 stem's operand, as to_nhwc4 forms it: the im2col matrix of `groups` views of imgs / groups images of the fp32 NCHW batch x
+static void debug_stem_col(fm_engine* e, const Conv& c, const float* x, int imgs, int groups)
+{
+    const int B = imgs / groups;
+    for (int g = 0; g < groups; ++g)
+        k_stem_im2col(x + (size_t)g * B * 3 * e->H * e->W, reinterpret_cast<bf16*>(e->stem_col) + (size_t)g * B * c.hout * c.wout * c.Kw, B,
+                      e->H, e->W, c.hout, c.wout, c.k, c.stride, c.pad, c.pad, e->main.st);
+}
+
 int fm_debug_pw(fm_engine* e, int32_t op, int32_t conv, const void* x_dev, const void* dy_dev, void* out_dev,
                 int32_t imgs, int32_t groups, const float* psc_dev, const float* psh_dev, const float* gate_dev,
                 float* stats_dev)
 {
     ARGCHK(e && out_dev && conv >= 0 && conv < (int)e->convs.size(), "conv index");
-    ARGCHK(e->precision == 1 && e->convs[conv].k == 1, "bf16 engine and a 1x1 convolution");
+    const bool stem = e->precision == 1 && e->model == 1 && e->convs[conv].cin == 3 && op == 2;    // the stem's weight gradient only
+    ARGCHK(e->precision == 1 && (e->convs[conv].k == 1 || stem), "bf16 engine and a 1x1 convolution");
     ARGCHK(imgs >= 1 && imgs <= e->maxB && groups >= 1 && imgs % groups == 0, "imgs/groups");
     Conv& c = e->convs[conv];
+    ARGCHK(!stem || (x_dev && !gate_dev && !psc_dev && !psh_dev), "the stem takes its NCHW batch and no prologue");
     ensure_packed(e);
+    if (stem) debug_stem_col(e, c, reinterpret_cast<const float*>(x_dev), imgs, groups);
     const Prologue pro{psc_dev, psh_dev, gate_dev};
     if (op == 0) {
         ARGCHK(x_dev, "x");
@@ -3621,6 +3633,36 @@ int fm_debug_pw(fm_engine* e, int32_t op, int32_t conv, const void* x_dev, const
     } else {
         ARGCHK(false, "op");
     }
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_debug_pw_fwd(fm_engine* e, int32_t conv, const void* x_dev, void* out_dev, int32_t imgs, int32_t groups,
+                    const float* scale_dev, const float* shift_dev, const void* res_dev, int32_t act, const float* psc_dev,
+                    const float* psh_dev, const float* gate_dev, float* stats_dev)
+{
+    ARGCHK(e && x_dev && out_dev && conv >= 0 && conv < (int)e->convs.size(), "conv index");
+    ARGCHK(e->precision == 1 && e->model == 1, "fm_debug_pw_fwd works on bf16 tensors: an EfficientNet-B0 engine with precision 1");
+    Conv& c = e->convs[conv];
+    const bool stem = c.cin == 3;
+    ARGCHK(c.k == 1 || stem, "a 1x1 convolution or the stem");
+    ARGCHK(imgs >= 1 && imgs <= e->maxB && groups >= 1 && imgs % groups == 0, "imgs/groups");
+    ARGCHK(act == 0 || act == 2, "act: 0 none / 2 swish");
+    // the forms the engine's graphs use (fm_debug_conv_fwd's rules on the bf16 kernels); nothing else has a caller
+    ARGCHK(!scale_dev == !shift_dev, "scale and shift come together");
+    ARGCHK(!psc_dev == !psh_dev, "psc and psh come together");
+    const bool epi = scale_dev != nullptr, pro = gate_dev != nullptr;
+    ARGCHK(epi || (!res_dev && act == 0), "res / act belong to the eval epilogue: give scale and shift");
+    ARGCHK(!epi || (!stats_dev && groups == 1), "the eval epilogue runs without statistics on one group");
+    ARGCHK(pro || !psc_dev, "psc / psh without a gate");
+    ARGCHK(!stem || (!res_dev && !pro), "no graph hands the stem a residual or an operand prologue");
+    ARGCHK(!(epi && psc_dev), "the eval forward carries the gate-only prologue");
+    ensure_packed(e);
+    if (stem) debug_stem_col(e, c, reinterpret_cast<const float*>(x_dev), imgs, groups);
+    const Prologue pr{psc_dev, psh_dev, gate_dev};
+    conv_fwd(e, e->main, conv, e->student, reinterpret_cast<const float*>(x_dev), reinterpret_cast<float*>(out_dev), imgs, groups,
+             scale_dev, shift_dev, reinterpret_cast<const float*>(res_dev), act, stats_dev ? e->ws_stats : nullptr, pro ? &pr : nullptr);
+    if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     HIPCHK(hipGetLastError());
     return FM_OK;
 }

@@ -770,6 +770,14 @@ class Engine:
         _lib.check(self.lib.fm_debug_pw(self.h, op, conv, _ptr(x), _ptr(dy), _ptr(out), imgs, groups, _ptr(psc),
                                         _ptr(psh), _ptr(gate), _ptr(stats)))
 
+    def debug_pw_fwd(self, conv, x, out, imgs, groups=1, scale=None, shift=None, res=None, act=0, psc=None, psh=None, gate=None,
+                     stats=None):
+        """one 1x1 convolution (x bf16) or the stem (x = the fp32 NCHW batch) of a bf16 handle through conv_fwd, with the eval
+        epilogue, the operand prologue or the train statistics (fm_debug_pw_fwd)"""
+        self._enqueue()
+        _lib.check(self.lib.fm_debug_pw_fwd(self.h, conv, _ptr(x), _ptr(out), imgs, groups, _ptr(scale), _ptr(shift), _ptr(res),
+                                            int(act), _ptr(psc), _ptr(psh), _ptr(gate), _ptr(stats)))
+
     def debug_proj_bwd(self, conv, phase, dyp, yd, bn, gate, ds, imgs, groups, out, pool5=None):
         self._enqueue()
         _lib.check(self.lib.fm_debug_proj_bwd(self.h, conv, phase, _ptr(dyp), _ptr(yd), _ptr(bn), _ptr(gate), _ptr(ds), imgs,

@@ -83,10 +83,34 @@ int fm_debug_block_dgrad(fm_engine* e, int32_t block, const float* dy1_dev, cons
  *       [groups][2][cout_p] fp32; gate_dev != NULL applies the operand prologue
  *       x <- swish(x*psc[g]+psh[g]) * gate[img]   (psc_dev NULL: x * gate[img]); psc/psh [groups][cin_p], gate [imgs][cin_p]
  * op 1: dy bf16 [imgs,h,w,cout_p] -> out bf16 [imgs,h,w,cin_p]; x_dev (optional) = residual added to the result
- * op 2: (x, dy) -> out fp32 [cout_p][cin_p], with the same optional prologue on x */
+ * op 2: (x, dy) -> out fp32 [cout_p][cin_p], with the same optional prologue on x; also the stem (see fm_debug_pw_fwd) */
 int fm_debug_pw(fm_engine* e, int32_t op, int32_t conv, const void* x_dev, const void* dy_dev, void* out_dev,
                 int32_t imgs, int32_t groups, const float* psc_dev, const float* psh_dev, const float* gate_dev,
                 float* stats_dev);
+
+/* The forward of one convolution of a precision-1 EfficientNet-B0 handle through conv_fwd, with the optional operands the engine's
+ * graphs hand to it: the bf16 counterpart of fm_debug_conv_fwd (weights are the engine's current state, i.e. its bf16 shadow).
+ * A 1x1 convolution: x bf16 [imgs,h,w,cin_p] -> out bf16 [imgs,h,w,cout_p].  The stem: x is the fp32 NCHW batch [imgs][3][H][W]; the
+ * hook first forms the stem's operand as the graphs do (k_stem_im2col into the handle's im2col buffer, for `groups` views of
+ * imgs / groups images), out bf16 [imgs,hout,wout,cout_p].
+ *   epilogue: scale, shift [cout_p] fp32, res bf16 [imgs,hout,wout,cout_p] | NULL, act 0 none / 2 swish:
+ *             out = act(conv * scale + shift + res)
+ *   prologue: gate [imgs][cin_p], psc, psh [groups][cin_p] | NULL, all fp32: the operand is x * gate[img], with psc / psh
+ *             swish(x * psc[g] + psh[g]) * gate[img], re-rounded to bf16
+ *   stats:    per-group per-channel (sum, sumsq) [groups][2][cout_p] fp32 of the raw convolution, taken from the fp32 accumulators
+ *             (not from the rounded bf16 output) and folded as by fm_debug_conv
+ * The forms taken:
+ *   plain / train  no epilogue, stats optional;
+ *   eval           scale + shift (+ res, act), no stats, groups = 1; may carry the gate-only prologue; no res on the stem;
+ *   prologue       what fm_debug_pw op 0 offers (gate, or psc + psh + gate; stats optional), on a 1x1 convolution.
+ * Anything else (half a pair, res or act without scale / shift, stats or groups > 1 with an epilogue, psc / psh under an epilogue,
+ * a prologue or a residual on the stem, act = 1, another kind of convolution, a precision-0 or ResNet-18 handle) returns FM_ERR_ARG
+ * before any launch and leaves the handle usable.
+ * The stem's weight gradient is fm_debug_pw op 2 on the stem conv: x = the fp32 NCHW batch (the im2col matrix is formed from it in
+ * the same way), dy bf16 [imgs,hout,wout,cout_p], out fp32 [cout_p][Kw]; no prologue. */
+int fm_debug_pw_fwd(fm_engine* e, int32_t conv, const void* x_dev, void* out_dev, int32_t imgs, int32_t groups,
+                    const float* scale_dev, const float* shift_dev, const void* res_dev, int32_t act, const float* psc_dev,
+                    const float* psh_dev, const float* gate_dev, float* stats_dev);
 
 /* Fused backward of a project convolution (pw_proj_bwd_kernel: blocks 0-4 of a precision-1 EfficientNet engine, tensors bf16;
  * pw_proj_bwd_f32_kernel: blocks 0-2 of a precision-0 one, every "bf16" below is then fp32):
