@@ -67,6 +67,12 @@ SYMBOLS = {
     "fm_loss_fedirm_sup": (C.c_int, [_P, _P, _P, _F, _F, _I32, _I32, _I32, _P, _P, _P]),
     "fm_loss_fedirm_rel": (C.c_int, [_P, _P, _P, _P, _F, _F, _I32, _I32, C.c_float, _P, _I32, _P, _P, _P]),
     "fm_step_fedlsr": (C.c_int, [_P, _P, _P, _P, _I32, _F, C.c_float, C.c_float, _P]),
+    "fm_loss_rscfed": (C.c_int, [_P, _P, _P, _P, _F, _F, _I32, _I32, _I32, _P, _P]),
+    "fm_loss_lakd": (C.c_int, [_P, _P, _P, _P, _F, C.c_float, _I32, _P, _P]),
+    "fm_loss_cbafed": (C.c_int, [_P, _P, _P, _F, _I32, _I32, _F, _I32, _P, _P, _P, _P]),
+    "fm_step_rscfed": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, _I32, _I32, C.c_float, C.c_float, _P]),
+    "fm_step_fednoro": (C.c_int, [_P, _P, _P, _I32, _F, C.c_float, _P]),
+    "fm_step_cbafed": (C.c_int, [_P, _P, _P, _I32, _F, _I32, _I32, _F, _P, _P, _P]),
     "fm_proto_reset": (C.c_int, [_P]),
     "fm_proto_accumulate": (C.c_int, [_P, _P, _P, _P, _I32, _F, _F, C.c_float, C.c_float]),
     "fm_proto_finalize": (C.c_int, [_P, _I32, _I64, _F, _P, _P]),

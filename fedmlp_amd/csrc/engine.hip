@@ -321,6 +321,9 @@ struct fm_engine {
     // side lane into the second activation set (side_ok; stream_mode 1: main lane, the student's set)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     bool side_ok = false;
+    // first image of the input staging (e->x4 / x3 / x3p / stem_col) the stem's FORWARD reads: 0, except while fm_step_rscfed
+    // enqueues its teacher's forward, whose view is the staging's second group
+    int in_img0 = 0;
     // backward: the weight gradients run on the side lane next to the data-gradient chain; the gradient tensors they read
     // are double-buffered by block parity (side_w; stream_mode 1 or 2: inline)
     bool side_w = false;
@@ -1164,7 +1167,7 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
     }
     if (e->stem_rows && c.stem3) {           // `x` is ignored: the operand is the framed image's planes (to_nhwc4)
         StemRowsParams q{};
-        q.Xp = e->x3p; q.Wst = W.wst; q.Y = y;
+        q.Xp = e->x3p + (size_t)e->in_img0 * c.Hp * c.Wp * 4; q.Wst = W.wst; q.Y = y;
         q.scale = scale; q.shift = shift; q.stats = stats; q.relu = relu;
         q.imgs = imgs; q.imgs_per_group = imgs / groups; q.Hp = c.Hp; q.Wp = c.Wp; q.Ho = c.hout; q.Wo = c.wout;
         q.sp = e->products; q.plane_bytes = e->x3p_plane_elems * 2;
@@ -1201,6 +1204,7 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
         q.zeros = e->zeros;
         q.W = W.wb + c.wb_off;
         q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x); q.Y = reinterpret_cast<bf16*>(y);
+        if (stem16) q.X += (size_t)e->in_img0 * c.hout * c.wout * c.Kw;
         q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p;
         q.npix = (imgs / groups) * c.hout * c.wout; q.groups = groups;
         q.scale = scale; q.shift = shift; q.res = reinterpret_cast<const bf16*>(res); q.act = relu;
@@ -1216,7 +1220,8 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
     if (c.sp_off >= 0 && W.wsp_f) p.Wsp = W.wsp_f + c.sp_off;
     if (c.cin == 3) {
         p.stem_kw = c.k; p.stem_pad = c.pad; p.stem_h2 = c.kw_p == 8 ? 1 : 0; p.stem3 = c.stem3 ? 1 : 0;
-        if (c.stem3) p.X = e->x3;               // `x` is ignored: the operand is the framed NHWC3 image
+        if (c.stem3) p.X = e->x3 + (size_t)e->in_img0 * c.Hp * c.Wp * 3;     // `x` is ignored: the operand is the framed NHWC3 image
+        else p.X = x + (size_t)e->in_img0 * c.hin * c.win * 4;
     } else {
         p.ntaps = c.k * c.k;
         for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
@@ -3043,6 +3048,160 @@ int fm_step_fedlsr(fm_engine* e, const float* x1_dev, const float* x2_dev, const
     k_loss_fedlsr(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, e->dlogits,
                   loss_dev, e->main.st);
     net_backward_and_step(e, 2, B);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+// ---- RSCFed / FedNoRo / CBAFed: the single-view heads on caller tensors, and their fused steps ----
+// the heads' common contract: at least one active and one missing class (torch forms 0/0 or the mean of an empty tensor otherwise)
+static int count_active(const fm_engine* e, const float* active_mask_host)
+{
+    int n = 0;
+    for (int c = 0; c < e->C; ++c) n += active_mask_host[c] != 0.f;
+    return n;
+}
+static const char* const kHeadClasses = "the head needs at least one active and one missing class";
+static const char* const kHeadNorm = "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24";
+#define HEAD_NORM_OK(B, ann, bs) ((B) >= 1 && (ann) >= 1 && (bs) >= 1 && (int64_t)(bs) * (ann) < (1 << 24))
+
+static void launch_rscfed(fm_engine* e, const float* z, const float* zt, const float* y, const float* pw, const float* am, int ann,
+                          int bs, int B, float* dz, float* loss)
+{
+    k_loss_rscfed(z, zt, y, to_cv(pw, e->C), to_cv(am, e->C), B, e->C, (float)bs * (float)ann, e->C - count_active(e, am), dz, loss,
+                  e->main.st);
+}
+static void launch_cbafed(fm_engine* e, const float* z, const float* y, const float* am, int ann, int bs, const float* tao, int B,
+                          float* pw_dev, int64_t* counts_dev, float* dz, float* loss)
+{
+    ClassVec t{};
+    if (tao) t = to_cv(tao, e->C);
+    k_loss_cbafed(z, y, to_cv(am, e->C), tao ? &t : nullptr, B, e->C, (float)bs * (float)ann, ann, pw_dev, counts_dev, dz, loss,
+                  e->main.st);
+}
+
+int fm_loss_rscfed(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* pos_weight_host,
+                   const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, int32_t B, float* dz_dev, float* loss_dev)
+{
+    ARGCHK(e && z_dev && zt_dev && y_dev && pos_weight_host && active_mask_host && dz_dev && loss_dev, "null");
+    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    launch_rscfed(e, z_dev, zt_dev, y_dev, pos_weight_host, active_mask_host, annotation_num, bs_norm, B, dz_dev, loss_dev);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_loss_lakd(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* active_mask_host, float w_kd,
+                 int32_t B, float* dz_dev, float* loss_dev)
+{
+    ARGCHK(e && z_dev && zt_dev && y_dev && active_mask_host && dz_dev && loss_dev, "null");
+    ARGCHK(B >= 1, "B >= 1");
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    k_loss_lakd(z_dev, zt_dev, y_dev, to_cv(active_mask_host, e->C), B, e->C, na, w_kd, dz_dev, loss_dev, e->main.st);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_loss_cbafed(fm_engine* e, const float* z_dev, const float* y_dev, const float* active_mask_host, int32_t annotation_num,
+                   int32_t bs_norm, const float* tao_host, int32_t B, float* pos_weight_dev, int64_t* counts_dev, float* dz_dev,
+                   float* loss_dev)
+{
+    ARGCHK(e && z_dev && y_dev && active_mask_host && pos_weight_dev && dz_dev && loss_dev, "null");
+    ARGCHK(!tao_host || counts_dev, "fm_loss_cbafed: stage 2 (tao given) needs counts_dev");
+    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    launch_cbafed(e, z_dev, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev, dz_dev, loss_dev);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+// The EMA teacher's eval forward of view 2 next to the student's train forward of view 1, then the head, backward, Adam and the
+// teacher's blend with the post-Adam student.  Lane order: both views are staged on the main lane (view 2 as the
+// staging's second group); the teacher's shadows are re-formed on the main lane, behind the previous step's blend; ev_in lets the
+// side lane start, ev_t brings it back before the head -- so the blend, on the main lane behind Adam, never meets a running
+// teacher forward, and the next step's fork is enqueued behind it.
+int fm_step_rscfed(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
+                   const float* pos_weight_host, const float* active_mask_host, int32_t annotation_num, int32_t bs_norm,
+                   float w_teacher, float w_student, float* loss_dev)
+{
+    ARGCHK(e && x1_dev && x2_dev && y_dev && pos_weight_host && active_mask_host && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
+    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    if (e->side_ok && 2 * B <= e->maxB) {
+        const float* xs[2] = {x1_dev, x2_dev};
+        to_nhwc4(e, e->main, xs, 2, B);
+        e->in_img0 = B;                      // the teacher's stem reads the second group
+        const int rc = teacher_forward_side(e, B);
+        e->in_img0 = 0;
+        RCCHK(rc);
+        net_forward_train(e, 1, B);
+        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
+    } else {
+        // one lane (or no room for both views in the staging): the teacher first, each view staged in turn
+        const float* xt[1] = {x2_dev};
+        to_nhwc4(e, e->main, xt, 1, B);
+        ensure_teacher_shadow(e);
+        net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
+        const float* xs[1] = {x1_dev};
+        to_nhwc4(e, e->main, xs, 1, B);
+        net_forward_train(e, 1, B);
+    }
+    launch_rscfed(e, e->logits, e->tlogits, y_dev, pos_weight_host, active_mask_host, annotation_num, bs_norm, B, e->dlogits,
+                  loss_dev);
+    net_backward_and_step(e, 1, B);
+    RCCHK(fm_teacher_axpby(e, w_teacher, w_student));
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_step_fednoro(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B, const float* active_mask_host, float w_kd,
+                    float* loss_dev)
+{
+    ARGCHK(e && x_dev && y_dev && active_mask_host && loss_dev, "null");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
+    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    const float* xs[1] = {x_dev};
+    to_nhwc4(e, e->main, xs, 1, B);
+    if (e->side_ok) {
+        // frozen teacher on the side lane (own activation set), student on the main lane, both reading the one staged view
+        RCCHK(teacher_forward_side(e, B));
+        net_forward_train(e, 1, B);
+        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
+    } else {
+        ensure_teacher_shadow(e);
+        net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
+        net_forward_train(e, 1, B);
+    }
+    k_loss_lakd(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C, na, w_kd, e->dlogits, loss_dev, e->main.st);
+    net_backward_and_step(e, 1, B);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B, const float* active_mask_host,
+                   int32_t annotation_num, int32_t bs_norm, const float* tao_host, float* pos_weight_dev, int64_t* counts_dev,
+                   float* loss_dev)
+{
+    ARGCHK(e && x_dev && y_dev && active_mask_host && pos_weight_dev && loss_dev, "null");
+    ARGCHK(!tao_host || counts_dev, "fm_step_cbafed: stage 2 (tao given) needs counts_dev");
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
+    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
+    const int na = count_active(e, active_mask_host);
+    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    const float* xs[1] = {x_dev};
+    to_nhwc4(e, e->main, xs, 1, B);
+    net_forward_train(e, 1, B);
+    launch_cbafed(e, e->logits, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev, e->dlogits,
+                  loss_dev);
+    net_backward_and_step(e, 1, B);
     STEP_DONE(e);
     return FM_OK;
 }

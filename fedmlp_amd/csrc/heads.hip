@@ -9,6 +9,9 @@
 //   FixMatch weak/strong loss                                         (:797-815)
 //   FedLSR mixed-prediction BCE + beta JS, two views                  (:1258-1269, 1294-1314)
 //   FedIRM supervised / relation-phase heads, relation matrices       (:73-113, 370-376, 421-452)
+//   RSCFed BCE(active) + probability MSE to the EMA teacher           (:719, 740-743)
+//   FedNoRo LA_KD: BCE-on-probabilities + MSE to sigmoid(teacher/0.8) (utils/FedNoRo.py:35-38, :143-151)
+//   CBAFed warm-up / stage-2 pseudo-labels, loss_w and counts         (:247-269, 303-333)
 //   prototype masked sums + confident-count t                         (:985-994, 1229-1238)
 //   CosineSimilarityFast difference                                   (:1417-1435, 1056-1057)
 //   stable top-k / bottom-k                                           (utils/utils.py:24-35)
@@ -516,6 +519,178 @@ void k_loss_fedirm_rel(const float* z, const float* zt, const float* y, ClassVec
 {
     hipLaunchKernelGGL(loss_fedirm_rel_kernel, dim3(1), dim3(256), 0, s, z, zt, y, pos_w, active, B, C, sup_norm, bs_norm, cw,
                        target, rel_acc, dz, loss);
+}
+
+// ------------------------------------------------------------ RSCFed / FedNoRo / CBAFed heads ---
+// Single-view heads of train_RSCFed (utils/local_training.py:719, 740-743), train_FedNoRo's warm-up (LA_KD.forward,
+// utils/FedNoRo.py:35-38) and train_CBAFed (:247-269 warm-up, :303-333 stage 2).  z, dz [B][C]; every element of dz is written,
+// exact zeros where an element is not in the loss.  One block, no atomics.  Value AND gradient are formed in double from the fp32
+// logits and rounded once (B C elements: microseconds of a step); only CBAFed's threshold decisions are fp32 compares, as the
+// trainer's torch code made them.
+__device__ __forceinline__ int wave_sum_i(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// BCEWithLogits(pos_weight) in double: the value, and d/dz = (1 - y) - lw sigmoid(-z)
+__device__ __forceinline__ double bce_logits_dd(double z, float y, float pw, double* dz)
+{
+    const double lw = 1.0 + ((double)pw - 1.0) * (double)y;
+    *dz = (1.0 - (double)y) - lw * sigmoid_d(-z);
+    return (1.0 - (double)y) * z + lw * (log1p(exp(-fabs(z))) + fmax(-z, 0.0));
+}
+
+// RSCFed: sum_active BCEWithLogits(pos_weight)(z, y) / sup_norm + mean over the B n_miss missing elements of
+// (sigmoid z - sigmoid zt)^2; zt gets no gradient
+__global__ void loss_rscfed_kernel(const float* __restrict__ z, const float* __restrict__ zt, const float* __restrict__ y,
+                                   ClassVec pw, ClassVec active, int B, int C, float sup_norm, int n_miss,
+                                   float* __restrict__ dz, float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    const double n_mse = (double)B * (double)n_miss;
+    double sup = 0.0, con = 0.0;
+    for (int i = threadIdx.x; i < B * C; i += 256) {
+        const int c = i % C;
+        double d;
+        if (active.v[c] != 0.f) {
+            sup += bce_logits_dd(z[i], y[i], pw.v[c], &d);
+            d /= (double)sup_norm;
+        } else {
+            const double P = sigmoid_d(z[i]), E = P - sigmoid_d(zt[i]);
+            con += E * E;
+            d = 2.0 * E * (P * (1.0 - P)) / n_mse;
+        }
+        dz[i] = (float)d;
+    }
+    const double t1 = block_sum_d(sup, shd);
+    const double t2 = block_sum_d(con, shd);
+    if (threadIdx.x == 0) *loss = (float)(t1 / (double)sup_norm + t2 / n_mse);
+}
+void k_loss_rscfed(const float* z, const float* zt, const float* y, ClassVec pos_w, ClassVec active, int B, int C, float sup_norm,
+                   int n_miss, float* dz, float* loss, hipStream_t s)
+{
+    hipLaunchKernelGGL(loss_rscfed_kernel, dim3(1), dim3(256), 0, s, z, zt, y, pos_w, active, B, C, sup_norm, n_miss, dz, loss);
+}
+
+// LA_KD: p = sigmoid(z), soft = sigmoid(zt / 0.8f);
+//   (1 - w_kd) sum_active BCE(p, y) / (B n_act) + w_kd sum_missing (p - soft)^2 / (B n_miss), log clamped at -100.
+// 1 - p is formed as torch forms it (1 - p, not sigmoid(-z)): where p rounds to 1 the log clamps at -100 and, like
+// binary_cross_entropy's backward, the gradient (p - y) / max(p (1 - p), 1e-12) * p (1 - p) is 0.
+__global__ void loss_lakd_kernel(const float* __restrict__ z, const float* __restrict__ zt, const float* __restrict__ y,
+                                 ClassVec active, int B, int C, int n_act, float w_kd, float* __restrict__ dz,
+                                 float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    const double n_bce = (double)B * (double)n_act, n_kd = (double)B * (double)(C - n_act);
+    const double wk = (double)w_kd, wb = 1.0 - (double)w_kd;
+    double bce = 0.0, kd = 0.0;
+    for (int i = threadIdx.x; i < B * C; i += 256) {
+        const int c = i % C;
+        const double P = sigmoid_d(z[i]), Q = 1.0 - P, PQ = P * Q;
+        double d;
+        if (active.v[c] != 0.f) {
+            const double yy = y[i];
+            bce -= yy * fmax(log(P), -100.0) + (1.0 - yy) * fmax(log(Q), -100.0);
+            d = wb * ((P - yy) / fmax(PQ, 1e-12) * PQ) / n_bce;
+        } else {
+            const double E = P - sigmoid_d((double)(zt[i] / 0.8f));
+            kd += E * E;
+            d = wk * 2.0 * E * PQ / n_kd;
+        }
+        dz[i] = (float)d;
+    }
+    const double t1 = block_sum_d(bce, shd);
+    const double t2 = block_sum_d(kd, shd);
+    if (threadIdx.x == 0) *loss = (float)(wk * (t2 / n_kd) + wb * (t1 / n_bce));
+}
+void k_loss_lakd(const float* z, const float* zt, const float* y, ClassVec active, int B, int C, int n_act, float w_kd, float* dz,
+                 float* loss, hipStream_t s)
+{
+    hipLaunchKernelGGL(loss_lakd_kernel, dim3(1), dim3(256), 0, s, z, zt, y, active, B, C, n_act, w_kd, dz, loss);
+}
+
+// CBAFed.  Warm-up (STAGE2 false): the active-class BCEWithLogits(pos_weight) / sup_norm; pos_weight [C] is only read, counts
+// is not touched.  Stage 2: pass 1 counts, per missing class i, hi = sigmoid(z) > tao[i], lo = sigmoid(z) < 1.f - tao[i] and their
+// union over the B rows (integers: wave w takes classes w, w + 4, ..., its lanes the rows); one thread per class then writes
+// pos_weight[i] = noise == 0 ? 1 : (float)((double)(noise + clean) / noise) and adds to counts [C + 1] (int64): n_i per missing
+// class, B per active class, and their total (sum n_i + B annotation_num) in counts[C].  Pass 2 forms the loss with the NEW
+// weights: the active term, plus per missing class with n_i > 0 the sum over its hi / lo rows of l / n_i, the label 1 where hi
+// (in registers: y is not written).  The decisions of pass 2 re-evaluate pass 1's fp32 expressions, so they agree.
+template <bool STAGE2>
+__global__ void loss_cbafed_kernel(const float* __restrict__ z, const float* __restrict__ y, ClassVec active, ClassVec tao,
+                                   int B, int C, float sup_norm, int annotation_num, float* __restrict__ pos_weight,
+                                   long long* __restrict__ counts, float* __restrict__ dz, float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    __shared__ int n_hi[FM_MAXC], n_lo[FM_MAXC], n_un[FM_MAXC];
+    __shared__ float pw[FM_MAXC];
+    if (STAGE2) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int c = wave; c < C; c += 4) {
+            int h = 0, l = 0, u = 0;
+            if (active.v[c] == 0.f) {
+                const float t = tao.v[c], t1 = 1.f - t;
+                for (int r = lane; r < B; r += 64) {
+                    const float p = sigmoidf_(z[r * C + c]);
+                    const bool hi = p > t, lo = p < t1;
+                    h += hi; l += lo; u += (hi || lo);
+                }
+            }
+            h = wave_sum_i(h); l = wave_sum_i(l); u = wave_sum_i(u);
+            if (lane == 0) { n_hi[c] = h; n_lo[c] = l; n_un[c] = u; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < C) {
+        const int c = threadIdx.x;
+        float w = pos_weight[c];
+        if (STAGE2) {
+            if (active.v[c] == 0.f) {
+                w = n_hi[c] == 0 ? 1.f : (float)((double)(n_hi[c] + n_lo[c]) / (double)n_hi[c]);
+                pos_weight[c] = w;
+                counts[c] += n_un[c];
+            } else counts[c] += B;
+        }
+        pw[c] = w;
+    }
+    __syncthreads();
+    if (STAGE2 && threadIdx.x == 0) {
+        long long tot = (long long)B * annotation_num;
+        for (int c = 0; c < C; ++c)
+            if (active.v[c] == 0.f) tot += n_un[c];
+        counts[C] += tot;
+    }
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < B * C; i += 256) {
+        const int c = i % C;
+        double d = 0.0;
+        if (active.v[c] != 0.f) {
+            acc += bce_logits_dd(z[i], y[i], pw[c], &d) / (double)sup_norm;
+            d /= (double)sup_norm;
+        } else if (STAGE2) {
+            const float p = sigmoidf_(z[i]);
+            const bool hi = p > tao.v[c], lo = p < 1.f - tao.v[c];
+            if (hi || lo) {
+                const double n = (double)n_un[c];
+                acc += bce_logits_dd(z[i], hi ? 1.f : y[i], pw[c], &d) / n;
+                d /= n;
+            }
+        }
+        dz[i] = (float)d;
+    }
+    const double tot = block_sum_d(acc, shd);
+    if (threadIdx.x == 0) *loss = (float)tot;
+}
+void k_loss_cbafed(const float* z, const float* y, ClassVec active, const ClassVec* tao, int B, int C, float sup_norm,
+                   int annotation_num, float* pos_weight, int64_t* counts, float* dz, float* loss, hipStream_t s)
+{
+    if (tao)
+        hipLaunchKernelGGL(loss_cbafed_kernel<true>, dim3(1), dim3(256), 0, s, z, y, active, *tao, B, C, sup_norm, annotation_num,
+                           pos_weight, reinterpret_cast<long long*>(counts), dz, loss);
+    else
+        hipLaunchKernelGGL(loss_cbafed_kernel<false>, dim3(1), dim3(256), 0, s, z, y, active, ClassVec{}, B, C, sup_norm,
+                           annotation_num, pos_weight, reinterpret_cast<long long*>(counts), dz, loss);
 }
 
 // ------------------------------------------------------------ prototypes -------

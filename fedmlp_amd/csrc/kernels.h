@@ -252,6 +252,15 @@ void k_loss_fedirm_sup(const float* z, const float* y, ClassVec pos_w, ClassVec 
 void k_loss_fedirm_rel(const float* z, const float* zt, const float* y, ClassVec pos_w, ClassVec active, int B, int C,
                        float sup_norm, float bs_norm, float cw, const float* target, float* rel_acc, float* dz, float* loss,
                        hipStream_t s);
+// RSCFed / FedNoRo (LA_KD) / CBAFed single-view heads: z, zt, y, dz [B][C]; value and gradient formed in double, rounded once.
+// k_loss_cbafed: tao null = warm-up (pos_weight [C] device, read only; counts untouched); else stage 2 (pos_weight of the missing
+// classes rewritten, counts int64 [C + 1] added to).
+void k_loss_rscfed(const float* z, const float* zt, const float* y, ClassVec pos_w, ClassVec active, int B, int C, float sup_norm,
+                   int n_miss, float* dz, float* loss, hipStream_t s);
+void k_loss_lakd(const float* z, const float* zt, const float* y, ClassVec active, int B, int C, int n_act, float w_kd, float* dz,
+                 float* loss, hipStream_t s);
+void k_loss_cbafed(const float* z, const float* y, ClassVec active, const ClassVec* tao, int B, int C, float sup_norm,
+                   int annotation_num, float* pos_weight, int64_t* counts, float* dz, float* loss, hipStream_t s);
 
 // ---- optimiser -------------------------------------------------------------------
 void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,

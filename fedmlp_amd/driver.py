@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Thin FL driver: the FedMLP / FedAVG / FedAVG+FixMatch / FedLSR / FedIRM rows of the reference's main.py
-(main.py:106-252, with the 'FeMLP' typos normalised) on the HIP engine, one process
+"""Thin FL driver: the FedMLP / FedAVG / FedAVG+FixMatch / FedLSR / FedIRM / RSCFed / FedNoRo / CBAFed rows of the
+reference's main.py (main.py:106-319, with the 'FeMLP' typos normalised) on the HIP engine, one process
 per GPU, clients dealt round-robin over the ranks, aggregation as RCCL all-reduces
 (fedmlp_amd/fedavg.py).  Data is synthetic and HBM-resident (the reference's datasets and
 ImageNet weights are not available offline).
@@ -20,7 +20,8 @@ import torch
 
 def args_parser(argv=None):
     p = argparse.ArgumentParser()      # flag names/defaults follow utils/options.py:4-81
-    p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch", "FedLSR", "FedIRM"])
+    p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch", "FedLSR", "FedIRM", "RSCFed", "FedNoRo",
+                                                      "CBAFed"])
     p.add_argument("--model", default="Resnet18")
     p.add_argument("--seed", type=int, default=1037)
     p.add_argument("--batch_size", type=int, default=32)
@@ -36,6 +37,11 @@ def args_parser(argv=None):
     p.add_argument("--consistency", type=float, default=1)        # utils/options.py:70
     p.add_argument("--consistency_rampup", type=float, default=30)    # utils/options.py:71
     p.add_argument("--ema_decay", type=float, default=0.99)       # utils/options.py:72
+    p.add_argument("--rounds_FedNoRo_warmup", type=int, default=500)  # utils/options.py:74
+    p.add_argument("--begin", type=int, default=10)               # utils/options.py:75 (FedNoRo: ramp-up begin)
+    p.add_argument("--end", type=int, default=499)                # utils/options.py:76
+    p.add_argument("--a", type=float, default=0.8)                # utils/options.py:77
+    p.add_argument("--rounds_CBAFed_warmup", type=int, default=50)    # utils/options.py:79
     p.add_argument("--U", type=float, default=0.7)
     p.add_argument("--L", type=float, default=0.3)
     p.add_argument("--clean_threshold", type=float, default=0.005)
@@ -60,7 +66,33 @@ def args_parser(argv=None):
                    help="globaltest of the new global model every K rounds (main.py:322-357 uses 10), the forward dealt over "
                         "the ranks and the metrics from fm_eval_metrics; 0 = never")
     p.add_argument("--n_test", type=int, default=1024, help="samples of the synthetic test set (--eval_every)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.exp == "RSCFed" and args.n_clients < RSCFED_K:
+        p.error(f"--exp RSCFed draws groups of {RSCFED_K} clients (main.py:116-119): --n_clients must be >= {RSCFED_K}")
+    if args.exp == "FedNoRo" and args.rounds_warmup > args.rounds_FedNoRo_warmup:
+        p.error("--exp FedNoRo: --rounds_warmup may not exceed --rounds_FedNoRo_warmup (after its warm-up the reference "
+                "trains and aggregates nothing, main.py:140-148, 269-272)")
+    return args
+
+
+RSCFED_M, RSCFED_K = 10, 6        # main.py:115-116: M groups of K clients per round
+
+
+def gather_client_states(eng, states, counters, n_clients, rank, world, dist):
+    """Every client's engine-layout state and counters on every rank: client c lives on rank c % world, so slot j of the
+    all-gather carries the clients j * world .. j * world + world - 1 (a rank without a client in the slot sends zeros)."""
+    like = eng.state_tensor()
+    out_s, out_c = [None] * n_clients, [None] * n_clients
+    for j in range((n_clients + world - 1) // world):
+        c = j * world + rank
+        parts = [torch.empty_like(like) for _ in range(world)]
+        dist.all_gather(parts, states[c] if c < n_clients else torch.zeros_like(like))
+        cnts = [None] * world
+        dist.all_gather_object(cnts, counters.get(c))
+        for r in range(world):
+            if j * world + r < n_clients:
+                out_s[j * world + r], out_c[j * world + r] = parts[r], np.asarray(cnts[r])
+    return out_s, out_c
 
 
 def AugmentedDeviceDataset(n, C, hw, seed, device, strong=False):
@@ -167,16 +199,19 @@ class RoundAccumulator:
             self.p += torch.where(torch.from_numpy(pa > 0)[:, None], torch.as_tensor(ret[7]) * n_c, torch.zeros(()))
             self.pn += n_c * act
 
-    def reduce(self, eng, dev, with_tao_proto):
-        """-> (global num_batches_tracked counters, tao or None, Prototype or None); the averaged state is in the engine"""
+    def reduce(self, eng, dev, with_tao_proto, scale=1.0):
+        """-> (global num_batches_tracked counters, tao or None, Prototype or None); the averaged state is in the engine.
+        scale: a factor common to every rank applied to the sums (CBAFed's 1 / sum(data_num)); cnt_float keeps the
+        counters' means before their truncation."""
         from fedmlp_amd.fedavg import fedavg_allreduce, tao_allreduce, proto_allreduce, state_agreement
         eng.state_tensor().copy_(self.acc)
         eng.counters(np.zeros(len(self.acc_cnt), np.int64))      # the counters are reduced as float64 below
-        fedavg_allreduce(eng, 1.0)                               # fm_fedavg_allreduce: ncclAllReduce of the state arena
+        fedavg_allreduce(eng, scale)                             # fm_fedavg_allreduce: ncclAllReduce of the state arena
         agree, worst = state_agreement(eng)                      # every rank starts the next round from the same w_glob
         if not agree:
             raise RuntimeError(f"the ranks' states differ after the FedAvg all-reduce (checksum spread {worst:.3e})")
-        cnt = np.trunc(rank_sum(self.acc_cnt, dev) + 1e-9).astype(np.int64)   # utils/FedAvg.py:13 + load_state_dict
+        self.cnt_float = rank_sum(self.acc_cnt, dev) * scale
+        cnt = np.trunc(self.cnt_float + 1e-9).astype(np.int64)   # utils/FedAvg.py:13 + load_state_dict
         eng.counters(cnt)
         if not with_tao_proto:
             return cnt, None, None
@@ -244,7 +279,8 @@ def main():
         pos = [np.where(ds.targets[:, k] == 1)[0] for k in range(C)]
         a = argparse.Namespace(**vars(args))
         # FedIRM: every client keeps its own EMA model (main.py hands LocalUpdate a teacher_neg; :31, 393-395)
-        ema = build_model(args) if args.exp == "FedIRM" else None
+        # RSCFed likewise (main.py:164-166: train_RSCFed blends into the client's own teacher_neg)
+        ema = build_model(args) if args.exp in ("FedIRM", "RSCFed") else None
         clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C], teacher_neg=ema)
     test = None
     if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
@@ -254,10 +290,25 @@ def main():
     # main.py:200-208: class k is annotated by the clients c with c mod C == k (every rank knows the whole assignment)
     class_active_client_list = [[c for c in range(args.n_clients) if c % C == k] for k in range(C)]
     log = []
+    # RSCFed: ONE generator seeded without the rank offset and stepped alike on every rank: the same DMA everywhere
+    dma_rng = random.Random(args.seed)
+    WC = args.rounds_CBAFed_warmup
+    cba_pt = cba_tao = None                              # CBAFed: pt and tao of main.py:289-300
+    cba_res = cba_res_cnt = None                         # CBAFed: the last blended model (w_glob_res) and its float counters
     for rnd in range(args.rounds_warmup):
         t0 = time.perf_counter()
-        acc = RoundAccumulator(glob, len(glob_cnt), C, args.feature_dim, float(sum(n_all)))
+        cba2 = args.exp == "CBAFed" and rnd >= WC        # stage 2: FedAvg weights data_num_c / sum(data_num), main.py:302
+        # (the sum is known only after every client trained: accumulate with the raw data_num, scale the all-reduce by 1 / sum)
+        acc = RoundAccumulator(glob, len(glob_cnt), C, args.feature_dim, 1.0 if cba2 else float(sum(n_all)))
         losses = []
+        DMA = None
+        if args.exp == "RSCFed":                          # main.py:114-121
+            DMA = [dma_rng.sample(range(args.n_clients), RSCFED_K) for _ in range(RSCFED_M)]
+        if args.exp == "FedNoRo":                         # main.py:127-128
+            from fedmlp_amd.fedavg import consistency_weight
+            weight_kd = consistency_weight(rnd, args.begin, args.end) * args.a
+        rsc_states, rsc_cnt = {}, {}                      # RSCFed: client -> device state / counters
+        cba_counts = {}                                   # CBAFed: client -> (class_num_list, data_num)
         relas = {}                                        # FedIRM: client -> its relation matrix (host), main.py:192-193
         for c in mine:
             loc = clients[c]
@@ -269,6 +320,14 @@ def main():
                 ret = loc.train_FixMatch(rnd, net)
             elif args.exp == "FedLSR":
                 ret = loc.train_FedLSR(rnd, net)          # main.py:161-163
+            elif args.exp == "RSCFed":                    # main.py:164-166
+                ret = loc.train_RSCFed(rnd, net)
+                rsc_states[c], rsc_cnt[c] = eng.state_tensor().clone(), eng.counters().copy()
+            elif args.exp == "FedNoRo":                   # main.py:140-144
+                ret = loc.train_FedNoRo(c, rnd, net, None, weight_kd=weight_kd)
+            elif args.exp == "CBAFed":                    # main.py:149-157
+                ret = loc.train_CBAFed(rnd, net) if rnd < WC else loc.train_CBAFed(rnd, net, pt=cba_pt, tao=cba_tao)
+                cba_counts[c] = (ret[6].clone(), int(ret[7]))
             elif args.exp == "FedIRM":                    # main.py:169-177
                 if rnd < SI - 1:
                     ret = loc.train_FedIRM(rnd, Prototype, None, None, None, net=net)
@@ -281,9 +340,40 @@ def main():
                 ret = loc.train_FedMLP(rnd, tao, Prototype, None, loc.negative_class_list,
                                        loc.active_class_list, net=net)
             losses.append(float(ret[1]))
-            acc.add(n_all[c], eng.state_tensor(), eng.counters(), loc.active_class_list, ret)
-        # ---- aggregation (main.py:216-234): every sum over clients is an RCCL all-reduce in the library
-        glob_cnt, tao_new, proto_new = acc.reduce(eng, dev, with_tao_proto=(args.exp == "FedMLP" and rnd >= S1 - 1))
+            if args.exp != "RSCFed":
+                # (CBAFed's return tuple is as long as a prototype pass's: only FedMLP's carries t and proto)
+                acc.add(cba_counts[c][1] if cba2 else n_all[c], eng.state_tensor(), eng.counters(), loc.active_class_list,
+                        ret if args.exp == "FedMLP" else ())
+        # ---- aggregation (main.py:213-319): every sum over clients is an RCCL all-reduce in the library
+        tao_new = proto_new = None
+        if args.exp == "RSCFed":                          # main.py:213-215
+            glob_cnt = rscfed_round(eng, DMA, rsc_states, rsc_cnt, n_all, rank, world, dist)
+        else:
+            scale = 1.0
+            if args.exp == "CBAFed":                      # every client's class_num_list / data_num on every rank
+                if dist is not None:
+                    parts = [None] * world
+                    dist.all_gather_object(parts, cba_counts)
+                    cba_counts = {k: v for part in parts for k, v in part.items()}
+                if cba2:
+                    scale = 1.0 / float(sum(cba_counts[c][1] for c in range(args.n_clients)))
+            glob_cnt, tao_new, proto_new = acc.reduce(eng, dev, with_tao_proto=(args.exp == "FedMLP" and rnd >= S1 - 1),
+                                                      scale=scale)
+            if args.exp == "CBAFed":
+                from fedmlp_amd.fedavg import cbafed_blend, cbafed_tao
+                w_new, w_res, store = cbafed_blend(rnd, WC)           # main.py:274-288, 303-316
+                cnt_f = acc.cnt_float
+                if w_res != 0.0:
+                    # two rounded products, then their sum: the reference's 0.2 * w + 0.8 * res (no fused multiply-add)
+                    eng.state_tensor().mul_(w_new).add_(cba_res * w_res)
+                    cnt_f = w_new * cnt_f + w_res * cba_res_cnt      # the counters follow the blend in float ...
+                    glob_cnt = np.trunc(cnt_f + 1e-9).astype(np.int64)   # ... and are truncated on load
+                    eng.counters(glob_cnt)
+                if store:
+                    cba_res, cba_res_cnt = eng.state_tensor().clone(), cnt_f
+                if rnd >= WC - 1:                                     # main.py:289-300
+                    order = range(args.n_clients)
+                    cba_pt, cba_tao = cbafed_tao([cba_counts[c][0] for c in order], [cba_counts[c][1] for c in order])
         glob.copy_(eng.state_tensor())
         if tao_new is not None:
             tao, Prototype = tao_new, proto_new
@@ -320,6 +410,29 @@ def main():
     if dist is not None:
         dist.barrier(); dist.destroy_process_group()
     return log
+
+
+def rscfed_round(eng, DMA, states, counters, n_all, rank, world, dist):
+    """main.py:213-215 on the device: RSCFed (utils/FedAvg.py:25-41) over every client's engine-layout state.  One rank: the
+    clients' DeviceStates through fedavg.RSCFed.  More ranks: the states are all-gathered and every rank runs the same
+    rscfed_device, so all of them hold the same global model (checked).  The float counters are truncated on load.
+    Leaves the result in the engine; -> its int64 counters."""
+    from fedmlp_amd import fedavg
+    n_clients = len(n_all)
+    if dist is None:
+        w_locals = [fedavg.DeviceState(eng, states[c], counters[c]) for c in range(n_clients)]
+        agg = fedavg.RSCFed(DMA, w_locals, RSCFED_K, n_all, RSCFED_M)
+        st, cnt_f = agg.tensor, agg.counters
+    else:
+        all_s, all_c = gather_client_states(eng, states, counters, n_clients, rank, world, dist)
+        st, cnt_f = fedavg.rscfed_device(eng, all_s, np.stack(all_c), DMA, n_all)
+    eng.state_tensor().copy_(st)
+    cnt = np.trunc(np.asarray(cnt_f, np.float64) + 1e-9).astype(np.int64)
+    eng.counters(cnt)
+    agree, worst = fedavg.state_agreement(eng)
+    if not agree:
+        raise RuntimeError(f"the ranks' states differ after the RSCFed aggregation (checksum spread {worst:.3e})")
+    return cnt
 
 
 def rank_sum(x, dev):

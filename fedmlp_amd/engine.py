@@ -380,6 +380,83 @@ class Engine:
                                                _ptr(self._rel_arg(rel_acc, "rel_acc")), _ptr(dz), _ptr(loss)))
         return dz, loss
 
+    # ---- RSCFed / FedNoRo / CBAFed: fused steps, and their heads on single-view logits z [B,C]: -> (dz [B,C], loss [1]) ------
+    def step_rscfed(self, x1, x2, y, pos_weight, active_mask, annotation_num, bs_norm, w_teacher, w_student, loss_out):
+        """train_RSCFed's step (utils/local_training.py:733-759) fused: teacher-slot eval forward of x2, train forward of x1,
+        loss_rscfed's head, backward, Adam, then teacher = w_teacher teacher + w_student student over every state entry"""
+        self._check_stream()
+        self._enqueue(weights=True)
+        n = self.n_classes
+        self._draw(x1.shape[0])
+        _lib.check(self.lib.fm_step_rscfed(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0], _lib.fvec(pos_weight, n),
+                                           _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(w_teacher),
+                                           C.c_float(w_student), _ptr(loss_out)))
+
+    def step_fednoro(self, x, y, active_mask, w_kd, loss_out):
+        """train_FedNoRo's warm-up step (:143-160) fused: frozen teacher's eval forward and the train forward of the same x,
+        loss_lakd's head, backward, Adam"""
+        self._check_stream()
+        self._enqueue(weights=True)
+        self._draw(x.shape[0])
+        _lib.check(self.lib.fm_step_fednoro(self.h, _ptr(x), _ptr(y), x.shape[0], _lib.fvec(active_mask, self.n_classes),
+                                            C.c_float(w_kd), _ptr(loss_out)))
+
+    def _cbafed_args(self, tao, pos_weight, counts):
+        n = self.n_classes
+        if tuple(pos_weight.shape) != (n,) or pos_weight.dtype != torch.float32 or not pos_weight.is_contiguous() \
+                or not pos_weight.is_cuda:
+            raise ValueError(f"cbafed: pos_weight must be a contiguous float32 [{n}] device tensor")
+        if counts is not None and (tuple(counts.shape) != (n + 1,) or counts.dtype != torch.int64
+                                   or not counts.is_contiguous() or not counts.is_cuda):
+            raise ValueError(f"cbafed: counts must be a contiguous int64 [{n + 1}] device tensor")
+        if tao is not None and counts is None:
+            raise ValueError("cbafed: stage 2 (tao given) needs counts")
+        return None if tao is None else _lib.fvec(tao, n)
+
+    def step_cbafed(self, x, y, active_mask, annotation_num, bs_norm, tao, pos_weight, counts, loss_out):
+        """train_CBAFed's step (:247-269, 303-340) fused.  tao None: warm-up.  pos_weight [C] float32 and counts [C+1] int64 are
+        DEVICE tensors of the caller's: stage 2 rewrites the missing classes' weights and adds to the counts, with no host read"""
+        self._check_stream()
+        self._enqueue(weights=True)
+        t = self._cbafed_args(tao, pos_weight, counts)
+        self._draw(x.shape[0])
+        _lib.check(self.lib.fm_step_cbafed(self.h, _ptr(x), _ptr(y), x.shape[0], _lib.fvec(active_mask, self.n_classes),
+                                           int(annotation_num), int(bs_norm), t, _ptr(pos_weight), None if counts is None else C.c_void_p(counts.data_ptr()), _ptr(loss_out)))
+
+    def _head_out1(self, z, y, zt=None):
+        B = y.shape[0]
+        for t in (z, y) if zt is None else (z, y, zt):
+            if tuple(t.shape) != (B, self.n_classes) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"single-view head: contiguous float32 [B, {self.n_classes}] tensors are required")
+        return B, torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
+
+    def loss_rscfed(self, z, zt, y, pos_weight, active_mask, annotation_num, bs_norm):
+        self._check_stream()
+        self._enqueue()
+        n = self.n_classes
+        B, dz, loss = self._head_out1(z, y, zt)
+        _lib.check(self.lib.fm_loss_rscfed(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(pos_weight, n), _lib.fvec(active_mask, n),
+                                           int(annotation_num), int(bs_norm), B, _ptr(dz), _ptr(loss)))
+        return dz, loss
+
+    def loss_lakd(self, z, zt, y, active_mask, w_kd):
+        self._check_stream()
+        self._enqueue()
+        B, dz, loss = self._head_out1(z, y, zt)
+        _lib.check(self.lib.fm_loss_lakd(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(active_mask, self.n_classes),
+                                         C.c_float(w_kd), B, _ptr(dz), _ptr(loss)))
+        return dz, loss
+
+    def loss_cbafed(self, z, y, active_mask, annotation_num, bs_norm, tao, pos_weight, counts=None):
+        """tao None: warm-up (pos_weight read, counts untouched); else stage 2 (see step_cbafed)"""
+        self._check_stream()
+        self._enqueue()
+        t = self._cbafed_args(tao, pos_weight, counts)
+        B, dz, loss = self._head_out1(z, y)
+        _lib.check(self.lib.fm_loss_cbafed(self.h, _ptr(z), _ptr(y), _lib.fvec(active_mask, self.n_classes), int(annotation_num),
+                                           int(bs_norm), t, B, _ptr(pos_weight), None if counts is None else C.c_void_p(counts.data_ptr()), _ptr(dz), _ptr(loss)))
+        return dz, loss
+
     # ---- prototypes / tagging ------------------------------------------------------
     # ---- generic split step (rank-4 baselines: loss head computed by the host mirror) -----------
     def forward_train(self, x1, x2=None):

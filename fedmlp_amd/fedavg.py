@@ -371,6 +371,37 @@ def proto_allreduce(proto, n_i, is_active_client_mask, device="cpu", engine=None
         return torch.from_numpy(num.cpu().numpy() / den.cpu().numpy()[:, None])   # 0/0 -> NaN
 
 
+# ---- CBAFed's host arithmetic (main.py:273-316) ---------------------------------------
+def cbafed_tao(class_num_lists, data_nums):
+    """main.py:289-300: pt = sum_clients class_num_list / sum_clients data_num (fp32 tensors, as there), the unbiased
+    standard deviation of pt over the classes, tao = clip(pt + 0.45 - std, 0.55, 0.95).  -> (pt, tao), fp32 tensors [C]."""
+    c_num = torch.zeros(len(class_num_lists[0]))
+    d_num = 0
+    for cn, dn in zip(class_num_lists, data_nums):
+        c_num += torch.as_tensor(cn, dtype=torch.float32)
+        d_num += dn
+    pt = c_num / d_num
+    avg_pt = pt.sum() / len(pt)
+    std_pt = torch.sqrt((1 / (len(pt) - 1)) * (((pt - avg_pt) ** 2).sum()))
+    tao = pt + 0.45 - std_pt
+    tao = torch.where(tao > 0.95, 0.95, tao)
+    tao = torch.where(tao < 0.55, 0.55, tao)
+    return pt, tao
+
+
+def cbafed_blend(rnd, warmup):
+    """The residual blend of main.py:274-288 (warm-up) and :301-316 (stage 2) at round `rnd`:
+    -> (w_new, w_res, store): the round's global model is w_new * FedAvg + w_res * res (w_res = 0: the plain FedAvg, res
+    not read), and store says whether it then becomes the new res.  Warm-up: every 5th round blends 0.2 / 0.8, round 0
+    only stores; stage 2: every 5th round after its first blends 0.5 / 0.5, the first (rnd == warmup) only stores."""
+    k, w = (rnd, 0.2) if rnd < warmup else (rnd - warmup, 0.5)
+    if k % 5 != 0:
+        return 1.0, 0.0, False
+    if k == 0:
+        return 1.0, 0.0, True
+    return w, 1.0 - w, True
+
+
 def consistency_weight(rnd, begin, end):
     """get_current_consistency_weight(rnd, args.begin, args.end) (utils/FedNoRo.py:72-81): the
     sigmoid ramp-up main.py:127-128 multiplies by args.a to get train_FedNoRo's weight_kd."""

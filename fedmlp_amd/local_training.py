@@ -1,6 +1,7 @@
 """LocalUpdate drop-in: the reference's per-client trainer surface
 (utils/local_training.py:26-55 ctor, :628-703 train, :771-825 train_FixMatch,
-:904-1256 train_FedMLP, :1270-1326 train_FedLSR, :344-464 train_FedIRM) driven through the HIP engine.
+:904-1256 train_FedMLP, :1270-1326 train_FedLSR, :344-464 train_FedIRM, :705-769 train_RSCFed, :115-234 train_FedNoRo,
+:236-342 train_CBAFed) driven through the HIP engine.
 
 Same constructor and method signatures, same return tuples (positions 3-4 are
 the reference's junk `_` placeholders -> None), same persistent per-client
@@ -196,16 +197,8 @@ class LocalUpdate(object):
             list(self.negative_class_list), list(self.active_class_list)
 
     # ==== SURVEY 8f rank 4: the other baselines of main.py's --exp switch =========================
-    # Their forward/backward/Adam run on the engine through the split step (fm_forward_train /
-    # fm_backward_step); only the loss head on the [B,C] logits is host-mirror code (torch ops on the
-    # device tensors, gradient by autograd on that [B,C] leaf).
-    @staticmethod
-    def _head_grad(z, loss_fn):
-        zl = z.detach().requires_grad_(True)
-        loss = loss_fn(zl)
-        (dz,) = torch.autograd.grad(loss, zl)
-        return loss.detach(), dz
-
+    # Each step is one fused engine call (fm_step_rscfed / fm_step_fednoro / fm_step_cbafed): forward(s), the loss head on the
+    # [B,C] logits, backward and Adam are enqueued together, with no host read inside a round.
     # ---- LocalUpdate.train_RSCFed (:705-769) ---------------------------------------------------------
     def train_RSCFed(self, rnd, net):
         a = self.args
@@ -220,25 +213,16 @@ class LocalUpdate(object):
         y = self._labels_dev(eng, self._y_masked, "y_masked")
         n = len(self.idxs)
         act, neg = list(self.active_class_list), list(self.negative_class_list)
-        pw = torch.tensor(self.loss_w, dtype=torch.float32, device=eng.device)
-        F = torch.nn.functional
+        amask = self._mask(act)
         epoch_loss = []
         for _ in range(a.local_ep):
             batches = _batches(self._order(n), a.batch_size)
             losses = torch.zeros(len(batches), device=eng.device)
             for k, pos in enumerate(batches):
-                yb = self._rows(y, pos, eng)
-                _, zt = eng.forward_eval(self._images(eng, "image_aug_2", pos), teacher=True)
-                _, z1 = eng.forward_train(self._images(eng, "image_aug_1", pos))
-
-                def head(z):
-                    l = F.binary_cross_entropy_with_logits(z, yb, pos_weight=pw, reduction="none")
-                    sup = l[:, act].sum() / (a.batch_size * a.annotation_num)
-                    return sup + F.mse_loss(torch.sigmoid(z)[:, neg], torch.sigmoid(zt)[:, neg])
-                loss, dz = self._head_grad(z1, head)
-                eng.backward_step(dz)
-                eng.teacher_axpby(1 - 0.001, 0.001)                 # :751-759
-                losses[k] = loss
+                # teacher(view 2), student(view 1), the head, backward, Adam and the EMA blend of :751-759 in one call
+                eng.step_rscfed(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
+                                self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num, a.batch_size,
+                                1 - 0.001, 0.001, losses[k:k + 1])
                 self.iter_num += 1
             self.epoch += 1
             epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
@@ -377,26 +361,13 @@ class LocalUpdate(object):
         for c in neg:                                               # :136-137
             self.class_num_list[c] = 0
         w_kd = float(weight_kd)
-        F = torch.nn.functional
+        amask = self._mask(act)
         epoch_loss = []
         for _ in range(a.local_ep):
             batches = _batches(self._order(n), a.batch_size)
             losses = torch.zeros(len(batches), device=eng.device)
             for k, pos in enumerate(batches):
-                x, yb = self._images(eng, "image", pos), self._rows(y, pos, eng)
-                _, zt = eng.forward_eval(x, teacher=True)
-                soft = torch.sigmoid(zt / 0.8)
-                _, z = eng.forward_train(x)
-
-                def head(zz):
-                    p = torch.sigmoid(zz)
-                    B = p.shape[0]
-                    bce = F.binary_cross_entropy(p, yb, reduction="none")[:, act].sum() / (B * len(act))
-                    kl = F.mse_loss(p, soft, reduction="none")[:, neg].sum() / (B * len(neg))
-                    return w_kd * kl + (1 - w_kd) * bce
-                loss, dz = self._head_grad(z, head)
-                eng.backward_step(dz)
-                losses[k] = loss
+                eng.step_fednoro(self._images(eng, "image", pos), self._rows(y, pos, eng), amask, w_kd, losses[k:k + 1])
                 self.iter_num += 1
             self.epoch += 1
             epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
@@ -412,52 +383,37 @@ class LocalUpdate(object):
         n = len(self.idxs)
         act, neg = list(self.active_class_list), list(self.negative_class_list)
         warm = rnd < a.rounds_CBAFed_warmup
-        class_num_list = torch.zeros(a.n_classes)
+        C = a.n_classes
+        amask = self._mask(act)
+        class_num_list = torch.zeros(C)
         data_num = 0
-        F = torch.nn.functional
+        # the client's loss_w and the round's counts ([C] class_num_list, then data_num) live on the device for the call: stage 2
+        # decides the pseudo-labels, rewrites the missing classes' weights and counts inside the step (:303-320)
+        pw = torch.tensor(self.loss_w, dtype=torch.float32, device=eng.device)
+        counts = torch.zeros(C + 1, dtype=torch.int64, device=eng.device)
+        tao_v = None if warm else [float(t) for t in tao]
         epoch_loss = []
         for _ in range(a.local_ep):
             batches = _batches(self._order(n), a.batch_size)
             losses = torch.zeros(len(batches), device=eng.device)
             for k, pos in enumerate(batches):
-                yb = self._rows(y, pos, eng)
-                _, z = eng.forward_train(self._images(eng, "image", pos))
-                labels, idx_neg = yb, []
+                eng.step_cbafed(self._images(eng, "image", pos), self._rows(y, pos, eng), amask, a.annotation_num,
+                                a.batch_size, tao_v, pw, counts, losses[k:k + 1])
                 if warm:
                     data_num += len(pos)
-                else:
-                    prob = torch.sigmoid(z)
-                    labels = yb.clone()
-                    for i in neg:                                    # :303-316 (one host sync per class, like the reference)
-                        hi, lo = prob[:, i] > tao[i], prob[:, i] < (1 - tao[i])
-                        noise_num, clean_num = int(hi.sum()), int(lo.sum())
-                        labels[:, i] = torch.where(hi, torch.ones_like(labels[:, i]), labels[:, i])
-                        pseudo = torch.where(hi | lo)[0]
-                        idx_neg.append(pseudo)
-                        class_num_list[i] += len(pseudo)
-                        data_num += len(pseudo)
-                        self.loss_w[i] = 1 if noise_num == 0 else (noise_num + clean_num) / noise_num
-                    for i in act:
-                        class_num_list[i] += len(pos)
-                    data_num += len(pos) * a.annotation_num
-                pw = torch.tensor(self.loss_w, dtype=torch.float32, device=eng.device)
-
-                def head(zz):
-                    l = F.binary_cross_entropy_with_logits(zz, labels, pos_weight=pw, reduction="none")
-                    loss = l[:, act].sum() / (a.batch_size * a.annotation_num)
-                    for kk, i in enumerate(neg if not warm else []):
-                        if len(idx_neg[kk]) != 0:
-                            loss = loss + l[idx_neg[kk], i].sum() / len(idx_neg[kk])
-                    return loss
-                loss, dz = self._head_grad(z, head)
-                eng.backward_step(dz)
-                losses[k] = loss
                 self.iter_num += 1
             if warm:
                 for c in act:
                     class_num_list[c] = data_num
             self.epoch += 1
             epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
+        if not warm:
+            # one transfer at the end of the call: loss_w, class_num_list, data_num
+            back = torch.cat([pw.double(), counts.double()]).cpu()
+            for i in neg:
+                self.loss_w[i] = float(back[i])
+            class_num_list += back[C:2 * C].float()
+            data_num = int(back[2 * C])
         net.mark_trained()
         return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, class_num_list, data_num
 

@@ -243,6 +243,54 @@ int fm_loss_fedirm_rel(fm_engine* e, const float* z_dev, const float* zt_dev, co
 int fm_step_fedlsr(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
                    const float* pos_weight_host, float mix1, float beta, float* loss_dev);
 
+/* ---- RSCFed, FedNoRo and CBAFed (utils/local_training.py:705-769, 115-234, 236-342) ---------
+ * Three loss heads on SINGLE-VIEW logits z_dev [B][C], y_dev [B][C], with fm_loss_fedirm_sup's conventions: one launch on the
+ * engine's stream, no synchronisation, no atomics, the same bits from run to run; every element of dz_dev [B][C] is written
+ * (exact zeros where an element is not in the loss) and the scalar *loss_dev.  Value and gradient are formed in double from the
+ * fp32 logits and rounded once.  There must be at least one active and one missing class (FM_ERR_ARG otherwise: torch forms
+ * 0/0 or the mean of an empty tensor there), and bs_norm annotation_num < 2^24.
+ *
+ * fm_loss_rscfed (:719, 740-743): sum over the active classes of BCEWithLogits(pos_weight)(z, y) / (bs_norm annotation_num)
+ *   + the mean over the actual B |missing| elements of (sigmoid z - sigmoid zt)^2.  zt_dev [B][C] (the EMA teacher's logits
+ *   of view 2) gets no gradient.
+ * fm_loss_lakd (LA_KD.forward, utils/FedNoRo.py:35-38, with train_FedNoRo's soft target): p = sigmoid(z),
+ *   soft = sigmoid(zt / 0.8f); (1 - w_kd) sum_active BCE(p, y) / (B |active|) + w_kd sum_missing (p - soft)^2 / (B |missing|),
+ *   the log clamped at -100 and binary_cross_entropy's backward (divisor max(p (1 - p), 1e-12)); both divisors use the actual B.
+ *   Because p is formed in double, the clamp binds where sigmoid(z) rounds to 1 in double (|z| > 36.7), not in fp32 (|z| > 16.6).
+ * fm_loss_cbafed (:247-269 warm-up, :303-333 stage 2): pos_weight_dev is a DEVICE vector [C], the client's loss_w, owned by the
+ *   caller (one handle serves several clients).
+ *   tao_host NULL (warm-up): the active-class BCEWithLogits(pos_weight) / (bs_norm annotation_num); pos_weight_dev is only
+ *   read, counts_dev is not touched (may be NULL).
+ *   tao_host [C] (stage 2): every decision of :303-316 is made on the device.  Per missing class i: hi = sigmoid(z) > tao[i],
+ *   lo = sigmoid(z) < 1.f - tao[i] (fp32 compares), noise = #hi, clean = #lo; the label is 1 where hi (in registers: y_dev is
+ *   not written); pos_weight_dev[i] = noise == 0 ? 1 : (float)((double)(noise + clean) / noise), written BEFORE the loss terms
+ *   are formed (the reference rebuilds its criterion after the loop); with n_i = #(hi or lo) > 0 the class adds the sum over
+ *   those rows of l[row][i] / n_i.  The active term is the warm-up's.  counts_dev int64 [C + 1] is ADDED to: n_i per missing
+ *   class, B per active class, and sum n_i + B annotation_num in counts[C] (class_num_list and data_num of :312-320).
+ * The fused steps return FM_ERR_ARG under a requires_grad mask, and give the bits of the split sequence
+ * fm_forward_eval(teacher) / fm_forward_train -> fm_loss_* -> fm_backward_step (-> fm_teacher_axpby):
+ * fm_step_rscfed: eval forward of x2 through the teacher slot (side lane where the engine has one), train forward of x1,
+ *   fm_loss_rscfed, backward, Adam, then fm_teacher_axpby(w_teacher, w_student) over every state entry, reading the post-Adam
+ *   student.  The next step's teacher forward sees the blended teacher.  With two lanes both views share the input staging:
+ *   2 B <= max_images there, else the step runs on one lane.
+ * fm_step_fednoro: teacher-slot eval forward and student train forward of the same x, fm_loss_lakd, backward, Adam.
+ * fm_step_cbafed: one-view train forward, fm_loss_cbafed, backward, Adam; no host read. */
+int fm_loss_rscfed(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* pos_weight_host,
+                   const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, int32_t B, float* dz_dev, float* loss_dev);
+int fm_loss_lakd(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* active_mask_host, float w_kd,
+                 int32_t B, float* dz_dev, float* loss_dev);
+int fm_loss_cbafed(fm_engine* e, const float* z_dev, const float* y_dev, const float* active_mask_host, int32_t annotation_num,
+                   int32_t bs_norm, const float* tao_host, int32_t B, float* pos_weight_dev, int64_t* counts_dev, float* dz_dev,
+                   float* loss_dev);
+int fm_step_rscfed(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
+                   const float* pos_weight_host, const float* active_mask_host, int32_t annotation_num, int32_t bs_norm,
+                   float w_teacher, float w_student, float* loss_dev);
+int fm_step_fednoro(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B, const float* active_mask_host, float w_kd,
+                    float* loss_dev);
+int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B, const float* active_mask_host,
+                   int32_t annotation_num, int32_t bs_norm, const float* tao_host, float* pos_weight_dev, int64_t* counts_dev,
+                   float* loss_dev);
+
 /* ---- prototype + t pass (utils/local_training.py:971-1002, 1208-1250) ---- */
 /* Accumulators live in the engine: proto sums [2C,D], counts [2C], t counts [C]. */
 int fm_proto_reset(fm_engine* e);
