@@ -786,13 +786,16 @@ void k_count_sign(const float* sim, int64_t N, int* counts, hipStream_t s)
     hipLaunchKernelGGL(count_sign_kernel, dim3(1), dim3(256), 0, s, sim, N, counts);
 }
 
-// rank of element i in a stable descending / ascending sort (first position wins ties)
+// rank of element i in a stable descending / ascending sort (first position wins ties).  A NaN element is left out: it is
+// ranked nowhere and selects nothing (every comparison with it is false, so the others' ranks are those of the row without it;
+// its own rank would come out 0 and race with the true largest / smallest for slot 0)
 __global__ void rank_select_kernel(const float* __restrict__ sim, int64_t N, int ktop, int kbot,
                                    int* __restrict__ top, int* __restrict__ bot)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const float v = sim[i];
+    if (v != v) return;
     int rd = 0, ra = 0;
     for (int64_t j = 0; j < N; ++j) {
         const float u = sim[j];
@@ -836,6 +839,7 @@ __global__ void rank_select_rows_kernel(const float* __restrict__ sim, int64_t N
     const float* sr = sim + (size_t)k * N;
     const int* rk = rows ? rows + (size_t)k * stride : nullptr;
     const float v = sr[rk ? rk[i] : i];
+    if (v != v) return;                                   // NaN: left out, as in rank_select_kernel
     int rd = 0, ra = 0;
     for (int j = 0; j < n; ++j) {
         const float u = sr[rk ? rk[j] : j];

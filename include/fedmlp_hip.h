@@ -315,7 +315,11 @@ int fm_cos_tag(fm_engine* e, const float* feat_dev, int64_t N, const float* prot
  * utils/local_training.py:1061-1075): n_clean = #(sim>=0), n_noise = #(sim<0),
  * k_top = (int)(clean_thr*n_clean), k_bot = (int)(noise_thr*n_noise); writes the
  * positions of the k_top largest (descending, first position wins ties) and the
- * k_bot smallest (ascending) values to host arrays of capacity cap. */
+ * k_bot smallest (ascending) values to host arrays of capacity cap.
+ * NaN: a NaN element counts as neither >= 0 nor < 0, is NEVER selected and is ranked nowhere -- the picks are those of the
+ * row with its NaN elements removed, mapped back to positions (the reference's sorted() has no defined answer on NaN keys;
+ * an all-zero feature row makes a NaN in every class).  -0.0 counts as >= 0 and ties with +0.0.  Thresholds are meant to
+ * lie in [0, 1]; entries of top_host / bot_host beyond n_top / n_bot are not written. */
 int fm_select_topk(fm_engine* e, const float* sim_dev, int64_t N, double clean_thr,
                    double noise_thr, int32_t cap, int32_t* top_host, int32_t* n_top,
                    int32_t* bot_host, int32_t* n_bot);
@@ -323,7 +327,8 @@ int fm_select_topk(fm_engine* e, const float* sim_dev, int64_t N, double clean_t
  * and one device-to-host read.  sim_dev [n_cls][N] (fm_cos_tag's output); class k's pool = the pool_n_host[k] positions
  * pool_rows_host[k*stride ..] of its similarity row, in pool order (find_indices_in_a, :901-902; ties go to the earlier pool
  * position), or all N rows when pool_rows_host is NULL.  Writes pool POSITIONS: top_host / bot_host [n_cls][cap],
- * n_top / n_bot [n_cls]. */
+ * n_top / n_bot [n_cls].  NaN elements of a pool are left out exactly as in fm_select_topk: never selected, ranked nowhere; a
+ * fully-NaN class selects nothing. */
 int fm_select_topk_rows(fm_engine* e, const float* sim_dev, int64_t N, int32_t n_cls, const int32_t* pool_rows_host,
                         const int32_t* pool_n_host, int32_t stride, double clean_thr, double noise_thr, int32_t cap,
                         int32_t* top_host, int32_t* n_top, int32_t* bot_host, int32_t* n_bot);
