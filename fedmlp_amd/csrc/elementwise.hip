@@ -1,11 +1,11 @@
 // HBM-bound kernels of the FedMLP engine: layout changes, BatchNorm (train/eval,
-// forward/backward), stem max-pool, Adam, split-K slab reduction.  gfx950.
+// forward/backward), stem max-pool, split-K slab reduction.  gfx950.
 //
 // Reference ops replaced (all reached through net(images) / loss.backward() /
 // optimizer.step() in utils/local_training.py:657-675, 937-966, 1178-1192):
 // nn.BatchNorm2d (train: batch statistics + running-stat update, momentum 0.1,
-// eps 1e-5; eval: folded affine), F.relu, residual add, nn.MaxPool2d(3,2,1),
-// torch.optim.Adam (coupled L2 weight decay).  Roofline: HBM bandwidth; every
+// eps 1e-5; eval: folded affine), F.relu, residual add, nn.MaxPool2d(3,2,1);
+// torch.optim.Adam is in optim.hip.  Roofline: HBM bandwidth; every
 // kernel moves 16 B per lane, NHWC so that the channel axis is contiguous.
 #include <stdlib.h>
 #include "common.h"
@@ -339,7 +339,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, int groups, 
                                    const int* __restrict__ skip)
 {
     __shared__ double red[2][4][64];
-    // (a kernel of this step reported a lost part, adam_kernel: the running statistics stay as they are too)
+    // (a kernel of this step reported a lost part, optim.hip's skip word: the running statistics stay as they are too)
     const bool keep_running = skip && *skip;
     const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const bool chv = blockIdx.x * 64 + cl < C;             // C need not be a multiple of 64
@@ -958,61 +958,7 @@ void k_bn_bwd_apply(const float* dz, const float* z, const float* y, const float
                        pix_per_group, C, mask_scale, mask_shift);
 }
 
-// ------------------------------------------------------------ optimiser --------
-// torch.optim.Adam single-tensor update order (exp_avg.lerp_, exp_avg_sq mul/addcmul,
-// denom = sqrt(v)/sqrt(bc2) + eps, p -= lr/bc1 * m/denom), L2 decay folded into g.
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, int64_t n4, float lr, float b1, float b2, float eps, float wd,
-                            float bc1, float bc2_sqrt, const int* __restrict__ skip)
-{
-    // a kernel of this step reported a lost part (pconv.hip's bounded stream-K wait): the gradients are poisoned, the weights
-    // and moments stay as they are; the host learns of it through the word's mapped twin at its next call
-    if (skip && *skip) return;
-    const float step = lr / bc1;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
-        f32x4 gg = reinterpret_cast<const f32x4*>(g)[i] + wd * pp;
-        f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
-        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-        mm = mm + (1.f - b1) * (gg - mm);
-        vv = vv * b2 + (1.f - b2) * gg * gg;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
-            pp[k] = pp[k] - step * (mm[k] / den);
-        }
-        reinterpret_cast<f32x4*>(p)[i] = pp;
-        reinterpret_cast<f32x4*>(m)[i] = mm;
-        reinterpret_cast<f32x4*>(v)[i] = vv;
-    }
-}
-void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-            float wd, float bc1, float bc2_sqrt, hipStream_t s, const int* skip)
-{
-    const int64_t n4 = n / 4;     // engine pads the parameter arena to a multiple of 4
-    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, p, g, m, v, n4, lr, b1, b2,
-                       eps, wd, bc1, bc2_sqrt, skip);
-}
-
-// gradient accumulator of the autograd path (fm_backward_grads): acc = g when the accumulator is empty (a copy, so one backward
-// after fm_zero_grad holds exactly the fused path's gradients), acc += g after it; one streaming float4 pass over the arena
-__global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4, int copy,
-                                       const int* __restrict__ skip)
-{
-    if (skip && *skip) return;      // a lost stream-K part poisoned g (adam_kernel): the accumulator stays as it is
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-        reinterpret_cast<f32x4*>(acc)[i] = copy ? gg : reinterpret_cast<const f32x4*>(acc)[i] + gg;
-    }
-}
-void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip)
-{
-    const int64_t n4 = n / 4;     // engine pads the parameter arena to a multiple of 4
-    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, acc, g, n4, copy ? 1 : 0, skip);
-}
-
+// ------------------------------------------------------- slab reduction --------
 // out[i] = sum_s slab[s][i]; block = 64 float4 columns x 16 split lanes, lanes combined through
 // LDS in a fixed order (deterministic), so a long split axis does not serialise on one thread.
 __global__ void reduce_slabs_kernel(const float* __restrict__ slab, float* __restrict__ out, int splits, int64_t n4)

@@ -1694,8 +1694,6 @@ void stem_dgrad_views(fm_engine* e, Lane& L, const void* dy, int groups, int B, 
         if (dx[g]) stem_dgrad(e, L, (const char*)dy + g * view_bytes, dx[g], B, false);
 }
 
-// optimizer.step(): one fused kernel over the whole trainable arena (torch Adam with coupled L2); g = e->grad (fused steps)
-// or the autograd path's accumulator (fm_adam_step)
 // what every optimizer step ends with: the student's weights moved on the main lane
 void weights_stepped(fm_engine* e)
 {
@@ -1703,32 +1701,45 @@ void weights_stepped(fm_engine* e)
     e->wpack_dirty = true;
     ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
 }
+// The scalars of step t of each rule (optim.hip), for the flat steps and, per group, the grouped ones: what torch forms in double
+// is formed in double here, from the fp32 values of fm_adam / fm_sgd.
+OptAdamHp adam_hp(const fm_adam& hp, int64_t t)
+{
+    const double bc1 = 1.0 - pow((double)hp.beta1, (double)t), bc2 = 1.0 - pow((double)hp.beta2, (double)t);
+    return {hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay, (float)bc1, (float)sqrt(bc2)};
+}
+OptAdamWHp adamw_hp(const fm_adam& hp, int64_t t)
+{
+    const double bc1 = 1.0 - pow((double)hp.beta1, (double)t), bc2 = 1.0 - pow((double)hp.beta2, (double)t);
+    return {(float)(1.0 - (double)hp.lr * (double)hp.weight_decay), (float)((double)hp.lr / bc1), hp.beta2, hp.eps, (float)sqrt(bc2),
+            1.0 - (double)hp.beta1};
+}
+// first: the first step after a reset (torch: the momentum buffer does not exist yet)
+OptSgdHp sgd_hp(const fm_sgd& hp, bool first)
+{
+    return {(double)hp.lr, (double)hp.momentum, 1.0 - (double)hp.dampening, (double)hp.weight_decay,
+            (hp.momentum != 0.f && hp.nesterov != 0) ? 1 : 0, hp.momentum == 0.f ? 0 : (first ? 1 : 2)};
+}
+// optimizer.step(): one kernel over the whole trainable arena.  torch Adam with coupled L2 and the handle's hyper-parameters:
+// g = e->grad (fused steps) or the autograd path's accumulator (fm_adam_step)
 void adam_step(fm_engine* e, const float* g)
 {
     e->adam_t += 1;
-    const double bc1 = 1.0 - pow((double)e->hp.beta1, (double)e->adam_t);
-    const double bc2 = 1.0 - pow((double)e->hp.beta2, (double)e->adam_t);
-    k_adam(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, e->hp.lr, e->hp.beta1, e->hp.beta2, e->hp.eps,
-           e->hp.weight_decay, (float)bc1, (float)sqrt(bc2), e->main.st, e->dev_err);
+    k_adam(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, adam_hp(e->hp, e->adam_t), e->main.st, e->dev_err);
     weights_stepped(e);
 }
 // torch.optim.AdamW / torch.optim.SGD over the autograd path's accumulator, with the handle's moment arenas and step count
-// (optim.hip); the scalars that torch forms in double are formed in double here
 void adamw_step(fm_engine* e, const fm_adam& hp)
 {
     e->adam_t += 1;
-    const double bc1 = 1.0 - pow((double)hp.beta1, (double)e->adam_t);
-    const double bc2 = 1.0 - pow((double)hp.beta2, (double)e->adam_t);
-    k_adamw(e->student.state, e->gacc, e->adam_m, e->adam_v, (int64_t)e->NP, (float)(1.0 - (double)hp.lr * (double)hp.weight_decay),
-            (float)((double)hp.lr / bc1), hp.beta1, hp.beta2, hp.eps, (float)sqrt(bc2), e->main.st, e->dev_err);
+    k_adamw(e->student.state, e->gacc, e->adam_m, e->adam_v, (int64_t)e->NP, adamw_hp(hp, e->adam_t), e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void sgd_step(fm_engine* e, const fm_sgd& hp)
 {
-    const bool first = e->adam_t == 0;        // torch: the momentum buffer does not exist yet
+    const bool first = e->adam_t == 0;
     e->adam_t += 1;
-    k_sgd(e->student.state, e->gacc, e->adam_m, (int64_t)e->NP, hp.lr, hp.momentum, 1.0 - (double)hp.dampening,
-          hp.weight_decay, hp.nesterov != 0, first, e->main.st, e->dev_err);
+    k_sgd(e->student.state, e->gacc, e->adam_m, (int64_t)e->NP, sgd_hp(hp, first), e->main.st, e->dev_err);
     weights_stepped(e);
 }
 // both moment arenas and the step count: a fresh optimizer of any kind
@@ -1744,6 +1755,12 @@ const char* sgd_bad(const fm_sgd* hp)
     if (!(hp->lr >= 0.f && hp->momentum >= 0.f && hp->weight_decay >= 0.f)) return "fm_sgd: lr, momentum and weight_decay must be >= 0";
     if (!(hp->dampening == hp->dampening)) return "fm_sgd: dampening is NaN";
     if (hp->nesterov && !(hp->momentum > 0.f && hp->dampening == 0.f)) return "fm_sgd: nesterov needs momentum > 0 and dampening = 0";
+    return nullptr;
+}
+const char* adam_bad(const fm_adam* hp)
+{
+    if (!(hp->lr >= 0.f && hp->eps >= 0.f && hp->weight_decay >= 0.f)) return "fm_adam: lr, eps and weight_decay must be >= 0";
+    if (!(hp->beta1 >= 0.f && hp->beta1 < 1.f && hp->beta2 >= 0.f && hp->beta2 < 1.f)) return "fm_adam: betas must be in [0, 1)";
     return nullptr;
 }
 // the L2 norm of the accumulator into *norm (device), deterministic two-stage sum (optim.hip)
@@ -1843,17 +1860,13 @@ OptSel mask_sel(const fm_engine* e, const int32_t* tr)
         if (e->opt_ent[i] >= 0) opt_sel_set(sel, e->opt_ent[i], tr[i] != 0 ? 0u : 1u);
     return sel;
 }
-// The grouped steps: hp[i] belongs to group i of fm_optim_groups' table; the scalars torch forms in double are formed per group
-// exactly as adam_step / adamw_step / sgd_step form them.  One step count per engine, as there.
+// The grouped steps: hp[i] belongs to group i of fm_optim_groups' table, and each group's scalars come from the function the flat
+// step calls (adam_hp / adamw_hp / sgd_hp).  One step count per engine, as there.
 void adam_step_groups(fm_engine* e, const fm_adam* hp, int n)
 {
     e->adam_t += 1;
     OptAdamArgs a{};
-    for (int i = 0; i < n; ++i) {
-        const double bc1 = 1.0 - pow((double)hp[i].beta1, (double)e->adam_t);
-        const double bc2 = 1.0 - pow((double)hp[i].beta2, (double)e->adam_t);
-        a.hp[i] = {hp[i].lr, hp[i].beta1, hp[i].beta2, hp[i].eps, hp[i].weight_decay, (float)bc1, (float)sqrt(bc2)};
-    }
+    for (int i = 0; i < n; ++i) a.hp[i] = adam_hp(hp[i], e->adam_t);
     k_adam_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
@@ -1861,12 +1874,7 @@ void adamw_step_groups(fm_engine* e, const fm_adam* hp, int n)
 {
     e->adam_t += 1;
     OptAdamWArgs a{};
-    for (int i = 0; i < n; ++i) {
-        const double bc1 = 1.0 - pow((double)hp[i].beta1, (double)e->adam_t);
-        const double bc2 = 1.0 - pow((double)hp[i].beta2, (double)e->adam_t);
-        a.hp[i] = {(float)(1.0 - (double)hp[i].lr * (double)hp[i].weight_decay), (float)((double)hp[i].lr / bc1), hp[i].beta2, hp[i].eps,
-                   (float)sqrt(bc2), 1.0 - (double)hp[i].beta1};
-    }
+    for (int i = 0; i < n; ++i) a.hp[i] = adamw_hp(hp[i], e->adam_t);
     k_adamw_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
@@ -1875,9 +1883,7 @@ void sgd_step_groups(fm_engine* e, const fm_sgd* hp, int n)
     const bool first = e->adam_t == 0;
     e->adam_t += 1;
     OptSgdArgs a{};
-    for (int i = 0; i < n; ++i)
-        a.hp[i] = {(double)hp[i].lr, (double)hp[i].momentum, 1.0 - (double)hp[i].dampening, (double)hp[i].weight_decay,
-                   (hp[i].momentum != 0.f && hp[i].nesterov != 0) ? 1 : 0, hp[i].momentum == 0.f ? 0 : (first ? 1 : 2)};
+    for (int i = 0; i < n; ++i) a.hp[i] = sgd_hp(hp[i], first);
     k_sgd_groups(e->student.state, e->gacc, e->adam_m, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
@@ -3536,8 +3542,8 @@ int fm_sgd_step(fm_engine* e, const fm_sgd* hp)
 int fm_adamw_step(fm_engine* e, const fm_adam* hp)
 {
     ARGCHK(e && hp, "null");
-    ARGCHK(hp->lr >= 0.f && hp->eps >= 0.f && hp->weight_decay >= 0.f, "fm_adamw_step: lr, eps and weight_decay must be >= 0");
-    ARGCHK(hp->beta1 >= 0.f && hp->beta1 < 1.f && hp->beta2 >= 0.f && hp->beta2 < 1.f, "fm_adamw_step: betas must be in [0, 1)");
+    const char* bad = adam_bad(hp);
+    ARGCHK(!bad, (bad ? bad : ""));
     if (!e->gacc_full) return FM_OK;
     adamw_step(e, *hp);
     STEP_DONE(e);
@@ -3591,8 +3597,8 @@ int fm_adam_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
     ARGCHK(e && hp, "null");
     ARGCHK(n >= 1 && n == e->n_groups, "fm_adam_step_groups: n must be the group count of the installed fm_optim_groups table");
     for (int i = 0; i < n; ++i) {
-        ARGCHK(hp[i].lr >= 0.f && hp[i].eps >= 0.f && hp[i].weight_decay >= 0.f, "fm_adam_step_groups: lr, eps and weight_decay must be >= 0");
-        ARGCHK(hp[i].beta1 >= 0.f && hp[i].beta1 < 1.f && hp[i].beta2 >= 0.f && hp[i].beta2 < 1.f, "fm_adam_step_groups: betas must be in [0, 1)");
+        const char* bad = adam_bad(&hp[i]);
+        ARGCHK(!bad, (bad ? bad : ""));
     }
     if (!e->gacc_full) return FM_OK;
     adam_step_groups(e, hp, n);
@@ -3605,8 +3611,8 @@ int fm_adamw_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
     ARGCHK(e && hp, "null");
     ARGCHK(n >= 1 && n == e->n_groups, "fm_adamw_step_groups: n must be the group count of the installed fm_optim_groups table");
     for (int i = 0; i < n; ++i) {
-        ARGCHK(hp[i].lr >= 0.f && hp[i].eps >= 0.f && hp[i].weight_decay >= 0.f, "fm_adamw_step_groups: lr, eps and weight_decay must be >= 0");
-        ARGCHK(hp[i].beta1 >= 0.f && hp[i].beta1 < 1.f && hp[i].beta2 >= 0.f && hp[i].beta2 < 1.f, "fm_adamw_step_groups: betas must be in [0, 1)");
+        const char* bad = adam_bad(&hp[i]);
+        ARGCHK(!bad, (bad ? bad : ""));
     }
     if (!e->gacc_full) return FM_OK;
     adamw_step_groups(e, hp, n);

@@ -262,20 +262,22 @@ void k_loss_lakd(const float* z, const float* zt, const float* y, ClassVec activ
 void k_loss_cbafed(const float* z, const float* y, ClassVec active, const ClassVec* tao, int B, int C, float sup_norm,
                    int annotation_num, float* pos_weight, int64_t* counts, float* dz, float* loss, hipStream_t s);
 
-// ---- optimiser -------------------------------------------------------------------
-void k_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
-            float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s, const int* skip = nullptr);   // *skip != 0: no update
+// ---- split-K slabs ---------------------------------------------------------------
 void k_reduce_slabs(const float* slab, float* out, int splits, int64_t n, hipStream_t s);
-// acc = g (copy) or acc += g over n floats (n a multiple of 4); *skip != 0: no update
+// ---- optimizers (optim.hip): n floats (a multiple of 4), *skip != 0: nothing is written ----
+// The scalars of one step of each rule, formed on the host in double where torch forms them in double (engine.hip: adam_hp /
+// adamw_hp / sgd_hp); the flat launchers take one, the parameter-group launchers one per group.
+struct OptAdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };                       // torch.optim.Adam, coupled L2
+struct OptAdamWHp { float decay, step, b2, eps, bc2_sqrt; double one_minus_b1; };     // decay = 1 - lr wd, step = lr / bc1
+// mode 0: momentum == 0, buf is left alone; 1: first step after a reset (buf = g + wd p, no dampening); 2: every later step.
+// The chain runs in double, one rounding per stored value.
+struct OptSgdHp { double lr, momentum, one_minus_damp, wd; int nesterov, mode; };
+// the fused steps' optimizer (g = the step's gradients) and fm_adam_step's (g = the accumulator): adam_kernel in traces
+void k_adam(float* p, const float* g, float* m, float* v, int64_t n, const OptAdamHp& hp, hipStream_t s, const int* skip = nullptr);
+void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, const OptAdamWHp& hp, hipStream_t s, const int* skip = nullptr);
+void k_sgd(float* p, const float* g, float* buf, int64_t n, const OptSgdHp& hp, hipStream_t s, const int* skip = nullptr);
+// acc = g (copy) or acc += g
 void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip = nullptr);
-// ---- optimizers of the autograd path (optim.hip): n floats (a multiple of 4), *skip != 0: nothing is written ----
-// torch.optim.SGD: momentum == 0 leaves buf alone; first = first step after a reset (buf = g + wd p, no dampening); the chain
-// runs in double, one rounding per stored value
-void k_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, double one_minus_damp, float wd,
-           bool nesterov, bool first, hipStream_t s, const int* skip = nullptr);
-// torch.optim.AdamW: decay = 1 - lr wd, step = lr / bc1
-void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float decay, float step, float b1, float b2, float eps,
-             float bc2_sqrt, hipStream_t s, const int* skip = nullptr);
 // *norm = sqrt(sum g^2), deterministic: every thread of stage 1 adds GRAD_NORM_F4 squares per vector component in fp32, a block
 // folds its 256 threads in a fixed tree of GRAD_NORM_TREE fp32 levels (2 over the components, 6 over the lanes, 2 over the
 // waves) into part[block] (double, grad_norm_parts(n) of them); one block sums those in double
@@ -296,10 +298,7 @@ void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int
 struct OptChunk { long long begin; int len; int ent; };
 struct OptSel { unsigned w[OPT_MAX_ENT / 8]; };
 static inline void opt_sel_set(OptSel& t, int ent, unsigned v) { t.w[ent >> 3] = (t.w[ent >> 3] & ~(15u << ((ent & 7) * 4))) | (v << ((ent & 7) * 4)); }
-// per-group scalars as the single-group launchers pass them (k_adam / k_adamw / k_sgd's arguments)
-struct OptAdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
-struct OptAdamWHp { float decay, step, b2, eps, bc2_sqrt; double one_minus_b1; };
-struct OptSgdHp { double lr, momentum, one_minus_damp, wd; int nesterov, mode; };     // mode: sgd_kernel's MODE
+// one Hp per group, by value with the launch
 struct OptAdamArgs { OptAdamHp hp[OPT_MAX_GROUPS]; };
 struct OptAdamWArgs { OptAdamWHp hp[OPT_MAX_GROUPS]; };
 struct OptSgdArgs { OptSgdHp hp[OPT_MAX_GROUPS]; };

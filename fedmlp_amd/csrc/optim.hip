@@ -1,97 +1,173 @@
-// Optimizer kernels of the autograd path over the engine's flat arenas (weights, gradient accumulator, moments: NP floats each,
-// NP a multiple of 4): torch.optim.SGD, torch.optim.AdamW, the L2 norm of the accumulator and the two clips.  gfx950.
+// Optimizer kernels over the engine's flat arenas (weights, gradient, moments: NP floats each, NP a multiple of 4): torch.optim
+// Adam (coupled L2: the fused steps' optimizer and fm_adam_step's), AdamW and SGD, each in a flat form over the whole arena and
+// in a form over the entry table for parameter groups and frozen entries; the gradient accumulator's passes, the L2 norm of the
+// accumulator and the two clips.  gfx950.
 //
 // All of them stream the arena once in 16-byte elements on the main lane's stream, take the engine's skip word (a kernel of
-// this step reported a lost part: nothing is written, like adam_kernel in elementwise.hip) and never synchronise with the host.
-// The element-wise ones run one 16-byte element per thread (k_bn_bwd_apply's launcher has the measurement); Adam with coupled
-// L2 stays where it was (adam_kernel, elementwise.hip), untouched, so the fused steps keep their code.
-// Bytes moved per parameter: SGD 12 (no momentum) / 20, AdamW 28, norm 4, clip 8.
+// this step reported a lost part -- pconv.hip's bounded stream-K wait -- so the gradients are poisoned: nothing is written, and
+// the host learns of it through the word's mapped twin at its next call) and never synchronise with the host.  The flat
+// element-wise ones run one 16-byte element per thread (k_bn_bwd_apply's launcher has the measurement).
+// Bytes moved per parameter: SGD 12 (no momentum) / 20, Adam and AdamW 28, accumulate 8 / 12, norm 4, clip 8.
 #include "common.h"
 #include "kernels.h"
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// ------------------------------------------------------------------ SGD --------
+// ------------------------------------------------------- the update rules --------
+// Each rule is stated ONCE: update(Quad&, Hp) holds its arithmetic for the four floats of a 16-byte element, and both the flat
+// kernels and the parameter-group kernels below call it, so the two forms compute the same bits by construction
+// (tests/test_param_groups_gpu.py compares them).  Every update is written under `fp contract(off)` with each multiply-add an
+// explicit fma: which product joins which addition decides the last bit, and left to the compiler that choice is made per
+// inlining -- it differed between two kernels holding the same AdamW expressions.  The fmas spelled out are the ones the
+// kernels held when each rule was still written as plain expressions, so the trajectories recorded then still hold.
+// A rule also carries its operand arenas: load() reads a quad of every operand at float offset o (a multiple of 4), store()
+// writes the floats of the quad that lie in [begin, end).
+__device__ __forceinline__ void store_own(float* __restrict__ a, int64_t o, int64_t begin, int64_t end, const f32x4 v)
+{
+    if (o >= begin && o + 4 <= end) {
+        *reinterpret_cast<f32x4*>(a + o) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (o + k >= begin && o + k < end) a[o + k] = v[k];
+    }
+}
+
+// the operands of the two rules with two moments
+struct PgmvRule {
+    float* p; const float* g; float* m; float* v;
+    struct Quad { f32x4 p, g, m, v; };
+    __device__ __forceinline__ void load(Quad& q, int64_t o) const
+    {
+        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
+        q.m = *reinterpret_cast<const f32x4*>(m + o); q.v = *reinterpret_cast<const f32x4*>(v + o);
+    }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end) const
+    {
+        store_own(p, o, begin, end, q.p); store_own(m, o, begin, end, q.m); store_own(v, o, begin, end, q.v);
+    }
+};
+
+// torch.optim.Adam's single-tensor update in its order, L2 decay folded into g: g += wd p; exp_avg.lerp_(g, 1 - beta1);
+// exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g g; denom = sqrt(exp_avg_sq) / sqrt(bc2) + eps; p -= lr / bc1 * exp_avg / denom.
+// All in fp32 (the fused steps' golden trajectories are recorded with this lerp).
+struct AdamRule : PgmvRule {
+    using Hp = OptAdamHp;
+    static __device__ __forceinline__ void update(Quad& q, const Hp& hp)
+    {
+#pragma clang fp contract(off)
+        const float nstep = -(hp.lr / hp.bc1), one_minus_b1 = 1.f - hp.b1, one_minus_b2 = 1.f - hp.b2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float g = __builtin_fmaf(hp.wd, q.p[k], q.g[k]);
+            q.m[k] = __builtin_fmaf(one_minus_b1, g - q.m[k], q.m[k]);
+            q.v[k] = __builtin_fmaf(q.v[k], hp.b2, (one_minus_b2 * g) * g);
+            const float den = sqrtf(q.v[k]) / hp.bc2_sqrt + hp.eps;
+            q.p[k] = __builtin_fmaf(nstep, q.m[k] / den, q.p[k]);
+        }
+    }
+};
+
+// torch.optim.AdamW's single-tensor update in its order: p *= 1 - lr wd; exp_avg.lerp_(g, 1 - beta1); exp_avg_sq = beta2
+// exp_avg_sq + (1 - beta2) g g; denom = sqrt(exp_avg_sq) / sqrt(bc2) + eps; p -= lr / bc1 * exp_avg / denom.  No L2 in g.
+// decay = 1 - lr wd and step = lr / bc1 are formed on the host in double.
+struct AdamWRule : PgmvRule {
+    using Hp = OptAdamWHp;
+    static __device__ __forceinline__ void update(Quad& q, const Hp& hp)
+    {
+#pragma clang fp contract(off)
+        const float one_minus_b2 = 1.f - hp.b2, nstep = -hp.step;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            q.v[k] = __builtin_fmaf(q.g[k], one_minus_b2 * q.g[k], q.v[k] * hp.b2);
+            // the lerp in double, rounded once: where beta1 m and (1 - beta1) g cancel, an fp32 lerp is half an ulp of its OPERANDS
+            // off, and lr / bc1 times that over denom is many ulps of a small p (SgdRule's note); everything after it carries
+            // errors relative to the update itself and stays in fp32
+            q.m[k] = (float)__builtin_fma(hp.one_minus_b1, (double)q.g[k] - (double)q.m[k], (double)q.m[k]);
+            const float den = sqrtf(q.v[k]) / hp.bc2_sqrt + hp.eps;
+            q.p[k] = __builtin_fmaf(hp.decay, q.p[k], nstep * (q.m[k] / den));       // (-step) x = -(step x), signed zeros included
+        }
+    }
+};
+
 // torch.optim.SGD's single-tensor update in its order: g += wd p; buf = g (first step after a reset) or momentum buf +
 // (1 - dampening) g; g = nesterov ? g + momentum buf : buf; p -= lr g.
 // MODE 0: momentum = 0, the buffer is neither read nor written; 1: first step (buf = g, no dampening: torch clones the
-// gradient); 2: every later step.
+// gradient); 2: every later step.  A template argument, chosen by the launcher (flat) or by the block from its group's mode: one
+// instantiation of the whole loop per MODE keeps the three expression trees apart (a run-time MODE inside the loop lets the
+// compiler merge them).
 // The chain is evaluated in double from the fp32 operands and each stored value (buf, p) is rounded once.  In fp32 the new p
 // would inherit the rounding of momentum buf + (1 - dampening) g, half an ulp of its OPERANDS: where the two terms cancel and p is
 // small against lr buf that is many ulps of p (tests/test_optim_gpu.py's bound, 4 ulp(p) + 1e-5 |dp|, is missed by a pure fp32
 // chain, torch's own included).  Five double operations per parameter beside 12 / 20 bytes of HBM traffic: still a streaming kernel.
 template <int MODE>
-__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n4, double lr,
-                           double momentum, double one_minus_damp, double wd, int nesterov, const int* __restrict__ skip)
+struct SgdRule {
+    float* p; const float* g; float* buf;
+    using Hp = OptSgdHp;
+    struct Quad { f32x4 p, g, b; };
+    __device__ __forceinline__ void load(Quad& q, int64_t o) const
+    {
+        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
+        q.b = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (MODE == 2) q.b = *reinterpret_cast<const f32x4*>(buf + o);
+    }
+    static __device__ __forceinline__ void update(Quad& q, const Hp& hp)
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double p = (double)q.p[k];
+            double d = __builtin_fma(hp.wd, p, (double)q.g[k]);
+            if (MODE != 0) {
+                const double b = MODE == 1 ? d : __builtin_fma(hp.momentum, (double)q.b[k], hp.one_minus_damp * d);
+                q.b[k] = (float)b;
+                d = hp.nesterov ? __builtin_fma(hp.momentum, b, d) : b;
+            }
+            q.p[k] = (float)__builtin_fma(-hp.lr, d, p);
+        }
+    }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end) const
+    {
+        if (MODE != 0) store_own(buf, o, begin, end, q.b);
+        store_own(p, o, begin, end, q.p);
+    }
+};
+
+// ------------------------------------------------------- the flat steps --------
+// One quad per thread over the first n4 quads of the arenas; the quad is its own span, so store() is three (two, one) 16-byte
+// stores.  adam_kernel is the same body under the name the fused steps' traces carry (tools/, profiles/).
+template <class R>
+__device__ __forceinline__ void opt_flat(const R& r, int64_t n4, const typename R::Hp& hp, const int* __restrict__ skip)
 {
     if (skip && *skip) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-    if (MODE == 2) bb = reinterpret_cast<const f32x4*>(buf)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double d = (double)gg[k] + wd * (double)pp[k];
-        if (MODE != 0) {
-            const double b = MODE == 1 ? d : momentum * (double)bb[k] + one_minus_damp * d;
-            bb[k] = (float)b;
-            d = nesterov ? d + momentum * b : b;
-        }
-        pp[k] = (float)((double)pp[k] - lr * d);
-    }
-    if (MODE != 0) reinterpret_cast<f32x4*>(buf)[i] = bb;
-    reinterpret_cast<f32x4*>(p)[i] = pp;
+    typename R::Quad q;
+    r.load(q, 4 * i);
+    R::update(q, hp);
+    r.store(q, 4 * i, 4 * i, 4 * i + 4);
 }
-void k_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, double one_minus_damp, float wd,
-           bool nesterov, bool first, hipStream_t s, const int* skip)
+template <class R>
+__global__ void opt_flat_kernel(const R r, int64_t n4, const typename R::Hp hp, const int* __restrict__ skip) { opt_flat(r, n4, hp, skip); }
+__global__ void adam_kernel(const AdamRule r, int64_t n4, const OptAdamHp hp, const int* __restrict__ skip) { opt_flat(r, n4, hp, skip); }
+
+void k_adam(float* p, const float* g, float* m, float* v, int64_t n, const OptAdamHp& hp, hipStream_t s, const int* skip)
+{
+    const int64_t n4 = n / 4;
+    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, AdamRule{{p, g, m, v}}, n4, hp, skip);
+}
+void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, const OptAdamWHp& hp, hipStream_t s, const int* skip)
+{
+    const int64_t n4 = n / 4;
+    hipLaunchKernelGGL(opt_flat_kernel<AdamWRule>, dim3(cdiv(n4, 256)), dim3(256), 0, s, AdamWRule{{p, g, m, v}}, n4, hp, skip);
+}
+void k_sgd(float* p, const float* g, float* buf, int64_t n, const OptSgdHp& hp, hipStream_t s, const int* skip)
 {
     const int64_t n4 = n / 4;
     const dim3 grid(cdiv(n4, 256)), block(256);
-    const double lr_ = lr, mom = momentum, wd_ = wd;
-    if (momentum == 0.f)
-        hipLaunchKernelGGL(sgd_kernel<0>, grid, block, 0, s, p, g, buf, n4, lr_, mom, one_minus_damp, wd_, 0, skip);
-    else if (first)
-        hipLaunchKernelGGL(sgd_kernel<1>, grid, block, 0, s, p, g, buf, n4, lr_, mom, one_minus_damp, wd_, nesterov ? 1 : 0, skip);
-    else
-        hipLaunchKernelGGL(sgd_kernel<2>, grid, block, 0, s, p, g, buf, n4, lr_, mom, one_minus_damp, wd_, nesterov ? 1 : 0, skip);
-}
-
-// ---------------------------------------------------------------- AdamW --------
-// torch.optim.AdamW's single-tensor update in its order: p *= 1 - lr wd; exp_avg.lerp_(g, 1 - beta1); exp_avg_sq = beta2
-// exp_avg_sq + (1 - beta2) g g; denom = sqrt(exp_avg_sq) / sqrt(bc2) + eps; p -= lr / bc1 * exp_avg / denom.  No L2 in g.
-// decay = 1 - lr wd and step = lr / bc1 are formed on the host in double.
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             int64_t n4, float decay, float step, double one_minus_b1, float b2, float eps, float bc2_sqrt,
-                             const int* __restrict__ skip)
-{
-    if (skip && *skip) return;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i] * decay;
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-    vv = vv * b2 + (1.f - b2) * gg * gg;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        // the lerp in double, rounded once: where beta1 m and (1 - beta1) g cancel, an fp32 lerp is half an ulp of its OPERANDS
-        // off, and lr / bc1 times that over denom is many ulps of a small p (the SGD kernel's note); everything after it carries
-        // errors relative to the update itself and stays in fp32
-        mm[k] = (float)((double)mm[k] + one_minus_b1 * ((double)gg[k] - (double)mm[k]));
-        const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
-        pp[k] = pp[k] - step * (mm[k] / den);
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pp;
-    reinterpret_cast<f32x4*>(m)[i] = mm;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-}
-void k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float decay, float step, float b1, float b2, float eps,
-             float bc2_sqrt, hipStream_t s, const int* skip)
-{
-    const int64_t n4 = n / 4;
-    hipLaunchKernelGGL(adamw_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, p, g, m, v, n4, decay, step, 1.0 - (double)b1, b2, eps, bc2_sqrt, skip);
+    if (hp.mode == 0) hipLaunchKernelGGL(opt_flat_kernel<SgdRule<0>>, grid, block, 0, s, SgdRule<0>{p, g, buf}, n4, hp, skip);
+    else if (hp.mode == 1) hipLaunchKernelGGL(opt_flat_kernel<SgdRule<1>>, grid, block, 0, s, SgdRule<1>{p, g, buf}, n4, hp, skip);
+    else hipLaunchKernelGGL(opt_flat_kernel<SgdRule<2>>, grid, block, 0, s, SgdRule<2>{p, g, buf}, n4, hp, skip);
 }
 
 // ------------------------------------------------------------- L2 norm ---------
@@ -200,140 +276,15 @@ void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int
 // span (padded input channels and taps, the packed stem's row tails) is stepped with its entry and stays zero under all three
 // rules (zero weight, zero gradient: DESIGN.md section 1's padding note).
 //
-// The arithmetic per element is adam_kernel's (elementwise.hip), adamw_kernel's and sgd_kernel<MODE>'s above, restated: Adam
-// and SGD on the same expressions, which the compiler contracts alike in both kernels; AdamW with its contraction spelled out
-// (AdamWRule).  tests/test_param_groups_gpu.py compares the bits of every pair.
+// The arithmetic per element is the rule's update(), the one the flat steps call.
 // A thread holds OPT_QPT quads of every operand: all its 16-byte loads are in flight before the first use.  A full chunk that
 // starts off a 16-byte boundary has one quad more (2049): thread 0 takes it after the others.
 #define OPT_QPT (FM_DIST_CHUNK / 4 / 256)
 
 __device__ __forceinline__ unsigned opt_sel_get(const OptSel& t, int ent) { return (t.w[ent >> 3] >> ((ent & 7) * 4)) & 15u; }
 
-__device__ __forceinline__ void store_own(float* __restrict__ a, int64_t o, int64_t begin, int64_t end, const f32x4 v)
-{
-    if (o >= begin && o + 4 <= end) {
-        *reinterpret_cast<f32x4*>(a + o) = v;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (o + k >= begin && o + k < end) a[o + k] = v[k];
-    }
-}
-
-struct AdamRule {
-    float* p; const float* g; float* m; float* v;
-    OptAdamArgs a;
-    struct Quad { f32x4 p, g, m, v; };
-    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
-    {
-        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
-        q.m = *reinterpret_cast<const f32x4*>(m + o); q.v = *reinterpret_cast<const f32x4*>(v + o);
-    }
-    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
-    {
-        const float lr = a.hp[gi].lr, b1 = a.hp[gi].b1, b2 = a.hp[gi].b2, eps = a.hp[gi].eps, wd = a.hp[gi].wd;
-        const float bc1 = a.hp[gi].bc1, bc2_sqrt = a.hp[gi].bc2_sqrt;
-        const float step = lr / bc1;
-        f32x4 pp = q.p;
-        f32x4 gg = q.g + wd * pp;
-        f32x4 mm = q.m;
-        f32x4 vv = q.v;
-        mm = mm + (1.f - b1) * (gg - mm);
-        vv = vv * b2 + (1.f - b2) * gg * gg;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
-            pp[k] = pp[k] - step * (mm[k] / den);
-        }
-        q.p = pp; q.m = mm; q.v = vv;
-    }
-    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
-    {
-        store_own(p, o, begin, end, q.p); store_own(m, o, begin, end, q.m); store_own(v, o, begin, end, q.v);
-    }
-};
-
-struct AdamWRule {
-    float* p; const float* g; float* m; float* v;
-    OptAdamWArgs a;
-    struct Quad { f32x4 p, g, m, v; };
-    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
-    {
-        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
-        q.m = *reinterpret_cast<const f32x4*>(m + o); q.v = *reinterpret_cast<const f32x4*>(v + o);
-    }
-    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
-    {
-#pragma clang fp contract(off)
-        const float decay = a.hp[gi].decay, step = a.hp[gi].step, b2 = a.hp[gi].b2, eps = a.hp[gi].eps;
-        const float bc2_sqrt = a.hp[gi].bc2_sqrt;
-        const double one_minus_b1 = a.hp[gi].one_minus_b1;
-        // adamw_kernel's expressions leave the compiler three choices of what to contract (which product of the exp_avg_sq
-        // update joins the addition, and whether p * decay or step * (m / denom) joins the subtraction), and it does not make them
-        // alike in two kernels.  So the choices adamw_kernel's code object holds are spelled out here with contraction off:
-        //   exp_avg_sq = fma(g, (1 - beta2) g, exp_avg_sq beta2);   p = fma(decay, p, -(step (exp_avg / denom)))
-        // and the lerp as there, one fma in double.  tests/test_param_groups_gpu.py holds the two kernels to the same bits.
-        f32x4 pp = q.p;
-        const f32x4 gg = q.g;
-        f32x4 mm = q.m;
-        f32x4 vv = q.v;
-        const float one_minus_b2 = 1.f - b2, nstep = -step;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            vv[k] = __builtin_fmaf(gg[k], one_minus_b2 * gg[k], vv[k] * b2);
-            mm[k] = (float)__builtin_fma(one_minus_b1, (double)gg[k] - (double)mm[k], (double)mm[k]);
-            const float den = sqrtf(vv[k]) / bc2_sqrt + eps;
-            pp[k] = __builtin_fmaf(decay, pp[k], nstep * (mm[k] / den));       // (-step) x = -(step x), signed zeros included
-        }
-        q.p = pp; q.m = mm; q.v = vv;
-    }
-    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
-    {
-        store_own(p, o, begin, end, q.p); store_own(m, o, begin, end, q.m); store_own(v, o, begin, end, q.v);
-    }
-};
-
-template <int MODE>
-__device__ __forceinline__ void sgd_quad(f32x4& pp, const f32x4 gg, f32x4& bb, double lr, double momentum, double one_minus_damp,
-                                         double wd, int nesterov)
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double d = (double)gg[k] + wd * (double)pp[k];
-        if (MODE != 0) {
-            const double b = MODE == 1 ? d : momentum * (double)bb[k] + one_minus_damp * d;
-            bb[k] = (float)b;
-            d = nesterov ? d + momentum * b : b;
-        }
-        pp[k] = (float)((double)pp[k] - lr * d);
-    }
-}
-// MODE is a template argument here too: one instantiation of the whole chunk loop per MODE, chosen by the block from its group's
-// mode, so that each keeps sgd_kernel<MODE>'s expression tree (a run-time MODE inside the loop lets the compiler merge the three)
-template <int MODE>
-struct SgdRule {
-    float* p; const float* g; float* buf;
-    const OptSgdArgs& a;
-    struct Quad { f32x4 p, g, b; };
-    __device__ __forceinline__ void load(Quad& q, int64_t o, unsigned) const
-    {
-        q.p = *reinterpret_cast<const f32x4*>(p + o); q.g = *reinterpret_cast<const f32x4*>(g + o);
-        q.b = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (MODE == 2) q.b = *reinterpret_cast<const f32x4*>(buf + o);
-    }
-    __device__ __forceinline__ void update(Quad& q, unsigned gi) const
-    {
-        sgd_quad<MODE>(q.p, q.g, q.b, a.hp[gi].lr, a.hp[gi].momentum, a.hp[gi].one_minus_damp, a.hp[gi].wd, a.hp[gi].nesterov);
-    }
-    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end, unsigned) const
-    {
-        if (MODE != 0) store_own(buf, o, begin, end, q.b);
-        store_own(p, o, begin, end, q.p);
-    }
-};
-
 template <class R>
-__device__ __forceinline__ void opt_chunk(const R& r, const OptChunk ch, unsigned gi)
+__device__ __forceinline__ void opt_chunk(const R& r, const OptChunk ch, const typename R::Hp& hp)
 {
     const int64_t begin = ch.begin, end = begin + ch.len;
     const int64_t o0 = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x;
@@ -341,33 +292,33 @@ __device__ __forceinline__ void opt_chunk(const R& r, const OptChunk ch, unsigne
 #pragma unroll
     for (int j = 0; j < OPT_QPT; ++j) {
         const int64_t o = o0 + (int64_t)j * 1024;
-        if (o < end) r.load(q[j], o, gi);
+        if (o < end) r.load(q[j], o);
     }
 #pragma unroll
     for (int j = 0; j < OPT_QPT; ++j) {
         const int64_t o = o0 + (int64_t)j * 1024;
         if (o < end) {
-            r.update(q[j], gi);
-            r.store(q[j], o, begin, end, gi);
+            R::update(q[j], hp);
+            r.store(q[j], o, begin, end);
         }
     }
     const int64_t o = o0 + (int64_t)OPT_QPT * 1024;
     if (o < end) {
         typename R::Quad t;
-        r.load(t, o, gi);
-        r.update(t, gi);
-        r.store(t, o, begin, end, gi);
+        r.load(t, o);
+        R::update(t, hp);
+        r.store(t, o, begin, end);
     }
 }
-template <class R>
-__global__ void __launch_bounds__(256) opt_groups_kernel(const R r, const OptChunk* __restrict__ chunks, const OptSel sel,
+template <class R, class Args>
+__global__ void __launch_bounds__(256) opt_groups_kernel(const R r, const Args a, const OptChunk* __restrict__ chunks, const OptSel sel,
                                                          const int* __restrict__ skip)
 {
     if (skip && *skip) return;
     const OptChunk ch = chunks[blockIdx.x];
     const unsigned gi = opt_sel_get(sel, ch.ent);
     if (gi >= OPT_MAX_GROUPS) return;             // in no group, or frozen: before any load
-    opt_chunk(r, ch, gi);
+    opt_chunk(r, ch, a.hp[gi]);
 }
 __global__ void __launch_bounds__(256) sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                          const OptSgdArgs a, const OptChunk* __restrict__ chunks, const OptSel sel,
@@ -378,27 +329,44 @@ __global__ void __launch_bounds__(256) sgd_groups_kernel(float* __restrict__ p, 
     const unsigned gi = opt_sel_get(sel, ch.ent);
     if (gi >= OPT_MAX_GROUPS) return;
     const int mode = a.hp[gi].mode;
-    if (mode == 0) opt_chunk(SgdRule<0>{p, g, buf, a}, ch, gi);
-    else if (mode == 1) opt_chunk(SgdRule<1>{p, g, buf, a}, ch, gi);
-    else opt_chunk(SgdRule<2>{p, g, buf, a}, ch, gi);
+    if (mode == 0) opt_chunk(SgdRule<0>{p, g, buf}, ch, a.hp[gi]);
+    else if (mode == 1) opt_chunk(SgdRule<1>{p, g, buf}, ch, a.hp[gi]);
+    else opt_chunk(SgdRule<2>{p, g, buf}, ch, a.hp[gi]);
 }
 
 void k_adam_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
                    const OptAdamArgs& a, hipStream_t s, const int* skip)
 {
-    const AdamRule r{p, g, m, v, a};
-    hipLaunchKernelGGL(opt_groups_kernel<AdamRule>, dim3(n_chunks), dim3(256), 0, s, r, chunks, sel, skip);
+    hipLaunchKernelGGL((opt_groups_kernel<AdamRule, OptAdamArgs>), dim3(n_chunks), dim3(256), 0, s, AdamRule{{p, g, m, v}}, a, chunks, sel, skip);
 }
 void k_adamw_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
                     const OptAdamWArgs& a, hipStream_t s, const int* skip)
 {
-    const AdamWRule r{p, g, m, v, a};
-    hipLaunchKernelGGL(opt_groups_kernel<AdamWRule>, dim3(n_chunks), dim3(256), 0, s, r, chunks, sel, skip);
+    hipLaunchKernelGGL((opt_groups_kernel<AdamWRule, OptAdamWArgs>), dim3(n_chunks), dim3(256), 0, s, AdamWRule{{p, g, m, v}}, a, chunks, sel, skip);
 }
 void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, int n_chunks, const OptSel& sel,
                   const OptSgdArgs& a, hipStream_t s, const int* skip)
 {
     hipLaunchKernelGGL(sgd_groups_kernel, dim3(n_chunks), dim3(256), 0, s, p, g, buf, a, chunks, sel, skip);
+}
+
+// ------------------------------------------------- gradient accumulator --------
+// The accumulator of the autograd path (fm_backward_grads): acc = g when the accumulator is empty (a copy, so one backward
+// after fm_zero_grad holds exactly the fused path's gradients), acc += g after it; one streaming float4 pass over the arena
+__global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4, int copy,
+                                       const int* __restrict__ skip)
+{
+    if (skip && *skip) return;      // a lost stream-K part poisoned g: the accumulator stays as it is
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        reinterpret_cast<f32x4*>(acc)[i] = copy ? gg : reinterpret_cast<const f32x4*>(acc)[i] + gg;
+    }
+}
+void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStream_t s, const int* skip)
+{
+    const int64_t n4 = n / 4;     // engine pads the parameter arena to a multiple of 4
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, acc, g, n4, copy ? 1 : 0, skip);
 }
 
 // k_grad_accumulate under a mask, over the same table with the same boundary rule: sel = 0 marks a trainable entry (acc = g or
