@@ -1094,17 +1094,17 @@ bool conv_uses_pconv(const fm_engine* e, const Conv& c, int imgs)
     return e->planes && c.bm_off >= 0 && pconv_takes(c.cout_p, c.cin_p, (long long)imgs * c.hin * c.win, c.win);
 }
 
-// the GEMM geometry of the planes kernel's launches -- taps, operand map, output grid: what pconv_uses_ts decides on.  conv_fwd /
-// conv_dgrad build their parameters from these, and fm_debug_conv_arm asks the same predicate about the same fields.
-static void pconv_fwd_geometry(const Conv& c, IgemmParams& p)
+// the GEMM geometry of a convolution's forward / data-gradient launches -- taps, operand map, output grid: what pconv_uses_ts
+// decides on and what launch_pconv and launch_igemm are handed.  The stem (cin == 3) has no tap list: its kernels walk kernel rows.
+static void conv_fwd_geometry(const Conv& c, IgemmParams& p)
 {
-    p.ntaps = c.k * c.k;
-    for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
+    p.ntaps = c.cin == 3 ? 0 : c.k * c.k;
+    for (int t = 0; t < p.ntaps; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
     p.M = c.cout_p;
     p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p;
     p.Hg = c.hout; p.Wg = c.wout; p.sg = c.stride;
 }
-static void pconv_dgrad_geometry(const Conv& c, const DgradClass& d, IgemmParams& p)
+static void conv_dgrad_geometry(const Conv& c, const DgradClass& d, IgemmParams& p)
 {
     p.ntaps = d.taps.n;
     for (int t = 0; t < d.taps.n; ++t) { p.dh[t] = d.dh[t]; p.dw[t] = d.dw[t]; }
@@ -1142,64 +1142,116 @@ static void wgrad_geometry(const fm_engine* e, const Conv& c, int imgs, WgradPar
     if (e->model == 1 && c.cin == 3) { p.gather_k = c.k; p.gather_pad = c.pad; p.gather_kw_p = c.kw_p; }
 }
 
-// xp: the input's block-major planes (planes mode; null = made here from x); yp: also / only write the output's planes
-// (eval epilogue; y may then be null)
-// partial-sum tiles per group the forward GEMM of conv c leaves in `stats` (pro_gate: this call carries an operand prologue)
-static int stats_tiles_for(fm_engine* e, const Conv& c, int imgs_per_group, int groups, bool pro_gate)
+// The launcher conv_fwd / conv_dgrad / conv_wgrad hand conv c to for `imgs` images: the one decision they switch on, stats_tiles_for
+// sizes the statistics by, the measurement family follows and fm_debug_conv_arm reports.  None: planes mode keeps no fp32 operands
+// for the non-stem convs (activations exist only as planes, no row-major weight planes): a shape the planes kernel does not take is
+// a graph error, not a reason to run the fp32-operand kernel on unwritten buffers.
+enum class Arm { None, StemRows, PconvTs, PconvTap, PwConv, Igemm, IgemmStem, Pwgrad, PwgradRing, PwWgrad, WgradSkinny, WgradGeneric,
+                 WgradGenericStem };
+
+static Arm pconv_arm(const IgemmParams& geometry) { return pconv_uses_ts(geometry) ? Arm::PconvTs : Arm::PconvTap; }
+static Arm fwd_arm(const fm_engine* e, const Conv& c, int imgs)
 {
-    if (e->stem_rows && c.stem3) return stem_rows_stats_tiles(imgs_per_group, c.hout);
-    if (e->precision && (c.k == 1 || c.cin == 3))
-        return pw_blocks(imgs_per_group * c.hout * c.wout, groups, c.cout_p, c.cin == 3 ? c.Kw : c.cin_p, pro_gate, c.hout * c.wout);
-    if (conv_uses_pconv(e, c, imgs_per_group * groups)) return (imgs_per_group * c.hout * c.wout + pconv_tile_n(c.cout_p) - 1) / pconv_tile_n(c.cout_p);
-    const int bn = igemm_tile_n(c.cout_p, c.cin == 3);
-    return (imgs_per_group * c.hout * c.wout + bn - 1) / bn;
+    if (e->stem_rows && c.stem3) return Arm::StemRows;
+    if (conv_uses_pconv(e, c, imgs)) {
+        IgemmParams p{};
+        conv_fwd_geometry(c, p);
+        return pconv_arm(p);
+    }
+    if (e->planes && c.cin != 3) return Arm::None;
+    if (e->precision && (c.k == 1 || c.cin == 3)) return Arm::PwConv;      // bf16 storage + bf16 MFMA (pwconv_bf16.hip)
+    return c.cin == 3 ? Arm::IgemmStem : Arm::Igemm;
+}
+// one launch per parity class: PconvTap if any class runs per tap (conv_dgrad asks pconv_arm about each class's own launch)
+static Arm dgrad_arm(const fm_engine* e, const Conv& c, int imgs)
+{
+    if (dgrad_uses_pconv(e, c, imgs)) {
+        for (int k = 0; k < c.ncls; ++k) {
+            IgemmParams p{};
+            conv_dgrad_geometry(c, c.cls[k], p);
+            if (pconv_arm(p) == Arm::PconvTap) return Arm::PconvTap;
+        }
+        return Arm::PconvTs;
+    }
+    if (e->planes && c.cin != 3) return Arm::None;
+    if (e->precision && c.k == 1) return Arm::PwConv;      // dX = dY W: the same streaming kernel with the transposed bf16 shadow
+    return Arm::Igemm;
+}
+// launch_wgrad_skinny refuses exactly what wgrad_skinny_takes refuses (the slab only bounds its splits), so the skinny kernels are
+// an arm of their own and nothing falls through to the generic kernel
+static Arm wgrad_arm(const fm_engine* e, const Conv& c, int imgs)
+{
+    if (wgrad_uses_pwgrad(e, c, imgs)) {
+        PwgradParams q{};
+        pwgrad_geometry(e, c, imgs, q);
+        return pwgrad_ring_takes(q) ? Arm::PwgradRing : Arm::Pwgrad;
+    }
+    if (e->planes && c.cin != 3) return Arm::None;
+    if (e->precision && (c.k == 1 || c.cin == 3)) return Arm::PwWgrad;
+    if (e->model == 1 && (c.k == 1 || c.cin == 3)) {
+        WgradParams p{};
+        wgrad_geometry(e, c, imgs, p);
+        if (wgrad_skinny_takes(p)) return Arm::WgradSkinny;
+    }
+    return c.cin == 3 ? Arm::WgradGenericStem : Arm::WgradGeneric;
+}
+// measurement families follow the kernel symbols: M = the rows of the GEMM (>= 128: the 128-row tiles).  0 / 1 = igemm and
+// pconv_kernel<4 | 2, ..., true> (tap rows shared), 6 / 7 = <..., false>, 2 = the stem kernels, 3 / 4 / 5 / 8 = the weight gradients
+static int prof_family(Arm a, int M)
+{
+    const bool big = M >= 128;
+    switch (a) {
+    case Arm::StemRows: case Arm::IgemmStem: return 2;
+    case Arm::PconvTs: case Arm::Igemm: return big ? 0 : 1;
+    case Arm::PconvTap: return big ? 6 : 7;
+    case Arm::Pwgrad: case Arm::WgradGeneric: return big ? 3 : 4;
+    case Arm::WgradGenericStem: return big ? 3 : 5;
+    case Arm::WgradSkinny: return 4;
+    case Arm::PwgradRing: return 8;
+    default: return -1;      // the bf16 pointwise launchers are not measured by family
+    }
 }
 
+// partial-sum tiles per group the forward GEMM of conv c leaves in `stats`, one per pixel tile of its grid (pro_gate: this call
+// carries an operand prologue)
+static int stats_tiles_for(Arm fwd, const Conv& c, int imgs_per_group, int groups, bool pro_gate)
+{
+    const int pix = imgs_per_group * c.hout * c.wout;
+    auto tiles = [&](int bn) { return (pix + bn - 1) / bn; };
+    switch (fwd) {
+    case Arm::StemRows: return stem_rows_stats_tiles(imgs_per_group, c.hout);
+    case Arm::PwConv: return pw_blocks(pix, groups, c.cout_p, c.cin == 3 ? c.Kw : c.cin_p, pro_gate, c.hout * c.wout);
+    case Arm::PconvTs: case Arm::PconvTap: return tiles(pconv_tile_n(c.cout_p));
+    default: return tiles(igemm_tile_n(c.cout_p, c.cin == 3));
+    }
+}
+
+// xp: the input's block-major planes (planes mode; null = made here from x); yp: also / only write the output's planes
+// (eval epilogue; y may then be null)
 void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, float* y, int imgs, int groups,
               const float* scale, const float* shift, const float* res, int relu, float* stats,
               const Prologue* pro = nullptr, const unsigned short* xp = nullptr, unsigned short* yp = nullptr,
               const unsigned short* resp = nullptr)
 {
     Conv& c = e->convs[ci];
-    if (stats) {
-        e->stats_conv = ci;
-        e->stats_tiles_n = stats_tiles_for(e, c, imgs / groups, groups, pro && pro->gate);
-    }
-    if (e->stem_rows && c.stem3) {           // `x` is ignored: the operand is the framed image's planes (to_nhwc4)
+    const Arm arm = fwd_arm(e, c, imgs);
+    const int tiles_n = stats_tiles_for(arm, c, imgs / groups, groups, pro && pro->gate);
+    if (stats) { e->stats_conv = ci; e->stats_tiles_n = tiles_n; }
+    const int fam = prof_family(arm, c.cout_p);
+    const double flops = 2.0 * c.macs_per_img * imgs;
+    switch (arm) {
+    case Arm::StemRows: {                    // `x` is ignored: the operand is the framed image's planes (to_nhwc4)
         StemRowsParams q{};
         q.Xp = e->x3p + (size_t)e->in_img0 * c.Hp * c.Wp * 4; q.Wst = W.wst; q.Y = y;
         q.scale = scale; q.shift = shift; q.stats = stats; q.relu = relu;
         q.imgs = imgs; q.imgs_per_group = imgs / groups; q.Hp = c.Hp; q.Wp = c.Wp; q.Ho = c.hout; q.Wo = c.wout;
         q.sp = e->products; q.plane_bytes = e->x3p_plane_elems * 2;
-        ProfScope ps(e, L, 2, 2.0 * c.macs_per_img * imgs);
+        ProfScope ps(e, L, fam, flops);
         launch_stem_rows(q, L.st);
         return;
     }
-    if (conv_uses_pconv(e, c, imgs)) {
-        IgemmParams p{};
-        p.xp_pix = (long long)imgs * c.hin * c.win;
-        p.Xp = xp ? xp : scratch_planes(e, L, x, p.xp_pix, c.cin_p);
-        p.Wsp = W.wbm_f + c.bm_off;
-        p.Y = y; p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout;
-        p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
-        pconv_fwd_geometry(c, p);
-        p.res = res; p.resp = resp; p.scale = scale; p.shift = shift; p.stats = stats;
-        p.Ho = c.hout; p.Wo = c.wout; p.Co = c.cout_p;
-        p.os = 1; p.oh0 = 0; p.ow0 = 0;
-        p.imgs_per_group = imgs / groups;
-        p.tilesM = c.cout_p / pconv_tile_m(c.cout_p);
-        p.tilesN = (p.imgs_per_group * c.hout * c.wout + pconv_tile_n(c.cout_p) - 1) / pconv_tile_n(c.cout_p);
-        p.relu = relu;
-        // measurement families follow the kernel symbols: 0 / 1 = pconv_kernel<4 | 2, ..., true> (tap rows shared), 6 / 7 = <..., false>
-        ProfScope ps(e, L, (c.cout_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs);
-        launch_pconv(p, groups, L.st);
-        return;
-    }
-    // planes mode keeps no fp32 operands for these convs (activations exist only as planes, no row-major weight planes): a shape
-    // the planes kernel does not take is a graph error, not a reason to run the fp32-operand kernel on unwritten buffers
-    if (e->planes && c.cin != 3) { soft(e, hipErrorInvalidValue); return; }
-    const bool stem16 = e->precision && c.cin == 3;     // `x` is ignored: the operand is the im2col matrix
-    if (e->precision && (c.k == 1 || stem16)) {          // bf16 storage + bf16 MFMA (pwconv_bf16.hip)
+    case Arm::PwConv: {
+        const bool stem16 = c.cin == 3;      // `x` is ignored: the operand is the im2col matrix
         PwParams q{};
         q.zeros = e->zeros;
         q.W = W.wb + c.wb_off;
@@ -1214,19 +1266,36 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
         launch_pw_conv(q, L.st);
         return;
     }
+    case Arm::PconvTs: case Arm::PconvTap: case Arm::Igemm: case Arm::IgemmStem: break;      // one parameter block, below
+    default: soft(e, hipErrorInvalidValue); return;
+    }
     IgemmParams p{};
-    p.W = W.state + c.w_off; p.X = x; p.Y = y; p.zeros = e->zeros; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
-    p.sp = e->products;
+    p.Y = y; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+    conv_fwd_geometry(c, p);
+    p.res = res; p.scale = scale; p.shift = shift; p.stats = stats;
+    p.Ho = c.hout; p.Wo = c.wout; p.Co = c.cout_p;
+    p.os = 1; p.oh0 = 0; p.ow0 = 0;
+    p.imgs_per_group = imgs / groups;
+    p.tilesN = tiles_n;
+    p.relu = relu;           // 0 none, 1 relu, 2 swish
+    if (arm == Arm::PconvTs || arm == Arm::PconvTap) {
+        p.xp_pix = (long long)imgs * c.hin * c.win;
+        p.Xp = xp ? xp : scratch_planes(e, L, x, p.xp_pix, c.cin_p);
+        p.Wsp = W.wbm_f + c.bm_off;
+        p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout; p.resp = resp;
+        p.tilesM = c.cout_p / pconv_tile_m(c.cout_p);
+        ProfScope ps(e, L, fam, flops);
+        launch_pconv(p, groups, L.st);
+        return;
+    }
+    p.W = W.state + c.w_off; p.X = x; p.zeros = e->zeros; p.nsteps = c.nsteps;
     if (c.sp_off >= 0 && W.wsp_f) p.Wsp = W.wsp_f + c.sp_off;
     if (c.cin == 3) {
         p.stem_kw = c.k; p.stem_pad = c.pad; p.stem_h2 = c.kw_p == 8 ? 1 : 0; p.stem3 = c.stem3 ? 1 : 0;
         if (c.stem3) p.X = e->x3 + (size_t)e->in_img0 * c.Hp * c.Wp * 3;     // `x` is ignored: the operand is the framed NHWC3 image
         else p.X = x + (size_t)e->in_img0 * c.hin * c.win * 4;
-    } else {
-        p.ntaps = c.k * c.k;
-        for (int t = 0; t < c.k * c.k; ++t) { p.dh[t] = t / c.k - c.pad; p.dw[t] = t % c.k - c.pad; }
     }
-    p.res = res; p.scale = scale; p.shift = shift; p.stats = stats;
+    if (c.stem3) { p.Hi = c.Hp; p.Wi = c.Wp; }
     if (pro && pro->gate) {       // fp32 project conv: only the streaming kernel (conv1x1.hip) applies the gate (eval) or BN1 + Swish + gate (train)
         p.gate = pro->gate; p.gate_HW = c.hout * c.wout; p.psc = pro->psc; p.psh = pro->psh;
         // the streaming kernel has a gate-only eval form (no statistics) and a BN1 + Swish + gate train form (statistics): a
@@ -1235,18 +1304,8 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
             (!pro->psc && stats))
             soft(e, hipErrorInvalidValue);
     }
-    p.M = c.cout_p; p.nsteps = c.nsteps;
-    p.Hi = c.hin; p.Wi = c.win; p.Ci = c.cin_p;
-    if (c.stem3) { p.Hi = c.Hp; p.Wi = c.Wp; }
-    p.Hg = c.hout; p.Wg = c.wout; p.sg = c.stride;
-    p.Ho = c.hout; p.Wo = c.wout; p.Co = c.cout_p;
-    p.os = 1; p.oh0 = 0; p.ow0 = 0;
-    p.imgs_per_group = imgs / groups;
     p.tilesM = (c.cout_p + igemm_tile_m(c.cout_p) - 1) / igemm_tile_m(c.cout_p);
-    const int bn = igemm_tile_n(c.cout_p, c.cin == 3);
-    p.tilesN = (p.imgs_per_group * c.hout * c.wout + bn - 1) / bn;
-    p.relu = relu;           // 0 none, 1 relu, 2 swish
-    ProfScope ps(e, L, c.cin == 3 ? 2 : (c.cout_p >= 128 ? 0 : 1), 2.0 * c.macs_per_img * imgs);
+    ProfScope ps(e, L, fam, flops);
     launch_igemm(p, groups, L.st);
 }
 
@@ -1264,29 +1323,10 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
                 bool acc_cls0, const unsigned short* dyp = nullptr)
 {
     Conv& c = e->convs[ci];
-    if (dgrad_uses_pconv(e, c, imgs)) {
-        const long long xp_pix = (long long)imgs * c.hout * c.wout;
-        if (!dyp) dyp = scratch_planes(e, L, dy, xp_pix, c.cout_p);
-        for (int k = 0; k < c.ncls; ++k) {
-            DgradClass& d = c.cls[k];
-            IgemmParams p{};
-            p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d + d.bm_off;
-            p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
-            pconv_dgrad_geometry(c, d, p);
-            p.res = res ? res : ((acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
-            p.Ho = c.hin; p.Wo = c.win; p.Co = c.cin_p;
-            p.os = c.stride; p.oh0 = d.ph; p.ow0 = d.pw;
-            p.imgs_per_group = imgs;
-            p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
-            p.tilesN = (imgs * p.Hg * p.Wg + pconv_tile_n(c.cin_p) - 1) / pconv_tile_n(c.cin_p);
-            p.relu = 0;
-            ProfScope ps(e, L, (c.cin_p >= 128 ? 0 : 1) + (pconv_uses_ts(p) ? 0 : 6), 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
-            launch_pconv(p, 1, L.st);
-        }
-        return;
-    }
-    if (e->planes && c.cin != 3) { soft(e, hipErrorInvalidValue); return; }      // (see conv_fwd: no fp32-operand fallback in planes mode)
-    if (e->precision && c.k == 1) {          // dX = dY W: the same streaming kernel with the transposed bf16 shadow
+    const Arm arm = dgrad_arm(e, c, imgs);
+    const long long xp_pix = (long long)imgs * c.hout * c.wout;
+    switch (arm) {
+    case Arm::PwConv: {
         PwParams q{};
         q.zeros = e->zeros;
         q.W = e->student.wb + c.wbt_off;
@@ -1298,29 +1338,36 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
         launch_pw_conv(q, L.st);
         return;
     }
+    case Arm::PconvTs: case Arm::PconvTap: case Arm::Igemm: break;      // one launch per parity class, below
+    default: soft(e, hipErrorInvalidValue); return;
+    }
+    const bool planes = arm != Arm::Igemm;
+    if (planes && !dyp) dyp = scratch_planes(e, L, dy, xp_pix, c.cout_p);
     for (int k = 0; k < c.ncls; ++k) {
         DgradClass& d = c.cls[k];
         IgemmParams p{};
-        p.W = d.wpack; p.X = dy; p.Y = dx; p.zeros = e->zeros; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev;
-        p.sp = e->products;
-        if (d.sp_off >= 0 && e->wsp_d) p.Wsp = e->wsp_d + d.sp_off;
-        p.ntaps = d.taps.n;
-        for (int t = 0; t < d.taps.n; ++t) { p.dh[t] = d.dh[t]; p.dw[t] = d.dw[t]; }
+        p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+        conv_dgrad_geometry(c, d, p);
         p.res = res ? res : ((acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
-        p.M = c.cin_p; p.nsteps = d.nsteps;
-        p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
-        p.Hg = (c.hin - d.ph + c.stride - 1) / c.stride;
-        p.Wg = (c.win - d.pw + c.stride - 1) / c.stride;
-        p.sg = 1;
         p.Ho = c.hin; p.Wo = c.win; p.Co = c.cin_p;
         p.os = c.stride; p.oh0 = d.ph; p.ow0 = d.pw;
         p.imgs_per_group = imgs;
-        p.tilesM = (c.cin_p + igemm_tile_m(c.cin_p) - 1) / igemm_tile_m(c.cin_p);
-        const int bn = igemm_tile_n(c.cin_p);
-        p.tilesN = (imgs * p.Hg * p.Wg + bn - 1) / bn;
         p.relu = 0;
-        ProfScope ps(e, L, c.cin_p >= 128 ? 0 : 1, 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k));
-        launch_igemm(p, 1, L.st);
+        const int bn = planes ? pconv_tile_n(c.cin_p) : igemm_tile_n(c.cin_p);
+        p.tilesN = (imgs * p.Hg * p.Wg + bn - 1) / bn;
+        const double flops = 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k);
+        if (planes) {
+            p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d + d.bm_off;
+            p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
+            ProfScope ps(e, L, prof_family(pconv_arm(p), c.cin_p), flops);       // this class's own kernel
+            launch_pconv(p, 1, L.st);
+        } else {
+            p.W = d.wpack; p.X = dy; p.zeros = e->zeros; p.nsteps = d.nsteps;
+            if (d.sp_off >= 0 && e->wsp_d) p.Wsp = e->wsp_d + d.sp_off;
+            p.tilesM = (c.cin_p + igemm_tile_m(c.cin_p) - 1) / igemm_tile_m(c.cin_p);
+            ProfScope ps(e, L, prof_family(arm, c.cin_p), flops);
+            launch_igemm(p, 1, L.st);
+        }
     }
 }
 
@@ -1335,9 +1382,7 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
     Conv& c = e->convs[c1i];
     Conv& d = e->convs[dsi];
     const long long xp_pix = (long long)imgs * c.hout * c.wout;
-    if (!e->planes || c.ncls != 4 || d.ncls != 1 || c.cls[0].bm_off < 0 || d.cls[0].bm_off < 0 ||
-        !pconv_takes(c.cin_p, c.cout_p, xp_pix, c.wout))
-        return false;
+    if (c.ncls != 4 || d.ncls != 1 || !dgrad_uses_pconv(e, c, imgs) || d.cls[0].bm_off < 0) return false;
     static_assert(PCONV_MAX_JOBS >= 4, "one job per parity class");
     const DgradClass& d0 = d.cls[0];
     if (c.stride != 2 || d.stride != 2 || d.k != 1 || d.cin_p != c.cin_p || d.cout_p != c.cout_p || d.hin != c.hin || d.win != c.win ||
@@ -1376,8 +1421,8 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
     }
     p.job[0].cib += d.cout_p >> 5;
     p.job[0].wofs2 = (unsigned)(d0.bm_off * 2);
-    // family 6 / 7 = pconv_kernel<4 | 2, ..., false>; the launch's algorithmic FLOPs = both convs'
-    ProfScope ps(e, L, (c.cin_p >= 128 ? 0 : 1) + 6, 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
+    // the per-tap kernel's family; the launch's algorithmic FLOPs = both convs'
+    ProfScope ps(e, L, prof_family(Arm::PconvTap, c.cin_p), 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
     launch_pconv(p, 1, L.st);
     return true;
 }
@@ -1387,7 +1432,13 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
                 int pix_per_group = 0, const unsigned short* xp = nullptr, const unsigned short* dyp = nullptr)
 {
     const Conv& c = e->convs[ci];
-    if (wgrad_uses_pwgrad(e, c, imgs)) {
+    const Arm arm = wgrad_arm(e, c, imgs);
+    const int fam = prof_family(arm, c.cout_p);
+    const double flops = 2.0 * c.macs_per_img * imgs;
+    int sk = 0;                              // partial slabs the arm's kernel leaves in L.ws_slab
+    switch (arm) {
+    case Arm::Pwgrad:
+    case Arm::PwgradRing: {
         PwgradParams q{};
         pwgrad_geometry(e, c, imgs, q);
         if (!xp) xp = scratch_planes(e, L, x, q.xpix, c.cin_p);
@@ -1397,64 +1448,56 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
             dyp = e->xp_scratch2;
         }
         q.dYp = dyp; q.Xp = xp; q.slab = L.ws_slab;
-        int sk;
-        {
-            const bool ring = pwgrad_ring_takes(q);
-            ProfScope ps(e, L, ring ? 8 : (c.cout_p >= 128 ? 3 : 4), 2.0 * c.macs_per_img * imgs);
-            sk = ring ? launch_pwgrad_ring(q, e->slab_floats, L.st) : launch_pwgrad(q, e->slab_floats, L.st);
-        }
-        if (sk > 0) k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
-        else soft(e, hipErrorInvalidValue);
-        return;
+        ProfScope ps(e, L, fam, flops);
+        sk = arm == Arm::PwgradRing ? launch_pwgrad_ring(q, e->slab_floats, L.st) : launch_pwgrad(q, e->slab_floats, L.st);
+        if (sk <= 0) soft(e, hipErrorInvalidValue);
+        break;
     }
-    if (e->planes && c.cin != 3) { soft(e, hipErrorInvalidValue); return; }      // (see conv_fwd: no fp32-operand fallback in planes mode)
-    const bool stem16 = e->precision && c.cin == 3;
-    if (e->precision && (c.k == 1 || stem16)) {
+    case Arm::PwWgrad: {
+        const bool stem16 = c.cin == 3;
         PwWgradParams q{};
         q.dY = reinterpret_cast<const bf16*>(dy); q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x);
         q.slab = L.ws_slab; q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p; q.npix = imgs * c.hout * c.wout;
         if (pro && pro->gate) { q.psc = pro->psc; q.psh = pro->psh; q.gate = pro->gate; }
         q.HW = c.hout * c.wout; q.pix_per_group = pix_per_group ? pix_per_group : q.npix;
-        const int sk = launch_pw_wgrad(q, e->slab_floats, L.st);
-        if (sk > 0) k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
-        else g_err = "pw_wgrad: shape not handled";
-        return;
+        sk = launch_pw_wgrad(q, e->slab_floats, L.st);
+        if (sk <= 0) g_err = "pw_wgrad: shape not handled";
+        break;
     }
-    WgradParams p{};
-    p.dY = dy; p.X = x; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
-    wgrad_geometry(e, c, imgs, p);
-    if (c.stem3) p.X = e->x3;
-    if (e->model == 1 && (c.k == 1 || c.cin == 3)) {
-        int sk;
-        {
-            ProfScope ps(e, L, 4, 2.0 * c.macs_per_img * imgs);
+    case Arm::WgradSkinny:
+    case Arm::WgradGeneric:
+    case Arm::WgradGenericStem: {
+        WgradParams p{};
+        p.dY = dy; p.X = x; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
+        wgrad_geometry(e, c, imgs, p);
+        if (c.stem3) p.X = e->x3;
+        ProfScope ps(e, L, fam, flops);
+        if (arm == Arm::WgradSkinny) {
             sk = launch_wgrad_skinny(p, e->slab_floats, L.st);
+            if (sk <= 0) soft(e, hipErrorInvalidValue);
+            break;
         }
-        if (sk > 0) {
-            k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
-            return;
-        }
+        const int bm = c.cout_p >= 128 ? 128 : 64, bn = wgrad_tile_n(c.cout_p, c.Kw);
+        p.bn = bn;
+        p.tilesM = (c.cout_p + bm - 1) / bm;
+        p.tilesN = (c.Kw + bn - 1) / bn;
+        const int tiles = p.tilesM * p.tilesN;
+        // tiles * splits <= 512 = ONE round of the 512 block slots: with the weight gradients on the side stream next to the
+        // BN-backward / data-gradient chain, a second round of their blocks holds slots the main stream's next GEMM is waiting for
+        // (two-stream step 36.8 -> 36.3 ms; one stream: 38.5 either way; 384: 37.3, 640: 37.4, 1024 = round 2's choice)
+        constexpr int WG_SLOTS = 512;
+        int splits = std::max(1, WG_SLOTS / tiles);
+        const int max_by_pix = std::max(1, p.npix / 256);
+        const int max_by_mem = (int)std::max<size_t>(1, e->slab_floats / c.w_numel);
+        splits = std::max(1, std::min(splits, std::min(max_by_pix, max_by_mem)));
+        p.pix_per_split = (((p.npix + splits - 1) / splits) + 31) & ~31;
+        sk = (p.npix + p.pix_per_split - 1) / p.pix_per_split;
+        if (!launch_wgrad(p, sk, L.st)) soft(e, hipErrorInvalidValue);     // surfaces through STEP_DONE as FM_ERR_HIP
+        break;
     }
-    const int bm = c.cout_p >= 128 ? 128 : 64, bn = wgrad_tile_n(c.cout_p, c.Kw);
-    p.bn = bn;
-    p.tilesM = (c.cout_p + bm - 1) / bm;
-    p.tilesN = (c.Kw + bn - 1) / bn;
-    const int tiles = p.tilesM * p.tilesN;
-    // tiles * splits <= 512 = ONE round of the 512 block slots: with the weight gradients on the side stream next to the
-    // BN-backward / data-gradient chain, a second round of their blocks holds slots the main stream's next GEMM is waiting for
-    // (two-stream step 36.8 -> 36.3 ms; one stream: 38.5 either way; 384: 37.3, 640: 37.4, 1024 = round 2's choice)
-    constexpr int WG_SLOTS = 512;
-    int splits = std::max(1, WG_SLOTS / tiles);
-    const int max_by_pix = std::max(1, p.npix / 256);
-    const int max_by_mem = (int)std::max<size_t>(1, e->slab_floats / c.w_numel);
-    splits = std::max(1, std::min(splits, std::min(max_by_pix, max_by_mem)));
-    p.pix_per_split = (((p.npix + splits - 1) / splits) + 31) & ~31;
-    splits = (p.npix + p.pix_per_split - 1) / p.pix_per_split;
-    {
-        ProfScope ps(e, L, c.cout_p >= 128 ? 3 : (c.cin == 3 ? 5 : 4), 2.0 * c.macs_per_img * imgs);
-        if (!launch_wgrad(p, splits, L.st)) soft(e, hipErrorInvalidValue);     // surfaces through STEP_DONE as FM_ERR_HIP
+    default: soft(e, hipErrorInvalidValue); return;
     }
-    k_reduce_slabs(L.ws_slab, e->grad + c.w_off, splits, (int64_t)c.w_numel, L.st);
+    if (sk > 0) k_reduce_slabs(L.ws_slab, e->grad + c.w_off, sk, (int64_t)c.w_numel, L.st);
     if (c.stem3) k_stem3_mask_grad(e->grad + c.w_off, c.cout_p, L.st);
 }
 
@@ -2204,6 +2247,57 @@ void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, floa
 }
 
 
+// per-channel BatchNorm vectors [groups][C] the fused backward launches of the early MBConv blocks read (the graph's and the test
+// hooks'): the forward's scale / shift (and mean / istd) and the backward's coefficients ca / cb / cc
+struct BnCoef { const float *sc, *sh, *mean, *istd, *ca, *cb, *cc; };
+
+// early blocks (62 % of the expanded-tensor bytes): BN0-backward apply + weight gradient + data gradient of the expand conv in ONE
+// kernel that reads d a_e and y_e once (pw_exp_bwd_kernel / pw_exp_bwd_f32_kernel) instead of five passes over them
+static bool exp_bwd_fuses(const Conv& c) { return (c.cout_p == 96 || c.cout_p == 144) && c.cin_p <= 32; }
+// operands in the handle's storage type; returns the slabs written to L.ws_slab (reduce with k_reduce_slabs), 0 = shape not handled
+static int launch_exp_bwd(fm_engine* e, Lane& L, const Conv& c, const void* dA, const void* Ye, const void* X, const void* res, void* dX,
+                          const BnCoef& bn, int imgs, int groups)
+{
+    if (!exp_bwd_fuses(c)) return 0;
+    PwExpBwdParams qb{};
+    PwExpBwdF32Params qf{};
+    auto fill = [&](auto& q) {             // the twin blocks differ in the element type and in the weight operand
+        using T = std::remove_pointer_t<decltype(q.dX)>;
+        q.dA = static_cast<const T*>(dA); q.Ye = static_cast<const T*>(Ye); q.X = static_cast<const T*>(X);
+        q.res = static_cast<const T*>(res); q.dX = static_cast<T*>(dX);
+        q.slab = L.ws_slab; q.ca = bn.ca; q.cb = bn.cb; q.cc = bn.cc; q.sc = bn.sc; q.sh = bn.sh;
+        q.L = c.cout_p; q.S = c.cin_p; q.groups = groups;
+        q.npix = imgs * c.hout * c.wout; q.pix_per_group = (imgs / groups) * c.hout * c.wout;
+    };
+    if (e->precision) { fill(qb); qb.Wt = e->student.wb + c.wbt_off; } else { fill(qf); qf.W = e->student.state + c.w_off; }
+    return e->precision ? launch_pw_exp_bwd(qb, e->slab_floats, L.st) : launch_pw_exp_bwd_f32(qf, e->slab_floats, L.st);
+}
+
+// pooling records per image of the fused project backward of conv c; 0 = shape not handled
+static int proj_bwd_nch(const fm_engine* e, const Conv& c, int imgs)
+{
+    const int HW = c.hout * c.wout;
+    return e->precision ? pw_proj_bwd_nch(c.cin_p, c.cout_p, imgs, HW) : pw_proj_bwd_f32_nch(c.cin_p, c.cout_p, imgs, HW);
+}
+// phase 0: returns the slabs written to L.ws_slab (0 = not handled) and leaves the five per-image sums in the activation set's
+// se_pool; phase 1: d y_d, 1 = launched.  ipg = images per statistics group, nch = proj_bwd_nch
+static int launch_proj_bwd(fm_engine* e, Lane& L, const Conv& c, int phase, const void* dYp, const void* Yd, void* dYd,
+                           const BnCoef& bn, const float* gate, const float* ds, int imgs, int ipg, int nch)
+{
+    PwProjBwdParams qb{};
+    PwProjBwdF32Params qf{};
+    auto fill = [&](auto& q) {
+        using T = std::remove_pointer_t<decltype(q.dYd)>;
+        q.dYp = static_cast<const T*>(dYp); q.Yd = static_cast<const T*>(Yd); q.dYd = static_cast<T*>(dYd);
+        q.slab = L.ws_slab; q.pool5 = e->acts.se_pool;
+        q.sc = bn.sc; q.sh = bn.sh; q.mean = bn.mean; q.istd = bn.istd; q.ca = bn.ca; q.cb = bn.cb; q.cc = bn.cc;
+        q.gate = gate; q.ds = ds;
+        q.L = c.cin_p; q.S = c.cout_p; q.imgs = imgs; q.HW = c.hout * c.wout; q.ipg = ipg; q.nch = nch;
+    };
+    if (e->precision) { fill(qb); qb.Wt = e->student.wb + c.wbt_off; } else { fill(qf); qf.W = e->student.state + c.w_off; }
+    return e->precision ? launch_pw_proj_bwd(qb, phase, e->slab_floats, L.st) : launch_pw_proj_bwd_f32(qf, phase, e->slab_floats, L.st);
+}
+
 // same contract as backward_and_step
 void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
 {
@@ -2272,40 +2366,28 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         float* drp = (sw && par) ? e->se_drp2 : e->se_drp;
         // early blocks (half of the depthwise-resolution bytes): d a_s is never stored -- pw_proj_bwd_kernel forms it twice on the
         // matrix pipe, once for the five per-image sums + the weight gradient, once for the BN1-backward apply (7 passes -> 3)
-        const int nch5 = e->precision ? pw_proj_bwd_nch(m.ce_p, cp.cout_p, imgs, HWo) : pw_proj_bwd_f32_nch(m.ce_p, cp.cout_p, imgs, HWo);
+        const int nch5 = proj_bwd_nch(e, cp, imgs);
+        // the squeeze-excite backward: ONE pass over (d a_s, y_d) -- or, behind the fused sums, over their nch pooling records with
+        // d a_s null -- yields its pooled sums and the BN1-backward sums; its weight gradient on side lane 3
+        auto se_bwd = [&](const float* das, int nch) {
+            side_guard(e, 3, par);
+            { OP(L, "k_se_bwd"); k_se_bwd_bn1(das, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
+                         S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st, nch); }
+            Lane& SL = side(3, par);
+            { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
+            side_end(e, 3, par);
+        };
         bool pfused = false;
         if (nch5) {
-            PwProjBwdParams q{};
-            PwProjBwdF32Params qf{};
-            if (e->precision) {
-                q.dYp = reinterpret_cast<const bf16*>(T_small); q.Yd = reinterpret_cast<const bf16*>(a.y_d);
-                q.Wt = e->student.wb + cp.wbt_off; q.dYd = reinterpret_cast<bf16*>(T_mid);
-                q.slab = L.ws_slab; q.pool5 = A.se_pool;
-                q.sc = b1.scale; q.sh = b1.shift; q.mean = b1.mean; q.istd = b1.istd; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc;
-                q.gate = a.gate; q.ds = e->se_ds;
-                q.L = m.ce_p; q.S = cp.cout_p; q.imgs = imgs; q.HW = HWo; q.ipg = B; q.nch = nch5;
-            } else {
-                qf.dYp = T_small; qf.Yd = a.y_d; qf.W = S + cp.w_off; qf.dYd = T_mid;
-                qf.slab = L.ws_slab; qf.pool5 = A.se_pool;
-                qf.sc = b1.scale; qf.sh = b1.shift; qf.mean = b1.mean; qf.istd = b1.istd; qf.ca = e->ca; qf.cb = e->cb; qf.cc = e->cc;
-                qf.gate = a.gate; qf.ds = e->se_ds;
-                qf.L = m.ce_p; qf.S = cp.cout_p; qf.imgs = imgs; qf.HW = HWo; qf.ipg = B; qf.nch = nch5;
-            }
             auto launch = [&](int phase) {
-                return e->precision ? launch_pw_proj_bwd(q, phase, e->slab_floats, L.st) : launch_pw_proj_bwd_f32(qf, phase, e->slab_floats, L.st);
+                return launch_proj_bwd(e, L, cp, phase, T_small, a.y_d, T_mid, {b1.scale, b1.shift, b1.mean, b1.istd, e->ca, e->cb, e->cc},
+                                       a.gate, e->se_ds, imgs, B, nch5);
             };
             int sk;
             { OP(L, "proj_bwd_sums"); sk = launch(0);
               if (sk > 0) k_reduce_slabs(L.ws_slab, G + cp.w_off, sk, (int64_t)cp.w_numel, L.st); }
             if (sk > 0) {
-                side_guard(e, 3, par);
-                { OP(L, "k_se_bwd"); k_se_bwd_bn1(nullptr, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
-                             S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st, nch5); }
-                {
-                    Lane& SL = side(3, par);
-                    { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
-                    side_end(e, 3, par);
-                }
+                se_bwd(nullptr, nch5);
                 side_guard(e, 1, par);
                 { OP(L, "proj_bwd_apply");
                   k_bn_bwd_finalize(e->ws_part, groups, se_bwd_bn1_splits(B), b1.C, B * HWo, e->student.state + e->off_gamma + b1.ch_off, b1.mean,
@@ -2329,16 +2411,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
             }
             side_guard(e, 1, par);
             { OP(L, "proj_dgrad"); conv_dgrad(e, L, m.c_proj, T_small, T_mid, imgs, nullptr, false); }          // d a_s
-            // a_s = a_d * gate(a_d)
-            // ONE pass over (d a_s, y_d) yields the squeeze-excite backward's pooled sums and the BN1-backward sums
-            side_guard(e, 3, par);
-            { OP(L, "k_se_bwd"); k_se_bwd_bn1(T_mid, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
-                         S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st); }
-            {
-                Lane& SL = side(3, par);
-                { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
-                side_end(e, 3, par);
-            }
+            se_bwd(T_mid, 0);                 // a_s = a_d * gate(a_d)
             // d a_d = d a_s * gate + ds/HW is formed on load inside the BN backward's apply pass
             { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn1, T_mid, a.y_d, T_mid, nullptr, groups, B * HWo, HWo, 2, bw.frozen, a.gate, e->se_ds, -1,
                                          se_bwd_bn1_splits(B)); }   // d y_d
@@ -2358,10 +2431,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
             { OP(L, "k_dw_dgrad"); sums = k_dw_dgrad(T_mid, S + m.dw_off, T_big, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
                        m.pad_t, m.pad_l, L.st, ce.y, b0.mean, b0.istd, b0.scale, b0.shift, L.rec, e->ws_part, groups); }
             bool fused = false;
-            if ((ce.cout_p == 96 || ce.cout_p == 144) && ce.cin_p <= 32) {
-                // early blocks (62 % of the expanded-tensor bytes): BN0-backward apply + weight gradient + data gradient of the
-                // expand conv in ONE kernel that reads d a_e and y_e once (pw_exp_bwd_kernel / pw_exp_bwd_f32_kernel) instead of
-                // five passes over them
+            if (exp_bwd_fuses(ce)) {
                 OP(L, "exp_bwd_fused");
                 const int pix = B * HWi;
                 if (!sums)
@@ -2370,22 +2440,8 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                 k_bn_bwd_finalize(e->ws_part, groups, sums ? dw_stats_tiles() : bn_bwd_blocks(pix), b0.C, pix,
                                   e->student.state + e->off_gamma + b0.ch_off, b0.mean, b0.istd, e->ca, e->cb, e->cc,
                                   e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
-                int sk;
-                if (e->precision) {
-                    PwExpBwdParams q{};
-                    q.dA = reinterpret_cast<const bf16*>(T_big); q.Ye = reinterpret_cast<const bf16*>(ce.y);
-                    q.X = reinterpret_cast<const bf16*>(in); q.Wt = e->student.wb + ce.wbt_off;
-                    q.res = reinterpret_cast<const bf16*>(m.skip ? go : nullptr); q.dX = reinterpret_cast<bf16*>(gi);
-                    q.slab = L.ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
-                    q.L = ce.cout_p; q.S = ce.cin_p; q.npix = imgs * HWi; q.pix_per_group = pix; q.groups = groups;
-                    sk = launch_pw_exp_bwd(q, e->slab_floats, L.st);
-                } else {
-                    PwExpBwdF32Params q{};
-                    q.dA = T_big; q.Ye = ce.y; q.X = in; q.W = S + ce.w_off; q.res = m.skip ? go : nullptr; q.dX = gi;
-                    q.slab = L.ws_slab; q.ca = e->ca; q.cb = e->cb; q.cc = e->cc; q.sc = b0.scale; q.sh = b0.shift;
-                    q.L = ce.cout_p; q.S = ce.cin_p; q.npix = imgs * HWi; q.pix_per_group = pix; q.groups = groups;
-                    sk = launch_pw_exp_bwd_f32(q, e->slab_floats, L.st);
-                }
+                const int sk = launch_exp_bwd(e, L, ce, T_big, ce.y, in, m.skip ? go : nullptr, gi,
+                                              {b0.scale, b0.shift, nullptr, nullptr, e->ca, e->cb, e->cc}, imgs, groups);
                 if (sk > 0) {
                     k_reduce_slabs(L.ws_slab, G + ce.w_off, sk, (int64_t)ce.w_numel, L.st);
                     fused = true;
@@ -2441,6 +2497,19 @@ int teacher_forward_side(fm_engine* e, int imgs)
     HIPCHK(hipStreamWaitEvent(e->side.st, e->ev_in, 0));
     net_forward_eval(e, e->side, e->teacher, e->tacts, imgs, e->tfeat, e->tlogits);
     HIPCHK(hipEventRecord(e->ev_t, e->side.st));
+    return FM_OK;
+}
+// the frozen teacher's eval forward of the staged batch (timgs images) beside the student's train forward of `groups` views of B: on
+// the side lane with its own activation set (they meet at the loss), else first (its activations may be overwritten by the student)
+int teacher_and_student_forward(fm_engine* e, int timgs, int groups, int B)
+{
+    if (e->side_ok) RCCHK(teacher_forward_side(e, timgs));
+    else {
+        ensure_teacher_shadow(e);
+        net_forward_eval(e, e->main, e->teacher, e->acts, timgs, e->tfeat, e->tlogits);
+    }
+    net_forward_train(e, groups, B);
+    if (e->side_ok) HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
     return FM_OK;
 }
 void net_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw = {})
@@ -2945,17 +3014,7 @@ int fm_step_stage1(fm_engine* e, const float* x1_dev, const float* x2_dev, const
     for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
     const float* xs[2] = {x1_dev, x2_dev};
     to_nhwc4(e, e->main, xs, 2, B);
-    if (e->side_ok) {
-        // frozen teacher on the side lane (own activation set), student on the main lane; they meet at the loss
-        RCCHK(teacher_forward_side(e, 2 * B));
-        net_forward_train(e, 2, B);
-        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
-    } else {
-        // frozen teacher first (eval mode; its activations may be overwritten by the student)
-        ensure_teacher_shadow(e);
-        net_forward_eval(e, e->main, e->teacher, e->acts, 2 * B, e->tfeat, e->tlogits);
-        net_forward_train(e, 2, B);
-    }
+    RCCHK(teacher_and_student_forward(e, 2 * B, 2, B));
     k_loss_stage1(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C,
                   1.f / ((float)bs_norm * (float)annotation_num),
                   n_neg ? 1.f / ((float)bs_norm * (float)n_neg) : 0.f, e->dlogits, loss_dev, e->main.st);
@@ -3175,16 +3234,7 @@ int fm_step_fednoro(fm_engine* e, const float* x_dev, const float* y_dev, int32_
     ARGCHK(na >= 1 && na < e->C, kHeadClasses);
     const float* xs[1] = {x_dev};
     to_nhwc4(e, e->main, xs, 1, B);
-    if (e->side_ok) {
-        // frozen teacher on the side lane (own activation set), student on the main lane, both reading the one staged view
-        RCCHK(teacher_forward_side(e, B));
-        net_forward_train(e, 1, B);
-        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
-    } else {
-        ensure_teacher_shadow(e);
-        net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
-        net_forward_train(e, 1, B);
-    }
+    RCCHK(teacher_and_student_forward(e, B, 1, B));      // both read the one staged view
     k_loss_lakd(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C, na, w_kd, e->dlogits, loss_dev, e->main.st);
     net_backward_and_step(e, 1, B);
     STEP_DONE(e);
@@ -3841,32 +3891,13 @@ int fm_debug_proj_bwd(fm_engine* e, int32_t conv, int32_t phase, const void* dyp
     ARGCHK(dyp_dev && yd_dev && bn_dev && gate_dev && (phase == 0 ? pool5_dev != nullptr : ds_dev != nullptr), "operands");
     Conv& c = e->convs[conv];
     ensure_packed(e);
-    const int L = c.cin_p, HW = c.hout * c.wout;
-    const int nch = e->precision ? pw_proj_bwd_nch(L, c.cout_p, imgs, HW) : pw_proj_bwd_f32_nch(L, c.cout_p, imgs, HW);
+    const int L = c.cin_p;
+    const int nch = proj_bwd_nch(e, c, imgs);
     ARGCHK(nch > 0, "shape not handled by the fused project backward");
+    const float* bn = bn_dev;
     const size_t gl = (size_t)groups * L;
-    int sk;
-    if (e->precision) {
-        PwProjBwdParams q{};
-        q.dYp = reinterpret_cast<const bf16*>(dyp_dev); q.Yd = reinterpret_cast<const bf16*>(yd_dev);
-        q.Wt = e->student.wb + c.wbt_off; q.dYd = reinterpret_cast<bf16*>(out_dev);
-        q.slab = e->main.ws_slab; q.pool5 = e->acts.se_pool;
-        q.sc = bn_dev; q.sh = bn_dev + gl; q.mean = bn_dev + 2 * gl; q.istd = bn_dev + 3 * gl;
-        q.ca = bn_dev + 4 * gl; q.cb = bn_dev + 5 * gl; q.cc = bn_dev + 6 * gl;
-        q.gate = gate_dev; q.ds = ds_dev;
-        q.L = L; q.S = c.cout_p; q.imgs = imgs; q.HW = HW; q.ipg = imgs / groups; q.nch = nch;
-        sk = launch_pw_proj_bwd(q, phase, e->slab_floats, e->main.st);
-    } else {
-        PwProjBwdF32Params q{};
-        q.dYp = reinterpret_cast<const float*>(dyp_dev); q.Yd = reinterpret_cast<const float*>(yd_dev);
-        q.W = e->student.state + c.w_off; q.dYd = reinterpret_cast<float*>(out_dev);
-        q.slab = e->main.ws_slab; q.pool5 = e->acts.se_pool;
-        q.sc = bn_dev; q.sh = bn_dev + gl; q.mean = bn_dev + 2 * gl; q.istd = bn_dev + 3 * gl;
-        q.ca = bn_dev + 4 * gl; q.cb = bn_dev + 5 * gl; q.cc = bn_dev + 6 * gl;
-        q.gate = gate_dev; q.ds = ds_dev;
-        q.L = L; q.S = c.cout_p; q.imgs = imgs; q.HW = HW; q.ipg = imgs / groups; q.nch = nch;
-        sk = launch_pw_proj_bwd_f32(q, phase, e->slab_floats, e->main.st);
-    }
+    const BnCoef coef{bn, bn + gl, bn + 2 * gl, bn + 3 * gl, bn + 4 * gl, bn + 5 * gl, bn + 6 * gl};
+    const int sk = launch_proj_bwd(e, e->main, c, phase, dyp_dev, yd_dev, out_dev, coef, gate_dev, ds_dev, imgs, imgs / groups, nch);
     ARGCHK(sk > 0, "launch refused");
     if (phase == 0) {
         k_reduce_slabs(e->main.ws_slab, reinterpret_cast<float*>(out_dev), sk, (int64_t)c.w_numel, e->main.st);
@@ -3893,26 +3924,10 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
     ARGCHK(imgs >= 1 && imgs <= e->maxB && groups >= 1 && groups <= 2 && imgs % groups == 0, "imgs/groups");
     Conv& c = e->convs[conv];
     ensure_packed(e);
-    const int L = c.cout_p, S = c.cin_p, HW = c.hout * c.wout;
-    const size_t gl = (size_t)groups * L;
-    int sk;
-    if (e->precision) {
-        PwExpBwdParams q{};
-        q.dA = reinterpret_cast<const bf16*>(da_dev); q.Ye = reinterpret_cast<const bf16*>(ye_dev);
-        q.X = reinterpret_cast<const bf16*>(x_dev); q.Wt = e->student.wb + c.wbt_off; q.res = reinterpret_cast<const bf16*>(res_dev);
-        q.dX = reinterpret_cast<bf16*>(dx_dev); q.slab = e->main.ws_slab;
-        q.ca = bn_dev; q.cb = bn_dev + gl; q.cc = bn_dev + 2 * gl; q.sc = bn_dev + 3 * gl; q.sh = bn_dev + 4 * gl;
-        q.L = L; q.S = S; q.npix = imgs * HW; q.pix_per_group = (imgs / groups) * HW; q.groups = groups;
-        sk = launch_pw_exp_bwd(q, e->slab_floats, e->main.st);
-    } else {
-        PwExpBwdF32Params q{};
-        q.dA = reinterpret_cast<const float*>(da_dev); q.Ye = reinterpret_cast<const float*>(ye_dev);
-        q.X = reinterpret_cast<const float*>(x_dev); q.W = e->student.state + c.w_off; q.res = reinterpret_cast<const float*>(res_dev);
-        q.dX = reinterpret_cast<float*>(dx_dev); q.slab = e->main.ws_slab;
-        q.ca = bn_dev; q.cb = bn_dev + gl; q.cc = bn_dev + 2 * gl; q.sc = bn_dev + 3 * gl; q.sh = bn_dev + 4 * gl;
-        q.L = L; q.S = S; q.npix = imgs * HW; q.pix_per_group = (imgs / groups) * HW; q.groups = groups;
-        sk = launch_pw_exp_bwd_f32(q, e->slab_floats, e->main.st);
-    }
+    const float* bn = bn_dev;
+    const size_t gl = (size_t)groups * c.cout_p;
+    const BnCoef coef{bn + 3 * gl, bn + 4 * gl, nullptr, nullptr, bn, bn + gl, bn + 2 * gl};
+    const int sk = launch_exp_bwd(e, e->main, c, da_dev, ye_dev, x_dev, res_dev, dx_dev, coef, imgs, groups);
     ARGCHK(sk > 0, "shape not handled by the fused expand backward");
     k_reduce_slabs(e->main.ws_slab, dw_dev, sk, (int64_t)c.w_numel, e->main.st);
     HIPCHK(hipGetLastError());
@@ -4156,41 +4171,23 @@ int fm_debug_conv_arm(fm_engine* e, int32_t op, int32_t conv, int32_t imgs)
     ARGCHK(!e->precision, "fm_debug_conv_arm: a precision-0 engine");
     ARGCHK(imgs >= 1 && imgs <= e->maxB && op >= 0 && op <= 2, "imgs / op");
     const Conv& c = e->convs[conv];
-    if (op == 0) {                      // conv_fwd
-        if (e->stem_rows && c.stem3) return FM_ARM_STEM_ROWS;
-        if (conv_uses_pconv(e, c, imgs)) {
-            IgemmParams p{};
-            pconv_fwd_geometry(c, p);
-            return pconv_uses_ts(p) ? FM_ARM_PCONV_TS : FM_ARM_PCONV_TAP;
-        }
-        ARGCHK(!(e->planes && c.cin != 3), "conv_fwd has no kernel for this shape in planes mode");
-        return c.cin == 3 ? FM_ARM_IGEMM_STEM : FM_ARM_IGEMM;
+    if (op == 1 && c.cin == 3) return FM_ARM_STEM_DGRAD;        // fm_debug_conv's data gradient of the stem: its own kernel
+    ARGCHK(op != 1 || c.ncls > 0, "dgrad unavailable for this conv");
+    switch (op == 0 ? fwd_arm(e, c, imgs) : (op == 1 ? dgrad_arm(e, c, imgs) : wgrad_arm(e, c, imgs))) {
+    case Arm::StemRows: return FM_ARM_STEM_ROWS;
+    case Arm::PconvTs: return FM_ARM_PCONV_TS;
+    case Arm::PconvTap: return FM_ARM_PCONV_TAP;
+    case Arm::Igemm: return FM_ARM_IGEMM;
+    case Arm::IgemmStem: return FM_ARM_IGEMM_STEM;
+    case Arm::Pwgrad: return FM_ARM_PWGRAD;
+    case Arm::PwgradRing: return FM_ARM_PWGRAD_RING;
+    case Arm::WgradSkinny: return FM_ARM_WGRAD_SKINNY;
+    case Arm::WgradGeneric:
+    case Arm::WgradGenericStem: return FM_ARM_WGRAD_GENERIC;
+    default: break;                     // None (the bf16 pointwise arms need precision 1)
     }
-    if (op == 1) {                      // fm_debug_conv's data gradient: the stem's kernel, else conv_dgrad
-        if (c.cin == 3) return FM_ARM_STEM_DGRAD;
-        ARGCHK(c.ncls > 0, "dgrad unavailable for this conv");
-        if (dgrad_uses_pconv(e, c, imgs)) {
-            bool ts = true;
-            for (int k = 0; k < c.ncls; ++k) {
-                IgemmParams p{};
-                pconv_dgrad_geometry(c, c.cls[k], p);
-                ts = ts && pconv_uses_ts(p);
-            }
-            return ts ? FM_ARM_PCONV_TS : FM_ARM_PCONV_TAP;
-        }
-        ARGCHK(!e->planes, "conv_dgrad has no kernel for this shape in planes mode");
-        return FM_ARM_IGEMM;
-    }
-    if (wgrad_uses_pwgrad(e, c, imgs)) {        // conv_wgrad
-        PwgradParams q{};
-        pwgrad_geometry(e, c, imgs, q);
-        return pwgrad_ring_takes(q) ? FM_ARM_PWGRAD_RING : FM_ARM_PWGRAD;
-    }
-    ARGCHK(!(e->planes && c.cin != 3), "conv_wgrad has no kernel for this shape in planes mode");
-    WgradParams p{};
-    wgrad_geometry(e, c, imgs, p);
-    if (e->model == 1 && (c.k == 1 || c.cin == 3) && wgrad_skinny_takes(p)) return FM_ARM_WGRAD_SKINNY;
-    return FM_ARM_WGRAD_GENERIC;
+    g_err = "bad argument: no kernel for this shape in planes mode";
+    return FM_ERR_ARG;
 }
 
 int fm_debug_ew(fm_engine* e, int32_t op, void* const* p, const int32_t* d, const float* sc)

@@ -65,8 +65,8 @@ int fm_debug_conv_planes(fm_engine* e, int32_t conv, const uint16_t* xp_dev, int
                          uint16_t* outp_dev);
 
 /* Which launcher fm_debug_conv's op (0 forward = conv_fwd, 1 data gradient, 2 weight gradient = conv_wgrad) takes for `imgs` images
- * on this handle (precision 0): a host-side query, nothing is launched.  It evaluates the predicates those functions branch on, on
- * the parameters they build.  A data gradient of several parity classes reports FM_ARM_PCONV_TAP if any class runs per tap.
+ * on this handle (precision 0): a host-side query, nothing is launched.  It returns the launchers' own decision: the arm those
+ * functions switch on.  A data gradient of several parity classes reports FM_ARM_PCONV_TAP if any class runs per tap.
  * Returns an FM_ARM_* code (>= 0) or a negative error code. */
 enum { FM_ARM_IGEMM = 0, FM_ARM_IGEMM_STEM, FM_ARM_STEM_ROWS, FM_ARM_PCONV_TS, FM_ARM_PCONV_TAP, FM_ARM_PWGRAD, FM_ARM_PWGRAD_RING,
        FM_ARM_WGRAD_GENERIC, FM_ARM_WGRAD_SKINNY, FM_ARM_STEM_DGRAD };
