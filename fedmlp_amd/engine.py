@@ -141,6 +141,8 @@ class Engine:
 
     def counters(self, new=None):
         c = np.zeros(self.ni, np.int64) if new is None else np.ascontiguousarray(new, dtype=np.int64)
+        if new is not None:
+            self._enqueue(weights=True)          # the counters are part of the resident state
         _lib.check(self.lib.fm_counters(self.h, c.ctypes.data_as(C.c_void_p), int(new is not None)))
         return c
 
