@@ -49,6 +49,11 @@ const char* fm_version(void) { return "fedmlp_hip 0.2 (gfx950)"; }
     do {                                                                     \
         if (!(c)) { g_err = std::string("bad argument: ") + msg; return FM_ERR_ARG; } \
     } while (0)
+// refuse with what a `*_bad` validator answers (nullptr: fine)
+#define BADCHK(x)                                                            \
+    do {                                                                     \
+        if (const char* bad_ = (x)) ARGCHK(false, bad_);                     \
+    } while (0)
 
 namespace {
 
@@ -2643,6 +2648,125 @@ static const char* const kMaskRefusal =
     "fm_backward_grads, fm_adam_step_groups / fm_adamw_step_groups / fm_sgd_step_groups), or restore the default mask with "
     "fm_set_trainable";
 
+// ---- the fused training steps: one skeleton, and per loss head its argument rules (`*_bad`) and its launcher ----
+namespace {
+
+int count_active(const fm_engine* e, const float* active_mask_host)
+{
+    int n = 0;
+    for (int c = 0; c < e->C; ++c) n += active_mask_host[c] != 0.f;
+    return n;
+}
+// the single-view heads' common contract: at least one active and one missing class (torch forms 0/0 or the mean of an empty
+// tensor otherwise)
+const char* classes_bad(const fm_engine* e, const float* active_mask_host)
+{
+    const int na = count_active(e, active_mask_host);
+    return na >= 1 && na < e->C ? nullptr : "the head needs at least one active and one missing class";
+}
+const char* norm_bad(int B, int ann, int bs)
+{
+    return B >= 1 && ann >= 1 && bs >= 1 && (int64_t)bs * ann < (1 << 24)
+               ? nullptr : "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24";
+}
+const char* fedlsr_bad(float mix1, bool step)
+{
+    if (mix1 >= 0.f && mix1 <= 1.f) return nullptr;
+    return step ? "fm_step_fedlsr: mix1 in [0, 1]" : "fm_loss_fedlsr: mix1 in [0, 1]";
+}
+const char* fedirm_bad(int B, int ann, int bs, bool rel)
+{
+    if (const char* bad = norm_bad(B, ann, bs)) return bad;
+    return rel && B > 2048 ? "fm_loss_fedirm_rel: B <= 2048 (the selected-row table)" : nullptr;
+}
+const char* rscfed_bad(const fm_engine* e, const float* am, int ann, int bs, int B)
+{
+    if (const char* bad = norm_bad(B, ann, bs)) return bad;
+    return classes_bad(e, am);
+}
+const char* cbafed_bad(const fm_engine* e, const float* am, int ann, int bs, const float* tao, const int64_t* counts_dev, int B,
+                       bool step)
+{
+    if (tao && !counts_dev)
+        return step ? "fm_step_cbafed: stage 2 (tao given) needs counts_dev" : "fm_loss_cbafed: stage 2 (tao given) needs counts_dev";
+    return rscfed_bad(e, am, ann, bs, B);
+}
+
+void launch_fedlsr(fm_engine* e, const float* z, const float* y, const float* pw, float mix1, float beta, int B, float* dz, float* loss)
+{
+    k_loss_fedlsr(z, y, to_cv(pw, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, dz, loss, e->main.st);
+}
+void launch_rscfed(fm_engine* e, const float* z, const float* zt, const float* y, const float* pw, const float* am, int ann, int bs,
+                   int B, float* dz, float* loss)
+{
+    k_loss_rscfed(z, zt, y, to_cv(pw, e->C), to_cv(am, e->C), B, e->C, (float)bs * (float)ann, e->C - count_active(e, am), dz, loss,
+                  e->main.st);
+}
+void launch_lakd(fm_engine* e, const float* z, const float* zt, const float* y, const float* am, float w_kd, int B, float* dz,
+                 float* loss)
+{
+    k_loss_lakd(z, zt, y, to_cv(am, e->C), B, e->C, count_active(e, am), w_kd, dz, loss, e->main.st);
+}
+void launch_cbafed(fm_engine* e, const float* z, const float* y, const float* am, int ann, int bs, const float* tao, int B,
+                   float* pw_dev, int64_t* counts_dev, float* dz, float* loss)
+{
+    ClassVec t{};
+    if (tao) t = to_cv(tao, e->C);
+    k_loss_cbafed(z, y, to_cv(am, e->C), tao ? &t : nullptr, B, e->C, (float)bs * (float)ann, ann, pw_dev, counts_dev, dz, loss,
+                  e->main.st);
+}
+
+// which forwards a fused step runs before its head
+enum class StepFwd {
+    Student,     // the student's train forward of every staged view
+    Frozen,      // the frozen teacher's eval forward of the staged batch beside it (teacher_and_student_forward)
+    Rscfed       // the EMA teacher's eval forward of view 2 beside the student's train forward of view 1
+};
+
+// A fused step: refusals (nothing is enqueued before the last of them), staging of x1 (and x2), the forwards, `head` on e->logits
+// (and e->tlogits) -> e->dlogits, backward and Adam.  head_bad is the head's `*_bad` answer for the caller's arguments.
+// Rscfed's lane order: both views are staged on the main lane (view 2 as the staging's second group); the teacher's
+// shadows are re-formed on the main lane, behind the previous step's blend; ev_in lets the side lane start, ev_t brings it back
+// before the head -- so the blend, on the main lane behind Adam, never meets a running teacher forward, and the next step's fork is
+// enqueued behind it.
+template <typename Head>
+int fused_step(fm_engine* e, StepFwd fwd, const float* x1, const float* x2, int B, const char* head_bad, Head head)
+{
+    const int views = x2 ? 2 : 1;                                 // staged
+    const int groups = fwd == StepFwd::Rscfed ? 1 : views;        // trained on
+    ARGCHK(e->trainable.empty(), kMaskRefusal);
+    if (groups == 2) ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
+    else ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    BADCHK(head_bad);
+    const float* xs[2] = {x1, x2};
+    if (fwd == StepFwd::Rscfed && !(e->side_ok && 2 * B <= e->maxB)) {
+        // one lane (or no room for both views in the staging): the teacher first, each view staged in turn
+        to_nhwc4(e, e->main, &x2, 1, B);
+        ensure_teacher_shadow(e);
+        net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
+        to_nhwc4(e, e->main, &x1, 1, B);
+        net_forward_train(e, 1, B);
+    } else {
+        to_nhwc4(e, e->main, xs, views, B);
+        if (fwd == StepFwd::Student) net_forward_train(e, groups, B);
+        else if (fwd == StepFwd::Frozen) RCCHK(teacher_and_student_forward(e, views * B, groups, B));
+        else {
+            e->in_img0 = B;                      // the teacher's stem reads the second group
+            const int rc = teacher_forward_side(e, B);
+            e->in_img0 = 0;
+            RCCHK(rc);
+            net_forward_train(e, 1, B);
+            HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
+        }
+    }
+    head();
+    net_backward_and_step(e, groups, B);
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+}  // namespace
+
 // =============================== C ABI =======================================
 extern "C" {
 
@@ -2992,50 +3116,30 @@ int fm_step_bce(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B,
                 int32_t bs_norm, float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && pos_weight_host && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
-    const float* xs[1] = {x_dev};
-    to_nhwc4(e, e->main, xs, 1, B);
-    net_forward_train(e, 1, B);
-    k_loss_bce(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, 1.f / ((float)bs_norm * (float)e->C),
-               e->dlogits, loss_dev, e->main.st);
-    net_backward_and_step(e, 1, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Student, x_dev, nullptr, B, nullptr, [&] {
+        k_loss_bce(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, 1.f / ((float)bs_norm * (float)e->C), e->dlogits,
+                   loss_dev, e->main.st);
+    });
 }
 
 int fm_step_stage1(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
                    const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, float* loss_dev)
 {
     ARGCHK(e && x1_dev && x2_dev && y_dev && active_mask_host && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
-    int n_neg = 0;
-    for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
-    const float* xs[2] = {x1_dev, x2_dev};
-    to_nhwc4(e, e->main, xs, 2, B);
-    RCCHK(teacher_and_student_forward(e, 2 * B, 2, B));
-    k_loss_stage1(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C,
-                  1.f / ((float)bs_norm * (float)annotation_num),
-                  n_neg ? 1.f / ((float)bs_norm * (float)n_neg) : 0.f, e->dlogits, loss_dev, e->main.st);
-    net_backward_and_step(e, 2, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Frozen, x1_dev, x2_dev, B, nullptr, [&] {
+        const int n_neg = e->C - count_active(e, active_mask_host);
+        k_loss_stage1(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C,
+                      1.f / ((float)bs_norm * (float)annotation_num),
+                      n_neg ? 1.f / ((float)bs_norm * (float)n_neg) : 0.f, e->dlogits, loss_dev, e->main.st);
+    });
 }
 
 int fm_step_stage2(fm_engine* e, const float* x_dev, const float* y_dev, const float* distill_dev, int32_t B,
                    float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && distill_dev && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
-    const float* xs[1] = {x_dev};
-    to_nhwc4(e, e->main, xs, 1, B);
-    net_forward_train(e, 1, B);
-    k_loss_stage2(e->logits, y_dev, distill_dev, B, e->C, e->dlogits, loss_dev, e->main.st);
-    net_backward_and_step(e, 1, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Student, x_dev, nullptr, B, nullptr,
+                      [&] { k_loss_stage2(e->logits, y_dev, distill_dev, B, e->C, e->dlogits, loss_dev, e->main.st); });
 }
 
 int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, const float* y_dev, int32_t B,
@@ -3044,19 +3148,12 @@ int fm_step_fixmatch(fm_engine* e, const float* xw_dev, const float* xs_dev, con
 {
     ARGCHK(e && xw_dev && xs_dev && y_dev && pos_weight_host && pos_weight_unk_host && active_mask_host && loss_dev,
            "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && 2 * B <= e->maxB && B <= 2048, "2*B exceeds max_images");
-    int n_neg = 0;
-    for (int c = 0; c < e->C; ++c) n_neg += active_mask_host[c] == 0.f;
-    const float* xs[2] = {xw_dev, xs_dev};
-    to_nhwc4(e, e->main, xs, 2, B);
-    net_forward_train(e, 2, B);
-    k_loss_fixmatch(e->logits, y_dev, to_cv(pos_weight_host, e->C), to_cv(pos_weight_unk_host, e->C),
-                    to_cv(active_mask_host, e->C), B, e->C, n_neg, 1.f / ((float)bs_norm * (float)annotation_num),
-                    e->C - annotation_num, e->dlogits, loss_dev, e->main.st);
-    net_backward_and_step(e, 2, B);
-    STEP_DONE(e);
-    return FM_OK;
+    // the head's selected-row table holds 2048 rows; past it the batch-size text answers, as it always has
+    return fused_step(e, StepFwd::Student, xw_dev, xs_dev, B, B <= 2048 ? nullptr : "2*B exceeds max_images", [&] {
+        k_loss_fixmatch(e->logits, y_dev, to_cv(pos_weight_host, e->C), to_cv(pos_weight_unk_host, e->C),
+                        to_cv(active_mask_host, e->C), B, e->C, e->C - count_active(e, active_mask_host),
+                        1.f / ((float)bs_norm * (float)annotation_num), e->C - annotation_num, e->dlogits, loss_dev, e->main.st);
+    });
 }
 
 // ---- FedLSR / FedIRM: the heads alone on caller tensors, and the fused FedLSR step ----
@@ -3065,9 +3162,8 @@ int fm_loss_fedlsr(fm_engine* e, const float* z_dev, const float* y_dev, const f
 {
     ARGCHK(e && z_dev && y_dev && pos_weight_host && dz_dev && loss_dev, "null");
     ARGCHK(B >= 1, "B >= 1");
-    ARGCHK(mix1 >= 0.f && mix1 <= 1.f, "fm_loss_fedlsr: mix1 in [0, 1]");
-    k_loss_fedlsr(z_dev, y_dev, to_cv(pos_weight_host, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, dz_dev, loss_dev,
-                  e->main.st);
+    BADCHK(fedlsr_bad(mix1, false));
+    launch_fedlsr(e, z_dev, y_dev, pos_weight_host, mix1, beta, B, dz_dev, loss_dev);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -3077,8 +3173,7 @@ int fm_loss_fedirm_sup(fm_engine* e, const float* z_dev, const float* y_dev, con
                        float* dz_dev, float* loss_dev)
 {
     ARGCHK(e && z_dev && y_dev && pos_weight_host && active_mask_host && dz_dev && loss_dev, "null");
-    ARGCHK(B >= 1 && annotation_num >= 1 && bs_norm >= 1 && (int64_t)bs_norm * annotation_num < (1 << 24),
-           "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24");
+    BADCHK(fedirm_bad(B, annotation_num, bs_norm, false));
     k_loss_fedirm_sup(z_dev, y_dev, to_cv(pos_weight_host, e->C), to_cv(active_mask_host, e->C), B, e->C,
                       (float)bs_norm * (float)annotation_num, rel_acc_dev, dz_dev, loss_dev, e->main.st);
     HIPCHK(hipGetLastError());
@@ -3090,9 +3185,7 @@ int fm_loss_fedirm_rel(fm_engine* e, const float* z_dev, const float* zt_dev, co
                        int32_t B, float* rel_acc_dev, float* dz_dev, float* loss_dev)
 {
     ARGCHK(e && z_dev && zt_dev && y_dev && pos_weight_host && active_mask_host && target_dev && dz_dev && loss_dev, "null");
-    ARGCHK(B >= 1 && annotation_num >= 1 && bs_norm >= 1 && (int64_t)bs_norm * annotation_num < (1 << 24),
-           "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24");
-    ARGCHK(B <= 2048, "fm_loss_fedirm_rel: B <= 2048 (the selected-row table)");
+    BADCHK(fedirm_bad(B, annotation_num, bs_norm, true));
     k_loss_fedirm_rel(z_dev, zt_dev, y_dev, to_cv(pos_weight_host, e->C), to_cv(active_mask_host, e->C), B, e->C,
                       (float)bs_norm * (float)annotation_num, (float)bs_norm, cw, target_dev, rel_acc_dev, dz_dev,
                       loss_dev, e->main.st);
@@ -3104,53 +3197,16 @@ int fm_step_fedlsr(fm_engine* e, const float* x1_dev, const float* x2_dev, const
                    const float* pos_weight_host, float mix1, float beta, float* loss_dev)
 {
     ARGCHK(e && x1_dev && x2_dev && y_dev && pos_weight_host && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
-    ARGCHK(mix1 >= 0.f && mix1 <= 1.f, "fm_step_fedlsr: mix1 in [0, 1]");
-    const float* xs[2] = {x1_dev, x2_dev};
-    to_nhwc4(e, e->main, xs, 2, B);
-    net_forward_train(e, 2, B);
-    k_loss_fedlsr(e->logits, y_dev, to_cv(pos_weight_host, e->C), B, e->C, mix1, (float)(1.0 - (double)mix1), beta, e->dlogits,
-                  loss_dev, e->main.st);
-    net_backward_and_step(e, 2, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Student, x1_dev, x2_dev, B, fedlsr_bad(mix1, true),
+                      [&] { launch_fedlsr(e, e->logits, y_dev, pos_weight_host, mix1, beta, B, e->dlogits, loss_dev); });
 }
 
 // ---- RSCFed / FedNoRo / CBAFed: the single-view heads on caller tensors, and their fused steps ----
-// the heads' common contract: at least one active and one missing class (torch forms 0/0 or the mean of an empty tensor otherwise)
-static int count_active(const fm_engine* e, const float* active_mask_host)
-{
-    int n = 0;
-    for (int c = 0; c < e->C; ++c) n += active_mask_host[c] != 0.f;
-    return n;
-}
-static const char* const kHeadClasses = "the head needs at least one active and one missing class";
-static const char* const kHeadNorm = "B, annotation_num, bs_norm >= 1; bs_norm * annotation_num < 2^24";
-#define HEAD_NORM_OK(B, ann, bs) ((B) >= 1 && (ann) >= 1 && (bs) >= 1 && (int64_t)(bs) * (ann) < (1 << 24))
-
-static void launch_rscfed(fm_engine* e, const float* z, const float* zt, const float* y, const float* pw, const float* am, int ann,
-                          int bs, int B, float* dz, float* loss)
-{
-    k_loss_rscfed(z, zt, y, to_cv(pw, e->C), to_cv(am, e->C), B, e->C, (float)bs * (float)ann, e->C - count_active(e, am), dz, loss,
-                  e->main.st);
-}
-static void launch_cbafed(fm_engine* e, const float* z, const float* y, const float* am, int ann, int bs, const float* tao, int B,
-                          float* pw_dev, int64_t* counts_dev, float* dz, float* loss)
-{
-    ClassVec t{};
-    if (tao) t = to_cv(tao, e->C);
-    k_loss_cbafed(z, y, to_cv(am, e->C), tao ? &t : nullptr, B, e->C, (float)bs * (float)ann, ann, pw_dev, counts_dev, dz, loss,
-                  e->main.st);
-}
-
 int fm_loss_rscfed(fm_engine* e, const float* z_dev, const float* zt_dev, const float* y_dev, const float* pos_weight_host,
                    const float* active_mask_host, int32_t annotation_num, int32_t bs_norm, int32_t B, float* dz_dev, float* loss_dev)
 {
     ARGCHK(e && z_dev && zt_dev && y_dev && pos_weight_host && active_mask_host && dz_dev && loss_dev, "null");
-    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    BADCHK(rscfed_bad(e, active_mask_host, annotation_num, bs_norm, B));
     launch_rscfed(e, z_dev, zt_dev, y_dev, pos_weight_host, active_mask_host, annotation_num, bs_norm, B, dz_dev, loss_dev);
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -3161,9 +3217,8 @@ int fm_loss_lakd(fm_engine* e, const float* z_dev, const float* zt_dev, const fl
 {
     ARGCHK(e && z_dev && zt_dev && y_dev && active_mask_host && dz_dev && loss_dev, "null");
     ARGCHK(B >= 1, "B >= 1");
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
-    k_loss_lakd(z_dev, zt_dev, y_dev, to_cv(active_mask_host, e->C), B, e->C, na, w_kd, dz_dev, loss_dev, e->main.st);
+    BADCHK(classes_bad(e, active_mask_host));
+    launch_lakd(e, z_dev, zt_dev, y_dev, active_mask_host, w_kd, B, dz_dev, loss_dev);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -3173,52 +3228,22 @@ int fm_loss_cbafed(fm_engine* e, const float* z_dev, const float* y_dev, const f
                    float* loss_dev)
 {
     ARGCHK(e && z_dev && y_dev && active_mask_host && pos_weight_dev && dz_dev && loss_dev, "null");
-    ARGCHK(!tao_host || counts_dev, "fm_loss_cbafed: stage 2 (tao given) needs counts_dev");
-    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
+    BADCHK(cbafed_bad(e, active_mask_host, annotation_num, bs_norm, tao_host, counts_dev, B, false));
     launch_cbafed(e, z_dev, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev, dz_dev, loss_dev);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
 
-// The EMA teacher's eval forward of view 2 next to the student's train forward of view 1, then the head, backward, Adam and the
-// teacher's blend with the post-Adam student.  Lane order: both views are staged on the main lane (view 2 as the
-// staging's second group); the teacher's shadows are re-formed on the main lane, behind the previous step's blend; ev_in lets the
-// side lane start, ev_t brings it back before the head -- so the blend, on the main lane behind Adam, never meets a running
-// teacher forward, and the next step's fork is enqueued behind it.
+// the skeleton's Rscfed forwards and head, then the teacher's blend with the post-Adam student
 int fm_step_rscfed(fm_engine* e, const float* x1_dev, const float* x2_dev, const float* y_dev, int32_t B,
                    const float* pos_weight_host, const float* active_mask_host, int32_t annotation_num, int32_t bs_norm,
                    float w_teacher, float w_student, float* loss_dev)
 {
     ARGCHK(e && x1_dev && x2_dev && y_dev && pos_weight_host && active_mask_host && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
-    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
-    if (e->side_ok && 2 * B <= e->maxB) {
-        const float* xs[2] = {x1_dev, x2_dev};
-        to_nhwc4(e, e->main, xs, 2, B);
-        e->in_img0 = B;                      // the teacher's stem reads the second group
-        const int rc = teacher_forward_side(e, B);
-        e->in_img0 = 0;
-        RCCHK(rc);
-        net_forward_train(e, 1, B);
-        HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
-    } else {
-        // one lane (or no room for both views in the staging): the teacher first, each view staged in turn
-        const float* xt[1] = {x2_dev};
-        to_nhwc4(e, e->main, xt, 1, B);
-        ensure_teacher_shadow(e);
-        net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
-        const float* xs[1] = {x1_dev};
-        to_nhwc4(e, e->main, xs, 1, B);
-        net_forward_train(e, 1, B);
-    }
-    launch_rscfed(e, e->logits, e->tlogits, y_dev, pos_weight_host, active_mask_host, annotation_num, bs_norm, B, e->dlogits,
-                  loss_dev);
-    net_backward_and_step(e, 1, B);
+    RCCHK(fused_step(e, StepFwd::Rscfed, x1_dev, x2_dev, B, rscfed_bad(e, active_mask_host, annotation_num, bs_norm, B), [&] {
+        launch_rscfed(e, e->logits, e->tlogits, y_dev, pos_weight_host, active_mask_host, annotation_num, bs_norm, B, e->dlogits,
+                      loss_dev);
+    }));
     RCCHK(fm_teacher_axpby(e, w_teacher, w_student));
     STEP_DONE(e);
     return FM_OK;
@@ -3228,17 +3253,8 @@ int fm_step_fednoro(fm_engine* e, const float* x_dev, const float* y_dev, int32_
                     float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && active_mask_host && loss_dev, "null");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
-    const float* xs[1] = {x_dev};
-    to_nhwc4(e, e->main, xs, 1, B);
-    RCCHK(teacher_and_student_forward(e, B, 1, B));      // both read the one staged view
-    k_loss_lakd(e->logits, e->tlogits, y_dev, to_cv(active_mask_host, e->C), B, e->C, na, w_kd, e->dlogits, loss_dev, e->main.st);
-    net_backward_and_step(e, 1, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Frozen, x_dev, nullptr, B, classes_bad(e, active_mask_host),      // both read the one staged view
+                      [&] { launch_lakd(e, e->logits, e->tlogits, y_dev, active_mask_host, w_kd, B, e->dlogits, loss_dev); });
 }
 
 int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t B, const float* active_mask_host,
@@ -3246,20 +3262,11 @@ int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t
                    float* loss_dev)
 {
     ARGCHK(e && x_dev && y_dev && active_mask_host && pos_weight_dev && loss_dev, "null");
-    ARGCHK(!tao_host || counts_dev, "fm_step_cbafed: stage 2 (tao given) needs counts_dev");
-    ARGCHK(e->trainable.empty(), kMaskRefusal);
-    ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
-    ARGCHK(HEAD_NORM_OK(B, annotation_num, bs_norm), kHeadNorm);
-    const int na = count_active(e, active_mask_host);
-    ARGCHK(na >= 1 && na < e->C, kHeadClasses);
-    const float* xs[1] = {x_dev};
-    to_nhwc4(e, e->main, xs, 1, B);
-    net_forward_train(e, 1, B);
-    launch_cbafed(e, e->logits, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev, e->dlogits,
-                  loss_dev);
-    net_backward_and_step(e, 1, B);
-    STEP_DONE(e);
-    return FM_OK;
+    return fused_step(e, StepFwd::Student, x_dev, nullptr, B,
+                      cbafed_bad(e, active_mask_host, annotation_num, bs_norm, tao_host, counts_dev, B, true), [&] {
+        launch_cbafed(e, e->logits, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev,
+                      e->dlogits, loss_dev);
+    });
 }
 
 int fm_proto_reset(fm_engine* e)
@@ -3573,16 +3580,14 @@ int fm_get_grads(fm_engine* e, float* dev_out)
 int fm_sgd_reset(fm_engine* e, const fm_sgd* hp)
 {
     ARGCHK(e, "null engine");
-    const char* bad = hp ? sgd_bad(hp) : nullptr;
-    ARGCHK(!bad, (bad ? bad : ""));
+    BADCHK(hp ? sgd_bad(hp) : nullptr);
     return optim_reset(e);
 }
 
 int fm_sgd_step(fm_engine* e, const fm_sgd* hp)
 {
     ARGCHK(e && hp, "null");
-    const char* bad = sgd_bad(hp);
-    ARGCHK(!bad, (bad ? bad : ""));
+    BADCHK(sgd_bad(hp));
     if (!e->gacc_full) return FM_OK;               // torch.optim.SGD skips parameters whose .grad is None
     sgd_step(e, *hp);
     STEP_DONE(e);
@@ -3592,8 +3597,7 @@ int fm_sgd_step(fm_engine* e, const fm_sgd* hp)
 int fm_adamw_step(fm_engine* e, const fm_adam* hp)
 {
     ARGCHK(e && hp, "null");
-    const char* bad = adam_bad(hp);
-    ARGCHK(!bad, (bad ? bad : ""));
+    BADCHK(adam_bad(hp));
     if (!e->gacc_full) return FM_OK;
     adamw_step(e, *hp);
     STEP_DONE(e);
@@ -3646,10 +3650,7 @@ int fm_adam_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
 {
     ARGCHK(e && hp, "null");
     ARGCHK(n >= 1 && n == e->n_groups, "fm_adam_step_groups: n must be the group count of the installed fm_optim_groups table");
-    for (int i = 0; i < n; ++i) {
-        const char* bad = adam_bad(&hp[i]);
-        ARGCHK(!bad, (bad ? bad : ""));
-    }
+    for (int i = 0; i < n; ++i) BADCHK(adam_bad(&hp[i]));
     if (!e->gacc_full) return FM_OK;
     adam_step_groups(e, hp, n);
     STEP_DONE(e);
@@ -3660,10 +3661,7 @@ int fm_adamw_step_groups(fm_engine* e, const fm_adam* hp, int32_t n)
 {
     ARGCHK(e && hp, "null");
     ARGCHK(n >= 1 && n == e->n_groups, "fm_adamw_step_groups: n must be the group count of the installed fm_optim_groups table");
-    for (int i = 0; i < n; ++i) {
-        const char* bad = adam_bad(&hp[i]);
-        ARGCHK(!bad, (bad ? bad : ""));
-    }
+    for (int i = 0; i < n; ++i) BADCHK(adam_bad(&hp[i]));
     if (!e->gacc_full) return FM_OK;
     adamw_step_groups(e, hp, n);
     STEP_DONE(e);
@@ -3674,10 +3672,7 @@ int fm_sgd_step_groups(fm_engine* e, const fm_sgd* hp, int32_t n)
 {
     ARGCHK(e && hp, "null");
     ARGCHK(n >= 1 && n == e->n_groups, "fm_sgd_step_groups: n must be the group count of the installed fm_optim_groups table");
-    for (int i = 0; i < n; ++i) {
-        const char* bad = sgd_bad(&hp[i]);
-        ARGCHK(!bad, (bad ? bad : ""));
-    }
+    for (int i = 0; i < n; ++i) BADCHK(sgd_bad(&hp[i]));
     if (!e->gacc_full) return FM_OK;
     sgd_step_groups(e, hp, n);
     STEP_DONE(e);
@@ -4342,8 +4337,7 @@ static const char* eff_dims_bad(int32_t op, const int32_t* d)
 int fm_debug_eff_ws(int32_t op, const int32_t* d, int64_t* floats)
 {
     ARGCHK(d && floats, "null argument");
-    const char* bad = eff_dims_bad(op, d);
-    ARGCHK(!bad, (bad ? bad : ""));
+    BADCHK(eff_dims_bad(op, d));
     for (int i = 0; i < FM_EFF_NWS; ++i) floats[i] = 0;
     switch (op) {
     case FM_EFF_DW_FWD:
@@ -4388,8 +4382,7 @@ int fm_debug_eff(fm_engine* e, int32_t op, void* const* p, const int32_t* d, con
     (void)sc;                           // reserved: no launcher of this family takes a scalar
     ARGCHK(e && p && d, "null argument");
     ARGCHK(e->model == 1, "fm_debug_eff: an EfficientNet-B0 engine");
-    const char* bad = eff_dims_bad(op, d);
-    ARGCHK(!bad, (bad ? bad : ""));
+    BADCHK(eff_dims_bad(op, d));
     hipStream_t s = e->main.st;
     auto F = [&](int i) { return static_cast<float*>(p[i]); };
     auto need = [&](std::initializer_list<int> idx) { for (int i : idx) if (!p[i]) return false; return true; };

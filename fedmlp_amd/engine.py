@@ -25,6 +25,10 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _cargs(args):
+    return [_ptr(a) if torch.is_tensor(a) else a for a in args]
+
+
 class Engine:
     """One per process/GPU. Owns the device-resident model state, optimiser
     moments, teacher snapshot and activation workspaces for `max_images`."""
@@ -288,58 +292,90 @@ class Engine:
         if self.stochastic:
             self.draw_stochastic(imgs, self.stochastic_generator)
 
-    def step_bce(self, x, y, pos_weight, bs_norm, loss_out):
+    def _step(self, fn, imgs, *args):
+        """A fused step: fn is the caller's own self.lib.fm_step_*, imgs the images its forward draws stochastic depth for, args
+        the C arguments (tensors as they are)"""
         self._check_stream()
         self._enqueue(weights=True)
-        self._draw(x.shape[0])
-        _lib.check(self.lib.fm_step_bce(self.h, _ptr(x), _ptr(y), x.shape[0],
-                                        _lib.fvec(pos_weight, self.n_classes), int(bs_norm),
-                                        _ptr(loss_out)))
+        self._draw(imgs)
+        _lib.check(fn(self.h, *_cargs(args)))
+
+    def step_bce(self, x, y, pos_weight, bs_norm, loss_out):
+        self._step(self.lib.fm_step_bce, x.shape[0], x, y, x.shape[0], _lib.fvec(pos_weight, self.n_classes),
+                   int(bs_norm), loss_out)
 
     def step_stage1(self, x1, x2, y, active_mask, annotation_num, bs_norm, loss_out):
-        self._check_stream()
-        self._enqueue(weights=True)
-        self._draw(2 * x1.shape[0])
-        _lib.check(self.lib.fm_step_stage1(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0],
-                                           _lib.fvec(active_mask, self.n_classes),
-                                           int(annotation_num), int(bs_norm), _ptr(loss_out)))
+        self._step(self.lib.fm_step_stage1, 2 * x1.shape[0], x1, x2, y, x1.shape[0],
+                   _lib.fvec(active_mask, self.n_classes), int(annotation_num), int(bs_norm), loss_out)
 
     def step_stage2(self, x, y, distill, loss_out):
-        self._check_stream()
-        self._enqueue(weights=True)
-        self._draw(x.shape[0])
-        _lib.check(self.lib.fm_step_stage2(self.h, _ptr(x), _ptr(y), _ptr(distill), x.shape[0],
-                                           _ptr(loss_out)))
+        self._step(self.lib.fm_step_stage2, x.shape[0], x, y, distill, x.shape[0], loss_out)
 
     def step_fixmatch(self, xw, xs, y, pos_weight, pos_weight_unk, active_mask, annotation_num,
                       bs_norm, loss_out):
-        self._check_stream()
-        self._enqueue(weights=True)
         n = self.n_classes
-        self._draw(2 * xw.shape[0])
-        _lib.check(self.lib.fm_step_fixmatch(
-            self.h, _ptr(xw), _ptr(xs), _ptr(y), xw.shape[0], _lib.fvec(pos_weight, n),
-            _lib.fvec(pos_weight_unk, n), _lib.fvec(active_mask, n), int(annotation_num),
-            int(bs_norm), _ptr(loss_out)))
+        self._step(self.lib.fm_step_fixmatch, 2 * xw.shape[0], xw, xs, y, xw.shape[0], _lib.fvec(pos_weight, n),
+                   _lib.fvec(pos_weight_unk, n), _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), loss_out)
 
     def step_fedlsr(self, x1, x2, y, pos_weight, mix1, beta, loss_out):
         """train_FedLSR's step (utils/local_training.py:1294-1319) fused: two-view forward, loss_fedlsr's head, backward, Adam"""
-        self._check_stream()
-        self._enqueue(weights=True)
-        self._draw(2 * x1.shape[0])
-        _lib.check(self.lib.fm_step_fedlsr(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0],
-                                           _lib.fvec(pos_weight, self.n_classes), C.c_float(mix1), C.c_float(beta),
-                                           _ptr(loss_out)))
+        self._step(self.lib.fm_step_fedlsr, 2 * x1.shape[0], x1, x2, y, x1.shape[0],
+                   _lib.fvec(pos_weight, self.n_classes), C.c_float(mix1), C.c_float(beta), loss_out)
 
-    # ---- FedLSR / FedIRM loss heads on two-view logits z [2B,C] (forward_train's layout): -> (dz [2B,C], loss [1]) ----------
-    def _head_out(self, z, y):
-        B = y.shape[0]
-        if tuple(z.shape) != (2 * B, self.n_classes) or tuple(y.shape) != (B, self.n_classes):
+    def step_rscfed(self, x1, x2, y, pos_weight, active_mask, annotation_num, bs_norm, w_teacher, w_student, loss_out):
+        """train_RSCFed's step (utils/local_training.py:733-759) fused: teacher-slot eval forward of x2, train forward of x1,
+        loss_rscfed's head, backward, Adam, then teacher = w_teacher teacher + w_student student over every state entry"""
+        n = self.n_classes
+        self._step(self.lib.fm_step_rscfed, x1.shape[0], x1, x2, y, x1.shape[0], _lib.fvec(pos_weight, n),
+                   _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(w_teacher), C.c_float(w_student),
+                   loss_out)
+
+    def step_fednoro(self, x, y, active_mask, w_kd, loss_out):
+        """train_FedNoRo's warm-up step (:143-160) fused: frozen teacher's eval forward and the train forward of the same x,
+        loss_lakd's head, backward, Adam"""
+        self._step(self.lib.fm_step_fednoro, x.shape[0], x, y, x.shape[0], _lib.fvec(active_mask, self.n_classes),
+                   C.c_float(w_kd), loss_out)
+
+    def _cbafed_args(self, tao, pos_weight, counts):
+        """-> (tao, pos_weight, counts) as the C arguments"""
+        n = self.n_classes
+        if tuple(pos_weight.shape) != (n,) or pos_weight.dtype != torch.float32 or not pos_weight.is_contiguous() \
+                or not pos_weight.is_cuda:
+            raise ValueError(f"cbafed: pos_weight must be a contiguous float32 [{n}] device tensor")
+        if counts is not None and (tuple(counts.shape) != (n + 1,) or counts.dtype != torch.int64
+                                   or not counts.is_contiguous() or not counts.is_cuda):
+            raise ValueError(f"cbafed: counts must be a contiguous int64 [{n + 1}] device tensor")
+        if tao is not None and counts is None:
+            raise ValueError("cbafed: stage 2 (tao given) needs counts")
+        return (None if tao is None else _lib.fvec(tao, n), _ptr(pos_weight),
+                None if counts is None else C.c_void_p(counts.data_ptr()))
+
+    def step_cbafed(self, x, y, active_mask, annotation_num, bs_norm, tao, pos_weight, counts, loss_out):
+        """train_CBAFed's step (:247-269, 303-340) fused.  tao None: warm-up.  pos_weight [C] float32 and counts [C+1] int64 are
+        DEVICE tensors of the caller's: stage 2 rewrites the missing classes' weights and adds to the counts, with no host read"""
+        t, pw, cn = self._cbafed_args(tao, pos_weight, counts)
+        self._step(self.lib.fm_step_cbafed, x.shape[0], x, y, x.shape[0], _lib.fvec(active_mask, self.n_classes),
+                   int(annotation_num), int(bs_norm), t, pw, cn, loss_out)
+
+    # ---- the loss heads alone, on caller logits: two-view z [2B,C] (forward_train's layout; FedLSR, FedIRM) or single-view
+    # z [B,C] (RSCFed, FedNoRo, CBAFed) -> (dz like z, loss [1]) ----------------------------------------------------------
+    def _head(self, fn, views, z, y, zt, *args):
+        """fn is the caller's own self.lib.fm_loss_*; its C arguments are args (tensors as they are), then dz and loss"""
+        self._check_stream()
+        self._enqueue()
+        B, n = y.shape[0], self.n_classes
+        ts = [(z, views * B), (y, B)] + ([] if zt is None else [(zt, B)])
+        shapes = all(tuple(t.shape) == (rows, n) for t, rows in ts)
+        plain = all(t.dtype == torch.float32 and t.is_contiguous() for t, _ in ts)
+        if views == 1 and not (shapes and plain):
+            raise ValueError(f"single-view head: contiguous float32 [B, {n}] tensors are required")
+        if not shapes:
             raise ValueError(f"two-view head: z must be [2B, C] and y [B, C], got {tuple(z.shape)} and {tuple(y.shape)}")
-        for t in (z, y):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("two-view head: contiguous float32 tensors are required")
-        return B, torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
+        if not plain:
+            raise ValueError("two-view head: contiguous float32 tensors are required")
+        dz, loss = torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
+        _lib.check(fn(self.h, *_cargs(args), _ptr(dz), _ptr(loss)))
+        return dz, loss
 
     def _rel_arg(self, t, what):
         if t is None:
@@ -350,114 +386,39 @@ class Engine:
         return t
 
     def loss_fedlsr(self, z, y, pos_weight, mix1, beta):
-        self._check_stream()
-        self._enqueue()
-        B, dz, loss = self._head_out(z, y)
-        _lib.check(self.lib.fm_loss_fedlsr(self.h, _ptr(z), _ptr(y), _lib.fvec(pos_weight, self.n_classes), C.c_float(mix1),
-                                           C.c_float(beta), B, _ptr(dz), _ptr(loss)))
-        return dz, loss
+        return self._head(self.lib.fm_loss_fedlsr, 2, z, y, None, z, y, _lib.fvec(pos_weight, self.n_classes),
+                          C.c_float(mix1), C.c_float(beta), y.shape[0])
 
     def loss_fedirm_sup(self, z, y, pos_weight, active_mask, annotation_num, bs_norm, rel_acc=None):
         """rel_acc [C,C] (optional) += get_confuse_matrix(z[:B], y)"""
-        self._check_stream()
-        self._enqueue()
         n = self.n_classes
-        B, dz, loss = self._head_out(z, y)
-        _lib.check(self.lib.fm_loss_fedirm_sup(self.h, _ptr(z), _ptr(y), _lib.fvec(pos_weight, n), _lib.fvec(active_mask, n),
-                                               int(annotation_num), int(bs_norm), B, _ptr(self._rel_arg(rel_acc, "rel_acc")),
-                                               _ptr(dz), _ptr(loss)))
-        return dz, loss
+        return self._head(self.lib.fm_loss_fedirm_sup, 2, z, y, None, z, y, _lib.fvec(pos_weight, n),
+                          _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), y.shape[0],
+                          self._rel_arg(rel_acc, "rel_acc"))
 
     def loss_fedirm_rel(self, z, zt, y, pos_weight, active_mask, annotation_num, bs_norm, cw, target, rel_acc=None):
         """zt [B,C]: the EMA model's logits on view 2; target [C,C]: the aggregated relation matrix (device)"""
-        self._check_stream()
-        self._enqueue()
-        n = self.n_classes
-        B, dz, loss = self._head_out(z, y)
+        B, n = y.shape[0], self.n_classes
         if tuple(zt.shape) != (B, n) or zt.dtype != torch.float32 or not zt.is_contiguous():
             raise ValueError(f"loss_fedirm_rel: zt must be a contiguous float32 [{B}, {n}] tensor")
-        _lib.check(self.lib.fm_loss_fedirm_rel(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(pos_weight, n),
-                                               _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(cw),
-                                               _ptr(self._rel_arg(target, "target")), B,
-                                               _ptr(self._rel_arg(rel_acc, "rel_acc")), _ptr(dz), _ptr(loss)))
-        return dz, loss
-
-    # ---- RSCFed / FedNoRo / CBAFed: fused steps, and their heads on single-view logits z [B,C]: -> (dz [B,C], loss [1]) ------
-    def step_rscfed(self, x1, x2, y, pos_weight, active_mask, annotation_num, bs_norm, w_teacher, w_student, loss_out):
-        """train_RSCFed's step (utils/local_training.py:733-759) fused: teacher-slot eval forward of x2, train forward of x1,
-        loss_rscfed's head, backward, Adam, then teacher = w_teacher teacher + w_student student over every state entry"""
-        self._check_stream()
-        self._enqueue(weights=True)
-        n = self.n_classes
-        self._draw(x1.shape[0])
-        _lib.check(self.lib.fm_step_rscfed(self.h, _ptr(x1), _ptr(x2), _ptr(y), x1.shape[0], _lib.fvec(pos_weight, n),
-                                           _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(w_teacher),
-                                           C.c_float(w_student), _ptr(loss_out)))
-
-    def step_fednoro(self, x, y, active_mask, w_kd, loss_out):
-        """train_FedNoRo's warm-up step (:143-160) fused: frozen teacher's eval forward and the train forward of the same x,
-        loss_lakd's head, backward, Adam"""
-        self._check_stream()
-        self._enqueue(weights=True)
-        self._draw(x.shape[0])
-        _lib.check(self.lib.fm_step_fednoro(self.h, _ptr(x), _ptr(y), x.shape[0], _lib.fvec(active_mask, self.n_classes),
-                                            C.c_float(w_kd), _ptr(loss_out)))
-
-    def _cbafed_args(self, tao, pos_weight, counts):
-        n = self.n_classes
-        if tuple(pos_weight.shape) != (n,) or pos_weight.dtype != torch.float32 or not pos_weight.is_contiguous() \
-                or not pos_weight.is_cuda:
-            raise ValueError(f"cbafed: pos_weight must be a contiguous float32 [{n}] device tensor")
-        if counts is not None and (tuple(counts.shape) != (n + 1,) or counts.dtype != torch.int64
-                                   or not counts.is_contiguous() or not counts.is_cuda):
-            raise ValueError(f"cbafed: counts must be a contiguous int64 [{n + 1}] device tensor")
-        if tao is not None and counts is None:
-            raise ValueError("cbafed: stage 2 (tao given) needs counts")
-        return None if tao is None else _lib.fvec(tao, n)
-
-    def step_cbafed(self, x, y, active_mask, annotation_num, bs_norm, tao, pos_weight, counts, loss_out):
-        """train_CBAFed's step (:247-269, 303-340) fused.  tao None: warm-up.  pos_weight [C] float32 and counts [C+1] int64 are
-        DEVICE tensors of the caller's: stage 2 rewrites the missing classes' weights and adds to the counts, with no host read"""
-        self._check_stream()
-        self._enqueue(weights=True)
-        t = self._cbafed_args(tao, pos_weight, counts)
-        self._draw(x.shape[0])
-        _lib.check(self.lib.fm_step_cbafed(self.h, _ptr(x), _ptr(y), x.shape[0], _lib.fvec(active_mask, self.n_classes),
-                                           int(annotation_num), int(bs_norm), t, _ptr(pos_weight), None if counts is None else C.c_void_p(counts.data_ptr()), _ptr(loss_out)))
-
-    def _head_out1(self, z, y, zt=None):
-        B = y.shape[0]
-        for t in (z, y) if zt is None else (z, y, zt):
-            if tuple(t.shape) != (B, self.n_classes) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"single-view head: contiguous float32 [B, {self.n_classes}] tensors are required")
-        return B, torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
+        return self._head(self.lib.fm_loss_fedirm_rel, 2, z, y, None, z, zt, y, _lib.fvec(pos_weight, n),
+                          _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), C.c_float(cw),
+                          self._rel_arg(target, "target"), B, self._rel_arg(rel_acc, "rel_acc"))
 
     def loss_rscfed(self, z, zt, y, pos_weight, active_mask, annotation_num, bs_norm):
-        self._check_stream()
-        self._enqueue()
         n = self.n_classes
-        B, dz, loss = self._head_out1(z, y, zt)
-        _lib.check(self.lib.fm_loss_rscfed(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(pos_weight, n), _lib.fvec(active_mask, n),
-                                           int(annotation_num), int(bs_norm), B, _ptr(dz), _ptr(loss)))
-        return dz, loss
+        return self._head(self.lib.fm_loss_rscfed, 1, z, y, zt, z, zt, y, _lib.fvec(pos_weight, n),
+                          _lib.fvec(active_mask, n), int(annotation_num), int(bs_norm), y.shape[0])
 
     def loss_lakd(self, z, zt, y, active_mask, w_kd):
-        self._check_stream()
-        self._enqueue()
-        B, dz, loss = self._head_out1(z, y, zt)
-        _lib.check(self.lib.fm_loss_lakd(self.h, _ptr(z), _ptr(zt), _ptr(y), _lib.fvec(active_mask, self.n_classes),
-                                         C.c_float(w_kd), B, _ptr(dz), _ptr(loss)))
-        return dz, loss
+        return self._head(self.lib.fm_loss_lakd, 1, z, y, zt, z, zt, y, _lib.fvec(active_mask, self.n_classes),
+                          C.c_float(w_kd), y.shape[0])
 
     def loss_cbafed(self, z, y, active_mask, annotation_num, bs_norm, tao, pos_weight, counts=None):
         """tao None: warm-up (pos_weight read, counts untouched); else stage 2 (see step_cbafed)"""
-        self._check_stream()
-        self._enqueue()
-        t = self._cbafed_args(tao, pos_weight, counts)
-        B, dz, loss = self._head_out1(z, y)
-        _lib.check(self.lib.fm_loss_cbafed(self.h, _ptr(z), _ptr(y), _lib.fvec(active_mask, self.n_classes), int(annotation_num),
-                                           int(bs_norm), t, B, _ptr(pos_weight), None if counts is None else C.c_void_p(counts.data_ptr()), _ptr(dz), _ptr(loss)))
-        return dz, loss
+        t, pw, cn = self._cbafed_args(tao, pos_weight, counts)
+        return self._head(self.lib.fm_loss_cbafed, 1, z, y, None, z, y, _lib.fvec(active_mask, self.n_classes),
+                          int(annotation_num), int(bs_norm), t, y.shape[0], pw, cn)
 
     # ---- prototypes / tagging ------------------------------------------------------
     # ---- generic split step (rank-4 baselines: loss head computed by the host mirror) -----------

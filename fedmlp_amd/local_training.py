@@ -20,6 +20,7 @@ Batch order: the reference's DataLoader(shuffle=True) draws from the global
 torch RNG (:47-48, 1166-1167).  Here `torch.randperm` does (`_order`; the parity
 tests replay recorded orders through a subclass, tests/helpers.ReplayLocalUpdate).
 """
+import contextlib
 import logging
 
 import numpy as np
@@ -152,26 +153,55 @@ class LocalUpdate(object):
     def _mask(self, classes):
         return [1.0 if c in classes else 0.0 for c in range(self.args.n_classes)]
 
+    # ---- what every trainer shares ---------------------------------------------------------------------
+    def _epochs(self, eng, epoch_loss):
+        """local_ep shuffled passes over the local set.  Yields one epoch at a time as its [(pos, loss slot)] batches: the
+        caller runs its step on each, writing the step's loss into the slot.  The slots are slices of one device buffer per
+        epoch, read once when the epoch is over: its float64 mean is appended to epoch_loss."""
+        a = self.args
+        for _ in range(a.local_ep):
+            batches = _batches(self._order(len(self.idxs)), a.batch_size)
+            losses = torch.zeros(len(batches), device=eng.device)
+            yield [(pos, losses[k:k + 1]) for k, pos in enumerate(batches)]
+            self.epoch += 1
+            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
+
+    @contextlib.contextmanager
+    def _teacher_slot(self, eng, snapshot=False):
+        """Inside the block the EMA teacher (self.teacher_neg) lives in the engine's teacher slot; it is read back at the end.
+        snapshot: the teacher starts as a copy of the student instead (ema_model.load_state_dict(net.state_dict()))"""
+        assert isinstance(self.teacher_neg, HipNet), "LocalUpdate(teacher_neg=build_model(...)) is required"
+        if snapshot:
+            eng.teacher_snapshot()
+        else:
+            self.teacher_neg._pull()
+            eng.teacher_swap()
+            eng.set_state(self.teacher_neg.flat, self.teacher_neg.counters)
+            eng.teacher_swap()
+        yield
+        eng.teacher_swap()
+        self.teacher_neg.flat, self.teacher_neg.counters = eng.get_state()
+        self.teacher_neg._version += 1
+        eng.teacher_swap()
+
+    def _result(self, net, epoch_loss, neg=None):
+        """the head of every trainer's return tuple (positions 3-4: the reference's placeholders)"""
+        return (self._sd(net), np.array(epoch_loss).mean(), None, None,
+                list(self.negative_class_list) if neg is None else neg, list(self.active_class_list))
+
     # ---- LocalUpdate.train (:628-703) ----------------------------------------------------------
     def train(self, rnd, net, writer1=None):
         a = self.args
         eng = self._bind(net, "image")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
-                eng.step_bce(self._images(eng, "image", pos), self._rows(y, pos, eng), self.loss_w,
-                             a.batch_size, losses[k:k + 1])
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
+                eng.step_bce(self._images(eng, "image", pos), self._rows(y, pos, eng), self.loss_w, a.batch_size, loss)
                 self.iter_num += 1
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, \
-            list(self.negative_class_list), list(self.active_class_list)
+        return self._result(net, epoch_loss)
 
     # ---- LocalUpdate.train_FixMatch (:771-825) ---------------------------------------------------
     def train_FixMatch(self, rnd, net):
@@ -179,22 +209,16 @@ class LocalUpdate(object):
         eng = self._bind(net, "image_aug_1")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
         act = self._mask(self.active_class_list)
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
                 eng.step_fixmatch(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
                                   self._rows(y, pos, eng), self.loss_w, self.loss_w_unknown, act,
-                                  a.annotation_num, a.batch_size, losses[k:k + 1])
+                                  a.annotation_num, a.batch_size, loss)
                 self.iter_num += 1
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, \
-            list(self.negative_class_list), list(self.active_class_list)
+        return self._result(net, epoch_loss)
 
     # ==== SURVEY 8f rank 4: the other baselines of main.py's --exp switch =========================
     # Each step is one fused engine call (fm_step_rscfed / fm_step_fednoro / fm_step_cbafed): forward(s), the loss head on the
@@ -202,36 +226,21 @@ class LocalUpdate(object):
     # ---- LocalUpdate.train_RSCFed (:705-769) ---------------------------------------------------------
     def train_RSCFed(self, rnd, net):
         a = self.args
-        assert isinstance(self.teacher_neg, HipNet), "LocalUpdate(teacher_neg=build_model(...)) is required"
         eng = self._bind(net, "image_aug_1")
-        # the EMA teacher lives in the engine's teacher slot for the duration of the call
-        self.teacher_neg._pull()
-        eng.teacher_swap()
-        eng.set_state(self.teacher_neg.flat, self.teacher_neg.counters)
-        eng.teacher_swap()
-        eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
-        y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
-        act, neg = list(self.active_class_list), list(self.negative_class_list)
-        amask = self._mask(act)
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
-                # teacher(view 2), student(view 1), the head, backward, Adam and the EMA blend of :751-759 in one call
-                eng.step_rscfed(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
-                                self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num, a.batch_size,
-                                1 - 0.001, 0.001, losses[k:k + 1])
-                self.iter_num += 1
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
-        eng.teacher_swap()
-        self.teacher_neg.flat, self.teacher_neg.counters = eng.get_state()
-        self.teacher_neg._version += 1
-        eng.teacher_swap()
+        with self._teacher_slot(eng):
+            eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+            y = self._labels_dev(eng, self._y_masked, "y_masked")
+            amask = self._mask(self.active_class_list)
+            for batches in self._epochs(eng, epoch_loss):
+                for pos, loss in batches:
+                    # teacher(view 2), student(view 1), the head, backward, Adam and the EMA blend of :751-759 in one call
+                    eng.step_rscfed(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
+                                    self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num, a.batch_size,
+                                    1 - 0.001, 0.001, loss)
+                    self.iter_num += 1
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act
+        return self._result(net, epoch_loss)
 
     # ---- LocalUpdate.train_FedLSR (:1270-1326) --------------------------------------------------------
     def train_FedLSR(self, rnd, net):
@@ -239,24 +248,18 @@ class LocalUpdate(object):
         eng = self._bind(net, "image_aug_1")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
         betaa = 0.4                                                 # :1309-1311
         if rnd < a.t_w:
             betaa = 0.4 * rnd / a.t_w
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
                 mix_1 = np.random.beta(1, 1)                        # :1296: one draw per step from numpy's global RNG
                 eng.step_fedlsr(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
-                                self._rows(y, pos, eng), self.loss_w, mix_1, betaa, losses[k:k + 1])
+                                self._rows(y, pos, eng), self.loss_w, mix_1, betaa, loss)
                 self.iter_num += 1                                  # :1321
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, \
-            list(self.negative_class_list), list(self.active_class_list)
+        return self._result(net, epoch_loss)
 
     # ---- LocalUpdate.train_FedIRM (:344-464) -----------------------------------------------------------
     @staticmethod
@@ -278,71 +281,48 @@ class LocalUpdate(object):
         C = a.n_classes
         eng = self._bind(net, "image_aug_1")
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
-        act, neg = list(self.active_class_list), list(self.negative_class_list)
-        amask = self._mask(act)
+        amask = self._mask(self.active_class_list)
         rel = torch.zeros((C, C), device=eng.device)                # self.confuse_matrix (:352, 403), C x C for the reference's 8 x 8
         epoch_loss = []
         if rnd < a.rounds_FedIRM_sup:
             eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
             first_rel = rnd == a.rounds_FedIRM_sup - 1              # :372: the first relation matrix
-            for _ in range(a.local_ep):
-                batches = _batches(self._order(n), a.batch_size)
-                losses = torch.zeros(len(batches), device=eng.device)
-                for k, pos in enumerate(batches):
+            for batches in self._epochs(eng, epoch_loss):
+                for pos, loss in batches:                           # (iter_num does not move in this phase)
                     _, z = eng.forward_train(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos))
-                    dz, loss = eng.loss_fedirm_sup(z, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
-                                                   a.batch_size, rel if first_rel else None)
+                    dz, loss[:] = eng.loss_fedirm_sup(z, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
+                                                      a.batch_size, rel if first_rel else None)
                     eng.backward_step(dz)
-                    losses[k:k + 1] = loss
-                self.epoch += 1
-                epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
             net.mark_trained()
             if first_rel:
                 rel = rel / (1.0 * a.local_ep * len(batches))       # :385, once, after the epochs (j + 1 = batches per epoch)
-                return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, rel
-            return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act
+                return self._result(net, epoch_loss) + (rel,)
+            return self._result(net, epoch_loss)
 
         # ---- inter-client relation matching (:392-464) ----
-        assert isinstance(self.teacher_neg, HipNet), "LocalUpdate(teacher_neg=build_model(...)) is required"
-        # the EMA model lives in the engine's teacher slot for the duration of the call (as in train_RSCFed)
-        if self.flag:                                               # :393-395: ema_model.load_state_dict(net.state_dict())
-            eng.teacher_snapshot()
+        # :393-395: the first call of this phase loads the EMA model from net
+        with self._teacher_slot(eng, snapshot=self.flag):
             self.flag = False
-        else:
-            self.teacher_neg._pull()
-            eng.teacher_swap()
-            eng.set_state(self.teacher_neg.flat, self.teacher_neg.counters)
-            eng.teacher_swap()
-        eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
-        target = torch.as_tensor(target_matrix, dtype=torch.float32).to(eng.device).contiguous()
-        cw = a.consistency * self.sigmoid_rampup(rnd, a.consistency_rampup)     # :91-92, 442
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
-                x1, x2 = self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos)
-                # :422-423: the reference never puts the EMA model in eval mode, so its no-grad forward is a TRAIN-mode
-                # forward: batch statistics, and its running statistics and counters move
-                eng.teacher_swap()
-                _, zt = eng.forward_train(x2)
-                eng.teacher_swap()
-                _, z = eng.forward_train(x1, x2)
-                dz, loss = eng.loss_fedirm_rel(z, zt, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
-                                               a.batch_size, cw, target, rel)
-                eng.backward_step(dz)
-                eng.teacher_ema_params(self.ema_alpha(self.iter_num, a.ema_decay))       # :456, parameters only
-                losses[k:k + 1] = loss
-                self.iter_num += 1                                  # :458: persists across rounds
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
-            rel = rel / (1.0 * a.local_ep * len(batches))           # :461-462: INSIDE the epoch loop, as the reference has it
-        eng.teacher_swap()
-        self.teacher_neg.flat, self.teacher_neg.counters = eng.get_state()
-        self.teacher_neg._version += 1
-        eng.teacher_swap()
+            eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+            target = torch.as_tensor(target_matrix, dtype=torch.float32).to(eng.device).contiguous()
+            cw = a.consistency * self.sigmoid_rampup(rnd, a.consistency_rampup)     # :91-92, 442
+            for batches in self._epochs(eng, epoch_loss):
+                for pos, loss in batches:
+                    x1, x2 = self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos)
+                    # :422-423: the reference never puts the EMA model in eval mode, so its no-grad forward is a TRAIN-mode
+                    # forward: batch statistics, and its running statistics and counters move
+                    eng.teacher_swap()
+                    _, zt = eng.forward_train(x2)
+                    eng.teacher_swap()
+                    _, z = eng.forward_train(x1, x2)
+                    dz, loss[:] = eng.loss_fedirm_rel(z, zt, self._rows(y, pos, eng), self.loss_w, amask, a.annotation_num,
+                                                      a.batch_size, cw, target, rel)
+                    eng.backward_step(dz)
+                    eng.teacher_ema_params(self.ema_alpha(self.iter_num, a.ema_decay))       # :456, parameters only
+                    self.iter_num += 1                              # :458: persists across rounds
+                rel = rel / (1.0 * a.local_ep * len(batches))       # :461-462: INSIDE the epoch loop, as the reference has it
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, rel
+        return self._result(net, epoch_loss) + (rel,)
 
     # ---- LocalUpdate.train_FedNoRo (:115-234) ----------------------------------------------------------
     def train_FedNoRo(self, id, rnd, net, writer1=None, weight_kd=None, clean_clients=None, noisy_clients=None):
@@ -356,23 +336,17 @@ class LocalUpdate(object):
         eng.teacher_snapshot()                                      # teacher_net = deepcopy(net), frozen
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
-        act, neg = list(self.active_class_list), list(self.negative_class_list)
-        for c in neg:                                               # :136-137
+        for c in self.negative_class_list:                          # :136-137
             self.class_num_list[c] = 0
         w_kd = float(weight_kd)
-        amask = self._mask(act)
+        amask = self._mask(self.active_class_list)
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
-                eng.step_fednoro(self._images(eng, "image", pos), self._rows(y, pos, eng), amask, w_kd, losses[k:k + 1])
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
+                eng.step_fednoro(self._images(eng, "image", pos), self._rows(y, pos, eng), amask, w_kd, loss)
                 self.iter_num += 1
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act
+        return self._result(net, epoch_loss)
 
     # ---- LocalUpdate.train_CBAFed (:236-342) -------------------------------------------------------------
     def train_CBAFed(self, rnd, net, pt=None, tao=None):
@@ -380,11 +354,9 @@ class LocalUpdate(object):
         eng = self._bind(net, "image")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
-        n = len(self.idxs)
-        act, neg = list(self.active_class_list), list(self.negative_class_list)
         warm = rnd < a.rounds_CBAFed_warmup
         C = a.n_classes
-        amask = self._mask(act)
+        amask = self._mask(self.active_class_list)
         class_num_list = torch.zeros(C)
         data_num = 0
         # the client's loss_w and the round's counts ([C] class_num_list, then data_num) live on the device for the call: stage 2
@@ -393,29 +365,25 @@ class LocalUpdate(object):
         counts = torch.zeros(C + 1, dtype=torch.int64, device=eng.device)
         tao_v = None if warm else [float(t) for t in tao]
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for k, pos in enumerate(batches):
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
                 eng.step_cbafed(self._images(eng, "image", pos), self._rows(y, pos, eng), amask, a.annotation_num,
-                                a.batch_size, tao_v, pw, counts, losses[k:k + 1])
+                                a.batch_size, tao_v, pw, counts, loss)
                 if warm:
                     data_num += len(pos)
                 self.iter_num += 1
             if warm:
-                for c in act:
+                for c in self.active_class_list:
                     class_num_list[c] = data_num
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         if not warm:
             # one transfer at the end of the call: loss_w, class_num_list, data_num
             back = torch.cat([pw.double(), counts.double()]).cpu()
-            for i in neg:
+            for i in self.negative_class_list:
                 self.loss_w[i] = float(back[i])
             class_num_list += back[C:2 * C].float()
             data_num = int(back[2 * C])
         net.mark_trained()
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, neg, act, class_num_list, data_num
+        return self._result(net, epoch_loss) + (class_num_list, data_num)
 
     # ---- prototype + t pass (:971-1002 unguarded, :1208-1250 zero-guarded) ----------------------------
     def _proto_pass(self, eng, negative_list, zero_guard):
@@ -430,18 +398,15 @@ class LocalUpdate(object):
         t, proto = eng.proto_finalize(zero_guard, n, act)
         return t, torch.from_numpy(proto)
 
-    # ---- cosine tagging + stable top-/bottom-k selection of one missing class (:1052-1112) ---------------
-    def _similarity(self, eng, rnd, cls, pool_f, pool_idx, proto_dev):
-        """cos(f, P0) - cos(f, P1) of every pool sample, on the device (CosineSimilarityFast :1417-1435)"""
-        return eng.cos_tag(pool_f.contiguous(), proto_dev, [cls])[0]
-
+    # ---- cosine tagging + stable top-/bottom-k selection of the missing classes (:1052-1112) ---------------
     def _log_similarity(self, rnd, cls, pool_idx, sim_of_pool):
         """hook: the similarities of one class's pool, in pool order (a callable returning the device tensor; tests record it)"""
 
     def _select_all(self, eng, rnd, classes, f, ds_idx, pools, proto_dev):
         """Every missing class of the round: ONE cosine-tagging launch over all local features, one selection launch pair and one
         device-to-host read (fm_cos_tag + fm_select_topk_rows).  pools[k] = rows of f forming class k's pool, in pool order
-        (None = all).  -> [(clean, noise)] dataset indices per class, with _select()'s semantics."""
+        (None = all).  -> [(clean, noise)] dataset indices per class: the int(clean_threshold * #(sim >= 0)) most similar and the
+        int(noise_threshold * #(sim < 0)) least similar pool samples (stable ranks, utils/utils.py:24-35)."""
         if not len(classes):
             return []
         sims = eng.cos_tag(f.contiguous(), proto_dev, list(classes))
@@ -463,19 +428,6 @@ class LocalUpdate(object):
             out.append(([int(pool_idx[j]) for j in top], [int(pool_idx[j]) for j in bot]))
         return out
 
-    def _select(self, eng, rnd, cls, pool_f, pool_idx, proto_dev):
-        """-> (clean, noise): dataset indices of the int(clean_threshold * #(sim >= 0)) most similar and the
-        int(noise_threshold * #(sim < 0)) least similar pool samples (stable ranks, utils/utils.py:24-35)"""
-        if not len(pool_idx):
-            return [], []
-        sim = self._similarity(eng, rnd, cls, pool_f, pool_idx, proto_dev)
-        top, bot = eng.select_topk(sim, self.args.clean_threshold, self.args.noise_threshold)
-        if not len(top):
-            # the reference's first branch tests the CLEAN list twice (`len(max_m_indices_list) == 0 and
-            # len(max_m_indices_list) == 0`, :1076 / :1099): without a clean pick it keeps no noise pick either
-            bot = []
-        return [int(pool_idx[j]) for j in top], [int(pool_idx[j]) for j in bot]
-
     # ---- LocalUpdate.train_FedMLP (:904-1256) --------------------------------------------------------
     def train_FedMLP(self, rnd, tao, Prototype, writer1, negetive_class_list, active_class_list_client_i, net):
         a = self.args
@@ -487,21 +439,15 @@ class LocalUpdate(object):
             y = self._labels_dev(eng, self._y_masked, "y_masked")
             act = self._mask(self.active_class_list)
             epoch_loss = []
-            for _ in range(a.local_ep):
-                batches = _batches(self._order(n), a.batch_size)
-                losses = torch.zeros(len(batches), device=eng.device)
-                for k, pos in enumerate(batches):
+            for batches in self._epochs(eng, epoch_loss):
+                for pos, loss in batches:
                     eng.step_stage1(self._images(eng, "image_aug_1", pos), self._images(eng, "image_aug_2", pos),
-                                    self._rows(y, pos, eng), act, a.annotation_num, a.batch_size,
-                                    losses[k:k + 1])
+                                    self._rows(y, pos, eng), act, a.annotation_num, a.batch_size, loss)
                     self.iter_num += 1
-                self.epoch += 1
-                epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
             for c in self.negative_class_list:                             # :932 "try noro"
                 self.class_num_list[c] = 0
             net.mark_trained()
-            ret = (self._sd(net), np.array(epoch_loss).mean(), None, None,
-                   list(self.negative_class_list), list(self.active_class_list))
+            ret = self._result(net, epoch_loss)
             if rnd == a.rounds_FedMLP_stage1 - 1:                          # first tao and proto :971
                 t, proto = self._proto_pass(eng, negetive_class_list, zero_guard=False)
                 ret = ret + (t, proto)
@@ -550,15 +496,11 @@ class LocalUpdate(object):
         dist_d = torch.from_numpy(dist).to(eng.device)
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
         epoch_loss = []
-        for _ in range(a.local_ep):
-            batches = _batches(self._order(n), a.batch_size)
-            losses = torch.zeros(len(batches), device=eng.device)
-            for kb, pos in enumerate(batches):
+        for batches in self._epochs(eng, epoch_loss):
+            for pos, loss in batches:
                 eng.step_stage2(self._images(eng, "image_aug_1", pos), self._rows(yp_d, pos, eng),
-                                self._rows(dist_d, pos, eng), losses[kb:kb + 1])
+                                self._rows(dist_d, pos, eng), loss)
                 self.iter_num += 1
-            self.epoch += 1
-            epoch_loss.append(losses.cpu().numpy().astype(np.float64).mean())
         net.mark_trained()
         self.idxss = []
         for k in range(len(self.traindata_idx) // 2):                      # :1197-1204
@@ -566,5 +508,4 @@ class LocalUpdate(object):
             self.idxss.append(list(set(self.idxs) - set(sel)))
         # (e) prototype + t pass, zero-count guarded (:1208-1250)
         t, proto = self._proto_pass(eng, negetive_class_list, zero_guard=True)
-        return self._sd(net), np.array(epoch_loss).mean(), None, None, \
-            negetive_class_list, list(self.active_class_list), t, proto
+        return self._result(net, epoch_loss, negetive_class_list) + (t, proto)
