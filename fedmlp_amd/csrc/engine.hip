@@ -63,8 +63,7 @@ struct DgradClass {
     int ph, pw;
     int nsteps;
     float* wpack = nullptr;
-    long long sp_off = -1;    // bf16 planes of wpack inside fm_engine::wsp_d (2-byte units), -1 = none
-    long long bm_off = -1;    // block-major planes of wpack inside fm_engine::wbm_d (pconv.hip), -1 = none
+    long long pl_off = -1;    // bf16 planes of wpack inside fm_engine::wpl_d (2-byte units), -1 = none
 };
 
 struct Conv {
@@ -82,8 +81,7 @@ struct Conv {
     int ncls = 0;
     DgradClass cls[4];
     int bn;                   // index of the BatchNorm that follows
-    long long sp_off = -1;    // bf16 planes of the forward weights inside Weights::wsp_f (2-byte units), -1 = none
-    long long bm_off = -1;    // block-major planes of the forward weights inside Weights::wbm_f (pconv.hip), -1 = none
+    long long pl_off = -1;    // bf16 planes of the forward weights inside Weights::wpl_f (2-byte units), -1 = none
     long long wb_off = -1, wbt_off = -1;   // bf16 shadow of a 1x1 conv's weights [cout_p][cin_p] / transposed (bf16 mode)
     double macs_per_img;      // algorithmic MACs (real k, real cin)
     float* y = nullptr;       // raw conv output (train) [max_images][hout][wout][cout]
@@ -124,12 +122,14 @@ struct Lane {
 struct Weights {
     float* state = nullptr;               // the state arena (layout at the top of this file)
     std::vector<int64_t> counters;        // num_batches_tracked per BN
-    float *ev_scale = nullptr, *ev_shift = nullptr;   // eval-mode BN affine of every channel, remade when ev_dirty
+    // Both flags are raised by net_changed() alone and travel with the copies they guard (fm_teacher_swap)
+    float *ev_scale = nullptr, *ev_shift = nullptr;   // eval-mode BN affine of every channel, remade when ev_dirty (ensure_eval_affine)
     bool ev_dirty = true;
-    // forward shadows, remade with fm_engine::wpack_dirty (student) / twb_dirty (teacher): bf16 W and W^T of the 1x1 convs (bf16
-    // mode), row-major / block-major bf16 planes of the conv weights (ResNet; split3.h, pconv.hip), the stem's planes (stem_rows.hip)
+    // forward shadows, remade when fwd_dirty (ensure_fwd_shadows): bf16 W and W^T of the 1x1 convs (bf16 mode); bf16 planes of the
+    // conv weights (ResNet; block-major in planes mode, pconv.hip, else row-major, split3.h); the stem's planes (stem_rows.hip)
     bf16* wb = nullptr;
-    unsigned short *wsp_f = nullptr, *wbm_f = nullptr, *wst = nullptr;
+    unsigned short *wpl_f = nullptr, *wst = nullptr;
+    bool fwd_dirty = true;
 };
 
 // The tensors a forward writes.  The student's set is what the backward reads; the second set (fm_engine::tacts) exists only
@@ -174,10 +174,22 @@ struct StateEntry {           // one state_dict entry, in reference key order
     int bn;                   // counter's BN index (kind 2)
     int O = 0, I = 0, KH = 0, KW = 0, Wpad = 0, Ipad = 0;   // kind 0 geometry
     int Ostride = 0;          // engine row stride when it exceeds KH*Wpad*Ipad (packed stem: 176), 0 = dense
+    // the entry's span in the arena: a conv weight's O rows of `dense` floats, `row` apart, the last row ending with its matrix; a
+    // vector's n elements as one row
+    struct Span { int dense, row; long long len; };
+    Span span() const
+    {
+        if (kind != 0) return {(int)n, (int)n, (long long)n};
+        const int dense = KH * Wpad * Ipad, row = Ostride ? Ostride : dense;
+        return {dense, row, (long long)(O - 1) * row + dense};
+    }
 };
 
 struct EvPair { hipEvent_t a, b; int family; double flops; };
 struct OpEv { hipEvent_t a, b; int id; };
+// a batched kernel's job table on the device (upload_jobs): the jobs, their count and the blocks of the one launch
+template <typename J>
+struct JobList { J* jobs = nullptr; int n = 0, blocks = 0; };
 
 }  // namespace
 
@@ -199,10 +211,7 @@ struct fm_engine {
     const float *dc_dev = nullptr, *drop_dev = nullptr;   // caller-owned stochastic multipliers (or null)
     int pending_views = 0, pending_B = 0;                 // fm_forward_train awaiting fm_backward_step
     // autograd path (fm_backward_grads / fm_adam_step): the gradient accumulator (NP floats, allocated on first use; `gacc_full`
-    // false = empty, the next backward copies).  ResNet-18: the stem's weights as the data gradient's B matrix (stem_dgrad.hip),
-    // made on first use and again after the weights change
-    float* stem_dpack = nullptr;
-    bool stem_dpack_stale = true;
+    // false = empty, the next backward copies)
     float* gacc = nullptr;
     bool gacc_full = false;
     // fm_grad_norm / fm_clip_grad_norm: the per-block partial sums of squares and the norm word of a call that gives no pointer
@@ -286,19 +295,20 @@ struct fm_engine {
     double prof_ms[FM_PROFILE_FAMILIES] = {}, prof_flops[FM_PROFILE_FAMILIES] = {};
     int64_t prof_n[FM_PROFILE_FAMILIES] = {};
     std::vector<void*> allocs;
-    // dgrad weight packs: rebuilt by ONE launch after every optimizer step (and lazily after any
-    // external change of the state), not per convolution call
-    PackJob* pack_jobs = nullptr;
-    int n_pack_jobs = 0, n_pack_blocks = 0;
-    bool wpack_dirty = true;
-    // bf16 planes of the data-gradient packs for the split-product GEMMs (split3.h; ResNet, fp32 mode), rebuilt with the packs
-    unsigned short* wsp_d = nullptr;
+    // The copies only the student has, raised by student_copies_stale() alone.  dgrad_dirty (remade by ensure_packed): the
+    // transposed weight packs of the data gradients (DgradClass::wpack), rebuilt by ONE launch after every optimizer step (and
+    // lazily after any other change of the state), and their bf16 planes wpl_d for the split-product GEMMs (ResNet, fp32 mode;
+    // layout as Weights::wpl_f).  stem_dpack_stale (ensure_stem_dpack): ResNet-18's stem weights as its data gradient's B matrix
+    // (stem_dgrad.hip), made on first use
+    JobList<PackJob> pack_jobs;
+    unsigned short* wpl_d = nullptr;
+    bool dgrad_dirty = true;
+    float* stem_dpack = nullptr;
+    bool stem_dpack_stale = true;
+    JobList<SplitJob> split_f, split_d;         // the plane jobs of the forward weights (either net's) / of the packs
     // planes mode (ResNet-18, split product forms): the 3x3 / 1x1 conv GEMMs take BOTH operands as block-major bf16 planes
     // (pconv.hip); the activation planes are written by the kernels that produce the tensors
     bool planes = false;
-    unsigned short* wbm_d = nullptr;
-    SplitJobBM *bm_f = nullptr, *bm_d = nullptr;
-    int n_bm_f = 0, n_bm_f_blocks = 0, n_bm_d = 0, n_bm_d_blocks = 0;
     unsigned short *GBp = nullptr, *GCp = nullptr, *GDp = nullptr;   // planes of d y2, d y_ds, d y1 (what the data gradients read)
     unsigned short *GB2p = nullptr, *GC2p = nullptr, *GD2p = nullptr;
     unsigned short* xp_scratch = nullptr;       // planes of an fp32 operand nobody produced planes for (test hooks)
@@ -306,8 +316,6 @@ struct fm_engine {
     size_t xp_scratch_elems = 0;
     const float* xp_scratch_src = nullptr;
     long long xp_scratch_npix = 0;
-    SplitJob *split_f = nullptr, *split_d = nullptr;
-    int n_split_f = 0, n_split_f_blocks = 0, n_split_d = 0, n_split_d_blocks = 0;
     // RCCL (comm.hip)
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -318,9 +326,7 @@ struct fm_engine {
     int stream_mode = 0;              // fm_config.reserved[1]: 0 side stream for teacher + weight gradients, 1 one stream, 2 teacher only
     int dt = DT_F32;                  // storage type of activations / their gradients (DT_F32 or DT_BF16)
     size_t wb_numel = 0;              // elements of Weights::wb
-    CastJob* cast_jobs = nullptr;
-    int n_cast_jobs = 0, n_cast_blocks = 0;
-    bool twb_dirty = true;            // the teacher's forward shadows are stale (the student's go with wpack_dirty)
+    JobList<CastJob> cast_jobs;
     bool fuse_gate = false;           // squeeze-excite gate applied on the project conv's operand load (a_s never stored)
     // stage-1 steps: the frozen teacher's forward is independent of the student's until the loss, so it is enqueued on the
     // side lane into the second activation set (side_ok; stream_mode 1: main lane, the student's set)
@@ -398,6 +404,14 @@ int upload_tab(fm_engine* e, const std::vector<int4>& h, int4** d)
 {
     DALLOC(*d, h.size());
     HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(int4), hipMemcpyHostToDevice));
+    return FM_OK;
+}
+template <typename J>
+int upload_jobs(fm_engine* e, const std::vector<J>& h, int blocks, JobList<J>& d)
+{
+    d.n = (int)h.size(); d.blocks = blocks;
+    DALLOC(d.jobs, h.size());
+    if (!h.empty()) HIPCHK(hipMemcpy(d.jobs, h.data(), h.size() * sizeof(J), hipMemcpyHostToDevice));
     return FM_OK;
 }
 
@@ -519,93 +533,43 @@ int build_tables(fm_engine* e)
             cb += (int)((n + 255) / 256);
         }
         e->wb_numel = (size_t)off;
-        e->n_cast_jobs = (int)cj.size(); e->n_cast_blocks = cb;
-        DALLOC(e->cast_jobs, cj.size());
-        HIPCHK(hipMemcpy(e->cast_jobs, cj.data(), cj.size() * sizeof(CastJob), hipMemcpyHostToDevice));
+        RCCHK(upload_jobs(e, cj, cb, e->cast_jobs));
         DALLOC(e->student.wb, e->wb_numel); DALLOC(e->teacher.wb, e->wb_numel);
     }
-    e->n_pack_jobs = (int)jobs.size();
-    e->n_pack_blocks = blk;
-    DALLOC(e->pack_jobs, jobs.size());
-    if (!jobs.empty())
-        HIPCHK(hipMemcpy(e->pack_jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    RCCHK(upload_jobs(e, jobs, blk, e->pack_jobs));
     if (e->model == 0 && !e->precision) {
-        // weight planes for the GEMMs with whole 64-row tiles and whole 32-k blocks per tap (igemm.hip, WP form)
+        // bf16 planes of the weights (forward) and of the packs (data gradient) for the GEMMs with whole 64-row tiles and whole
+        // 32-k blocks per tap: every non-stem conv of ResNet-18 and every parity class of its data gradients.  The jobs, sizes
+        // and offsets are the same for both layouts; e->planes says which kernel fills them (ensure_fwd_shadows, ensure_packed)
+        // and which GEMM reads them (pconv.hip: block-major; igemm.hip, WP form: row-major, read where the product form splits)
         std::vector<SplitJob> jf, jd;
         long long off_f = 0, off_d = 0;
         int bf = 0, bd = 0;
         for (auto& c : e->convs) {
-            if (c.cin == 3 || e->planes) continue;      // (planes mode: the fp32-operand kernels never run on these convs)
+            if (c.cin == 3) continue;
             if (c.cout_p % 64 == 0 && c.cin_p % 32 == 0) {
-                c.sp_off = off_f;
-                jf.push_back({(long long)c.w_off, nullptr, off_f, c.cout_p, c.Kw / 32, bf});
-                bf += split_job_blocks(c.cout_p, c.Kw / 32);
+                c.pl_off = off_f;
+                jf.push_back({(long long)c.w_off, nullptr, off_f, c.cout_p, c.k * c.k, c.cin_p / 32, bf});
+                bf += split_job_blocks(c.cout_p, c.k * c.k, c.cin_p / 32);
                 off_f += (long long)c.cout_p * c.Kw * 3;
             }
             if (c.cin_p % 64 == 0 && c.cout_p % 32 == 0)
                 for (int k = 0; k < c.ncls; ++k) {
                     DgradClass& d = c.cls[k];
-                    const int K = d.taps.n * c.cout_p;
-                    d.sp_off = off_d;
-                    jd.push_back({0, d.wpack, off_d, c.cin_p, K / 32, bd});
-                    bd += split_job_blocks(c.cin_p, K / 32);
-                    off_d += (long long)c.cin_p * K * 3;
+                    d.pl_off = off_d;
+                    jd.push_back({0, d.wpack, off_d, c.cin_p, d.taps.n, c.cout_p / 32, bd});
+                    bd += split_job_blocks(c.cin_p, d.taps.n, c.cout_p / 32);
+                    off_d += (long long)c.cin_p * d.taps.n * c.cout_p * 3;
                 }
-        }
-        if (e->planes) {
-            // block-major planes (pconv.hip): every non-stem conv of ResNet-18 and every parity class of its data gradients
-            std::vector<SplitJobBM> bf_, bd_;
-            long long o_f = 0, o_d = 0;
-            int nbf = 0, nbd = 0;
-            for (auto& c : e->convs) {
-                if (c.cin == 3) continue;
-                if (c.cout_p % 64 == 0 && c.cin_p % 32 == 0) {
-                    c.bm_off = o_f;
-                    bf_.push_back({(long long)c.w_off, nullptr, o_f, c.cout_p, c.k * c.k, c.cin_p / 32, nbf});
-                    nbf += split_job_bm_blocks(c.cout_p, c.Kw / 32);
-                    o_f += (long long)c.cout_p * c.Kw * 3;
-                }
-                if (c.cin_p % 64 == 0 && c.cout_p % 32 == 0)
-                    for (int k = 0; k < c.ncls; ++k) {
-                        DgradClass& d = c.cls[k];
-                        const int K = d.taps.n * c.cout_p;
-                        d.bm_off = o_d;
-                        bd_.push_back({0, d.wpack, o_d, c.cin_p, d.taps.n, c.cout_p / 32, nbd});
-                        nbd += split_job_bm_blocks(c.cin_p, K / 32);
-                        o_d += (long long)c.cin_p * K * 3;
-                    }
-            }
-            float* t2 = nullptr;
-            if (o_f) {
-                DALLOC(t2, (size_t)(o_f + 1) / 2); e->student.wbm_f = reinterpret_cast<unsigned short*>(t2);
-                DALLOC(t2, (size_t)(o_f + 1) / 2); e->teacher.wbm_f = reinterpret_cast<unsigned short*>(t2);
-            }
-            if (o_d) { DALLOC(t2, (size_t)(o_d + 1) / 2); e->wbm_d = reinterpret_cast<unsigned short*>(t2); }
-            e->n_bm_f = (int)bf_.size(); e->n_bm_f_blocks = nbf; e->n_bm_d = (int)bd_.size(); e->n_bm_d_blocks = nbd;
-            if (!bf_.empty()) {
-                DALLOC(e->bm_f, bf_.size());
-                HIPCHK(hipMemcpy(e->bm_f, bf_.data(), bf_.size() * sizeof(SplitJobBM), hipMemcpyHostToDevice));
-            }
-            if (!bd_.empty()) {
-                DALLOC(e->bm_d, bd_.size());
-                HIPCHK(hipMemcpy(e->bm_d, bd_.data(), bd_.size() * sizeof(SplitJobBM), hipMemcpyHostToDevice));
-            }
         }
         float* tmp = nullptr;
         if (off_f) {
-            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->student.wsp_f = reinterpret_cast<unsigned short*>(tmp);
-            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->teacher.wsp_f = reinterpret_cast<unsigned short*>(tmp);
+            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->student.wpl_f = reinterpret_cast<unsigned short*>(tmp);
+            DALLOC(tmp, (size_t)(off_f + 1) / 2); e->teacher.wpl_f = reinterpret_cast<unsigned short*>(tmp);
         }
-        if (off_d) { DALLOC(tmp, (size_t)(off_d + 1) / 2); e->wsp_d = reinterpret_cast<unsigned short*>(tmp); }
-        e->n_split_f = (int)jf.size(); e->n_split_f_blocks = bf; e->n_split_d = (int)jd.size(); e->n_split_d_blocks = bd;
-        if (!jf.empty()) {
-            DALLOC(e->split_f, jf.size());
-            HIPCHK(hipMemcpy(e->split_f, jf.data(), jf.size() * sizeof(SplitJob), hipMemcpyHostToDevice));
-        }
-        if (!jd.empty()) {
-            DALLOC(e->split_d, jd.size());
-            HIPCHK(hipMemcpy(e->split_d, jd.data(), jd.size() * sizeof(SplitJob), hipMemcpyHostToDevice));
-        }
+        if (off_d) { DALLOC(tmp, (size_t)(off_d + 1) / 2); e->wpl_d = reinterpret_cast<unsigned short*>(tmp); }
+        RCCHK(upload_jobs(e, jf, bf, e->split_f));
+        RCCHK(upload_jobs(e, jd, bd, e->split_d));
     }
     return FM_OK;
 }
@@ -1096,7 +1060,7 @@ const unsigned short* scratch_planes(fm_engine* e, Lane& L, const float* x, long
 }
 bool conv_uses_pconv(const fm_engine* e, const Conv& c, int imgs)
 {
-    return e->planes && c.bm_off >= 0 && pconv_takes(c.cout_p, c.cin_p, (long long)imgs * c.hin * c.win, c.win);
+    return e->planes && c.pl_off >= 0 && pconv_takes(c.cout_p, c.cin_p, (long long)imgs * c.hin * c.win, c.win);
 }
 
 // the GEMM geometry of a convolution's forward / data-gradient launches -- taps, operand map, output grid: what pconv_uses_ts
@@ -1121,7 +1085,7 @@ static void conv_dgrad_geometry(const Conv& c, const DgradClass& d, IgemmParams&
 }
 static bool dgrad_uses_pconv(const fm_engine* e, const Conv& c, int imgs)
 {
-    return e->planes && c.ncls > 0 && c.cls[0].bm_off >= 0 && pconv_takes(c.cin_p, c.cout_p, (long long)imgs * c.hout * c.wout, c.wout);
+    return e->planes && c.ncls > 0 && c.cls[0].pl_off >= 0 && pconv_takes(c.cin_p, c.cout_p, (long long)imgs * c.hout * c.wout, c.wout);
 }
 // the operand shapes of the planes weight gradient: what pwgrad_takes admitted and pwgrad_ring_takes decides on
 static bool wgrad_uses_pwgrad(const fm_engine* e, const Conv& c, int imgs)
@@ -1286,7 +1250,7 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
     if (arm == Arm::PconvTs || arm == Arm::PconvTap) {
         p.xp_pix = (long long)imgs * c.hin * c.win;
         p.Xp = xp ? xp : scratch_planes(e, L, x, p.xp_pix, c.cin_p);
-        p.Wsp = W.wbm_f + c.bm_off;
+        p.Wsp = W.wpl_f + c.pl_off;
         p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout; p.resp = resp;
         p.tilesM = c.cout_p / pconv_tile_m(c.cout_p);
         ProfScope ps(e, L, fam, flops);
@@ -1294,7 +1258,7 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
         return;
     }
     p.W = W.state + c.w_off; p.X = x; p.zeros = e->zeros; p.nsteps = c.nsteps;
-    if (c.sp_off >= 0 && W.wsp_f) p.Wsp = W.wsp_f + c.sp_off;
+    if (!e->planes && c.pl_off >= 0) p.Wsp = W.wpl_f + c.pl_off;      // row-major planes
     if (c.cin == 3) {
         p.stem_kw = c.k; p.stem_pad = c.pad; p.stem_h2 = c.kw_p == 8 ? 1 : 0; p.stem3 = c.stem3 ? 1 : 0;
         if (c.stem3) p.X = e->x3 + (size_t)e->in_img0 * c.Hp * c.Wp * 3;     // `x` is ignored: the operand is the framed NHWC3 image
@@ -1362,13 +1326,13 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
         p.tilesN = (imgs * p.Hg * p.Wg + bn - 1) / bn;
         const double flops = 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k);
         if (planes) {
-            p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d + d.bm_off;
+            p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wpl_d + d.pl_off;
             p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
             ProfScope ps(e, L, prof_family(pconv_arm(p), c.cin_p), flops);       // this class's own kernel
             launch_pconv(p, 1, L.st);
         } else {
             p.W = d.wpack; p.X = dy; p.zeros = e->zeros; p.nsteps = d.nsteps;
-            if (d.sp_off >= 0 && e->wsp_d) p.Wsp = e->wsp_d + d.sp_off;
+            if (!e->planes && d.pl_off >= 0) p.Wsp = e->wpl_d + d.pl_off;
             p.tilesM = (c.cin_p + igemm_tile_m(c.cin_p) - 1) / igemm_tile_m(c.cin_p);
             ProfScope ps(e, L, prof_family(arm, c.cin_p), flops);
             launch_igemm(p, 1, L.st);
@@ -1387,7 +1351,7 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
     Conv& c = e->convs[c1i];
     Conv& d = e->convs[dsi];
     const long long xp_pix = (long long)imgs * c.hout * c.wout;
-    if (c.ncls != 4 || d.ncls != 1 || !dgrad_uses_pconv(e, c, imgs) || d.cls[0].bm_off < 0) return false;
+    if (c.ncls != 4 || d.ncls != 1 || !dgrad_uses_pconv(e, c, imgs) || d.cls[0].pl_off < 0) return false;
     static_assert(PCONV_MAX_JOBS >= 4, "one job per parity class");
     const DgradClass& d0 = d.cls[0];
     if (c.stride != 2 || d.stride != 2 || d.k != 1 || d.cin_p != c.cin_p || d.cout_p != c.cout_p || d.hin != c.hin || d.win != c.win ||
@@ -1403,7 +1367,7 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
     }
     if (!dy1p) return true;                    // (scratch_planes reported it)
     IgemmParams p{};
-    p.Xp = dy1p; p.Xp2 = dydp; p.xp_pix = xp_pix; p.Wsp = e->wbm_d;
+    p.Xp = dy1p; p.Xp2 = dydp; p.xp_pix = xp_pix; p.Wsp = e->wpl_d;
     p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
     p.M = c.cin_p;
     p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
@@ -1419,13 +1383,13 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
         PconvJob& j = p.job[k];
         j.ntaps = q.taps.n; j.tapcode = pconv_tapcode(q.dh, q.dw, q.taps.n);
         j.cib = j.icc2 = c.cout_p >> 5;
-        j.wofs = j.wofs2 = (unsigned)(q.bm_off * 2);
+        j.wofs = j.wofs2 = (unsigned)(q.pl_off * 2);
         j.Hg = (c.hin - q.ph + c.stride - 1) / c.stride;
         j.Wg = (c.win - q.pw + c.stride - 1) / c.stride;
         j.oh0 = q.ph; j.ow0 = q.pw;
     }
     p.job[0].cib += d.cout_p >> 5;
-    p.job[0].wofs2 = (unsigned)(d0.bm_off * 2);
+    p.job[0].wofs2 = (unsigned)(d0.pl_off * 2);
     // the per-tap kernel's family; the launch's algorithmic FLOPs = both convs'
     ProfScope ps(e, L, prof_family(Arm::PconvTap, c.cin_p), 2.0 * (c.macs_per_img + d.macs_per_img) * imgs);
     launch_pconv(p, 1, L.st);
@@ -1572,6 +1536,60 @@ void to_nhwc4(fm_engine* e, Lane& L, const float* const* xs, int groups, int B)
         k_nchw_to_nhwc4(xs[g], e->x4 + (size_t)g * B * e->H * e->W * 4, B, e->H, e->W, L.st);
 }
 
+// ---- coherence of the copies derived from a net's state ----------------------------------------------------------
+// The staleness flags are raised in the two functions below and nowhere else, and cleared only by the ensure_* function that
+// remakes the copy (tests/test_coherence_cpu.py holds both).
+// fm_teacher_swap alone calls this directly: the copies only the student has were made for the net that left its slot
+void student_copies_stale(fm_engine* e)
+{
+    e->dgrad_dirty = true;
+    e->stem_dpack_stale = true;
+}
+// Net W's state changed: its weights (and whatever else), or -- second form -- only its BatchNorm running statistics, which
+// nothing but the folded eval affine reads.  Every entry point that writes a state, or hands out the pointer to it, says so here.
+enum class Moved { Weights, Stats };
+void net_changed(fm_engine* e, Weights& W, Moved what = Moved::Weights)
+{
+    W.ev_dirty = true;
+    if (what == Moved::Stats) return;
+    W.fwd_dirty = true;
+    if (&W == &e->student) student_copies_stale(e);
+}
+// the folded eval BatchNorm affine of W, on the lane the forward that reads it runs on
+void ensure_eval_affine(fm_engine* e, Lane& L, Weights& W)
+{
+    if (!W.ev_dirty) return;
+    const float* S = W.state;
+    k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, W.ev_scale, W.ev_shift, e->n_bn_ch, e->bn_eps, L.st);
+    W.ev_dirty = false;
+}
+// Everything else derived from the weights is (re)made on the main lane, where the weights change.
+// W's forward shadows: the bf16 cast of the 1x1 convs, or the weight planes in the engine's layout and the stem's planes
+void ensure_fwd_shadows(fm_engine* e, Weights& W)
+{
+    if (!W.fwd_dirty) return;
+    Lane& L = e->main;
+    if (e->precision) launch_cast_weights(W.state, W.wb, e->cast_jobs.jobs, e->cast_jobs.n, e->cast_jobs.blocks, L.st);
+    else if (e->planes) {
+        k_split_weights_bm(W.state, W.wpl_f, e->split_f.jobs, e->split_f.n, e->split_f.blocks, L.st);
+        if (e->stem_rows) k_stem_weight_planes(W.state + e->convs[0].w_off, W.wst, e->convs[0].Kw, L.st);
+    } else
+        k_split_weights(W.state, W.wpl_f, e->split_f.jobs, e->split_f.n, e->split_f.blocks, L.st);
+    W.fwd_dirty = false;
+}
+// the student's forward shadows and what only the student has: the transposed weight packs of every data-gradient GEMM, all in
+// ONE launch, then the planes of the packs just made
+void ensure_packed(fm_engine* e)
+{
+    ensure_fwd_shadows(e, e->student);
+    if (!e->dgrad_dirty) return;
+    Lane& L = e->main;
+    if (!e->precision && e->pack_jobs.n)
+        k_pack_dgrad_all(e->student.state, e->pack_jobs.jobs, e->pack_jobs.n, e->pack_jobs.blocks, L.st);
+    (e->planes ? k_split_weights_bm : k_split_weights)(nullptr, e->wpl_d, e->split_d.jobs, e->split_d.n, e->split_d.blocks, L.st);
+    e->dgrad_dirty = false;
+}
+
 // train-mode forward (the student's) of groups*B images already in e->x4; fills A and feat/logits
 void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mode)
 {
@@ -1632,18 +1650,14 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
     const Conv& cl = e->convs[e->blocks.back().c2];
     k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
     k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, L.st);
-    if (mode != BnMode::Frozen) e->student.ev_dirty = true;      // running stats moved
+    if (mode != BnMode::Frozen) net_changed(e, e->student, Moved::Stats);
 }
 
 // eval-mode forward (BN folded into the conv epilogue) of `imgs` images in e->x4
 void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
     const float* S = W.state;
-    if (W.ev_dirty) {
-        k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, W.ev_scale, W.ev_shift, e->n_bn_ch,
-                         e->bn_eps, L.st);
-        W.ev_dirty = false;
-    }
+    ensure_eval_affine(e, L, W);
     auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
     auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
     Conv& c0 = e->convs[0];
@@ -1680,47 +1694,14 @@ void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* f
     k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, L.st);
 }
 
-// Everything derived from the weights is (re)made on the main lane, where the weights change.
-// The student's: transposed weight packs of every data-gradient GEMM, all in ONE launch, and the forward shadows
-void ensure_packed(fm_engine* e)
-{
-    if (!e->wpack_dirty) return;
-    Lane& L = e->main;
-    Weights& W = e->student;
-    e->stem_dpack_stale = true;
-    if (e->precision) launch_cast_weights(W.state, W.wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, L.st);
-    else if (e->n_pack_jobs) k_pack_dgrad_all(W.state, e->pack_jobs, e->n_pack_jobs, e->n_pack_blocks, L.st);
-    if (e->planes) {
-        k_split_weights_bm(W.state, W.wbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, L.st);
-        k_split_weights_bm(nullptr, e->wbm_d, e->bm_d, e->n_bm_d, e->n_bm_d_blocks, L.st);      // planes of the packs just made
-        if (e->stem_rows) k_stem_weight_planes(W.state + e->convs[0].w_off, W.wst, e->convs[0].Kw, L.st);
-    } else {
-        k_split_weights(W.state, W.wsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, L.st);
-        k_split_weights(nullptr, e->wsp_d, e->split_d, e->n_split_d, e->n_split_d_blocks, L.st);     // planes of the packs just made
-    }
-    e->wpack_dirty = false;
-}
-void ensure_teacher_shadow(fm_engine* e)
-{
-    if (!e->twb_dirty) return;
-    Lane& L = e->main;
-    Weights& W = e->teacher;
-    if (e->precision) launch_cast_weights(W.state, W.wb, e->cast_jobs, e->n_cast_jobs, e->n_cast_blocks, L.st);
-    else if (e->planes) {
-        k_split_weights_bm(W.state, W.wbm_f, e->bm_f, e->n_bm_f, e->n_bm_f_blocks, L.st);
-        if (e->stem_rows) k_stem_weight_planes(W.state + e->convs[0].w_off, W.wst, e->convs[0].Kw, L.st);
-    }
-    else k_split_weights(W.state, W.wsp_f, e->split_f, e->n_split_f, e->n_split_f_blocks, L.st);
-    e->twb_dirty = false;
-}
-
 // d loss / d image of `imgs` images from the gradient of the stem's raw output (stem_dgrad.hip): dy [imgs][hout][wout][cout_p] in
 // the engine's storage type, dx fp32 NCHW (NHWC through fm_debug_conv).  Written, not accumulated.
+// The stem's data-gradient matrix is allocated at its first use (stale from the start: nothing clears its flag before)
 int ensure_stem_dpack(fm_engine* e)
 {
     if (e->model != 0) return FM_OK;
     const Conv& c0 = e->convs[0];
-    if (!e->stem_dpack) { DALLOC(e->stem_dpack, stem_dgrad_pack_floats()); e->stem_dpack_stale = true; }
+    if (!e->stem_dpack) DALLOC(e->stem_dpack, stem_dgrad_pack_floats());
     if (e->stem_dpack_stale) k_stem_dgrad_pack(e->student.state + c0.w_off, e->stem_dpack, c0.Kw, c0.kw_p, c0.cin_p, e->main.st);
     e->stem_dpack_stale = false;
     return FM_OK;
@@ -1745,8 +1726,7 @@ void stem_dgrad_views(fm_engine* e, Lane& L, const void* dy, int groups, int B, 
 // what every optimizer step ends with: the student's weights moved on the main lane
 void weights_stepped(fm_engine* e)
 {
-    e->student.ev_dirty = true;
-    e->wpack_dirty = true;
+    net_changed(e, e->student);
     ensure_packed(e);        // the next step's data gradients read the packed (transposed) weights
 }
 // The scalars of step t of each rule (optim.hip), for the flat steps and, per group, the grouped ones: what torch forms in double
@@ -1839,11 +1819,7 @@ int build_opt_table(const std::vector<StateEntry>& entries, size_t NP, std::vect
     for (size_t i = 0; i < entries.size(); ++i) {
         const StateEntry& en = entries[i];
         if (en.kind == 2 || en.eng_off >= NP) continue;
-        long long len = (long long)en.n;
-        if (en.kind == 0) {
-            const long long dense = (long long)en.KH * en.Wpad * en.Ipad, row = en.Ostride ? en.Ostride : dense;
-            len = (en.O - 1) * row + dense;
-        }
+        const long long len = en.span().len;
         if (len <= 0 || en.eng_off + (size_t)len > NP) return -1;
         opt_ent[i] = n_ent;
         ent_at[en.eng_off] = (int)i;
@@ -2202,17 +2178,13 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
         h = e->hfeat;
     }
     { OP(L, "k_fc_fwd"); k_fc_fwd(h, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, e->D, e->C, L.st); }
-    if (mode != BnMode::Frozen) e->student.ev_dirty = true;
+    if (mode != BnMode::Frozen) net_changed(e, e->student, Moved::Stats);
 }
 
 void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
     const float* S = W.state;
-    if (W.ev_dirty) {
-        { OP(L, "k_bn_eval_affine"); k_bn_eval_affine(S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, W.ev_scale, W.ev_shift,
-                         e->n_bn_ch, e->bn_eps, L.st); }
-        W.ev_dirty = false;
-    }
+    if (W.ev_dirty) { OP(L, "k_bn_eval_affine"); ensure_eval_affine(e, L, W); }
     auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
     auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
     { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_stem, W, e->x4, A.a0, imgs, 1, sc(e->bn_stem), sh(e->bn_stem), nullptr, 2, nullptr); }
@@ -2488,7 +2460,7 @@ void net_forward_train(fm_engine* e, int groups, int B, BnMode mode = BnMode::Ba
     if (e->model == 1) eff_forward_train(e, e->main, e->acts, groups, B, mode);
     else forward_train(e, e->main, e->acts, groups, B, mode);
 }
-// W's shadows are the caller's to ensure (ensure_packed / ensure_teacher_shadow: main lane)
+// W's shadows are the caller's to ensure (ensure_packed / ensure_fwd_shadows: main lane)
 void net_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
     if (e->model == 1) eff_forward_eval(e, L, W, A, imgs, feat, logits);
@@ -2497,7 +2469,7 @@ void net_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, floa
 // the teacher's forward on the side lane, into the second activation set: the same code as on the main lane
 int teacher_forward_side(fm_engine* e, int imgs)
 {
-    ensure_teacher_shadow(e);                                   // weight shadows on the main lane, before the fork
+    ensure_fwd_shadows(e, e->teacher);                          // weight shadows on the main lane, before the fork
     HIPCHK(hipEventRecord(e->ev_in, e->main.st));
     HIPCHK(hipStreamWaitEvent(e->side.st, e->ev_in, 0));
     net_forward_eval(e, e->side, e->teacher, e->tacts, imgs, e->tfeat, e->tlogits);
@@ -2510,7 +2482,7 @@ int teacher_and_student_forward(fm_engine* e, int timgs, int groups, int B)
 {
     if (e->side_ok) RCCHK(teacher_forward_side(e, timgs));
     else {
-        ensure_teacher_shadow(e);
+        ensure_fwd_shadows(e, e->teacher);
         net_forward_eval(e, e->main, e->teacher, e->acts, timgs, e->tfeat, e->tlogits);
     }
     net_forward_train(e, groups, B);
@@ -2524,9 +2496,9 @@ void net_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw = {})
     else backward_and_step(e, groups, B, bw);
 }
 
-// an engine-layout gradient arena (e->grad or the accumulator) -> dst in state_dict order (conv weights OIHW, BN running
-// statistics as zeros; e->nf_sd floats), enqueued on the main lane
-int grads_to_state_dict(fm_engine* e, const float* src, float* dst)
+// an engine-layout arena -> dst in state_dict order (conv weights OIHW; e->nf_sd floats), enqueued on the main lane.  np_only: an
+// arena of NP floats (e->grad, the accumulator, the moments): the BN running statistics come out as zeros
+int arena_to_state_dict(fm_engine* e, const float* src, float* dst, bool np_only)
 {
     Lane& L = e->main;
     size_t off = 0;
@@ -2535,7 +2507,7 @@ int grads_to_state_dict(fm_engine* e, const float* src, float* dst)
             k_ohwi_to_oihw(src + en.eng_off, dst + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, L.st, en.Ostride);
             off += en.n;
         } else if (en.kind == 1) {
-            if (en.eng_off < e->NP)
+            if (!np_only || en.eng_off < e->NP)
                 HIPCHK(hipMemcpyAsync(dst + off, src + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, L.st));
             else
                 HIPCHK(hipMemsetAsync(dst + off, 0, en.n * 4, L.st));
@@ -2595,14 +2567,12 @@ int ensure_dist_table(fm_engine* e)
         if (en.kind == 2) continue;
         DistEntry d{};
         d.off = (long long)en.eng_off;
+        const StateEntry::Span sp = en.span();
+        d.dense = sp.dense; d.row = sp.row; d.len = (int)sp.len;
         if (en.kind == 0) {
-            d.dense = en.KH * en.Wpad * en.Ipad;
-            d.row = en.Ostride ? en.Ostride : d.dense;
-            d.len = (en.O - 1) * d.row + d.dense;          // the last row ends with its matrix
             d.Ipad = en.Ipad; d.I = en.I; d.Wpad = en.Wpad; d.W = en.KW;
             d.all_real = d.row == d.dense && en.Ipad == en.I && en.Wpad == en.KW;
         } else {
-            d.len = (int)en.n; d.row = d.dense = d.len;
             d.Ipad = d.I = d.Wpad = d.W = 1;
             d.all_real = 1;
         }
@@ -2628,7 +2598,7 @@ int ensure_dist_table(fm_engine* e)
 int fold_states(fm_engine* e, const FoldArgs& a, int K, float tot, float* out_dev)
 {
     k_fedavg_fold(a, K, tot, out_dev, (int64_t)e->NS, e->main.st);
-    if (out_dev == e->student.state) { e->student.ev_dirty = true; e->wpack_dirty = true; }
+    if (out_dev == e->student.state) net_changed(e, e->student);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -2742,7 +2712,7 @@ int fused_step(fm_engine* e, StepFwd fwd, const float* x1, const float* x2, int 
     if (fwd == StepFwd::Rscfed && !(e->side_ok && 2 * B <= e->maxB)) {
         // one lane (or no room for both views in the staging): the teacher first, each view staged in turn
         to_nhwc4(e, e->main, &x2, 1, B);
-        ensure_teacher_shadow(e);
+        ensure_fwd_shadows(e, e->teacher);
         net_forward_eval(e, e->main, e->teacher, e->acts, B, e->tfeat, e->tlogits);
         to_nhwc4(e, e->main, &x1, 1, B);
         net_forward_train(e, 1, B);
@@ -2856,28 +2826,15 @@ int fm_set_state(fm_engine* e, const float* host_f32, const int64_t* host_i64)
             ++ic;
         }
     HIPCHK(hipStreamSynchronize(e->main.st));
-    e->student.ev_dirty = true;
-    e->wpack_dirty = true;
+    net_changed(e, e->student);
     return FM_OK;
 }
 
 int fm_get_state(fm_engine* e, float* host_f32, int64_t* host_i64)
 {
     ARGCHK(e && host_f32, "null engine/state");
-    size_t off = 0;
-    int ic = 0;
-    for (auto& en : e->entries) {
-        if (en.kind == 0) {
-            k_ohwi_to_oihw(e->student.state + en.eng_off, e->stage_sd + off, en.O, en.I, en.KH, en.KW, en.Wpad, en.Ipad, e->main.st, en.Ostride);
-            off += en.n;
-        } else if (en.kind == 1) {
-            HIPCHK(hipMemcpyAsync(e->stage_sd + off, e->student.state + en.eng_off, en.n * 4, hipMemcpyDeviceToDevice, e->main.st));
-            off += en.n;
-        } else {
-            if (host_i64) host_i64[ic] = e->student.counters[en.bn];
-            ++ic;
-        }
-    }
+    RCCHK(arena_to_state_dict(e, e->student.state, e->stage_sd, false));
+    if (host_i64) RCCHK(fm_counters(e, host_i64, 0));
     HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->main.st));
     HIPCHK(hipStreamSynchronize(e->main.st));
     return FM_OK;
@@ -2888,8 +2845,7 @@ int fm_state_device(fm_engine* e, float** dev_ptr, int64_t* numel)
     ARGCHK(e && dev_ptr && numel, "null");
     *dev_ptr = e->student.state;
     *numel = (int64_t)e->NS;
-    e->student.ev_dirty = true;       // the caller is about to overwrite it (all-reduce)
-    e->wpack_dirty = true;
+    net_changed(e, e->student);       // the caller is about to overwrite it (all-reduce)
     return FM_OK;
 }
 
@@ -2910,8 +2866,7 @@ int fm_state_scale(fm_engine* e, float w)
 {
     ARGCHK(e, "null engine");
     k_scale(e->student.state, w, (int64_t)e->NS, e->main.st);
-    e->student.ev_dirty = true;
-    e->wpack_dirty = true;
+    net_changed(e, e->student);
     return FM_OK;
 }
 
@@ -3018,8 +2973,8 @@ int fm_fedavg_allreduce(fm_engine* e, float w)
 {
     ARGCHK(e, "null engine");
     k_scale(e->student.state, w, (int64_t)e->NS, e->main.st);
-    e->student.ev_dirty = true; e->wpack_dirty = true;
-    if (!e->comm) return FM_OK;       // no communicator: a single client, FedAvg of one = w * state
+    net_changed(e, e->student);
+    if (!e->comm) return FM_OK;      // no communicator: a single client, FedAvg of one = w * state
     // (1) the whole fp32 arena, in place, on the engine stream: the next round's first kernels queue behind it
     COMMCHK(fmcomm_allreduce_sum(e->comm, e->student.state, e->NS, false, e->main.st));
     // (2) num_batches_tracked: weighted mean in float64, truncated on load like utils/FedAvg.py:13 + load_state_dict
@@ -3082,8 +3037,7 @@ int fm_teacher_snapshot(fm_engine* e)
     ARGCHK(e, "null engine");
     HIPCHK(hipMemcpyAsync(e->teacher.state, e->student.state, e->NS * 4, hipMemcpyDeviceToDevice, e->main.st));
     e->teacher.counters = e->student.counters;
-    e->teacher.ev_dirty = true;
-    e->twb_dirty = true;
+    net_changed(e, e->teacher);
     return FM_OK;
 }
 
@@ -3103,7 +3057,7 @@ int fm_forward_eval(fm_engine* e, const float* x_dev, int32_t B, int32_t use_tea
     to_nhwc4(e, e->main, xs, 1, B);
     float* feat = use_teacher ? e->tfeat : e->feat;
     float* logits = use_teacher ? e->tlogits : e->logits;
-    if (use_teacher) ensure_teacher_shadow(e);
+    if (use_teacher) ensure_fwd_shadows(e, e->teacher);
     else ensure_packed(e);
     net_forward_eval(e, e->main, use_teacher ? e->teacher : e->student, e->acts, B, feat, logits);
     if (feat_dev) HIPCHK(hipMemcpyAsync(feat_dev, feat, (size_t)B * e->D * 4, hipMemcpyDeviceToDevice, e->main.st));
@@ -3571,7 +3525,7 @@ int fm_get_grads(fm_engine* e, float* dev_out)
     ARGCHK(e && dev_out, "null");
     if (!e->gacc_full) HIPCHK(hipMemsetAsync(dev_out, 0, (size_t)e->nf_sd * 4, e->main.st));
     else {
-        RCCHK(grads_to_state_dict(e, e->gacc, dev_out));
+        RCCHK(arena_to_state_dict(e, e->gacc, dev_out, true));
     }
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -3715,8 +3669,8 @@ int fm_clip_grad_value(fm_engine* e, float clip)
 int fm_optim_get_state(fm_engine* e, float* m_dev, float* v_dev, int64_t* step_host)
 {
     ARGCHK(e, "null engine");
-    if (m_dev) RCCHK(grads_to_state_dict(e, e->adam_m, m_dev));
-    if (v_dev) RCCHK(grads_to_state_dict(e, e->adam_v, v_dev));
+    if (m_dev) RCCHK(arena_to_state_dict(e, e->adam_m, m_dev, true));
+    if (v_dev) RCCHK(arena_to_state_dict(e, e->adam_v, v_dev, true));
     if (step_host) *step_host = e->adam_t;
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -3741,8 +3695,7 @@ int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
     // int64 num_batches_tracked: the float result is truncated when it is loaded back (like FedAvg, Q7)
     for (size_t i = 0; i < e->student.counters.size(); ++i)
         e->teacher.counters[i] = (int64_t)(w_teacher * (float)e->teacher.counters[i] + w_student * (float)e->student.counters[i]);
-    e->teacher.ev_dirty = true;
-    e->twb_dirty = true;
+    net_changed(e, e->teacher);
     return FM_OK;
 }
 
@@ -3752,8 +3705,7 @@ int fm_teacher_ema_params(fm_engine* e, double alpha)
     ARGCHK(alpha >= 0.0 && alpha <= 1.0, "fm_teacher_ema_params: alpha in [0, 1]");
     // the trainable part of the arena only: running statistics (behind NP) and the counters stay as they are
     k_axpby(e->teacher.state, e->student.state, (float)alpha, (float)(1.0 - alpha), (int64_t)e->NP, e->main.st);
-    e->teacher.ev_dirty = true;
-    e->twb_dirty = true;
+    net_changed(e, e->teacher);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -3761,9 +3713,8 @@ int fm_teacher_ema_params(fm_engine* e, double alpha)
 int fm_teacher_swap(fm_engine* e)
 {
     ARGCHK(e, "null engine");
-    std::swap(e->student, e->teacher);
-    e->wpack_dirty = true;        // the shadows went along; both sets are remade all the same, as they always were
-    e->twb_dirty = true;
+    std::swap(e->student, e->teacher);        // each net's affine and forward shadows go along, and so do their flags
+    student_copies_stale(e);
     return FM_OK;
 }
 
@@ -3964,7 +3915,7 @@ int fm_debug_entry_spans(fm_engine* e, int64_t* off_len, int32_t n_entries)
 int fm_debug_get_grads(fm_engine* e, float* host_f32)
 {
     ARGCHK(e && host_f32, "null");
-    RCCHK(grads_to_state_dict(e, e->grad, e->stage_sd));
+    RCCHK(arena_to_state_dict(e, e->grad, e->stage_sd, true));
     HIPCHK(hipMemcpyAsync(host_f32, e->stage_sd, (size_t)e->nf_sd * 4, hipMemcpyDeviceToHost, e->main.st));
     HIPCHK(hipStreamSynchronize(e->main.st));
     return FM_OK;

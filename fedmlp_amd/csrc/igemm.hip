@@ -495,9 +495,9 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].blk0) ++j;
     const SplitJob jb = jobs[j];
     const long long idx = (long long)((int)blockIdx.x - jb.blk0) * 256 + threadIdx.x;
-    if (idx >= (long long)jb.M * jb.nkb * 4) return;
+    if (idx >= (long long)jb.M * (jb.ntaps * jb.cib) * 4) return;
     const int g = (int)(idx & 3);
-    const long long blk = idx >> 2;                       // m * nkb + kb
+    const long long blk = idx >> 2;                       // m * nkb + kb, nkb = ntaps * cib
     const float* src = (jb.src ? jb.src : src_base + jb.src_off) + blk * 32;
     sp_u32x4 H, M, L;
     split3(ld4(src + 4 * g), ld4(src + 16 + 4 * g), H, M, L);
@@ -507,7 +507,6 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     *reinterpret_cast<sp_u32x4*>(dst + 128) = L;
 #endif
 }
-int split_job_blocks(int M, int nkb) { return (int)(((long long)M * nkb * 4 + 255) / 256); }
 void k_split_weights(const float* src_base, unsigned short* dst_base, const SplitJob* jobs, int njobs, int nblocks, hipStream_t s)
 {
     if (njobs > 0) hipLaunchKernelGGL(split_weights_kernel, dim3(nblocks), dim3(256), 0, s, src_base, dst_base, jobs, njobs);

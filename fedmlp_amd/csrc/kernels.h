@@ -29,16 +29,16 @@ void k_pack_dgrad(const float* w, float* out, int Co, int T, int Ci, TapList tap
 struct PackJob { long long w_off; float* out; int Co, T, Ci, ntaps; int taps[9]; int blk0; };
 void k_pack_dgrad_all(const float* state, const PackJob* jobs, int njobs, int nblocks, hipStream_t s);
 int pack_job_blocks(int Co, int Ci, int ntaps);      // blocks of one job (32 x 32 tiles per tap); PackJob.blk0 = running sum
-// bf16 planes (split3.h) of [M][32 nkb] fp32 weight matrices for the split-product conv GEMMs, every matrix of a list in ONE
-// launch: job j reads src (or src_base + src_off when src is null) and writes dst_base + dst_off (in 2-byte units) as
-// [M][nkb][3 planes][32]; inside a 32-k block, 8-value chunk g holds k = 4g..4g+3, 16+4g..16+4g+3 (the igemm lane groups' order)
-struct SplitJob { long long src_off; const float* src; long long dst_off; int M, nkb, blk0; };
+// bf16 planes (split3.h) of fp32 weight matrices W[M][ntaps][cib * 32] for the split-product conv GEMMs, every matrix of a list in
+// ONE launch: job j reads src (or src_base + src_off when src is null) and writes 3 * M * ntaps * cib * 32 two-byte units at
+// dst_base + dst_off; one thread per 8-value chunk, blk0 = the job's first block (running sum of split_job_blocks).  Two layouts:
+// row-major (igemm.hip): [M][nkb = ntaps * cib][3 planes][32]; inside a 32-k block, 8-value chunk g holds k = 4g..4g+3,
+// 16+4g..16+4g+3 (the igemm lane groups' order)
+struct SplitJob { long long src_off; const float* src; long long dst_off; int M, ntaps, cib, blk0; };
+inline int split_job_blocks(int M, int ntaps, int cib) { return (int)(((long long)M * ntaps * cib * 4 + 255) / 256); }
 void k_split_weights(const float* src_base, unsigned short* dst_base, const SplitJob* jobs, int njobs, int nblocks, hipStream_t s);
-int split_job_blocks(int M, int nkb);
-// block-major planes for pconv.hip: dst[K block s = (channel block, tap), tap-minor][3 planes][M][32] from W[M][ntaps][cib * 32]
-struct SplitJobBM { long long src_off; const float* src; long long dst_off; int M, ntaps, cib, blk0; };
-void k_split_weights_bm(const float* src_base, unsigned short* dst_base, const SplitJobBM* jobs, int njobs, int nblocks, hipStream_t s);
-int split_job_bm_blocks(int M, int nsteps);
+// block-major (pconv.hip): dst[K block s = (channel block, tap), tap-minor][3 planes][M][32]
+void k_split_weights_bm(const float* src_base, unsigned short* dst_base, const SplitJob* jobs, int njobs, int nblocks, hipStream_t s);
 // block-major planes [C/32][3][npix][32] of an fp32 NHWC tensor [npix][C] (C % 32 == 0), and back (x = (h + m) + l, exact)
 void k_split_planes(const float* x, unsigned short* dst, long long npix, int C, hipStream_t s);
 void k_planes_to_f32(const unsigned short* src, float* x, long long npix, int C, hipStream_t s);

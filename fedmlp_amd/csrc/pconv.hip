@@ -814,12 +814,12 @@ extern "C" int fm_debug_pconv_prof(unsigned long long* out)
 // One thread = one 8-value chunk (channels 4g..4g+3, 16+4g..16+4g+3 of a 32-channel block): two 16-B reads 64 B apart, three
 // 16-B writes (4 threads = 64 B of one row of one plane).  Thread order: (s, m, g) with g fastest, then m: writes are contiguous.
 __global__ __launch_bounds__(256) void split_weights_bm_kernel(const float* __restrict__ src_base, unsigned short* __restrict__ dst_base,
-                                                               const SplitJobBM* __restrict__ jobs, int njobs)
+                                                               const SplitJob* __restrict__ jobs, int njobs)
 {
 #if __HIP_DEVICE_COMPILE__
     int j = 0;
     while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].blk0) ++j;
-    const SplitJobBM jb = jobs[j];
+    const SplitJob jb = jobs[j];
     const long long idx = (long long)((int)blockIdx.x - jb.blk0) * 256 + threadIdx.x;
     const int nsteps = jb.ntaps * jb.cib;
     if (idx >= (long long)nsteps * jb.M * 4) return;
@@ -836,8 +836,7 @@ __global__ __launch_bounds__(256) void split_weights_bm_kernel(const float* __re
     *reinterpret_cast<sp_u32x4*>(dst + (size_t)jb.M * 128) = L;
 #endif
 }
-int split_job_bm_blocks(int M, int nsteps) { return (int)(((long long)M * nsteps * 4 + 255) / 256); }
-void k_split_weights_bm(const float* src_base, unsigned short* dst_base, const SplitJobBM* jobs, int njobs, int nblocks, hipStream_t s)
+void k_split_weights_bm(const float* src_base, unsigned short* dst_base, const SplitJob* jobs, int njobs, int nblocks, hipStream_t s)
 {
     if (njobs > 0) hipLaunchKernelGGL(split_weights_bm_kernel, dim3(nblocks), dim3(256), 0, s, src_base, dst_base, jobs, njobs);
 }

@@ -1,9 +1,11 @@
 """The ledger behind tests/test_coherence_gpu.py, checked without a GPU: every fm_* entry point of include/fedmlp_hip.h has a class
 (tests/coherence_cases.FM_CLASS), every Engine wrapper bumps the version counters its class demands, every state-changing entry
 point is in the matrix or excused by name, and every caller of a state-changing Engine method in local_training.py / optim.py
-tells the net (mark_trained).  Sources are read with ast; nothing is imported from the library."""
+tells the net (mark_trained), and csrc/engine.hip assigns its staleness flags only in the helpers and remake functions made for it.
+Sources are read with ast (engine.hip with re); nothing is imported from the library."""
 import ast
 import os
+import re
 
 from tests import coherence_cases as CC
 
@@ -106,6 +108,85 @@ def test_affects_table():
     n = sum(CC.affects(m, r) for m in CC.MUTATORS for r in CC.READERS)
     assert 0 < n < len(CC.MUTATORS) * len(CC.READERS)
     assert len(CC.cells("r18_224")) == 18 and len(CC.cells("r18_64")) == len(CC.MUTATORS) * len(CC.READERS)
+
+
+# ---- the staleness flags of csrc/engine.hip ----------------------------------------------------------------------
+FLAGS = ("ev_dirty", "fwd_dirty", "dgrad_dirty", "stem_dpack_stale")
+RAISED_IN = {"net_changed": {"ev_dirty", "fwd_dirty"}, "student_copies_stale": {"dgrad_dirty", "stem_dpack_stale"}}
+CLEARED_IN = {"ensure_eval_affine": {"ev_dirty"}, "ensure_fwd_shadows": {"fwd_dirty"}, "ensure_packed": {"dgrad_dirty"},
+              "ensure_stem_dpack": {"stem_dpack_stale"}}
+# who says "a state changed": the entry points and graph functions of the issue's list, and the helper that calls the other
+SAYS_SO = {"net_changed": {"weights_stepped", "fold_states", "fm_set_state", "fm_state_device", "fm_state_scale", "fm_fedavg_allreduce",
+                           "forward_train", "eff_forward_train", "fm_teacher_snapshot", "fm_teacher_axpby", "fm_teacher_ema_params"},
+           "student_copies_stale": {"net_changed", "fm_teacher_swap"}}
+
+
+def _engine_functions(text):
+    """(name, body) of every function of a source whose definitions open with a `{` alone in column 0 and close with a `}` there"""
+    out, head, name, body = [], None, None, None
+    for line in text.splitlines():
+        if name is None:
+            if line == "{" and head:
+                name, body = re.match(r"[^(]*?(\w+)\s*\(", head).group(1), []
+            elif line[:1] not in ("", " ", "\t", "/", "#", "}"):
+                head = line
+        elif line == "}":
+            out.append((name, "\n".join(body)))
+            head = name = None
+        else:
+            body.append(line)
+    return out
+
+
+_ASSIGNS = re.compile(r"(?:\.|->)\s*(%s)\s*[|&^]?=(?!=)\s*([^;]*);" % "|".join(FLAGS))
+
+
+def flag_assignments(text):
+    """[(function, flag, right-hand side)] of every assignment to a staleness flag through an object (`x.flag =`, `x->flag =`)"""
+    return [(fn, m.group(1), m.group(2).strip()) for fn, body in _engine_functions(text) for m in _ASSIGNS.finditer(body)]
+
+
+def check_flag_sites(text):
+    sites = flag_assignments(text)
+    assert len(sites) == len(_ASSIGNS.findall(text)), "a staleness flag is assigned outside every function _engine_functions sees"
+    raised, cleared = {}, {}
+    for fn, flag, rhs in sites:
+        assert rhs in ("true", "false"), f"{fn}: {flag} = {rhs}: a staleness flag takes a literal, in its helper or its remake function"
+        (raised if rhs == "true" else cleared).setdefault(fn, set()).add(flag)
+    assert raised == RAISED_IN, f"staleness flags are raised outside the helpers (or a helper lost one): {raised}"
+    assert cleared == CLEARED_IN, f"staleness flags are cleared outside the functions that remake the copies: {cleared}"
+
+
+def _engine_source():
+    with open(os.path.join(CC.ROOT, "fedmlp_amd", "csrc", "engine.hip")) as f:
+        return f.read()
+
+
+def test_staleness_flags_are_raised_by_the_helpers_and_cleared_by_the_remakes():
+    """What the GPU matrix cannot reach (fm_fedavg_allreduce needs a communicator) is held against the source: a flag is assigned
+    `true` only inside net_changed / student_copies_stale, `false` only inside the function that remakes the copy it guards, and
+    the helpers are called by exactly the functions that move a state.  The check itself is shown to see a hand-set flag."""
+    text = _engine_source()
+    for flag in FLAGS:                           # each is a member with a default, and each is assigned somewhere
+        assert len(re.findall(r"\bbool %s = true;" % flag, text)) == 1, flag
+    for gone in ("wpack_dirty", "twb_dirty", "ensure_teacher_shadow", "SplitJobBM", "sp_off", "bm_off"):
+        assert gone not in text, gone
+    check_flag_sites(text)
+    fns = dict(_engine_functions(text))
+    assert len(fns) > 150 and set(RAISED_IN) | set(CLEARED_IN) | set().union(*SAYS_SO.values()) <= set(fns)
+    for helper, callers in SAYS_SO.items():
+        got = {fn for fn, body in fns.items() if re.search(r"\b%s\(" % helper, body)}
+        assert got == callers, (helper, sorted(got ^ callers))
+    # the negative control: one entry point setting a flag by hand, as fm_fedavg_allreduce did, must be seen
+    by_hand = text.replace("    net_changed(e, e->student);\n    if (!e->comm) return FM_OK;",
+                           "    e->student.ev_dirty = true; e->student.fwd_dirty = true;\n    if (!e->comm) return FM_OK;")
+    assert by_hand != text
+    try:
+        check_flag_sites(by_hand)
+    except AssertionError as err:
+        assert "fm_fedavg_allreduce" in str(err)
+    else:
+        raise AssertionError("a flag set by hand in fm_fedavg_allreduce went unnoticed")
 
 
 # ---- callers of mark_trained ---------------------------------------------------------------------------------------------------

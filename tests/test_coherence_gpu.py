@@ -77,7 +77,7 @@ def warm(e, ctx):
         CC.r_hooks(e, ctx)
     e.zero_grad()
     assert _state_eq(e.get_state(), ctx.S0), "warm moved the student's state"
-    # (the swap raises the shadows' flags of both nets: the forwards after it rebuild them for the same states)
+    # (a swap pair leaves each net's own copies valid and the student-only ones stale: the readers below rebuild those)
     assert _state_eq(_teacher_state(e), ctx.T0), "warm moved the teacher's state"
     CC.r_eval(e, ctx)
     CC.r_eval_teacher(e, ctx)
@@ -168,8 +168,8 @@ def test_cell(handle, mutator, reader):
     _dump()
 
 
-# The twin of test_cell has lived through the earlier cells: a copy it built lazily then (the stem's data-gradient matrix, whose
-# flag only ensure_packed raises) is rebuilt only if that flag chain works, so a chain broken everywhere would leave both handles
+# The twin of test_cell has lived through the earlier cells: a copy it built lazily then (the stem's data-gradient matrix, remade
+# at its first consumer only) is rebuilt only if its flag was raised, so a flag broken everywhere would leave both handles
 # stale alike.  A twin created inside the test has built nothing: the identity cells the matrix asks for, and three weight
 # changes against the two readers of that matrix (c: dx, e: the stem's data gradient).
 FRESH = [(h, "identity", r) for h in ("r18_64", "eff_64_bf16") for r in CC.READERS] + \
