@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 SRC   := $(wildcard fedmlp_amd/csrc/*.hip)
-HDR   := $(wildcard fedmlp_amd/csrc/*.h) include/fedmlp_hip.h include/fedmlp_hip_debug.h
+HDR   := $(wildcard fedmlp_amd/csrc/*.h) include/fedmlp_hip.h include/fedmlp_hip_debug.h include/fedmlp_hip_rofl.h
 OBJ   := $(patsubst fedmlp_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB   := fedmlp_amd/libfedmlp_hip.so
 

@@ -148,6 +148,12 @@ SYMBOLS = {
     "fm_debug_head": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
 }
 
+# the RoFL client's entry points: include/fedmlp_hip_rofl.h (a header and a table of their own, see there)
+ROFL_SYMBOLS = {
+    "fm_loss_rofl": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _F, C.c_float, C.c_float, _I32, _P, _P, _I64, _P, _P, _P]),
+    "fm_step_rofl": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, C.c_float, C.c_float, _I32, _P, _P, _I64, _P]),
+}
+
 _lib = None
 
 
@@ -164,7 +170,7 @@ def load():
     # (loading ours first leaves two runtimes and hipMalloc reports "no ROCm-capable device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(ROFL_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)    # AttributeError if the .so lacks a declared symbol
         except AttributeError:

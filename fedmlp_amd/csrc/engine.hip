@@ -26,6 +26,7 @@
 
 #include "../../include/fedmlp_hip.h"
 #include "../../include/fedmlp_hip_debug.h"
+#include "../../include/fedmlp_hip_rofl.h"
 #include "comm.h"
 #include "common.h"
 #include "kernels.h"
@@ -273,6 +274,10 @@ struct fm_engine {
     float* zeros = nullptr;
     int *sel_counts = nullptr, *sel_top = nullptr, *sel_bot = nullptr, *cls_dev = nullptr;
     int sel_cap = 0;
+    // fm_loss_rofl / fm_step_rofl workspaces for max_images rows, allocated at the first RoFL call (rofl_ws)
+    double *rofl_rowloss = nullptr, *rofl_dist = nullptr;
+    float* rofl_cos = nullptr;
+    int* rofl_keep = nullptr;
     int* tag_buf = nullptr;           // fm_select_topk_rows: [pool sizes ncls | counts 2 ncls | top ncls*cap | bot ncls*cap | rows ncls*stride]
     size_t tag_buf_ints = 0;
     // profiling
@@ -2661,6 +2666,36 @@ const char* cbafed_bad(const fm_engine* e, const float* am, int ann, int bs, con
         return step ? "fm_step_cbafed: stage 2 (tao given) needs counts_dev" : "fm_loss_cbafed: stage 2 (tao given) needs counts_dev";
     return rscfed_bad(e, am, ann, bs, B);
 }
+// fm_loss_rofl / fm_step_rofl: what the host can check of the caller's arguments
+const char* rofl_bad(const fm_engine* e, const void* feat, const void* item, const void* centroids, const void* pseudo, int B,
+                     int n_keep, int64_t N)
+{
+    if (!feat || !item || !centroids || !pseudo) return "null";
+    if (B < 1) return "B >= 1";
+    if (B > e->maxB) return "B exceeds max_images";
+    if (n_keep < 1) return "rofl: n_keep < 1 (int((1 - forget_rate) * B) of a batch this small keeps no row)";
+    if (n_keep > B) return "rofl: n_keep > B";
+    if (N < 1 || N * e->C > INT32_MAX) return "rofl: 1 <= N, N * n_classes < 2^31";
+    if (e->D % 4 || ((uintptr_t)feat | (uintptr_t)centroids) % 16) return "rofl: feature and centroid rows must be 16-byte aligned";
+    return nullptr;
+}
+// the RoFL workspaces, at the first call that needs them
+int rofl_ws(fm_engine* e)
+{
+    if (e->rofl_keep) return FM_OK;
+    DALLOC(e->rofl_rowloss, (size_t)e->maxB);
+    DALLOC(e->rofl_dist, (size_t)e->maxB * e->C);
+    DALLOC(e->rofl_cos, (size_t)e->maxB * 2 * e->C);
+    DALLOC(e->rofl_keep, (size_t)e->maxB);
+    return FM_OK;
+}
+void launch_rofl(fm_engine* e, const float* z, const float* feat, const float* y, const int32_t* item, int B, int n_keep,
+                 const float* pw, float lambda_cen, float lambda_e, int write_labels, float* centroids, uint8_t* pseudo, int64_t N,
+                 float* dz, float* loss, int32_t* keep)
+{
+    k_loss_rofl(z, feat, y, item, B, e->C, e->D, n_keep, to_cv(pw, e->C), lambda_cen, lambda_e, write_labels, centroids, pseudo,
+                (int)N, e->rofl_rowloss, e->rofl_cos, e->rofl_dist, e->rofl_keep, keep, dz, loss, e->main.st);
+}
 
 void launch_fedlsr(fm_engine* e, const float* z, const float* y, const float* pw, float mix1, float beta, int B, float* dz, float* loss)
 {
@@ -3220,6 +3255,33 @@ int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t
                       cbafed_bad(e, active_mask_host, annotation_num, bs_norm, tao_host, counts_dev, B, true), [&] {
         launch_cbafed(e, e->logits, y_dev, active_mask_host, annotation_num, bs_norm, tao_host, B, pos_weight_dev, counts_dev,
                       e->dlogits, loss_dev);
+    });
+}
+
+// ---- RoFL: the head on caller tensors, and its fused step (the head reads the train forward's pooled feature) ----
+int fm_loss_rofl(fm_engine* e, const float* z_dev, const float* feat_dev, const float* y_dev, const int32_t* item_dev, int32_t B,
+                 int32_t n_keep, const float* pos_weight_host, float lambda_cen_eff, float lambda_e, int32_t write_labels,
+                 float* centroids_dev, uint8_t* pseudo_dev, int64_t N, float* dz_dev, float* loss_dev, int32_t* keep_dev)
+{
+    ARGCHK(e && z_dev && y_dev && pos_weight_host && dz_dev && loss_dev, "null");
+    BADCHK(rofl_bad(e, feat_dev, item_dev, centroids_dev, pseudo_dev, B, n_keep, N));
+    RCCHK(rofl_ws(e));
+    launch_rofl(e, z_dev, feat_dev, y_dev, item_dev, B, n_keep, pos_weight_host, lambda_cen_eff, lambda_e, write_labels,
+                centroids_dev, pseudo_dev, N, dz_dev, loss_dev, keep_dev);
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_step_rofl(fm_engine* e, const float* x_dev, const float* y_dev, const int32_t* item_dev, int32_t B, int32_t n_keep,
+                 const float* pos_weight_host, float lambda_cen_eff, float lambda_e, int32_t write_labels, float* centroids_dev,
+                 uint8_t* pseudo_dev, int64_t N, float* loss_dev)
+{
+    ARGCHK(e && x_dev && y_dev && pos_weight_host && loss_dev, "null");
+    const char* bad = rofl_bad(e, e->feat, item_dev, centroids_dev, pseudo_dev, B, n_keep, N);
+    if (!bad && e->trainable.empty()) RCCHK(rofl_ws(e));          // a refused call allocates nothing
+    return fused_step(e, StepFwd::Student, x_dev, nullptr, B, bad, [&] {
+        launch_rofl(e, e->logits, e->feat, y_dev, item_dev, B, n_keep, pos_weight_host, lambda_cen_eff, lambda_e, write_labels,
+                    centroids_dev, pseudo_dev, N, e->dlogits, loss_dev, nullptr);
     });
 }
 

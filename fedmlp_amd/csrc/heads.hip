@@ -12,6 +12,7 @@
 //   RSCFed BCE(active) + probability MSE to the EMA teacher           (:719, 740-743)
 //   FedNoRo LA_KD: BCE-on-probabilities + MSE to sigmoid(teacher/0.8) (utils/FedNoRo.py:35-38, :143-151)
 //   CBAFed warm-up / stage-2 pseudo-labels, loss_w and counts         (:247-269, 303-333)
+//   RoFL small-loss selection, centroid vote, RFLloss, centroid blend (:524-572, 582-626)
 //   prototype masked sums + confident-count t                         (:985-994, 1229-1238)
 //   CosineSimilarityFast difference                                   (:1417-1435, 1056-1057)
 //   stable top-k / bottom-k                                           (utils/utils.py:24-35)
@@ -691,6 +692,174 @@ void k_loss_cbafed(const float* z, const float* y, ClassVec active, const ClassV
     else
         hipLaunchKernelGGL(loss_cbafed_kernel<false>, dim3(1), dim3(256), 0, s, z, y, active, ClassVec{}, B, C, sup_norm,
                            annotation_num, pos_weight, reinterpret_cast<long long*>(counts), dz, loss);
+}
+
+// ------------------------------------------------------------ RoFL head ---------
+// train_RoFL's batch (utils/local_training.py:524-572, 582-626) in three launches on one stream: no host read, no atomics, the
+// same bits from run to run.  z, y [B][C], feat [B][D] (the train forward's pooled feature, a constant of the loss),
+// fk [2C][D] the client's centroids (row 2c + t: class c, label value t), D a multiple of 4.
+//   rofl_rows_kernel      one wave per row: the row's small-loss key sum_c BCEWithLogits(pos_weight)(z, y) in double, the
+//                         cosines of the row's feature with every centroid (fp32, lane-strided then a fixed butterfly: they
+//                         only decide the vote), and per class the squared distance to the centroid of the row's own label
+//                         (double: it is part of the loss value)
+//   rofl_select_kernel    one block: rank by counting (ties to the lower row, NaN keys last), keep the n_keep smallest; the
+//                         vote, the mask, the label table, the loss and dz (double, rounded once; exact 0 off the kept rows)
+//   rofl_centroid_kernel  one block per centroid row: the kept rows' feature mean in row order, s = cos(fk, mean) and the blend
+//                         fk <- (1 - s^2) fk + s^2 mean, in double, rounded once -- launched last: the loss reads the old fk.
+// Cosine is a.b / (|a| |b|), and exactly 0 when a norm is 0.
+__global__ void rofl_rows_kernel(const float* __restrict__ z, const float* __restrict__ y, const float* __restrict__ feat,
+                                 const float* __restrict__ fk, ClassVec pw, int B, int C, int D, double* __restrict__ rowloss,
+                                 float* __restrict__ cosv, double* __restrict__ dist)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;                                     // wave-uniform
+    double l = 0.0;
+    if (lane < C) {
+        l = bce_logits_d(z[(size_t)i * C + lane], y[(size_t)i * C + lane], pw.v[lane]);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d);
+    if (lane == 0) rowloss[i] = l;
+    const float4* f = reinterpret_cast<const float4*>(feat + (size_t)i * D);
+    const int D4 = D >> 2;
+    float ff = 0.f;
+    for (int d = lane; d < D4; d += 64) {
+        const float4 x = f[d];
+        ff += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
+    }
+    const float fn = sqrtf(wave_sum(ff));
+    for (int c = 0; c < C; ++c) {
+        const float4* p0 = reinterpret_cast<const float4*>(fk + (size_t)(2 * c) * D);
+        const float4* p1 = p0 + D4;
+        const bool one = y[(size_t)i * C + c] != 0.f;
+        float d0 = 0.f, d1 = 0.f, n0 = 0.f, n1 = 0.f;
+        double dd = 0.0;
+        for (int d = lane; d < D4; d += 64) {
+            const float4 x = f[d], a = p0[d], b = p1[d];
+            d0 += (x.x * a.x + x.y * a.y) + (x.z * a.z + x.w * a.w);
+            d1 += (x.x * b.x + x.y * b.y) + (x.z * b.z + x.w * b.w);
+            n0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+            n1 += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
+            const float4 t = one ? b : a;
+            const double e0 = (double)x.x - (double)t.x, e1 = (double)x.y - (double)t.y, e2 = (double)x.z - (double)t.z,
+                         e3 = (double)x.w - (double)t.w;
+            dd += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
+        }
+        d0 = wave_sum(d0); d1 = wave_sum(d1);
+        n0 = sqrtf(wave_sum(n0)); n1 = sqrtf(wave_sum(n1));
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) dd += __shfl_xor(dd, d);
+        if (lane == 0) {
+            cosv[(size_t)i * 2 * C + 2 * c] = (fn == 0.f || n0 == 0.f) ? 0.f : d0 / (fn * n0);
+            cosv[(size_t)i * 2 * C + 2 * c + 1] = (fn == 0.f || n1 == 0.f) ? 0.f : d1 / (fn * n1);
+            dist[(size_t)i * C + c] = dd;
+        }
+    }
+}
+
+// key order of the small-loss selection: ascending, NaN last, ties to the lower row
+__device__ __forceinline__ bool rofl_before(double a, int ia, double b, int ib)
+{
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return an == bn ? ia < ib : bn;
+    return a < b || (a == b && ia < ib);
+}
+
+// keepw [B]: bit 0 kept, bit 1 mask (the workspace rofl_centroid_kernel reads; keep_out, may be null, gets a copy).
+// pseudo uint8 [N][C]: rows item[i] of the kept rows are read and, with write_labels, written.  The items of one batch are
+// distinct (a loader without replacement), so each thread owns its rows' table entries; an item outside [0, N) is never
+// dereferenced (the row then stands on its own label).
+__global__ void rofl_select_kernel(const float* __restrict__ z, const float* __restrict__ y, const int* __restrict__ item,
+                                   const double* __restrict__ rowloss, const float* __restrict__ cosv,
+                                   const double* __restrict__ dist, ClassVec pw, int B, int C, int D, int n_keep, int N,
+                                   double lam_cen, double lam_e, int write_labels, unsigned char* __restrict__ pseudo,
+                                   int* __restrict__ keepw, int* __restrict__ keep_out, float* __restrict__ dz,
+                                   float* __restrict__ loss)
+{
+    __shared__ double shd[4];
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const double li = rowloss[i];
+        int rank = 0;
+        for (int j = 0; j < B; ++j) rank += rofl_before(rowloss[j], j, li, i);
+        int flags = 0;
+        if (rank < n_keep) {
+            bool agree = true;
+            for (int c = 0; c < C; ++c) {
+                const float vote = cosv[(size_t)i * 2 * C + 2 * c + 1] > cosv[(size_t)i * 2 * C + 2 * c] ? 1.f : 0.f;
+                agree = agree && vote == y[(size_t)i * C + c];
+            }
+            flags = 1 | (agree ? 2 : 0);
+            const int it = item[i];
+            if (write_labels && it >= 0 && it < N)
+                for (int c = 0; c < C; ++c) pseudo[(size_t)it * C + c] = y[(size_t)i * C + c] != 0.f ? 1 : 0;
+        }
+        keepw[i] = flags;
+        if (keep_out) keep_out[i] = flags;
+    }
+    __syncthreads();                                        // keepw and the table rows written above are visible to the block
+    const double nk = (double)n_keep, inv = 1.0 / (nk * (double)C);
+    double lc = 0.0, le = 0.0, cen = 0.0;
+    for (int e = threadIdx.x; e < B * C; e += 256) {
+        const int i = e / C, c = e % C;
+        const int flags = keepw[i];
+        double g = 0.0;
+        if (flags & 1) {
+            const int it = item[i];
+            float lab = y[e];
+            if (!(flags & 2) && it >= 0 && it < N) lab = (float)pseudo[(size_t)it * C + c];
+            const double zz = z[e], p = sigmoid_d(zz), q = sigmoid_d(-zz);
+            lc += bce_logits_dd(zz, lab, pw.v[c], &g);
+            le += (log1p(exp(-fabs(zz))) + fmax(zz, 0.0)) - zz * p;          // H = softplus(z) - z p, finite everywhere
+            g = (g - lam_e * zz * p * q) * inv;
+            if (flags & 2) cen += dist[e];
+        }
+        dz[e] = (float)g;
+    }
+    const double t1 = block_sum_d(lc, shd);
+    const double t2 = block_sum_d(le, shd);
+    const double t3 = block_sum_d(cen, shd);
+    if (threadIdx.x == 0) *loss = (float)(t1 * inv + lam_cen * (t3 / (nk * (double)D) / (double)C) + lam_e * (t2 * inv));
+}
+
+__global__ void rofl_centroid_kernel(const float* __restrict__ y, const float* __restrict__ feat, const int* __restrict__ keepw,
+                                     int B, int C, int D, float* __restrict__ fk)
+{
+    extern __shared__ double rofl_mean[];                   // [D]
+    __shared__ double shd[4];
+    const int r = blockIdx.x, c = r >> 1;
+    const float want = (float)(r & 1);
+    int n = 0;
+    for (int i = 0; i < B; ++i) n += (keepw[i] & 1) && y[(size_t)i * C + c] == want;        // block-uniform
+    const double den = n ? (double)n : 1.0;
+    float* row = fk + (size_t)r * D;
+    double ab = 0.0, aa = 0.0, bb = 0.0;
+    for (int d = threadIdx.x; d < D; d += 256) {
+        double s = 0.0;
+        for (int i = 0; i < B; ++i)
+            if ((keepw[i] & 1) && y[(size_t)i * C + c] == want) s += (double)feat[(size_t)i * D + d];
+        const double m = s / den, a = row[d];
+        rofl_mean[d] = m;
+        ab += a * m; aa += a * a; bb += m * m;
+    }
+    ab = block_sum_d(ab, shd);
+    aa = block_sum_d(aa, shd);
+    bb = block_sum_d(bb, shd);
+    const double s = (aa == 0.0 || bb == 0.0) ? 0.0 : ab / (sqrt(aa) * sqrt(bb)), s2 = s * s;
+    for (int d = threadIdx.x; d < D; d += 256) row[d] = (float)((1.0 - s2) * (double)row[d] + s2 * rofl_mean[d]);
+}
+
+void k_loss_rofl(const float* z, const float* feat, const float* y, const int* item, int B, int C, int D, int n_keep,
+                 ClassVec pos_w, float lambda_cen, float lambda_e, int write_labels, float* centroids, unsigned char* pseudo,
+                 int N, double* ws_rowloss, float* ws_cos, double* ws_dist, int* ws_keep, int* keep_out, float* dz, float* loss,
+                 hipStream_t s)
+{
+    hipLaunchKernelGGL(rofl_rows_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, z, y, feat, centroids, pos_w, B, C, D, ws_rowloss,
+                       ws_cos, ws_dist);
+    hipLaunchKernelGGL(rofl_select_kernel, dim3(1), dim3(256), 0, s, z, y, item, ws_rowloss, ws_cos, ws_dist, pos_w, B, C, D,
+                       n_keep, N, (double)lambda_cen, (double)lambda_e, write_labels, pseudo, ws_keep, keep_out, dz, loss);
+    hipLaunchKernelGGL(rofl_centroid_kernel, dim3(2 * C), dim3(256), (size_t)D * sizeof(double), s, y, feat, ws_keep, B, C, D,
+                       centroids);
 }
 
 // ------------------------------------------------------------ prototypes -------

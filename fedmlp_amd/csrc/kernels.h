@@ -261,6 +261,13 @@ void k_loss_lakd(const float* z, const float* zt, const float* y, ClassVec activ
                  float* loss, hipStream_t s);
 void k_loss_cbafed(const float* z, const float* y, ClassVec active, const ClassVec* tao, int B, int C, float sup_norm,
                    int annotation_num, float* pos_weight, int64_t* counts, float* dz, float* loss, hipStream_t s);
+// RoFL head (three launches): z, y, dz [B][C], feat [B][D] (D % 4 == 0, 16-byte aligned rows), item int32 [B], centroids [2C][D]
+// read by the loss and THEN updated, pseudo uint8 [N][C]; workspaces rowloss double [B], cos float [B][2C], dist double [B][C],
+// keep int [B] (bit 0 kept, bit 1 mask; keep_out, may be null, gets a copy).  B >= n_keep >= 1.
+void k_loss_rofl(const float* z, const float* feat, const float* y, const int* item, int B, int C, int D, int n_keep,
+                 ClassVec pos_w, float lambda_cen, float lambda_e, int write_labels, float* centroids, unsigned char* pseudo,
+                 int N, double* ws_rowloss, float* ws_cos, double* ws_dist, int* ws_keep, int* keep_out, float* dz, float* loss,
+                 hipStream_t s);
 
 // ---- split-K slabs ---------------------------------------------------------------
 void k_reduce_slabs(const float* slab, float* out, int splits, int64_t n, hipStream_t s);

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 
-def args_parser(argv=None):
+def build_parser():
+    """the driver's flags, before any are parsed (fedmlp_amd/driver_rofl.py starts from the same parser)"""
     p = argparse.ArgumentParser()      # flag names/defaults follow utils/options.py:4-81
     p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch", "FedLSR", "FedIRM", "RSCFed", "FedNoRo",
                                                       "CBAFed"])
@@ -42,6 +43,10 @@ def args_parser(argv=None):
     p.add_argument("--end", type=int, default=499)                # utils/options.py:76
     p.add_argument("--a", type=float, default=0.8)                # utils/options.py:77
     p.add_argument("--rounds_CBAFed_warmup", type=int, default=50)    # utils/options.py:79
+    p.add_argument("--forget_rate", type=float, default=0.2)      # utils/options.py:53 (RoFL; constant: main.py's schedule is applied nowhere)
+    p.add_argument("--T_pl", type=int, default=100)               # utils/options.py:55 (RoFL: rounds before the global-guided pseudo labels)
+    p.add_argument("--lambda_cen", type=float, default=1.0)       # utils/options.py:56
+    p.add_argument("--lambda_e", type=float, default=0.8)         # utils/options.py:57
     p.add_argument("--U", type=float, default=0.7)
     p.add_argument("--L", type=float, default=0.3)
     p.add_argument("--clean_threshold", type=float, default=0.005)
@@ -66,6 +71,11 @@ def args_parser(argv=None):
                    help="globaltest of the new global model every K rounds (main.py:322-357 uses 10), the forward dealt over "
                         "the ranks and the metrics from fm_eval_metrics; 0 = never")
     p.add_argument("--n_test", type=int, default=1024, help="samples of the synthetic test set (--eval_every)")
+    return p
+
+
+def args_parser(argv=None):
+    p = build_parser()
     args = p.parse_args(argv)
     if args.exp == "RSCFed" and args.n_clients < RSCFED_K:
         p.error(f"--exp RSCFed draws groups of {RSCFED_K} clients (main.py:116-119): --n_clients must be >= {RSCFED_K}")
@@ -225,12 +235,14 @@ class RoundAccumulator:
         return cnt, tao, proto
 
 
-def main():
-    args = args_parser()
+def main(args=None, module="fedmlp_amd.driver"):
+    """args: a parsed namespace (default: args_parser() of the command line); module: what a multi-GPU run starts per rank"""
+    if args is None:
+        args = args_parser()
     from fedmlp_amd.launch import launched_by_torchrun, spawn_ranks
     if args.gpus > 1 and not launched_by_torchrun():
         import sys
-        sys.exit(spawn_ranks("fedmlp_amd.driver", sys.argv[1:], args.gpus, module=True))
+        sys.exit(spawn_ranks(module, sys.argv[1:], args.gpus, module=True))
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local_rank)
@@ -295,6 +307,8 @@ def main():
     WC = args.rounds_CBAFed_warmup
     cba_pt = cba_tao = None                              # CBAFed: pt and tao of main.py:289-300
     cba_res = cba_res_cnt = None                         # CBAFed: the last blended model (w_glob_res) and its float counters
+    # RoFL: the global centroids (main.py:99) from a CPU generator seeded without the rank offset: the same f_G on every rank
+    f_G = torch.randn((2 * C, args.feature_dim), generator=torch.Generator().manual_seed(args.seed))
     for rnd in range(args.rounds_warmup):
         t0 = time.perf_counter()
         cba2 = args.exp == "CBAFed" and rnd >= WC        # stage 2: FedAvg weights data_num_c / sum(data_num), main.py:302
@@ -310,6 +324,7 @@ def main():
         rsc_states, rsc_cnt = {}, {}                      # RSCFed: client -> device state / counters
         cba_counts = {}                                   # CBAFed: client -> (class_num_list, data_num)
         relas = {}                                        # FedIRM: client -> its relation matrix (host), main.py:192-193
+        f_locals = {}                                     # RoFL: client -> its centroids f_k (host)
         for c in mine:
             loc = clients[c]
             eng.state_tensor().copy_(glob)                # net = deepcopy(netglob)  (main.py:181-184)
@@ -328,6 +343,9 @@ def main():
             elif args.exp == "CBAFed":                    # main.py:149-157
                 ret = loc.train_CBAFed(rnd, net) if rnd < WC else loc.train_CBAFed(rnd, net, pt=cba_pt, tao=cba_tao)
                 cba_counts[c] = (ret[6].clone(), int(ret[7]))
+            elif args.exp == "RoFL":                      # main.py:167-168
+                ret = loc.train_RoFL(net, f_G, rnd)
+                f_locals[c] = ret[2]
             elif args.exp == "FedIRM":                    # main.py:169-177
                 if rnd < SI - 1:
                     ret = loc.train_FedIRM(rnd, Prototype, None, None, None, net=net)
@@ -374,6 +392,13 @@ def main():
                 if rnd >= WC - 1:                                     # main.py:289-300
                     order = range(args.n_clients)
                     cba_pt, cba_tao = cbafed_tao([cba_counts[c][0] for c in order], [cba_counts[c][1] for c in order])
+            if args.exp == "RoFL":                        # main.py:253-268: FedAvg above, then the centroids' cosine-weighted fold
+                from fedmlp_amd import fedavg
+                if dist is not None:                      # 2C x D floats per client: gathered as objects, folded on every rank alike
+                    parts = [None] * world
+                    dist.all_gather_object(parts, f_locals)
+                    f_locals = {k: v for part in parts for k, v in part.items()}
+                f_G = fedavg.rofl_centroids(f_G, [f_locals[c] for c in range(args.n_clients)])
         glob.copy_(eng.state_tensor())
         if tao_new is not None:
             tao, Prototype = tao_new, proto_new

@@ -29,7 +29,47 @@ def _cargs(args):
     return [_ptr(a) if torch.is_tensor(a) else a for a in args]
 
 
-class Engine:
+class RoflHeads:
+    """The RoFL client's wrappers (include/fedmlp_hip_rofl.h), a base of Engine.  They go through Engine._step / Engine._head
+    like every fused step and head, so a step bumps serial and weights_version and a head bumps serial."""
+
+    def _rofl_args(self, item, B, centroids, pseudo):
+        """-> (item, centroids, pseudo, N) as the C arguments.  centroids None passes a null pointer (the library refuses it)"""
+        n, D = self.n_classes, self.feature_dim
+        if tuple(item.shape) != (B,) or item.dtype != torch.int32 or not item.is_contiguous() or not item.is_cuda:
+            raise ValueError(f"rofl: item must be a contiguous int32 [{B}] device tensor")
+        if centroids is not None and (tuple(centroids.shape) != (2 * n, D) or centroids.dtype != torch.float32
+                                      or not centroids.is_contiguous() or not centroids.is_cuda):
+            raise ValueError(f"rofl: centroids must be a contiguous float32 [{2 * n}, {D}] device tensor")
+        if pseudo.dim() != 2 or pseudo.shape[1] != n or pseudo.dtype != torch.uint8 or not pseudo.is_contiguous() \
+                or not pseudo.is_cuda:
+            raise ValueError(f"rofl: pseudo must be a contiguous uint8 [N, {n}] device tensor")
+        return item, centroids, C.c_void_p(pseudo.data_ptr()), C.c_int64(pseudo.shape[0])
+
+    def step_rofl(self, x, y, item, n_keep, pos_weight, lambda_cen_eff, lambda_e, write_labels, centroids, pseudo, loss_out):
+        """train_RoFL's step (utils/local_training.py:516-574) fused: train forward, loss_rofl's head on the engine's logits and
+        pooled feature, backward, Adam.  centroids [2C,D] float32 and pseudo [N,C] uint8 are DEVICE tensors of the caller's (the
+        client's f_k and the round's pseudo-label table): the step reads and updates both, with no host read"""
+        it, ce, ps, N = self._rofl_args(item, x.shape[0], centroids, pseudo)
+        self._step(self.lib.fm_step_rofl, x.shape[0], x, y, it, x.shape[0], int(n_keep), _lib.fvec(pos_weight, self.n_classes),
+                   C.c_float(lambda_cen_eff), C.c_float(lambda_e), int(bool(write_labels)), ce, ps, N, loss_out)
+
+    def loss_rofl(self, z, feat, y, item, n_keep, pos_weight, lambda_cen_eff, lambda_e, write_labels, centroids, pseudo,
+                  keep=None):
+        """RoFL's head on caller tensors: z, y [B,C], feat [B,D] (forward_train's feature), item int32 [B]; see step_rofl.
+        keep (optional int32 [B] device tensor) receives bit 0 = kept, bit 1 = mask"""
+        B = y.shape[0]
+        if tuple(feat.shape) != (B, self.feature_dim) or feat.dtype != torch.float32 or not feat.is_contiguous():
+            raise ValueError(f"loss_rofl: feat must be a contiguous float32 [{B}, {self.feature_dim}] tensor")
+        if keep is not None and (tuple(keep.shape) != (B,) or keep.dtype != torch.int32 or not keep.is_contiguous()):
+            raise ValueError(f"loss_rofl: keep must be a contiguous int32 [{B}] tensor")
+        it, ce, ps, N = self._rofl_args(item, B, centroids, pseudo)
+        return self._head(self.lib.fm_loss_rofl, 1, z, y, None, z, feat, y, it, B, int(n_keep),
+                          _lib.fvec(pos_weight, self.n_classes), C.c_float(lambda_cen_eff), C.c_float(lambda_e),
+                          int(bool(write_labels)), ce, ps, N, tail=(keep,))
+
+
+class Engine(RoflHeads):
     """One per process/GPU. Owns the device-resident model state, optimiser
     moments, teacher snapshot and activation workspaces for `max_images`."""
 
@@ -359,8 +399,9 @@ class Engine:
 
     # ---- the loss heads alone, on caller logits: two-view z [2B,C] (forward_train's layout; FedLSR, FedIRM) or single-view
     # z [B,C] (RSCFed, FedNoRo, CBAFed) -> (dz like z, loss [1]) ----------------------------------------------------------
-    def _head(self, fn, views, z, y, zt, *args):
-        """fn is the caller's own self.lib.fm_loss_*; its C arguments are args (tensors as they are), then dz and loss"""
+    def _head(self, fn, views, z, y, zt, *args, tail=()):
+        """fn is the caller's own self.lib.fm_loss_*; its C arguments are args (tensors as they are), then dz and loss (then
+        tail, for a head with outputs behind them)"""
         self._check_stream()
         self._enqueue()
         B, n = y.shape[0], self.n_classes
@@ -374,7 +415,7 @@ class Engine:
         if not plain:
             raise ValueError("two-view head: contiguous float32 tensors are required")
         dz, loss = torch.empty_like(z), torch.empty(1, device=z.device, dtype=torch.float32)
-        _lib.check(fn(self.h, *_cargs(args), _ptr(dz), _ptr(loss)))
+        _lib.check(fn(self.h, *_cargs(args), _ptr(dz), _ptr(loss), *_cargs(tail)))
         return dz, loss
 
     def _rel_arg(self, t, what):

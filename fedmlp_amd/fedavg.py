@@ -402,6 +402,23 @@ def cbafed_blend(rnd, warmup):
     return w, 1.0 - w, True
 
 
+# ---- RoFL's server step (main.py:98-99, 253-268) ----------------------------------------
+def rofl_centroids(f_G, f_locals):
+    """The global centroids after a round: per row r, w_i = cos(f_G[r], f_k_i[r]) (torch's CosineSimilarity), then
+    f_G[r] <- sum_i w_i f_k_i[r] / sum_i w_i, a zero weight sum dividing by 1.  The weights may be negative, as in the
+    reference.  fp32 torch tensors [2C, D] on one device; f_G is not modified."""
+    sim = torch.nn.CosineSimilarity(dim=1)
+    f_G = torch.as_tensor(f_G, dtype=torch.float32)
+    tmp = torch.zeros_like(f_G)
+    w_sum = torch.zeros((f_G.shape[0], 1), dtype=torch.float32, device=f_G.device)
+    for f in f_locals:
+        f = torch.as_tensor(f, dtype=torch.float32).to(f_G.device)
+        w = sim(f_G, f).reshape(-1, 1)
+        w_sum = w_sum + w
+        tmp = tmp + w * f
+    return tmp / torch.where(w_sum == 0, torch.ones_like(w_sum), w_sum)
+
+
 def consistency_weight(rnd, begin, end):
     """get_current_consistency_weight(rnd, args.begin, args.end) (utils/FedNoRo.py:72-81): the
     sigmoid ramp-up main.py:127-128 multiplies by args.a to get train_FedNoRo's weight_kd."""

@@ -1,7 +1,7 @@
 """LocalUpdate drop-in: the reference's per-client trainer surface
 (utils/local_training.py:26-55 ctor, :628-703 train, :771-825 train_FixMatch,
 :904-1256 train_FedMLP, :1270-1326 train_FedLSR, :344-464 train_FedIRM, :705-769 train_RSCFed, :115-234 train_FedNoRo,
-:236-342 train_CBAFed) driven through the HIP engine.
+:236-342 train_CBAFed, :466-626 train_RoFL) driven through the HIP engine.
 
 Same constructor and method signatures, same return tuples (positions 3-4 are
 the reference's junk `_` placeholders -> None), same persistent per-client
@@ -154,13 +154,16 @@ class LocalUpdate(object):
         return [1.0 if c in classes else 0.0 for c in range(self.args.n_classes)]
 
     # ---- what every trainer shares ---------------------------------------------------------------------
-    def _epochs(self, eng, epoch_loss):
+    def _epochs(self, eng, epoch_loss, skip=None):
         """local_ep shuffled passes over the local set.  Yields one epoch at a time as its [(pos, loss slot)] batches: the
         caller runs its step on each, writing the step's loss into the slot.  The slots are slices of one device buffer per
-        epoch, read once when the epoch is over: its float64 mean is appended to epoch_loss."""
+        epoch, read once when the epoch is over: its float64 mean is appended to epoch_loss.  skip(pos) true: the batch is
+        left out of the epoch (no step, no slot)."""
         a = self.args
         for _ in range(a.local_ep):
             batches = _batches(self._order(len(self.idxs)), a.batch_size)
+            if skip is not None:
+                batches = [pos for pos in batches if not skip(pos)]
             losses = torch.zeros(len(batches), device=eng.device)
             yield [(pos, losses[k:k + 1]) for k, pos in enumerate(batches)]
             self.epoch += 1
@@ -384,6 +387,52 @@ class LocalUpdate(object):
             data_num = int(back[2 * C])
         net.mark_trained()
         return self._result(net, epoch_loss) + (class_num_list, data_num)
+
+    # ---- LocalUpdate.train_RoFL (:466-626) -----------------------------------------------------------------
+    def train_RoFL(self, net, f_G, epoch):
+        """-> (state_dict, mean loss, f_k [2C, D] on the CPU).  epoch is the round number.  The pseudo-label table of the round
+        and the client's centroids f_k live on the device; a step makes no host read.  One deviation: a batch so small that
+        int((1 - forget_rate) * len(batch)) is 0 (a tail of 1 at the default 0.2) is skipped and counted in neither the loss
+        mean nor iter_num -- the reference takes the mean of an empty tensor there and writes NaN into every weight."""
+        a = self.args
+        C = a.n_classes
+        eng = self._bind(net, "image")
+        n = len(self.idxs)
+        y = self._labels_dev(eng, self._y_masked, "y_masked")
+        # (A) eval-mode pass over the shuffled local loader (:473-510): the global-guided pseudo labels of every local sample
+        # and, in round 0, the label-wise mean features of EVERY class as the first centroids (a zero count divides by 1)
+        pseudo = torch.empty((n, C), dtype=torch.uint8, device=eng.device)
+        ones, zeros = [1.0] * C, [0.0] * C
+        if epoch == 0:
+            eng.proto_reset()
+        for pos in _batches(self._order(n), a.batch_size):
+            f, z = eng.forward_eval(self._images(eng, "image", pos))
+            pseudo[torch.as_tensor(pos, device=eng.device, dtype=torch.long)] = (torch.sigmoid(z) > 0.5).to(torch.uint8)
+            if epoch == 0:
+                eng.proto_accumulate(f, z, self._rows(y, pos, eng), ones, zeros, 0.0, 1.0)
+        if epoch == 0:
+            f_k = torch.from_numpy(eng.proto_finalize(True, n, ones)[1]).to(eng.device)
+        else:
+            f_k = torch.as_tensor(f_G, dtype=torch.float32).to(eng.device).clone()
+        f_k = f_k.contiguous()
+        # (B) :514-577
+        for c in self.negative_class_list:                          # get_small_loss_samples :616-618: persists on the client
+            self.loss_w[c] = 5.0
+        eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        write_labels = epoch < a.T_pl
+        lam_cen = (a.lambda_cen * epoch) / a.T_pl if write_labels else a.lambda_cen        # RFLloss :605-606
+
+        def n_keep(pos):
+            return int((1 - a.forget_rate) * len(pos))              # :623-624, Python double arithmetic
+        epoch_loss = []
+        for batches in self._epochs(eng, epoch_loss, skip=lambda pos: n_keep(pos) < 1):
+            for pos, loss in batches:
+                item = torch.as_tensor(pos, device=eng.device, dtype=torch.int32)
+                eng.step_rofl(self._images(eng, "image", pos), self._rows(y, pos, eng), item, n_keep(pos), self.loss_w,
+                              lam_cen, a.lambda_e, write_labels, f_k, pseudo, loss)
+                self.iter_num += 1
+        net.mark_trained()
+        return self._sd(net), np.array(epoch_loss).mean(), f_k.cpu()
 
     # ---- prototype + t pass (:971-1002 unguarded, :1208-1250 zero-guarded) ----------------------------
     def _proto_pass(self, eng, negative_list, zero_guard):

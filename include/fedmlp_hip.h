@@ -291,6 +291,8 @@ int fm_step_cbafed(fm_engine* e, const float* x_dev, const float* y_dev, int32_t
                    int32_t annotation_num, int32_t bs_norm, const float* tao_host, float* pos_weight_dev, int64_t* counts_dev,
                    float* loss_dev);
 
+/* The RoFL client's head and fused step: include/fedmlp_hip_rofl.h. */
+
 /* ---- prototype + t pass (utils/local_training.py:971-1002, 1208-1250) ---- */
 /* Accumulators live in the engine: proto sums [2C,D], counts [2C], t counts [C]. */
 int fm_proto_reset(fm_engine* e);
