@@ -142,6 +142,9 @@ SYMBOLS = {
     "fm_debug_activation": (C.c_int, [_P, _I32, _I32, _I32, _P, C.POINTER(_I32)]),
     "fm_debug_stem_masks": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "fm_debug_lose_part": (C.c_int, [_I32]),
+    "fm_debug_lane_delay": (C.c_int, [_P, _I32, _I64, _I32]),
+    "fm_debug_lane_points": (C.c_int, [_P, C.POINTER(_I64), _I32]),
+    "fm_debug_drop_wait": (C.c_int, [_P, _I32, _I32]),
     "fm_debug_ew": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
     "fm_debug_eff": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _F]),
     "fm_debug_eff_ws": (C.c_int, [_I32, C.POINTER(_I32), C.POINTER(C.c_int64)]),

@@ -989,3 +989,19 @@ void k_reduce_slabs(const float* slab, float* out, int splits, int64_t n, hipStr
     const int64_t n4 = n / 4;
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3(cdiv(n4, 64)), dim3(1024), 0, s, slab, out, splits, n4);
 }
+
+// Lane-delay test hook (fm_debug_lane_delay): one workgroup of one wave holds its stream for `ticks` of the constant-rate wall
+// clock.  It touches no memory.  Bounded twice: by the clock, and by `cap` iterations of a sleep of 32 * 64 cycles each (>= 0.8 us
+// at any core clock of the part), so that a clock that does not advance still ends it.
+__global__ void __launch_bounds__(64) lane_delay_kernel(long long ticks, int cap)
+{
+    const long long t0 = wall_clock64();
+    for (int i = 0; i < cap; ++i) {
+        if (wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(32);
+    }
+}
+void k_lane_delay(int64_t ticks, int cap, hipStream_t s)
+{
+    hipLaunchKernelGGL(lane_delay_kernel, dim3(1), dim3(64), 0, s, (long long)ticks, cap);
+}

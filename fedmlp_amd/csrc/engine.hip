@@ -348,7 +348,31 @@ struct fm_engine {
     hipEvent_t ev_p[4][2] = {}, ev_c[4][2] = {}, ev_wdone = nullptr;    // [tensor: d y_p, d y_d, d y_e, SE vectors][block parity]
     float *se_dgp2 = nullptr, *se_drp2 = nullptr;
     float* stem_col = nullptr;        // bf16 mode: [images][hout][wout][k][4][4] bf16 im2col of the input (the stem's X operand)
+    // Lane-order test hooks (fm_debug_lane_delay, fm_debug_drop_wait; fedmlp_hip_debug.h).  armed: the delay points count and the
+    // `at`-th one of `lane` enqueues the delay kernel once; drop: bit k skips the cross-lane wait of kind k (lane_wait)
+    struct LaneDbg {
+        bool armed = false, fired = false;
+        int lane = 0, micros = 0;
+        int64_t at = 0, ticks = 0;
+        int64_t points[2] = {0, 0};
+        uint32_t drop = 0;
+        int64_t waits[FM_WAIT_KINDS] = {}, skipped[FM_WAIT_KINDS] = {};
+    } ldbg;
 };
+// a delay point of lane 0 (main) / 1 (side): see fm_debug_lane_delay
+static void lane_point_armed(fm_engine* e, int lane);
+static inline void lane_point(fm_engine* e, int lane)
+{
+    if (e->ldbg.armed) lane_point_armed(e, lane);
+}
+// Every cross-lane hipStreamWaitEvent of the lane protocol goes through here, so that fm_debug_drop_wait can leave one kind out
+static inline hipError_t lane_wait(fm_engine* e, int kind, hipStream_t st, hipEvent_t ev)
+{
+    fm_engine::LaneDbg& d = e->ldbg;
+    d.waits[kind] += 1;
+    if (d.drop >> kind & 1) { d.skipped[kind] += 1; return hipSuccess; }
+    return hipStreamWaitEvent(st, ev, 0);
+}
 static inline void soft(fm_engine* e, hipError_t rc)
 {
     if (rc != hipSuccess && e->soft_err == hipSuccess) e->soft_err = rc;
@@ -1032,6 +1056,7 @@ struct OpScope {
     fm_engine* e; hipStream_t st; hipEvent_t a{}, b{}; int id = -1; bool on;
     OpScope(fm_engine* e_, const Lane& L, const char* op) : e(e_), st(L.st), on(e_->oprof)
     {
+        lane_point(e_, &L == &e_->side);
         if (!on) return;
         char lab[96];
         snprintf(lab, sizeof lab, "%s@%d", op, e->ctx);
@@ -1047,6 +1072,8 @@ struct OpScope {
     }
 };
 #define OP(lane, name) OpScope os_(e, lane, name)
+// a delay point without a profiling scope: ResNet-18's forwards, whose launches fm_profile_ops does not list
+#define LP(lane) lane_point(e, &(lane) == &e->side)
 
 // ---- layer launchers --------------------------------------------------------------
 // operand prologue of a pointwise conv (bf16 mode): Xe = swish(X*psc+psh)*gate, psc == null: X*gate
@@ -1602,9 +1629,10 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
     const Weights& W = e->student;
     const float* S = W.state;
     Conv& c0 = e->convs[0];
-    conv_fwd(e, L, 0, W, e->x4, c0.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats);
-    bn_fwd_finalize(e, L, 0, groups, B, mode);
+    LP(L); conv_fwd(e, L, 0, W, e->x4, c0.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats);
+    LP(L); bn_fwd_finalize(e, L, 0, groups, B, mode);
     const bool pm = e->planes;
+    LP(L);
     if (pm) k_stem_pool_planes(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, A.p0p, groups, B, c0.hout, c0.wout, 64, L.st);
     else k_stem_pool(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, groups, B, c0.hout, c0.wout, 64, L.st);
     // BatchNorm apply.  Planes mode: the activations z1 / out exist ONLY as planes (what the conv GEMMs read; the residual add
@@ -1613,6 +1641,7 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
     auto apply = [&](const float* y, int b1, const float* res, const unsigned short* resp, const float* y2, int b2, float* out,
                      unsigned short* outp, int pix, int C) {
         const float *s2 = y2 ? e->bns[b2].scale : nullptr, *h2 = y2 ? e->bns[b2].shift : nullptr;
+        LP(L);
         if (pm && outp)
             k_bn_apply_planes(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, nullptr, outp, groups, pix, C, 1, L.st, resp);
         else
@@ -1628,20 +1657,20 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
         Conv& c2 = e->convs[blk.c2];
         const int pix = B * c1.hout * c1.wout;
         const bool last = bi + 1 == e->blocks.size();
-        conv_fwd(e, L, blk.c1, W, cur, c1.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-        bn_fwd_finalize(e, L, blk.c1, groups, B, mode);
+        LP(L); conv_fwd(e, L, blk.c1, W, cur, c1.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
+        LP(L); bn_fwd_finalize(e, L, blk.c1, groups, B, mode);
         apply(c1.y, blk.c1, nullptr, nullptr, nullptr, -1, a.z1, a.z1p, pix, c1.cout);
-        conv_fwd(e, L, blk.c2, W, a.z1, c2.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, a.z1p);
-        bn_fwd_finalize(e, L, blk.c2, groups, B, mode);
+        LP(L); conv_fwd(e, L, blk.c2, W, a.z1, c2.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, a.z1p);
+        LP(L); bn_fwd_finalize(e, L, blk.c2, groups, B, mode);
         unsigned short* outp = (pm && !last) ? a.outp : nullptr;
         if (blk.ds >= 0) {
             Conv& cd = e->convs[blk.ds];
-            conv_fwd(e, L, blk.ds, W, cur, cd.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-            bn_fwd_finalize(e, L, blk.ds, groups, B, mode);
+            LP(L); conv_fwd(e, L, blk.ds, W, cur, cd.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
+            LP(L); bn_fwd_finalize(e, L, blk.ds, groups, B, mode);
             apply(c2.y, blk.c2, nullptr, nullptr, cd.y, blk.ds, a.out, outp, pix, c2.cout);
         } else if (pm && !cur_f32) {
             if (last) {      // the last block adds a planes-only residual into an fp32 output: re-form the residual first
-                k_planes_to_f32(curp, A.blk[bi - 1].out, (long long)imgs * c1.hin * c1.win, c1.cin, L.st);
+                LP(L); k_planes_to_f32(curp, A.blk[bi - 1].out, (long long)imgs * c1.hin * c1.win, c1.cin, L.st);
                 apply(c2.y, blk.c2, A.blk[bi - 1].out, nullptr, nullptr, -1, a.out, nullptr, pix, c2.cout);
             } else
                 apply(c2.y, blk.c2, nullptr, curp, nullptr, -1, a.out, outp, pix, c2.cout);
@@ -1653,8 +1682,8 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
         cur_f32 = !(pm && !last);
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
-    k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, L.st);
+    LP(L); k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
+    LP(L); k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, L.st);
     if (mode != BnMode::Frozen) net_changed(e, e->student, Moved::Stats);
 }
 
@@ -1662,12 +1691,13 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
 void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* feat, float* logits)
 {
     const float* S = W.state;
-    ensure_eval_affine(e, L, W);
+    LP(L); ensure_eval_affine(e, L, W);
     auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
     auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
     Conv& c0 = e->convs[0];
-    conv_fwd(e, L, 0, W, e->x4, A.stem_y, imgs, 1, sc(0), sh(0), nullptr, 1, nullptr);
+    LP(L); conv_fwd(e, L, 0, W, e->x4, A.stem_y, imgs, 1, sc(0), sh(0), nullptr, 1, nullptr);
     const bool pm = e->planes;
+    LP(L);
     if (pm) k_stem_pool_planes(A.stem_y, nullptr, nullptr, A.p0, nullptr, A.p0p, 1, imgs, c0.hout, c0.wout, 64, L.st);
     else k_stem_pool(A.stem_y, nullptr, nullptr, A.p0, nullptr, 1, imgs, c0.hout, c0.wout, 64, L.st);
     const float* cur = A.p0;
@@ -1679,24 +1709,24 @@ void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* f
         // planes mode: z1 and `out` exist only as planes (the next convs read them; the next block's residual add re-forms the fp32
         // values in the epilogue) -- except the last block's `out`, which feeds the average pool: fp32 only
         const bool last = bi + 1 == e->blocks.size();
-        conv_fwd(e, L, blk.c1, W, cur, pm ? nullptr : a.z1, imgs, 1, sc(blk.c1), sh(blk.c1), nullptr, 1, nullptr, nullptr, curp,
+        LP(L); conv_fwd(e, L, blk.c1, W, cur, pm ? nullptr : a.z1, imgs, 1, sc(blk.c1), sh(blk.c1), nullptr, 1, nullptr, nullptr, curp,
                  pm ? a.z1p : nullptr);
         const float* idt = cur;
         const unsigned short* idtp = nullptr;
         if (blk.ds >= 0) {
-            conv_fwd(e, L, blk.ds, W, cur, a.ds_y, imgs, 1, sc(blk.ds), sh(blk.ds), nullptr, 0, nullptr, nullptr, curp);
+            LP(L); conv_fwd(e, L, blk.ds, W, cur, a.ds_y, imgs, 1, sc(blk.ds), sh(blk.ds), nullptr, 0, nullptr, nullptr, curp);
             idt = a.ds_y;
         } else if (!cur_f32) { idt = nullptr; idtp = curp; }
         const bool planes_only = pm && !last;
-        conv_fwd(e, L, blk.c2, W, a.z1, planes_only ? nullptr : a.out, imgs, 1, sc(blk.c2), sh(blk.c2), idt, 1, nullptr, nullptr,
+        LP(L); conv_fwd(e, L, blk.c2, W, a.z1, planes_only ? nullptr : a.out, imgs, 1, sc(blk.c2), sh(blk.c2), idt, 1, nullptr, nullptr,
                  a.z1p, planes_only ? a.outp : nullptr, idtp);
         cur = a.out;
         curp = a.outp;
         cur_f32 = !planes_only;
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    k_avgpool(cur, DT_F32, feat, imgs, cl.hout * cl.wout, 512, L.st);
-    k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, L.st);
+    LP(L); k_avgpool(cur, DT_F32, feat, imgs, cl.hout * cl.wout, 512, L.st);
+    LP(L); k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, L.st);
 }
 
 // d loss / d image of `imgs` images from the gradient of the stem's raw output (stem_dgrad.hip): dy [imgs][hout][wout][cout_p] in
@@ -1927,7 +1957,7 @@ Lane& side_begin(fm_engine* e, int k, int par)
 {
     if (!e->side_w) return e->main;
     soft(e, hipEventRecord(e->ev_p[k][par], e->main.st));
-    soft(e, hipStreamWaitEvent(e->side.st, e->ev_p[k][par], 0));
+    soft(e, lane_wait(e, FM_WAIT_SIDE_BEGIN, e->side.st, e->ev_p[k][par]));
     return e->side;
 }
 void side_end(fm_engine* e, int k, int par)
@@ -1936,13 +1966,13 @@ void side_end(fm_engine* e, int k, int par)
 }
 void side_guard(fm_engine* e, int k, int par)
 {
-    if (e->side_w) soft(e, hipStreamWaitEvent(e->main.st, e->ev_c[k][par], 0));
+    if (e->side_w) soft(e, lane_wait(e, FM_WAIT_SIDE_GUARD, e->main.st, e->ev_c[k][par]));
 }
 void side_join(fm_engine* e)
 {
     if (!e->side_w) return;
     soft(e, hipEventRecord(e->ev_wdone, e->side.st));
-    soft(e, hipStreamWaitEvent(e->main.st, e->ev_wdone, 0));
+    soft(e, lane_wait(e, FM_WAIT_SIDE_JOIN, e->main.st, e->ev_wdone));
 }
 
 // backward from e->dlogits (and bw.dfeat) through the student's activation set, as forward_train left it, into e->grad on the
@@ -2476,7 +2506,7 @@ int teacher_forward_side(fm_engine* e, int imgs)
 {
     ensure_fwd_shadows(e, e->teacher);                          // weight shadows on the main lane, before the fork
     HIPCHK(hipEventRecord(e->ev_in, e->main.st));
-    HIPCHK(hipStreamWaitEvent(e->side.st, e->ev_in, 0));
+    HIPCHK(lane_wait(e, FM_WAIT_EV_IN, e->side.st, e->ev_in));
     net_forward_eval(e, e->side, e->teacher, e->tacts, imgs, e->tfeat, e->tlogits);
     HIPCHK(hipEventRecord(e->ev_t, e->side.st));
     return FM_OK;
@@ -2491,7 +2521,7 @@ int teacher_and_student_forward(fm_engine* e, int timgs, int groups, int B)
         net_forward_eval(e, e->main, e->teacher, e->acts, timgs, e->tfeat, e->tlogits);
     }
     net_forward_train(e, groups, B);
-    if (e->side_ok) HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
+    if (e->side_ok) HIPCHK(lane_wait(e, FM_WAIT_EV_T, e->main.st, e->ev_t));
     return FM_OK;
 }
 void net_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw = {})
@@ -2743,6 +2773,7 @@ int fused_step(fm_engine* e, StepFwd fwd, const float* x1, const float* x2, int 
     if (groups == 2) ARGCHK(B >= 1 && 2 * B <= e->maxB, "2*B exceeds max_images");
     else ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
     BADCHK(head_bad);
+    lane_point(e, 0);
     const float* xs[2] = {x1, x2};
     if (fwd == StepFwd::Rscfed && !(e->side_ok && 2 * B <= e->maxB)) {
         // one lane (or no room for both views in the staging): the teacher first, each view staged in turn
@@ -2761,7 +2792,7 @@ int fused_step(fm_engine* e, StepFwd fwd, const float* x1, const float* x2, int 
             e->in_img0 = 0;
             RCCHK(rc);
             net_forward_train(e, 1, B);
-            HIPCHK(hipStreamWaitEvent(e->main.st, e->ev_t, 0));
+            HIPCHK(lane_wait(e, FM_WAIT_EV_T, e->main.st, e->ev_t));
         }
     }
     head();
@@ -3088,6 +3119,7 @@ int fm_forward_eval(fm_engine* e, const float* x_dev, int32_t B, int32_t use_tea
 {
     ARGCHK(e && x_dev, "null");
     ARGCHK(B >= 1 && B <= e->maxB, "B exceeds max_images");
+    lane_point(e, 0);
     const float* xs[1] = {x_dev};
     to_nhwc4(e, e->main, xs, 1, B);
     float* feat = use_teacher ? e->tfeat : e->feat;
@@ -3472,6 +3504,7 @@ int fm_forward_train(fm_engine* e, const float* x1_dev, const float* x2_dev, int
     ARGCHK(e && x1_dev, "null");
     const int views = x2_dev ? 2 : 1;
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
+    lane_point(e, 0);
     const float* xs[2] = {x1_dev, x2_dev};
     to_nhwc4(e, e->main, xs, views, B);
     net_forward_train(e, views, B, e->bn_freeze ? BnMode::Frozen : BnMode::Batch);
@@ -3503,6 +3536,7 @@ int fm_backward_step(fm_engine* e, const float* dlogits_dev)
     ARGCHK(e->pending_views > 0, "fm_backward_step without a preceding fm_forward_train");
     ARGCHK(e->trainable.empty() && e->pending_trainable.empty(), kMaskRefusal);      // the current mask and the pending forward's
     const int views = e->pending_views, B = e->pending_B;
+    lane_point(e, 0);
     HIPCHK(hipMemcpyAsync(e->dlogits, dlogits_dev, (size_t)views * B * e->C * 4, hipMemcpyDeviceToDevice, e->main.st));
     Bwd bw;
     bw.frozen = e->pending_fixed;
@@ -3523,6 +3557,7 @@ int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfe
     ARGCHK(e->pending_views > 0, "fm_backward_grads(_x) without a preceding fm_forward_train / fm_forward_recompute");
     const int views = e->pending_views, B = e->pending_B;
     ARGCHK(views == 2 || !dx2_dev, "fm_backward_grads_x: dx2 given, but the pending forward has one view");
+    lane_point(e, 0);
     if (dx1_dev || dx2_dev) {                      // first use: the stem's weights as the data gradient's B matrix
         RCCHK(ensure_stem_dpack(e));
     }
@@ -3556,6 +3591,7 @@ int fm_forward_recompute(fm_engine* e, const float* x1_dev, const float* x2_dev,
     ARGCHK(e && x1_dev, "null");
     const int views = x2_dev ? 2 : 1;
     ARGCHK(B >= 1 && views * B <= e->maxB, "views*B exceeds max_images");
+    lane_point(e, 0);
     const float* xs[2] = {x1_dev, x2_dev};
     to_nhwc4(e, e->main, xs, views, B);
     net_forward_train(e, views, B, e->bn_freeze ? BnMode::Frozen : BnMode::BatchNoUpdate);
@@ -3944,12 +3980,12 @@ int fm_debug_exp_bwd(fm_engine* e, int32_t conv, const void* da_dev, const void*
 
 int fm_debug_optim_arena(fm_engine* e, int32_t which, float** dev_ptr, int64_t* numel)
 {
-    ARGCHK(e && dev_ptr && numel && which >= 0 && which <= 2, "null / which");
+    ARGCHK(e && dev_ptr && numel && which >= 0 && which <= 3, "null / which");
     if (which == 2 && !e->gacc) {
         DALLOC(e->gacc, e->NP);
         HIPCHK(hipMemsetAsync(e->gacc, 0, e->NP * 4, e->main.st));
     }
-    *dev_ptr = which == 0 ? e->adam_m : (which == 1 ? e->adam_v : e->gacc);
+    *dev_ptr = which == 0 ? e->adam_m : (which == 1 ? e->adam_v : (which == 2 ? e->gacc : e->grad));
     *numel = (int64_t)e->NP;
     return FM_OK;
 }
@@ -4031,6 +4067,57 @@ int fm_debug_activation(fm_engine* e, int32_t kind, int32_t block, int32_t imgs,
 int fm_debug_lose_part(int32_t on)
 {
     pconv_debug_lose_part(on);
+    return FM_OK;
+}
+
+// ---- lane-order test hooks ----
+static void lane_point_armed(fm_engine* e, int lane)
+{
+    fm_engine::LaneDbg& d = e->ldbg;
+    const int64_t pos = d.points[lane]++;
+    if (d.fired || lane != d.lane || pos != d.at || d.micros <= 0) return;
+    d.fired = true;
+    // >= 0.8 us per sleep iteration: three per microsecond cover the time asked for, and end the kernel within a few times it
+    k_lane_delay(d.ticks, 3 * d.micros, lane ? e->side.st : e->main.st);
+}
+
+int fm_debug_lane_delay(fm_engine* e, int32_t lane, int64_t at, int32_t micros)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(lane == 0 || lane == 1, "fm_debug_lane_delay: lane is 0 (main) or 1 (side)");
+    ARGCHK(lane == 0 || e->side_ok, "fm_debug_lane_delay: lane 1 on a handle without a side stream");
+    ARGCHK(at >= 0, "fm_debug_lane_delay: at >= 0");
+    ARGCHK(micros >= 0 && micros <= FM_LANE_DELAY_MAX_US, "fm_debug_lane_delay: 0 <= micros <= FM_LANE_DELAY_MAX_US");
+    int dev = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
+        khz = 100000;                  // wall_clock64() counts at 100 MHz on CDNA
+    fm_engine::LaneDbg& d = e->ldbg;
+    const uint32_t drop = d.drop;      // the dropped waits are a switch of their own
+    d = fm_engine::LaneDbg{};
+    d.drop = drop;
+    d.armed = true;
+    d.lane = lane; d.at = at; d.micros = micros;
+    d.ticks = (int64_t)micros * khz / 1000;
+    return FM_OK;
+}
+
+int fm_debug_lane_points(fm_engine* e, int64_t* out16, int32_t disarm)
+{
+    ARGCHK(e && out16, "null");
+    fm_engine::LaneDbg& d = e->ldbg;
+    for (int i = 0; i < 16; ++i) out16[i] = 0;
+    out16[0] = d.points[0]; out16[1] = d.points[1]; out16[2] = d.fired;
+    for (int k = 0; k < FM_WAIT_KINDS; ++k) { out16[3 + k] = d.waits[k]; out16[3 + FM_WAIT_KINDS + k] = d.skipped[k]; }
+    if (disarm) d.armed = false;
+    return FM_OK;
+}
+
+int fm_debug_drop_wait(fm_engine* e, int32_t which, int32_t on)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(which >= 0 && which < FM_WAIT_KINDS, "fm_debug_drop_wait: unknown wait kind");
+    if (on) e->ldbg.drop |= 1u << which;
+    else e->ldbg.drop &= ~(1u << which);
     return FM_OK;
 }
 

@@ -223,6 +223,8 @@ int se_wgrad_splits();
 int se_wgrad_max_cs();
 void k_mul(const float* a, const float* b, float* y, int64_t n, hipStream_t s);
 void k_add_inplace(void* y, const void* a, int dt, int64_t n, hipStream_t s);
+// test hook: hold stream s for `ticks` of wall_clock64(), at most `cap` sleep iterations (elementwise.hip)
+void k_lane_delay(int64_t ticks, int cap, hipStream_t s);
 
 // ---- head ---------------------------------------------------------------------
 void k_avgpool(const void* x, int dt, float* feat, int imgs, int HW, int C, hipStream_t s);

@@ -833,8 +833,30 @@ class Engine(RoflHeads):
         _lib.check(self.lib.fm_debug_get_grads(self.h, flat.ctypes.data_as(C.c_void_p)))
         return flat
 
+    WAIT_KINDS = ("side_begin", "side_guard", "side_join", "ev_in", "ev_t")     # FM_WAIT_* of fedmlp_hip_debug.h, in order
+
+    def debug_lane_delay(self, lane, at, micros):
+        """Arm one delay of `micros` us at delay point `at` of lane 0 (main) / 1 (side); restarts the point and wait counts
+        (fm_debug_lane_delay).  micros = 0 only counts."""
+        _lib.check(self.lib.fm_debug_lane_delay(self.h, int(lane), int(at), int(micros)))
+
+    def debug_lane_points(self, disarm=False):
+        """Since the last debug_lane_delay: {"points": (main, side), "fired": bool, "waits" / "skipped": {kind: count}}."""
+        o = (C.c_int64 * 16)()
+        _lib.check(self.lib.fm_debug_lane_points(self.h, o, int(bool(disarm))))
+        n = len(self.WAIT_KINDS)
+        return {"points": (int(o[0]), int(o[1])), "fired": bool(o[2]),
+                "waits": {k: int(o[3 + i]) for i, k in enumerate(self.WAIT_KINDS)},
+                "skipped": {k: int(o[3 + n + i]) for i, k in enumerate(self.WAIT_KINDS)}}
+
+    def debug_drop_wait(self, kind, on=True):
+        """Skip (on) / keep the cross-lane wait of one kind (a name of WAIT_KINDS or its index): fm_debug_drop_wait."""
+        which = self.WAIT_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        _lib.check(self.lib.fm_debug_drop_wait(self.h, which, int(bool(on))))
+
     def debug_optim_arena(self, which):
-        """torch view of a raw engine-layout arena of the optimizers: 0 / 1 the moments, 2 the gradient accumulator."""
+        """torch view of a raw engine-layout arena of the optimizers: 0 / 1 the moments, 2 the gradient accumulator, 3 the
+        gradients of the last backward."""
         p, n = C.c_void_p(), C.c_int64()
         _lib.check(self.lib.fm_debug_optim_arena(self.h, int(which), C.byref(p), C.byref(n)))
         return _device_view(p.value, n.value, self.device)

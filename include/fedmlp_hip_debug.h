@@ -152,10 +152,44 @@ int fm_debug_stem_masks(fm_engine* e, int32_t imgs, int32_t groups, uint8_t* rel
  * moments unchanged) and the NEXT call that ends a step or synchronises returns FM_ERR_HIP once.  Process-wide; on = 0 restores. */
 int fm_debug_lose_part(int32_t on);
 
+/* Schedule perturbation for the two-lane order (main lane = the caller's stream, side lane = teacher forward and weight
+ * gradients): hold one lane back at one of its launch points, so that the other lane runs as far ahead as its event waits allow.
+ * With every wait in place the results are the bits of a one-stream handle, wherever the delay sits (tests/test_lane_delay_gpu.py).
+ *
+ * Delay points, counted per lane (0 main, 1 side) from the arming call on: every launcher of the engine's graphs (the OP(lane, ..)
+ * scopes), and -- on the main lane -- one point at the entry of every call that enqueues a step, a forward or a backward, ahead of
+ * its first enqueue (input staging and weight-shadow rebuilds included).
+ *
+ * fm_debug_lane_delay arms the handle: both counters and the wait counts below restart at 0, and when lane `lane` reaches its
+ * point number `at` (0-based) the engine first enqueues, once, a delay kernel of `micros` microseconds on that lane's stream: one
+ * workgroup of 64 threads that touches no memory and spins on the wall clock, bounded by the time asked for and by an iteration cap
+ * that ends it within a small multiple of that time.  micros = 0 only counts.  FM_ERR_ARG, with nothing armed or enqueued: a lane
+ * other than 0 / 1, lane 1 on a handle without a side stream, at < 0, micros outside 0 .. FM_LANE_DELAY_MAX_US.
+ * fm_debug_lane_points: out16[0], [1] = points passed by the main / side lane since arming, [2] = 1 once the delay kernel was
+ * enqueued, [3 + k] = cross-lane waits of kind k reached, [3 + FM_WAIT_KINDS + k] = those of them that were skipped; disarm != 0
+ * ends the counting (a disarmed handle pays one predictable branch per launch).
+ *
+ * fm_debug_drop_wait (on = 1 / 0; per handle, off by default, kept across arming calls) is the mutant that shows the delay sweep
+ * sees a lost dependency: the engine skips the hipStreamWaitEvent of ONE kind, the event records stay:
+ *   FM_WAIT_SIDE_BEGIN  the side lane's wait for the main lane's producer of a gradient tensor (side_begin)
+ *   FM_WAIT_SIDE_GUARD  the main lane's wait for the side lane's weight gradient before it overwrites that tensor (side_guard)
+ *   FM_WAIT_SIDE_JOIN   the main lane's wait for every weight gradient before the optimizer (side_join)
+ *   FM_WAIT_EV_IN       the side lane's wait before the teacher's forward (ev_in)
+ *   FM_WAIT_EV_T        the main lane's wait for the teacher before the loss head (ev_t; both call sites)
+ * A dropped wait only reorders reads and writes of buffers the step owns: allocations, sizes and kernel arguments are what they
+ * always are, so the outcome is wrong values, never an access outside those buffers.  Neither hook reads the environment. */
+enum { FM_WAIT_SIDE_BEGIN = 0, FM_WAIT_SIDE_GUARD, FM_WAIT_SIDE_JOIN, FM_WAIT_EV_IN, FM_WAIT_EV_T };
+#define FM_WAIT_KINDS 5
+#define FM_LANE_DELAY_MAX_US 20000
+int fm_debug_lane_delay(fm_engine* e, int32_t lane, int64_t at, int32_t micros);
+int fm_debug_lane_points(fm_engine* e, int64_t* out16, int32_t disarm);
+int fm_debug_drop_wait(fm_engine* e, int32_t which, int32_t on);
+
 /* Gradients of the last step in state_dict order (running-stat slots are 0). */
 int fm_debug_get_grads(fm_engine* e, float* host_f32);
 /* The raw engine-layout arenas behind the optimizers (NP floats each, layout padding included; the trainable part of
- * fm_state_device's layout): which = 0 first moment, 1 second moment, 2 the gradient accumulator (allocated if it was not). */
+ * fm_state_device's layout): which = 0 first moment, 1 second moment, 2 the gradient accumulator (allocated if it was not), 3 the gradients of the last backward (what fm_debug_get_grads
+ * reorders; for comparisons on the device). */
 int fm_debug_optim_arena(fm_engine* e, int32_t which, float** dev_ptr, int64_t* numel);
 /* The entry table of the grouped optimizer steps and the masked accumulate: off_len[2 i] = arena offset, off_len[2 i + 1] =
  * span length in floats of state entry i (reference key order), summed over its chunks; -1 / 0 for running statistics and
