@@ -135,16 +135,27 @@ struct Weights {
 
 // The tensors a forward writes.  The student's set is what the backward reads; the second set (fm_engine::tacts) exists only
 // with the side stream, for the teacher's eval forward next to the student's train forward.
+// A tensor that exists as fp32, as block-major bf16 planes (planes mode: what the conv GEMMs read), or both; a form that does not
+// exist is null.  In: an operand a launcher reads; Out: one it writes, and whatever holds the buffers.  Planes nobody produced
+// (In::p null where a planes kernel runs: test hooks) are made by scratch_planes.
+struct In { const float* f = nullptr; const unsigned short* p = nullptr; };
+struct Out {
+    float* f = nullptr; unsigned short* p = nullptr;
+    operator In() const { return {f, p}; }
+};
+// The form the graphs keep a block tensor in: planes only where it has planes (its fp32 buffer then idles: fm_debug_activation
+// and the last block's residual re-form fp32 values into it), fp32 otherwise
+inline Out kept(Out t) { return t.p ? Out{nullptr, t.p} : t; }
+
 struct BlockActs {
-    float *z1 = nullptr, *out = nullptr;
+    Out z1, out;
     float* ds_y = nullptr;            // the downsample conv's output (student: that Conv::y)
-    unsigned short *z1p = nullptr, *outp = nullptr;   // planes mode: block-major bf16 planes of z1 / out (what the conv GEMMs read)
 };
 struct MBActs { float *a_e = nullptr, *y_d = nullptr, *a_s = nullptr, *out = nullptr, *sq = nullptr, *rpre = nullptr, *gate = nullptr; };
 struct Acts {
-    // ResNet-18: the stem's raw output (student: convs[0].y), its pooled output and that one's planes
-    float *stem_y = nullptr, *p0 = nullptr;
-    unsigned short* p0p = nullptr;
+    // ResNet-18: the stem's raw output (student: convs[0].y) and its pooled output (planes mode: written both ways)
+    float* stem_y = nullptr;
+    Out p0;
     float* a0 = nullptr;              // EfficientNet: swish(bn(stem))
     std::vector<BlockActs> blk;
     std::vector<MBActs> mb;
@@ -166,6 +177,11 @@ struct Bwd {
     // stale values at the frozen entries: the caller masks them (fm_backward_grads_x: k_grad_accumulate_masked)
     const int32_t* train = nullptr;
 };
+
+// The gradient tensors a backward's weight gradients read, one set per block parity (fm_engine::rg / eg): with the weight gradients
+// on the side lane (side_w) the two sets are buffers of their own, otherwise set [1] IS set [0] (alloc_workspaces / alloc_side)
+struct ResGrads { Out dy2, dyd, dy1; };       // ResNet-18: d y2, d y_ds, d y1 (planes mode: the planes are what the GEMMs read)
+struct EffGrads { float *dyp = nullptr, *dyd = nullptr, *dye = nullptr, *se_dg = nullptr, *se_dr = nullptr; };   // EfficientNet-B0: d y_p, d y_d, d y_e; the SE vectors
 
 struct StateEntry {           // one state_dict entry, in reference key order
     int kind;                 // 0 OIHW weight (re-laid out to O,H,W(pad),I(pad)), 1 float vector, 2 int64 counter
@@ -207,8 +223,9 @@ struct fm_engine {
     int model = 0, c_stem = 0, c_head = -1, bn_stem = 0, bn_head = -1;
     float bn_eps = 1e-5f, bn_mom = 0.1f;
     int maxC = 512;                   // widest BN (sizes ca/cb/cc and the partial-sum workspace)
-    float *T_small = nullptr, *T_big = nullptr;       // EfficientNet backward: d y_p, d y_e (d y_d lives in acts.T_mid)
-    float *se_dgp = nullptr, *se_drp = nullptr, *se_ds = nullptr, *hfeat = nullptr;
+    ResGrads rg[2];                   // the backward's gradient sets by block parity (set [0]'s d y_d of EfficientNet-B0 is acts.T_mid)
+    EffGrads eg[2];
+    float *se_ds = nullptr, *hfeat = nullptr;
     const float *dc_dev = nullptr, *drop_dev = nullptr;   // caller-owned stochastic multipliers (or null)
     int pending_views = 0, pending_B = 0;                 // fm_forward_train awaiting fm_backward_step
     // autograd path (fm_backward_grads / fm_adam_step): the gradient accumulator (NP floats, allocated on first use; `gacc_full`
@@ -260,7 +277,7 @@ struct fm_engine {
     unsigned short* x3p = nullptr;
     long long x3p_plane_elems = 0;
     uint8_t* idx0 = nullptr;
-    float *GA = nullptr, *GB = nullptr, *GC = nullptr, *GD = nullptr, *GE = nullptr;
+    float *GA = nullptr, *GB = nullptr, *GE = nullptr;      // block input / output gradients (GB: EfficientNet-B0, GE: ResNet-18)
     float *ws_stats = nullptr, *ws_part = nullptr;
     // what ws_stats holds: the BN partial sums of conv `stats_conv`, `stats_tiles_n` tiles per group -- written by the conv_fwd
     // that launched the GEMM (the count depends on the kernel and on that call's operand prologue), read by the finalize
@@ -314,8 +331,6 @@ struct fm_engine {
     // planes mode (ResNet-18, split product forms): the 3x3 / 1x1 conv GEMMs take BOTH operands as block-major bf16 planes
     // (pconv.hip); the activation planes are written by the kernels that produce the tensors
     bool planes = false;
-    unsigned short *GBp = nullptr, *GCp = nullptr, *GDp = nullptr;   // planes of d y2, d y_ds, d y1 (what the data gradients read)
-    unsigned short *GB2p = nullptr, *GC2p = nullptr, *GD2p = nullptr;
     unsigned short* xp_scratch = nullptr;       // planes of an fp32 operand nobody produced planes for (test hooks)
     unsigned short* xp_scratch2 = nullptr;      // ... and of the second operand of a weight gradient
     size_t xp_scratch_elems = 0;
@@ -341,12 +356,9 @@ struct fm_engine {
     // enqueues its teacher's forward, whose view is the staging's second group
     int in_img0 = 0;
     // backward: the weight gradients run on the side lane next to the data-gradient chain; the gradient tensors they read
-    // are double-buffered by block parity (side_w; stream_mode 1 or 2: inline)
+    // (rg / eg) are double-buffered by block parity (side_w; stream_mode 1 or 2: inline)
     bool side_w = false;
-    float *T_small2 = nullptr, *T_mid2 = nullptr, *T_big2 = nullptr;
-    float *GB2 = nullptr, *GC2 = nullptr, *GD2 = nullptr;           // ResNet-18 (stream_mode 0): the same for d y2 / d y_ds / d y1
     hipEvent_t ev_p[4][2] = {}, ev_c[4][2] = {}, ev_wdone = nullptr;    // [tensor: d y_p, d y_d, d y_e, SE vectors][block parity]
-    float *se_dgp2 = nullptr, *se_drp2 = nullptr;
     float* stem_col = nullptr;        // bf16 mode: [images][hout][wout][k][4][4] bf16 im2col of the input (the stem's X operand)
     // Lane-order test hooks (fm_debug_lane_delay, fm_debug_drop_wait; fedmlp_hip_debug.h).  armed: the delay points count and the
     // `at`-th one of `lane` enqueues the delay kernel once; drop: bit k skips the cross-lane wait of kind k (lane_wait)
@@ -822,20 +834,20 @@ int alloc_acts(fm_engine* e, Acts& a, bool second)
         const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
         a.stem_y = c0.y;
         if (second) DALLOC(a.stem_y, B * c0.hout * c0.wout * c0.cout_p);
-        DALLOC(a.p0, pooled);
-        if (e->planes) PALLOC(a.p0p, pooled);
+        DALLOC(a.p0.f, pooled);
+        if (e->planes) PALLOC(a.p0.p, pooled);
         a.blk.resize(e->blocks.size());
         for (size_t i = 0; i < e->blocks.size(); ++i) {
             const Block& blk = e->blocks[i];
             BlockActs& ba = a.blk[i];
             const Conv& c = e->convs[blk.c1];
             const size_t n = B * c.hout * c.wout * c.cout;
-            DALLOC(ba.z1, n); DALLOC(ba.out, n);
+            DALLOC(ba.z1.f, n); DALLOC(ba.out.f, n);
             if (blk.ds >= 0) {
                 ba.ds_y = e->convs[blk.ds].y;
                 if (second) DALLOC(ba.ds_y, n);
             }
-            if (e->planes) { PALLOC(ba.z1p, n); PALLOC(ba.outp, n); }
+            if (e->planes) { PALLOC(ba.z1.p, n); PALLOC(ba.out.p, n); }
         }
         return FM_OK;
     }
@@ -914,12 +926,14 @@ int alloc_side(fm_engine* e)
     if (e->model == 0) {
         const Conv& c0 = e->convs[0];
         const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
-        DALLOC(e->GB2, pooled); DALLOC(e->GC2, pooled); DALLOC(e->GD2, pooled);
-        if (e->planes) { PALLOC(e->GB2p, pooled); PALLOC(e->GC2p, pooled); PALLOC(e->GD2p, pooled); }
+        ResGrads& g = e->rg[1];
+        DALLOC(g.dy2.f, pooled); DALLOC(g.dyd.f, pooled); DALLOC(g.dy1.f, pooled);
+        if (e->planes) { PALLOC(g.dy2.p, pooled); PALLOC(g.dyd.p, pooled); PALLOC(g.dy1.p, pooled); }
     } else {
         const EffSizes z = eff_sizes(e);
-        AALLOC(e->T_small2, z.t_small); AALLOC(e->T_mid2, z.t_mid); AALLOC(e->T_big2, z.t_big);
-        DALLOC(e->se_dgp2, B * z.max_ce); DALLOC(e->se_drp2, B * z.max_cs);
+        EffGrads& g = e->eg[1];
+        AALLOC(g.dyp, z.t_small); AALLOC(g.dyd, z.t_mid); AALLOC(g.dye, z.t_big);
+        DALLOC(g.se_dg, B * z.max_ce); DALLOC(g.se_dr, B * z.max_cs);
     }
     for (int k = 0; k < 4; ++k)
         for (int q = 0; q < 2; ++q) {
@@ -976,12 +990,15 @@ int alloc_workspaces(fm_engine* e)
         const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
         DALLOC(e->idx0, pooled);
         DALLOC(e->dyh0, B * c0.hout * c0.wout * 64);
-        DALLOC(e->GA, pooled); DALLOC(e->GB, pooled); DALLOC(e->GC, pooled); DALLOC(e->GD, pooled); DALLOC(e->GE, pooled);
+        ResGrads& g = e->rg[0];
+        DALLOC(e->GA, pooled); DALLOC(g.dy2.f, pooled); DALLOC(g.dyd.f, pooled); DALLOC(g.dy1.f, pooled); DALLOC(e->GE, pooled);
     } else {
         const EffSizes z = eff_sizes(e);
         AALLOC(e->GA, z.g_io); AALLOC(e->GB, z.g_io);
-        AALLOC(e->T_small, z.t_small); AALLOC(e->T_big, z.t_big);
-        DALLOC(e->se_dgp, B * z.max_ce); DALLOC(e->se_drp, B * z.max_cs); DALLOC(e->se_ds, B * z.max_ce);
+        EffGrads& g = e->eg[0];
+        g.dyd = e->acts.T_mid;
+        AALLOC(g.dyp, z.t_small); AALLOC(g.dye, z.t_big);
+        DALLOC(g.se_dg, B * z.max_ce); DALLOC(g.se_dr, B * z.max_cs); DALLOC(e->se_ds, B * z.max_ce);
         side = side && side_fits(e);
         DALLOC(e->hfeat, B * e->D);
     }
@@ -998,7 +1015,7 @@ int alloc_workspaces(fm_engine* e)
     DALLOC(e->zeros, 64);
     if (e->planes) {
         const size_t pooled = B * (c0.hout / 2) * (c0.wout / 2) * 64;
-        PALLOC(e->GBp, pooled); PALLOC(e->GCp, pooled); PALLOC(e->GDp, pooled);
+        PALLOC(e->rg[0].dy2.p, pooled); PALLOC(e->rg[0].dyd.p, pooled); PALLOC(e->rg[0].dy1.p, pooled);
         // scratch planes for operands that arrive as fp32 (test hooks): the largest conv input / output-gradient tensor
         size_t mx = 0;
         for (auto& c : e->convs) {
@@ -1022,6 +1039,7 @@ int alloc_workspaces(fm_engine* e)
     HIPCHK(hipMemset(e->main.sk_counters, 0, ((size_t)1 << 20) * 4));
     HIPCHK(hipMemset(e->zeros, 0, 64 * 4));
     if (e->model == 0) side = side && side_fits(e);
+    e->rg[1] = e->rg[0]; e->eg[1] = e->eg[0];       // one set for both parities, unless alloc_side gives the second its own buffers
     return side ? alloc_side(e) : FM_OK;
 }
 
@@ -1076,8 +1094,13 @@ struct OpScope {
 #define LP(lane) lane_point(e, &(lane) == &e->side)
 
 // ---- layer launchers --------------------------------------------------------------
-// operand prologue of a pointwise conv (bf16 mode): Xe = swish(X*psc+psh)*gate, psc == null: X*gate
-struct Prologue { const float* psc; const float* psh; const float* gate; };
+// operand prologue of a pointwise conv: Xe = swish(X*psc+psh)*gate, psc == null: X*gate, gate == null: none
+struct Prologue { const float *psc = nullptr, *psh = nullptr, *gate = nullptr; };
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2 };      // the `act` of the kernels' epilogues
+// epilogue of a forward conv: y = act(conv * scale + shift + res); scale == null: the raw output
+struct Epilogue { const float *scale = nullptr, *shift = nullptr; In res; int act = ACT_NONE; };
+// what a forward conv takes beyond operand and output; `stats`: where the BatchNorm partial sums of the raw output go
+struct FwdOps { float* stats = nullptr; Prologue pro; Epilogue epi; };
 
 // planes of an fp32 NHWC operand nobody produced planes for (test hooks): [C/32][3][npix][32] in the scratch buffer
 const unsigned short* scratch_planes(fm_engine* e, Lane& L, const float* x, long long npix, int C)
@@ -1227,24 +1250,24 @@ static int stats_tiles_for(Arm fwd, const Conv& c, int imgs_per_group, int group
     }
 }
 
-// xp: the input's block-major planes (planes mode; null = made here from x); yp: also / only write the output's planes
-// (eval epilogue; y may then be null)
-void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, float* y, int imgs, int groups,
-              const float* scale, const float* shift, const float* res, int relu, float* stats,
-              const Prologue* pro = nullptr, const unsigned short* xp = nullptr, unsigned short* yp = nullptr,
-              const unsigned short* resp = nullptr)
+// The forward conv in its raw form (no FwdOps: the test hooks) and as conv_fwd_train / conv_fwd_eval hand it on.  The planes
+// kernels read x.p, write y.p and add res.p; only their eval epilogue writes planes, and y.f may then be null
+void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, In x, Out y, int imgs, int groups, const FwdOps& o = {})
 {
     Conv& c = e->convs[ci];
+    const Epilogue& ep = o.epi;
+    const Prologue& pro = o.pro;
+    float* const stats = o.stats;
     const Arm arm = fwd_arm(e, c, imgs);
-    const int tiles_n = stats_tiles_for(arm, c, imgs / groups, groups, pro && pro->gate);
+    const int tiles_n = stats_tiles_for(arm, c, imgs / groups, groups, pro.gate != nullptr);
     if (stats) { e->stats_conv = ci; e->stats_tiles_n = tiles_n; }
     const int fam = prof_family(arm, c.cout_p);
     const double flops = 2.0 * c.macs_per_img * imgs;
     switch (arm) {
     case Arm::StemRows: {                    // `x` is ignored: the operand is the framed image's planes (to_nhwc4)
         StemRowsParams q{};
-        q.Xp = e->x3p + (size_t)e->in_img0 * c.Hp * c.Wp * 4; q.Wst = W.wst; q.Y = y;
-        q.scale = scale; q.shift = shift; q.stats = stats; q.relu = relu;
+        q.Xp = e->x3p + (size_t)e->in_img0 * c.Hp * c.Wp * 4; q.Wst = W.wst; q.Y = y.f;
+        q.scale = ep.scale; q.shift = ep.shift; q.stats = stats; q.relu = ep.act;
         q.imgs = imgs; q.imgs_per_group = imgs / groups; q.Hp = c.Hp; q.Wp = c.Wp; q.Ho = c.hout; q.Wo = c.wout;
         q.sp = e->products; q.plane_bytes = e->x3p_plane_elems * 2;
         ProfScope ps(e, L, fam, flops);
@@ -1256,13 +1279,13 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
         PwParams q{};
         q.zeros = e->zeros;
         q.W = W.wb + c.wb_off;
-        q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x); q.Y = reinterpret_cast<bf16*>(y);
+        q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x.f); q.Y = reinterpret_cast<bf16*>(y.f);
         if (stem16) q.X += (size_t)e->in_img0 * c.hout * c.wout * c.Kw;
         q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p;
         q.npix = (imgs / groups) * c.hout * c.wout; q.groups = groups;
-        q.scale = scale; q.shift = shift; q.res = reinterpret_cast<const bf16*>(res); q.act = relu;
+        q.scale = ep.scale; q.shift = ep.shift; q.res = reinterpret_cast<const bf16*>(ep.res.f); q.act = ep.act;
         q.stats = stats;
-        if (pro && pro->gate) { q.psc = pro->psc; q.psh = pro->psh; q.gate = pro->gate; }
+        if (pro.gate) { q.psc = pro.psc; q.psh = pro.psh; q.gate = pro.gate; }
         q.HW = c.hout * c.wout;
         launch_pw_conv(q, L.st);
         return;
@@ -1271,38 +1294,38 @@ void conv_fwd(fm_engine* e, Lane& L, int ci, const Weights& W, const float* x, f
     default: soft(e, hipErrorInvalidValue); return;
     }
     IgemmParams p{};
-    p.Y = y; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
+    p.Y = y.f; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
     conv_fwd_geometry(c, p);
-    p.res = res; p.scale = scale; p.shift = shift; p.stats = stats;
+    p.res = ep.res.f; p.scale = ep.scale; p.shift = ep.shift; p.stats = stats;
     p.Ho = c.hout; p.Wo = c.wout; p.Co = c.cout_p;
     p.os = 1; p.oh0 = 0; p.ow0 = 0;
     p.imgs_per_group = imgs / groups;
     p.tilesN = tiles_n;
-    p.relu = relu;           // 0 none, 1 relu, 2 swish
+    p.relu = ep.act;
     if (arm == Arm::PconvTs || arm == Arm::PconvTap) {
         p.xp_pix = (long long)imgs * c.hin * c.win;
-        p.Xp = xp ? xp : scratch_planes(e, L, x, p.xp_pix, c.cin_p);
+        p.Xp = x.p ? x.p : scratch_planes(e, L, x.f, p.xp_pix, c.cin_p);
         p.Wsp = W.wpl_f + c.pl_off;
-        p.Yp = yp; p.yp_pix = (long long)imgs * c.hout * c.wout; p.resp = resp;
+        p.Yp = y.p; p.yp_pix = (long long)imgs * c.hout * c.wout; p.resp = ep.res.p;
         p.tilesM = c.cout_p / pconv_tile_m(c.cout_p);
         ProfScope ps(e, L, fam, flops);
         launch_pconv(p, groups, L.st);
         return;
     }
-    p.W = W.state + c.w_off; p.X = x; p.zeros = e->zeros; p.nsteps = c.nsteps;
+    p.W = W.state + c.w_off; p.X = x.f; p.zeros = e->zeros; p.nsteps = c.nsteps;
     if (!e->planes && c.pl_off >= 0) p.Wsp = W.wpl_f + c.pl_off;      // row-major planes
     if (c.cin == 3) {
         p.stem_kw = c.k; p.stem_pad = c.pad; p.stem_h2 = c.kw_p == 8 ? 1 : 0; p.stem3 = c.stem3 ? 1 : 0;
         if (c.stem3) p.X = e->x3 + (size_t)e->in_img0 * c.Hp * c.Wp * 3;     // `x` is ignored: the operand is the framed NHWC3 image
-        else p.X = x + (size_t)e->in_img0 * c.hin * c.win * 4;
+        else p.X = x.f + (size_t)e->in_img0 * c.hin * c.win * 4;
     }
     if (c.stem3) { p.Hi = c.Hp; p.Wi = c.Wp; }
-    if (pro && pro->gate) {       // fp32 project conv: only the streaming kernel (conv1x1.hip) applies the gate (eval) or BN1 + Swish + gate (train)
-        p.gate = pro->gate; p.gate_HW = c.hout * c.wout; p.psc = pro->psc; p.psh = pro->psh;
+    if (pro.gate) {       // fp32 project conv: only the streaming kernel (conv1x1.hip) applies the gate (eval) or BN1 + Swish + gate (train)
+        p.gate = pro.gate; p.gate_HW = c.hout * c.wout; p.psc = pro.psc; p.psh = pro.psh;
         // the streaming kernel has a gate-only eval form (no statistics) and a BN1 + Swish + gate train form (statistics): a
         // gate-only prologue WITH statistics, or a full prologue without them, has no instantiation
-        if (!conv1x1_stream_takes(c.cin_p, c.cout_p, c.cout_p) || c.k != 1 || c.stride != 1 || (pro->psc && !stats) ||
-            (!pro->psc && stats))
+        if (!conv1x1_stream_takes(c.cin_p, c.cout_p, c.cout_p) || c.k != 1 || c.stride != 1 || (pro.psc && !stats) ||
+            (!pro.psc && stats))
             soft(e, hipErrorInvalidValue);
     }
     p.tilesM = (c.cout_p + igemm_tile_m(c.cout_p) - 1) / igemm_tile_m(c.cout_p);
@@ -1318,10 +1341,10 @@ int stats_tiles(fm_engine* e, int ci)
     return e->stats_tiles_n;
 }
 
-// dx[imgs][hin][win][cin] = dgrad(dy[imgs][hout][wout][cout]); res: optional residual added
-// (for stride-2 convs `acc_cls0` adds the existing dx contents for parity class (0,0))
-void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int imgs, const float* res,
-                bool acc_cls0, const unsigned short* dyp = nullptr)
+// what a data gradient adds to its output: a residual, or (stride-2 convs) dx's own contents at parity class (0,0)
+struct DgradAdd { const float* res = nullptr; bool acc_cls0 = false; };
+// dx[imgs][hin][win][cin] = dgrad(dy[imgs][hout][wout][cout])
+void conv_dgrad(fm_engine* e, Lane& L, int ci, In dy, float* dx, int imgs, const DgradAdd& add = {})
 {
     Conv& c = e->convs[ci];
     const Arm arm = dgrad_arm(e, c, imgs);
@@ -1331,10 +1354,10 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
         PwParams q{};
         q.zeros = e->zeros;
         q.W = e->student.wb + c.wbt_off;
-        q.X = reinterpret_cast<const bf16*>(dy); q.Y = reinterpret_cast<bf16*>(dx);
+        q.X = reinterpret_cast<const bf16*>(dy.f); q.Y = reinterpret_cast<bf16*>(dx);
         q.M = c.cin_p; q.K = c.cout_p;
         q.npix = imgs * c.hout * c.wout; q.groups = 1;
-        q.res = reinterpret_cast<const bf16*>(res);
+        q.res = reinterpret_cast<const bf16*>(add.res);
         q.HW = c.hout * c.wout;
         launch_pw_conv(q, L.st);
         return;
@@ -1343,13 +1366,13 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
     default: soft(e, hipErrorInvalidValue); return;
     }
     const bool planes = arm != Arm::Igemm;
-    if (planes && !dyp) dyp = scratch_planes(e, L, dy, xp_pix, c.cout_p);
+    if (planes && !dy.p) dy.p = scratch_planes(e, L, dy.f, xp_pix, c.cout_p);
     for (int k = 0; k < c.ncls; ++k) {
         DgradClass& d = c.cls[k];
         IgemmParams p{};
         p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
         conv_dgrad_geometry(c, d, p);
-        p.res = res ? res : ((acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
+        p.res = add.res ? add.res : ((add.acc_cls0 && d.ph == 0 && d.pw == 0) ? dx : nullptr);
         p.Ho = c.hin; p.Wo = c.win; p.Co = c.cin_p;
         p.os = c.stride; p.oh0 = d.ph; p.ow0 = d.pw;
         p.imgs_per_group = imgs;
@@ -1358,12 +1381,12 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
         p.tilesN = (imgs * p.Hg * p.Wg + bn - 1) / bn;
         const double flops = 2.0 * c.macs_per_img * imgs * d.taps.n / (double)(c.k * c.k);
         if (planes) {
-            p.Xp = dyp; p.xp_pix = xp_pix; p.Wsp = e->wpl_d + d.pl_off;
+            p.Xp = dy.p; p.xp_pix = xp_pix; p.Wsp = e->wpl_d + d.pl_off;
             p.tilesM = c.cin_p / pconv_tile_m(c.cin_p);
             ProfScope ps(e, L, prof_family(pconv_arm(p), c.cin_p), flops);       // this class's own kernel
             launch_pconv(p, 1, L.st);
         } else {
-            p.W = d.wpack; p.X = dy; p.zeros = e->zeros; p.nsteps = d.nsteps;
+            p.W = d.wpack; p.X = dy.f; p.zeros = e->zeros; p.nsteps = d.nsteps;
             if (!e->planes && d.pl_off >= 0) p.Wsp = e->wpl_d + d.pl_off;
             p.tilesM = (c.cin_p + igemm_tile_m(c.cin_p) - 1) / igemm_tile_m(c.cin_p);
             ProfScope ps(e, L, prof_family(arm, c.cin_p), flops);
@@ -1377,8 +1400,7 @@ void conv_dgrad(fm_engine* e, Lane& L, int ci, const float* dy, float* dx, int i
 // 3x3's class (0,0) -- the same dy pixel -- and the same output grid: its K-steps ride behind that job's own, with dyd's planes
 // as the job's second operand.  Every element of dx is written once; nothing is read back.  false = the shapes are not of that
 // kind (or not planes mode): the caller runs the two conv_dgrad calls.
-bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, const float* dyd, float* dx, int imgs,
-                 const unsigned short* dy1p = nullptr, const unsigned short* dydp = nullptr)
+bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, In dy1, In dyd, float* dx, int imgs)
 {
     Conv& c = e->convs[c1i];
     Conv& d = e->convs[dsi];
@@ -1391,15 +1413,15 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
         return false;
     const DgradClass& c0 = c.cls[0];
     if (c0.ph != 0 || c0.pw != 0 || c0.taps.n != 1 || c0.dh[0] != 0 || c0.dw[0] != 0) return false;
-    if (!dy1p) dy1p = scratch_planes(e, L, dy1, xp_pix, c.cout_p);
-    if (!dydp) {
+    if (!dy1.p) dy1.p = scratch_planes(e, L, dy1.f, xp_pix, c.cout_p);
+    if (!dyd.p) {
         if ((size_t)xp_pix * d.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return true; }
-        k_split_planes(dyd, e->xp_scratch2, xp_pix, d.cout_p, L.st);
-        dydp = e->xp_scratch2;
+        k_split_planes(dyd.f, e->xp_scratch2, xp_pix, d.cout_p, L.st);
+        dyd.p = e->xp_scratch2;
     }
-    if (!dy1p) return true;                    // (scratch_planes reported it)
+    if (!dy1.p) return true;                    // (scratch_planes reported it)
     IgemmParams p{};
-    p.Xp = dy1p; p.Xp2 = dydp; p.xp_pix = xp_pix; p.Wsp = e->wpl_d;
+    p.Xp = dy1.p; p.Xp2 = dyd.p; p.xp_pix = xp_pix; p.Wsp = e->wpl_d;
     p.Y = dx; p.slab = L.sk_slab; p.counters = L.sk_counters; p.err = e->dev_err; p.err_host = e->host_err_dev; p.sp = e->products;
     p.M = c.cin_p;
     p.Hi = c.hout; p.Wi = c.wout; p.Ci = c.cout_p;
@@ -1428,9 +1450,8 @@ bool block_dgrad(fm_engine* e, Lane& L, int c1i, int dsi, const float* dy1, cons
     return true;
 }
 
-// xp / dyp (planes mode): block-major planes of x / dy (null = made here from the fp32 tensors: test hooks)
-void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, int imgs, const Prologue* pro = nullptr,
-                int pix_per_group = 0, const unsigned short* xp = nullptr, const unsigned short* dyp = nullptr)
+// pro: the operand x is re-formed on load (bf16 project conv), its BatchNorm statistics per group of pix_per_group pixels
+void conv_wgrad(fm_engine* e, Lane& L, int ci, In x, In dy, int imgs, const Prologue& pro = {}, int pix_per_group = 0)
 {
     const Conv& c = e->convs[ci];
     const Arm arm = wgrad_arm(e, c, imgs);
@@ -1442,13 +1463,13 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
     case Arm::PwgradRing: {
         PwgradParams q{};
         pwgrad_geometry(e, c, imgs, q);
-        if (!xp) xp = scratch_planes(e, L, x, q.xpix, c.cin_p);
-        if (!dyp) {
+        if (!x.p) x.p = scratch_planes(e, L, x.f, q.xpix, c.cin_p);
+        if (!dy.p) {
             if ((size_t)q.npix * c.cout_p * 3 > e->xp_scratch_elems) { soft(e, hipErrorInvalidValue); return; }
-            k_split_planes(dy, e->xp_scratch2, q.npix, c.cout_p, L.st);
-            dyp = e->xp_scratch2;
+            k_split_planes(dy.f, e->xp_scratch2, q.npix, c.cout_p, L.st);
+            dy.p = e->xp_scratch2;
         }
-        q.dYp = dyp; q.Xp = xp; q.slab = L.ws_slab;
+        q.dYp = dy.p; q.Xp = x.p; q.slab = L.ws_slab;
         ProfScope ps(e, L, fam, flops);
         sk = arm == Arm::PwgradRing ? launch_pwgrad_ring(q, e->slab_floats, L.st) : launch_pwgrad(q, e->slab_floats, L.st);
         if (sk <= 0) soft(e, hipErrorInvalidValue);
@@ -1457,9 +1478,9 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
     case Arm::PwWgrad: {
         const bool stem16 = c.cin == 3;
         PwWgradParams q{};
-        q.dY = reinterpret_cast<const bf16*>(dy); q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x);
+        q.dY = reinterpret_cast<const bf16*>(dy.f); q.X = reinterpret_cast<const bf16*>(stem16 ? e->stem_col : x.f);
         q.slab = L.ws_slab; q.M = c.cout_p; q.K = stem16 ? c.Kw : c.cin_p; q.npix = imgs * c.hout * c.wout;
-        if (pro && pro->gate) { q.psc = pro->psc; q.psh = pro->psh; q.gate = pro->gate; }
+        if (pro.gate) { q.psc = pro.psc; q.psh = pro.psh; q.gate = pro.gate; }
         q.HW = c.hout * c.wout; q.pix_per_group = pix_per_group ? pix_per_group : q.npix;
         sk = launch_pw_wgrad(q, e->slab_floats, L.st);
         if (sk <= 0) g_err = "pw_wgrad: shape not handled";
@@ -1469,7 +1490,7 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
     case Arm::WgradGeneric:
     case Arm::WgradGenericStem: {
         WgradParams p{};
-        p.dY = dy; p.X = x; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
+        p.dY = dy.f; p.X = x.f; p.slab = L.ws_slab; p.tab = c.tab; p.zeros = e->zeros;
         wgrad_geometry(e, c, imgs, p);
         if (c.stem3) p.X = e->x3;
         ProfScope ps(e, L, fam, flops);
@@ -1502,50 +1523,92 @@ void conv_wgrad(fm_engine* e, Lane& L, int ci, const float* x, const float* dy, 
     if (c.stem3) k_stem3_mask_grad(e->grad + c.w_off, c.cout_p, L.st);
 }
 
+// where BatchNorm b's parameters live: the student's gamma / beta / running statistics and the gradient arena's dgamma / dbeta
+struct BnSlots { float *gamma, *beta, *run_mean, *run_var, *dgamma, *dbeta; };
+BnSlots bn_slots(const fm_engine* e, const Bn& b)
+{
+    float *S = e->student.state + b.ch_off, *G = e->grad + b.ch_off;
+    return {S + e->off_gamma, S + e->off_beta, S + e->off_rm, S + e->off_rv, G + e->off_gamma, G + e->off_beta};
+}
+
 // frozen statistics: mean / istd / scale / shift of every group from the running statistics, which stay as they are
 void bn_fwd_fixed(fm_engine* e, Lane& L, Bn& b, int groups)
 {
-    k_bn_finalize_frozen(groups, b.C, e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
-                         e->student.state + e->off_rm + b.ch_off, e->student.state + e->off_rv + b.ch_off, b.mean, b.istd, b.scale, b.shift,
-                         e->bn_eps, L.st, e->dev_err);
+    const BnSlots s = bn_slots(e, b);
+    k_bn_finalize_frozen(groups, b.C, s.gamma, s.beta, s.run_mean, s.run_var, b.mean, b.istd, b.scale, b.shift, e->bn_eps, L.st, e->dev_err);
 }
-
+// The finalize of a train-mode BatchNorm bi from `tiles` partial sums per group in `part`, `count` values per group and channel;
+// the running statistics and the counter move in BnMode::Batch alone.  skip: the step's skip word, where the caller has one
+void bn_fwd_stats(fm_engine* e, Lane& L, int bi, const float* part, int groups, int tiles, int count, BnMode mode, const int* skip)
+{
+    Bn& b = e->bns[bi];
+    if (mode == BnMode::Frozen) { bn_fwd_fixed(e, L, b, groups); return; }
+    const BnSlots s = bn_slots(e, b);
+    const bool run = mode == BnMode::Batch;
+    k_bn_finalize(part, groups, tiles, b.C, count, s.gamma, s.beta, run ? s.run_mean : nullptr, run ? s.run_var : nullptr, b.mean, b.istd,
+                  b.scale, b.shift, e->bn_eps, e->bn_mom, L.st, skip);
+    if (run) e->student.counters[bi] += groups;
+}
 // BN statistics of conv `ci`'s output (partials left in ws_stats by the conv epilogue)
 void bn_fwd_finalize(fm_engine* e, Lane& L, int ci, int groups, int imgs_per_group, BnMode mode)
 {
     const Conv& c = e->convs[ci];
-    const int bi = c.bn;
-    Bn& b = e->bns[bi];
-    if (mode == BnMode::Frozen) { bn_fwd_fixed(e, L, b, groups); return; }
-    const bool run = mode == BnMode::Batch;
-    k_bn_finalize(e->ws_stats, groups, stats_tiles(e, ci), b.C, imgs_per_group * c.hout * c.wout,
-                  e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
-                  run ? e->student.state + e->off_rm + b.ch_off : nullptr, run ? e->student.state + e->off_rv + b.ch_off : nullptr, b.mean,
-                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, L.st, e->dev_err);
-    if (run) e->student.counters[bi] += groups;
+    // (frozen statistics read no partials: nothing is asked of ws_stats)
+    const int tiles = mode == BnMode::Frozen ? 0 : stats_tiles(e, ci);
+    bn_fwd_stats(e, L, c.bn, e->ws_stats, groups, tiles, imgs_per_group * c.hout * c.wout, mode, e->dev_err);
 }
 
-// backward through BN bi: dz (+ optional relu mask source z) -> dy ; optional masked grad out
-// z_is_relu_of_bn: z = relu(bn(y)) of THIS BatchNorm with nothing added (bn1 of a basic block): the ReLU mask is then
-// recomputed from y, which both passes read anyway, and z is not read (FM_BN_MASK_FROM_Y=0 reads z as before)
-// dyp (planes mode): also write dy's block-major planes (what the data gradient reads)
-// zh (planes mode): z is kept only as planes: the mask is the sign of its h plane (z is then null)
-void bn_bwd(fm_engine* e, Lane& L, int bi, const float* dz, const float* z, float* dy, float* dyh_out, int groups,
-            int imgs_per_group, bool frozen, bool z_is_relu_of_bn = false, unsigned short* dyp = nullptr, const unsigned short* zh = nullptr)
+// The forward conv as the train graphs run it: the raw output into Conv::y, its partial statistics into ws_stats, then the
+// BatchNorm finalize.  op: the conv's label for fm_profile_ops (EfficientNet-B0); ResNet-18's forwards are delay points only
+void conv_fwd_train(fm_engine* e, Lane& L, int ci, const Weights& W, In x, int groups, int B, BnMode mode, const char* op = nullptr,
+                    const Prologue& pro = {})
+{
+    const Out y{e->convs[ci].y};
+    const FwdOps o{.stats = e->ws_stats, .pro = pro};
+    if (op) {
+        { OP(L, op); conv_fwd(e, L, ci, W, x, y, groups * B, groups, o); }
+        { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, ci, groups, B, mode); }
+    } else {
+        LP(L); conv_fwd(e, L, ci, W, x, y, groups * B, groups, o);
+        LP(L); bn_fwd_finalize(e, L, ci, groups, B, mode);
+    }
+}
+// ... and as the eval graphs do: BatchNorm folded into the epilogue (W's eval affine of the conv's BatchNorm), one group
+void conv_fwd_eval(fm_engine* e, Lane& L, int ci, const Weights& W, In x, Out y, int imgs, int act, In res = {}, const Prologue& pro = {})
+{
+    const int ch = e->bns[e->convs[ci].bn].ch_off;
+    conv_fwd(e, L, ci, W, x, y, imgs, 1, {.pro = pro, .epi = {W.ev_scale + ch, W.ev_shift + ch, res, act}});
+}
+
+// The finalize of BatchNorm b's backward from `partials` partial sums per group in ws_part: the coefficients ca / cb / cc of the
+// apply pass, dgamma and dbeta
+void bn_bwd_finalize(fm_engine* e, Lane& L, const Bn& b, int groups, int partials, int count, bool frozen)
+{
+    const BnSlots s = bn_slots(e, b);
+    k_bn_bwd_finalize(e->ws_part, groups, partials, b.C, count, s.gamma, b.mean, b.istd, e->ca, e->cb, e->cc, s.dgamma, s.dbeta, L.st, frozen);
+}
+// Where bn_bwd takes the mask of the ReLU behind the BatchNorm from.  Z: the fp32 z; ZPlane: z is kept only as planes, the mask is
+// the sign of its h plane; OwnOutput: z = relu(bn(y)) of THIS BatchNorm with nothing added (bn1 of a basic block): the mask is
+// recomputed from y, which both passes read anyway, and z is not read (FM_BN_MASK_FROM_Y=0 reads an fp32 z as before)
+enum class Mask { None, Z, ZPlane, OwnOutput };
+// backward through BN bi: dz -> dy in the forms dy names (planes: what the data gradient reads); dyh_out: the masked gradient
+void bn_bwd(fm_engine* e, Lane& L, int bi, const float* dz, Out dy, int groups, int imgs_per_group, bool frozen, Mask mask = Mask::None,
+            In z = {}, float* dyh_out = nullptr)
 {
     const Conv& c = e->convs[bi];
     Bn& b = e->bns[bi];
     const int pix = imgs_per_group * c.hout * c.wout;
     const char* fy = getenv("FM_BN_MASK_FROM_Y");          // read per call: tests compare both forms in one process
     const int from_y = fy ? atoi(fy) : 1;
-    const float *msc = nullptr, *msh = nullptr;
-    if (z_is_relu_of_bn && (z || zh) && (from_y || !z)) { msc = b.scale; msh = b.shift; z = nullptr; zh = nullptr; }
-    k_bn_bwd_reduce(dz, z, c.y, b.mean, b.istd, e->ws_part, groups, pix, b.C, L.st, msc, msh, zh);
-    k_bn_bwd_finalize(e->ws_part, groups, bn_bwd_blocks(pix), b.C, pix, e->student.state + e->off_gamma + b.ch_off, b.mean,
-                      b.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b.ch_off,
-                      e->grad + e->off_beta + b.ch_off, L.st, frozen);
-    if (dyp) k_bn_bwd_apply_planes(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyp, dyh_out, groups, pix, b.C, L.st, msc, msh, zh);
-    else k_bn_bwd_apply(dz, z, c.y, e->ca, e->cb, e->cc, dy, dyh_out, groups, pix, b.C, L.st, msc, msh);
+    const float *msc = nullptr, *msh = nullptr, *zf = nullptr;
+    const unsigned short* zh = nullptr;
+    if (mask == Mask::Z || (mask == Mask::OwnOutput && !from_y && z.f)) zf = z.f;
+    else if (mask == Mask::ZPlane) zh = z.p;
+    else if (mask == Mask::OwnOutput) { msc = b.scale; msh = b.shift; }
+    k_bn_bwd_reduce(dz, zf, c.y, b.mean, b.istd, e->ws_part, groups, pix, b.C, L.st, msc, msh, zh);
+    bn_bwd_finalize(e, L, b, groups, bn_bwd_blocks(pix), pix, frozen);
+    if (dy.p) k_bn_bwd_apply_planes(dz, zf, c.y, e->ca, e->cb, e->cc, dy.f, dy.p, dyh_out, groups, pix, b.C, L.st, msc, msh, zh);
+    else k_bn_bwd_apply(dz, zf, c.y, e->ca, e->cb, e->cc, dy.f, dyh_out, groups, pix, b.C, L.st, msc, msh);
 }
 
 void to_nhwc4(fm_engine* e, Lane& L, const float* const* xs, int groups, int B)
@@ -1629,60 +1692,50 @@ void forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mod
     const Weights& W = e->student;
     const float* S = W.state;
     Conv& c0 = e->convs[0];
-    LP(L); conv_fwd(e, L, 0, W, e->x4, c0.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats);
-    LP(L); bn_fwd_finalize(e, L, 0, groups, B, mode);
-    const bool pm = e->planes;
+    conv_fwd_train(e, L, 0, W, {e->x4}, groups, B, mode);
     LP(L);
-    if (pm) k_stem_pool_planes(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, A.p0p, groups, B, c0.hout, c0.wout, 64, L.st);
-    else k_stem_pool(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0, e->idx0, groups, B, c0.hout, c0.wout, 64, L.st);
-    // BatchNorm apply.  Planes mode: the activations z1 / out exist ONLY as planes (what the conv GEMMs read; the residual add
-    // and the ReLU masks of the backward re-form the fp32 value / its sign from them) -- except the last block's `out`, which
-    // feeds the average pool: fp32 only
-    auto apply = [&](const float* y, int b1, const float* res, const unsigned short* resp, const float* y2, int b2, float* out,
-                     unsigned short* outp, int pix, int C) {
-        const float *s2 = y2 ? e->bns[b2].scale : nullptr, *h2 = y2 ? e->bns[b2].shift : nullptr;
+    if (A.p0.p) k_stem_pool_planes(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0.f, e->idx0, A.p0.p, groups, B, c0.hout, c0.wout, 64, L.st);
+    else k_stem_pool(c0.y, e->bns[0].scale, e->bns[0].shift, A.p0.f, e->idx0, groups, B, c0.hout, c0.wout, 64, L.st);
+    // BatchNorm apply of conv ci's output into `out`: + the residual `res`, or + BatchNorm ds of the downsample conv's output; ReLU.
+    // Planes mode: the activations z1 / out exist ONLY as planes (what the conv GEMMs read; the residual add and the ReLU masks of
+    // the backward re-form the fp32 value / its sign from them) -- except the last block's `out`, which feeds the average pool:
+    // fp32 only
+    auto apply = [&](int ci, Out out, In res = {}, int ds = -1) {
+        const Conv& c = e->convs[ci];
+        const Bn& b = e->bns[ci];
+        const float* y2 = ds >= 0 ? e->convs[ds].y : nullptr;
+        const float *s2 = y2 ? e->bns[ds].scale : nullptr, *h2 = y2 ? e->bns[ds].shift : nullptr;
+        const int pix = B * c.hout * c.wout;
         LP(L);
-        if (pm && outp)
-            k_bn_apply_planes(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, nullptr, outp, groups, pix, C, 1, L.st, resp);
-        else
-            k_bn_apply(y, e->bns[b1].scale, e->bns[b1].shift, res, y2, s2, h2, out, groups, pix, C, 1, L.st);
+        if (out.p) k_bn_apply_planes(c.y, b.scale, b.shift, res.f, y2, s2, h2, out.f, out.p, groups, pix, c.cout, 1, L.st, res.p);
+        else k_bn_apply(c.y, b.scale, b.shift, res.f, y2, s2, h2, out.f, groups, pix, c.cout, 1, L.st);
     };
-    const float* cur = A.p0;
-    const unsigned short* curp = A.p0p;
-    bool cur_f32 = true;                 // is `cur` valid as fp32?  (p0 is written both ways)
+    In cur = A.p0;                       // the block's input in the forms that are valid (p0 is written both ways)
     for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
         const Block& blk = e->blocks[bi];
         BlockActs& a = A.blk[bi];
-        Conv& c1 = e->convs[blk.c1];
-        Conv& c2 = e->convs[blk.c2];
-        const int pix = B * c1.hout * c1.wout;
+        const Conv& c1 = e->convs[blk.c1];
         const bool last = bi + 1 == e->blocks.size();
-        LP(L); conv_fwd(e, L, blk.c1, W, cur, c1.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-        LP(L); bn_fwd_finalize(e, L, blk.c1, groups, B, mode);
-        apply(c1.y, blk.c1, nullptr, nullptr, nullptr, -1, a.z1, a.z1p, pix, c1.cout);
-        LP(L); conv_fwd(e, L, blk.c2, W, a.z1, c2.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, a.z1p);
-        LP(L); bn_fwd_finalize(e, L, blk.c2, groups, B, mode);
-        unsigned short* outp = (pm && !last) ? a.outp : nullptr;
+        conv_fwd_train(e, L, blk.c1, W, cur, groups, B, mode);
+        apply(blk.c1, kept(a.z1));
+        conv_fwd_train(e, L, blk.c2, W, kept(a.z1), groups, B, mode);
+        const Out out = last ? Out{a.out.f} : kept(a.out);
         if (blk.ds >= 0) {
-            Conv& cd = e->convs[blk.ds];
-            LP(L); conv_fwd(e, L, blk.ds, W, cur, cd.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, nullptr, curp);
-            LP(L); bn_fwd_finalize(e, L, blk.ds, groups, B, mode);
-            apply(c2.y, blk.c2, nullptr, nullptr, cd.y, blk.ds, a.out, outp, pix, c2.cout);
-        } else if (pm && !cur_f32) {
-            if (last) {      // the last block adds a planes-only residual into an fp32 output: re-form the residual first
-                LP(L); k_planes_to_f32(curp, A.blk[bi - 1].out, (long long)imgs * c1.hin * c1.win, c1.cin, L.st);
-                apply(c2.y, blk.c2, A.blk[bi - 1].out, nullptr, nullptr, -1, a.out, nullptr, pix, c2.cout);
-            } else
-                apply(c2.y, blk.c2, nullptr, curp, nullptr, -1, a.out, outp, pix, c2.cout);
+            conv_fwd_train(e, L, blk.ds, W, cur, groups, B, mode);
+            apply(blk.c2, out, {}, blk.ds);
         } else {
-            apply(c2.y, blk.c2, cur, nullptr, nullptr, -1, a.out, outp, pix, c2.cout);
+            In idt = cur.f ? In{cur.f} : cur;
+            if (last && !idt.f) {      // the last block adds a planes-only residual into an fp32 output: re-form the residual first
+                float* f32 = A.blk[bi - 1].out.f;
+                LP(L); k_planes_to_f32(cur.p, f32, (long long)imgs * c1.hin * c1.win, c1.cin, L.st);
+                idt = {f32};
+            }
+            apply(blk.c2, out, idt);
         }
-        cur = a.out;
-        curp = a.outp;
-        cur_f32 = !(pm && !last);
+        cur = out;
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    LP(L); k_avgpool(cur, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
+    LP(L); k_avgpool(cur.f, DT_F32, e->feat, imgs, cl.hout * cl.wout, 512, L.st);
     LP(L); k_fc_fwd(e->feat, S + e->off_fcw, S + e->off_fcb, e->logits, imgs, 512, e->C, L.st);
     if (mode != BnMode::Frozen) net_changed(e, e->student, Moved::Stats);
 }
@@ -1692,40 +1745,30 @@ void forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, float* f
 {
     const float* S = W.state;
     LP(L); ensure_eval_affine(e, L, W);
-    auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
-    auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
     Conv& c0 = e->convs[0];
-    LP(L); conv_fwd(e, L, 0, W, e->x4, A.stem_y, imgs, 1, sc(0), sh(0), nullptr, 1, nullptr);
-    const bool pm = e->planes;
+    LP(L); conv_fwd_eval(e, L, 0, W, {e->x4}, {A.stem_y}, imgs, ACT_RELU);
     LP(L);
-    if (pm) k_stem_pool_planes(A.stem_y, nullptr, nullptr, A.p0, nullptr, A.p0p, 1, imgs, c0.hout, c0.wout, 64, L.st);
-    else k_stem_pool(A.stem_y, nullptr, nullptr, A.p0, nullptr, 1, imgs, c0.hout, c0.wout, 64, L.st);
-    const float* cur = A.p0;
-    const unsigned short* curp = A.p0p;
-    bool cur_f32 = true;
+    if (A.p0.p) k_stem_pool_planes(A.stem_y, nullptr, nullptr, A.p0.f, nullptr, A.p0.p, 1, imgs, c0.hout, c0.wout, 64, L.st);
+    else k_stem_pool(A.stem_y, nullptr, nullptr, A.p0.f, nullptr, 1, imgs, c0.hout, c0.wout, 64, L.st);
+    In cur = A.p0;
     for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
         const Block& blk = e->blocks[bi];
         BlockActs& a = A.blk[bi];
         // planes mode: z1 and `out` exist only as planes (the next convs read them; the next block's residual add re-forms the fp32
         // values in the epilogue) -- except the last block's `out`, which feeds the average pool: fp32 only
         const bool last = bi + 1 == e->blocks.size();
-        LP(L); conv_fwd(e, L, blk.c1, W, cur, pm ? nullptr : a.z1, imgs, 1, sc(blk.c1), sh(blk.c1), nullptr, 1, nullptr, nullptr, curp,
-                 pm ? a.z1p : nullptr);
-        const float* idt = cur;
-        const unsigned short* idtp = nullptr;
+        LP(L); conv_fwd_eval(e, L, blk.c1, W, cur, kept(a.z1), imgs, ACT_RELU);
+        In idt = cur.f ? In{cur.f} : cur;
         if (blk.ds >= 0) {
-            LP(L); conv_fwd(e, L, blk.ds, W, cur, a.ds_y, imgs, 1, sc(blk.ds), sh(blk.ds), nullptr, 0, nullptr, nullptr, curp);
-            idt = a.ds_y;
-        } else if (!cur_f32) { idt = nullptr; idtp = curp; }
-        const bool planes_only = pm && !last;
-        LP(L); conv_fwd(e, L, blk.c2, W, a.z1, planes_only ? nullptr : a.out, imgs, 1, sc(blk.c2), sh(blk.c2), idt, 1, nullptr, nullptr,
-                 a.z1p, planes_only ? a.outp : nullptr, idtp);
-        cur = a.out;
-        curp = a.outp;
-        cur_f32 = !planes_only;
+            LP(L); conv_fwd_eval(e, L, blk.ds, W, cur, {a.ds_y}, imgs, ACT_NONE);
+            idt = {a.ds_y};
+        }
+        const Out out = last ? Out{a.out.f} : kept(a.out);
+        LP(L); conv_fwd_eval(e, L, blk.c2, W, kept(a.z1), out, imgs, ACT_RELU, idt);
+        cur = out;
     }
     const Conv& cl = e->convs[e->blocks.back().c2];
-    LP(L); k_avgpool(cur, DT_F32, feat, imgs, cl.hout * cl.wout, 512, L.st);
+    LP(L); k_avgpool(cur.f, DT_F32, feat, imgs, cl.hout * cl.wout, 512, L.st);
     LP(L); k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, 512, e->C, L.st);
 }
 
@@ -1974,6 +2017,16 @@ void side_join(fm_engine* e)
     soft(e, hipEventRecord(e->ev_wdone, e->side.st));
     soft(e, lane_wait(e, FM_WAIT_SIDE_JOIN, e->main.st, e->ev_wdone));
 }
+// One weight gradient on the side lane: the fork behind tensor k of parity par, its fm_profile_ops scope, `launch(lane)`, the
+// "consumed" event.  forked: the backward's note that side_join has something to bring back
+template <typename Launch>
+void side_wgrad(fm_engine* e, bool& forked, int k, int par, const char* op, Launch&& launch)
+{
+    forked = true;
+    Lane& SL = side_begin(e, k, par);
+    { OP(SL, op); launch(SL); }
+    side_end(e, k, par);
+}
 
 // backward from e->dlogits (and bw.dfeat) through the student's activation set, as forward_train left it, into e->grad on the
 // main lane, the weight gradients on the side lane; then Adam unless bw.step is false (fm_backward_grads)
@@ -1984,15 +2037,6 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     const Acts& A = e->acts;
     const float* S = e->student.state;
     const Conv& cl = e->convs[e->blocks.back().c2];
-    // side_w (stream_mode 0): d y2, d y_ds, d y1 double-buffered by block parity for the weight gradients on the side lane
-    const bool sw = e->side_w;
-    float* GBp[2] = {e->GB, sw ? e->GB2 : e->GB};
-    float* GCp[2] = {e->GC, sw ? e->GC2 : e->GC};
-    float* GDp[2] = {e->GD, sw ? e->GD2 : e->GD};
-    const bool pm = e->planes;
-    unsigned short* PB[2] = {e->GBp, sw ? e->GB2p : e->GBp};
-    unsigned short* PC[2] = {e->GCp, sw ? e->GC2p : e->GCp};
-    unsigned short* PD[2] = {e->GDp, sw ? e->GD2p : e->GDp};
     // Under a mask (bw.train): units in forward order are the stem (0), the BasicBlocks (1 + b) and fc (nb + 1); `first` is the
     // first one with a trainable parameter.  Without a wanted dx nothing of a unit before it is enqueued, and a frozen conv's
     // weight gradient is not launched (nor its side-lane fork opened).  No mask: first = 0, every flag true, the list below
@@ -2012,7 +2056,6 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         if (conv_on(e, tr, 0) || bn_on(e, tr, 0)) first = 0;
     }
     bool forked = false;               // a weight gradient went to the side lane: join it at the end
-    auto side = [&](int k, int par) -> Lane& { forked = true; return side_begin(e, k, par); };
     if (first > nb + 1) return;        // nothing is trainable and no dx is wanted
     e->ctx = 500;
     { OP(L, "k_fc_bwd"); k_fc_bwd(e->dlogits, e->feat, S + e->off_fcw, nullptr, e->grad + e->off_fcw, e->grad + e->off_fcb, e->GA, DT_F32, imgs,
@@ -2023,53 +2066,40 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         e->ctx = 400 + b;                          // backward ops @400..@407 (fc @500, stem @399), like EfficientNet's
         const BlockActs& a = A.blk[b];
         const int par = b & 1;
-        float *GB = GBp[par], *GC = GCp[par], *GD = GDp[par];
-        unsigned short *gbp = pm ? PB[par] : nullptr, *gcp = pm ? PC[par] : nullptr, *gdp = pm ? PD[par] : nullptr;
-        const float* in = b == 0 ? A.p0 : A.blk[b - 1].out;
-        // out = relu(bn2(y2) + identity): masked grad dyh goes to bn2 and to the identity path
-        // planes mode: d y2 / d y_ds / d y1 exist only as planes (read by the data gradients and the weight gradients); the ReLU
-        // mask of `out` is the sign of its h plane (the last block's `out` is fp32: it feeds the average pool)
+        // side_w (stream_mode 0): d y2, d y_ds, d y1 double-buffered by block parity for the weight gradients on the side lane.
+        // planes mode: they exist only as planes (read by the data gradients and the weight gradients) -- d y1's fp32 buffer still
+        // takes d z1, the data gradient of conv 2
+        const ResGrads& g = e->rg[par];
+        const Out dy2 = kept(g.dy2), dyd = kept(g.dyd), dy1 = kept(g.dy1);
+        const In in = b == 0 ? In(A.p0) : In(A.blk[b - 1].out);
+        // out = relu(bn2(y2) + identity): masked grad dyh goes to bn2 and to the identity path.  The ReLU mask of an `out` kept as
+        // planes is the sign of its h plane (the last block's `out` is fp32: it feeds the average pool)
         const bool last = b + 1 == (int)e->blocks.size();
+        const In zo = last ? In{a.out.f} : In(kept(a.out));
         side_guard(e, 0, par);
-        { OP(L, "bn_bwd");
-          if (pm && !last) bn_bwd(e, L, blk.c2, ga, nullptr, nullptr, ga, groups, B, bw.frozen, false, gbp, a.outp);
-          else bn_bwd(e, L, blk.c2, ga, a.out, pm ? nullptr : GB, ga, groups, B, bw.frozen, false, gbp); }
-        if (blk.ds >= 0) { side_guard(e, 1, par); OP(L, "bn_bwd"); bn_bwd(e, L, blk.ds, ga, nullptr, pm ? nullptr : GC, nullptr, groups, B, bw.frozen, false, gcp); }
+        { OP(L, "bn_bwd"); bn_bwd(e, L, blk.c2, ga, dy2, groups, B, bw.frozen, zo.f ? Mask::Z : Mask::ZPlane, zo, ga); }
+        if (blk.ds >= 0) { side_guard(e, 1, par); OP(L, "bn_bwd"); bn_bwd(e, L, blk.ds, ga, dyd, groups, B, bw.frozen); }
         // Where a weight gradient enters the side stream (round 6): behind the data gradient of the same conv, i.e. beside the
         // NEXT BatchNorm-backward passes of the main stream: a streaming kernel lives beside a GEMM's waves on a CU (the GEMMs leave
         // it the registers since their K-steps run row-major), two GEMMs do not (LDS).  Entering as soon as its dy exists put two
         // GEMMs beside each other and left the BatchNorm-backward passes that follow with nothing beside them.
         side_guard(e, 2, par);
-        { OP(L, "conv_dgrad"); conv_dgrad(e, L, blk.c2, GB, GD, imgs, nullptr, false, gbp); }
-        if (conv_on(e, tr, blk.c2)) {
-            Lane& SL = side(0, par);
-            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.c2, a.z1, GB, imgs, nullptr, 0, pm ? a.z1p : nullptr, gbp); }
-            side_end(e, 0, par);
-        }
-        { OP(L, "bn_bwd");
-          if (pm) bn_bwd(e, L, blk.c1, GD, nullptr, nullptr, nullptr, groups, B, bw.frozen, true, gdp, a.z1p);      // mask from y1 (z1 = relu(bn1(y1)))
-          else bn_bwd(e, L, blk.c1, GD, a.z1, GD, nullptr, groups, B, bw.frozen, true); }
+        { OP(L, "conv_dgrad"); conv_dgrad(e, L, blk.c2, dy2, g.dy1.f, imgs); }
+        if (conv_on(e, tr, blk.c2))
+            side_wgrad(e, forked, 0, par, "conv_wgrad", [&](Lane& SL) { conv_wgrad(e, SL, blk.c2, kept(a.z1), dy2, imgs); });
+        // z1 = relu(bn1(y1)): the mask comes from y1
+        { OP(L, "bn_bwd"); bn_bwd(e, L, blk.c1, g.dy1.f, dy1, groups, B, bw.frozen, Mask::OwnOutput, kept(a.z1)); }
         // (the block the backward stops behind keeps its own data gradient: a unit runs whole or not at all)
         { OP(L, "conv_dgrad");
-          if (blk.ds >= 0) {
-              if (!block_dgrad(e, L, blk.c1, blk.ds, GD, GC, ge, imgs, gdp, gcp)) {     // one launch: four classes + the downsample
-                  conv_dgrad(e, L, blk.ds, GC, ge, imgs, nullptr, false, gcp);   // writes parity class (0,0)
-                  conv_dgrad(e, L, blk.c1, GD, ge, imgs, nullptr, true, gdp);    // all classes, (0,0) accumulates
-              }
-          } else {
-              conv_dgrad(e, L, blk.c1, GD, ge, imgs, ga, false, gdp);
+          if (blk.ds < 0) conv_dgrad(e, L, blk.c1, dy1, ge, imgs, {.res = ga});
+          else if (!block_dgrad(e, L, blk.c1, blk.ds, dy1, dyd, ge, imgs)) {     // one launch: four classes + the downsample
+              conv_dgrad(e, L, blk.ds, dyd, ge, imgs);                          // writes parity class (0,0)
+              conv_dgrad(e, L, blk.c1, dy1, ge, imgs, {.acc_cls0 = true});      // all classes, (0,0) accumulates
           } }
-        const unsigned short* inp = pm ? (b == 0 ? A.p0p : A.blk[b - 1].outp) : nullptr;
-        if (conv_on(e, tr, blk.c1)) {
-            Lane& SL = side(2, par);
-            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.c1, in, GD, imgs, nullptr, 0, inp, gdp); }
-            side_end(e, 2, par);
-        }
-        if (blk.ds >= 0 && conv_on(e, tr, blk.ds)) {
-            Lane& SL = side(1, par);
-            { OP(SL, "conv_wgrad"); conv_wgrad(e, SL, blk.ds, in, GC, imgs, nullptr, 0, inp, gcp); }
-            side_end(e, 1, par);
-        }
+        if (conv_on(e, tr, blk.c1))
+            side_wgrad(e, forked, 2, par, "conv_wgrad", [&](Lane& SL) { conv_wgrad(e, SL, blk.c1, in, dy1, imgs); });
+        if (blk.ds >= 0 && conv_on(e, tr, blk.ds))
+            side_wgrad(e, forked, 1, par, "conv_wgrad", [&](Lane& SL) { conv_wgrad(e, SL, blk.ds, in, dyd, imgs); });
         std::swap(ga, ge);
     }
     const Conv& c0 = e->convs[0];
@@ -2078,17 +2108,16 @@ void backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         // max-pool backward + BatchNorm backward of the stem in two passes, without the dense intermediate (elementwise.hip)
         OP(L, "stem_pool_bn_bwd");
         Bn& b0 = e->bns[0];
+        const BnSlots s0 = bn_slots(e, b0);
         const int pooled_pg = B * (c0.hout / 2) * (c0.wout / 2), pix = B * c0.hout * c0.wout;
-        k_stem_pool_bn_reduce(ga, A.p0, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, L.st,
-                              e->student.state + e->off_gamma + b0.ch_off, e->student.state + e->off_beta + b0.ch_off);
-        k_bn_bwd_finalize(e->ws_part, groups, stem_pool_bn_blocks(pooled_pg), 64, pix, e->student.state + e->off_gamma + b0.ch_off,
-                          b0.mean, b0.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b0.ch_off,
-                          e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
-        k_stem_pool_bn_apply(ga, A.p0, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, L.st);
+        k_stem_pool_bn_reduce(ga, A.p0.f, e->idx0, c0.y, b0.mean, b0.istd, e->ws_part, groups, B, c0.hout, c0.wout, 64, L.st, s0.gamma,
+                              s0.beta);
+        bn_bwd_finalize(e, L, b0, groups, stem_pool_bn_blocks(pooled_pg), pix, bw.frozen);
+        k_stem_pool_bn_apply(ga, A.p0.f, e->idx0, c0.y, e->ca, e->cb, e->cc, e->dyh0, groups, B, c0.hout, c0.wout, 64, L.st);
     }
     if (first == 0) {
         if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, e->dyh0, groups, B, bw.dx); }
-        if (conv_on(e, tr, 0)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, 0, e->x4, e->dyh0, imgs); }
+        if (conv_on(e, tr, 0)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, 0, {e->x4}, {e->dyh0}, imgs); }
     }
     if (forked) side_join(e);
     if (bw.step) adam_step(e, e->grad);      // optimizer.step()
@@ -2107,39 +2136,30 @@ bool fuse_for(fm_engine* e, const MBConv& m)
 }
 
 // BN over an arbitrary NHWC tensor (depthwise output): statistics by chan_reduce, then the same finalize
-// sums_ready: ws_part already holds dw_stats_tiles() partials per group (left by the depthwise forward)
-void bn_fwd_tensor(fm_engine* e, Lane& L, int bi, const float* y, int groups, int pix_per_group, int HW, BnMode mode,
-                   bool sums_ready = false)
+// partials: ws_part already holds that many partial sums per group (left by the depthwise forward); 0 = reduce here
+void bn_fwd_tensor(fm_engine* e, Lane& L, int bi, const float* y, int groups, int pix_per_group, int HW, BnMode mode, int partials)
 {
-    Bn& b = e->bns[bi];
-    if (mode == BnMode::Frozen) { bn_fwd_fixed(e, L, b, groups); return; }       // (no statistics pass either)
-    if (!sums_ready)
+    if (!partials && mode != BnMode::Frozen)       // (frozen statistics need no statistics pass either)
         k_chan_reduce(nullptr, e->dt, y, e->dt, nullptr, nullptr, nullptr, nullptr, nullptr, e->ws_part, groups, pix_per_group,
-                      HW, b.C, 0, 0, nullptr, nullptr, L.st);
-    const bool run = mode == BnMode::Batch;
-    k_bn_finalize(e->ws_part, groups, sums_ready ? dw_stats_tiles() : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
-                  e->student.state + e->off_gamma + b.ch_off, e->student.state + e->off_beta + b.ch_off,
-                  run ? e->student.state + e->off_rm + b.ch_off : nullptr, run ? e->student.state + e->off_rv + b.ch_off : nullptr, b.mean,
-                  b.istd, b.scale, b.shift, e->bn_eps, e->bn_mom, L.st);
-    if (run) e->student.counters[bi] += groups;
+                      HW, e->bns[bi].C, 0, 0, nullptr, nullptr, L.st);
+    bn_fwd_stats(e, L, bi, e->ws_part, groups, partials ? partials : bn_bwd_blocks(pix_per_group), pix_per_group, mode, nullptr);
 }
 
-// backward through act(bn(y))*rowscale: dz -> dy (may alias dz); writes dgamma/dbeta
-void bnact_bwd(fm_engine* e, Lane& L, int bi, const float* dz, const float* y, float* dy, const float* rowscale, int groups,
-               int pix_per_group, int HW, int act, bool frozen, const float* gate = nullptr, const float* dsv = nullptr,
-               int ty = -1, int sums_ready = 0)
+// what bnact_bwd's tensor carries beyond act(bn(y)).  rowscale: z = act(bn(y)) * rowscale[image]; gate / dsv: the squeeze-excite
+// gate and pooled gradient, d a_d = dz * gate + dsv / HW formed on load; partials: ws_part already holds the two backward sums as
+// that many partials per group (k_se_bwd_bn1, the depthwise data gradient), 0 = reduce here
+struct BnActOps { const float *rowscale = nullptr, *gate = nullptr, *dsv = nullptr; int partials = 0; };
+// backward through act(bn(y)): dz -> dy (may alias dz); writes dgamma/dbeta
+void bnact_bwd(fm_engine* e, Lane& L, int bi, const float* dz, const float* y, float* dy, int groups, int pix_per_group, int HW, int act,
+               bool frozen, const BnActOps& o = {})
 {
     Bn& b = e->bns[bi];
-    if (ty < 0) ty = e->dt;                  // storage type of y / dy (the stem's are fp32 in every mode)
-    // sums_ready > 0: ws_part already holds the two backward sums as that many partials per group (k_se_bwd_bn1)
-    if (!sums_ready)
-        k_chan_reduce(dz, e->dt, y, ty, b.mean, b.istd, b.scale, b.shift, rowscale, e->ws_part, groups, pix_per_group, HW, b.C,
-                      1, act, gate, dsv, L.st);
-    k_bn_bwd_finalize(e->ws_part, groups, sums_ready ? sums_ready : bn_bwd_blocks(pix_per_group), b.C, pix_per_group,
-                      e->student.state + e->off_gamma + b.ch_off, b.mean, b.istd, e->ca, e->cb, e->cc,
-                      e->grad + e->off_gamma + b.ch_off, e->grad + e->off_beta + b.ch_off, L.st, frozen);
-    k_bnact_bwd_apply(dz, e->dt, y, ty, e->ca, e->cb, e->cc, b.scale, b.shift, rowscale, dy, groups, pix_per_group, HW,
-                      b.C, act, gate, dsv, L.st);
+    if (!o.partials)
+        k_chan_reduce(dz, e->dt, y, e->dt, b.mean, b.istd, b.scale, b.shift, o.rowscale, e->ws_part, groups, pix_per_group, HW, b.C,
+                      1, act, o.gate, o.dsv, L.st);
+    bn_bwd_finalize(e, L, b, groups, o.partials ? o.partials : bn_bwd_blocks(pix_per_group), pix_per_group, frozen);
+    k_bnact_bwd_apply(dz, e->dt, y, e->dt, e->ca, e->cb, e->cc, b.scale, b.shift, o.rowscale, dy, groups, pix_per_group, HW,
+                      b.C, act, o.gate, o.dsv, L.st);
 }
 
 void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode mode)
@@ -2149,8 +2169,7 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
     const float* S = W.state;
     Conv& cs = e->convs[e->c_stem];
     e->ctx = -1;
-    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_stem, W, e->x4, cs.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-    { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, e->c_stem, groups, B, mode); }
+    conv_fwd_train(e, L, e->c_stem, W, {e->x4}, groups, B, mode, "conv_fwd");
     {
         Bn& b = e->bns[e->bn_stem];
         { OP(L, "k_bnact_apply"); k_bnact_apply(cs.y, e->dt, b.scale, b.shift, nullptr, nullptr, A.a0, e->dt, groups, B * cs.hout * cs.wout,
@@ -2165,8 +2184,7 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
         const float* a_e = cur;
         if (m.c_exp >= 0) {
             Conv& ce = e->convs[m.c_exp];
-            { OP(L, "exp_fwd"); conv_fwd(e, L, m.c_exp, W, cur, ce.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-            { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, m.c_exp, groups, B, mode); }
+            conv_fwd_train(e, L, m.c_exp, W, {cur}, groups, B, mode, "exp_fwd");
             Bn& b = e->bns[m.bn0];
             { OP(L, "k_bnact_apply"); k_bnact_apply(ce.y, e->dt, b.scale, b.shift, nullptr, nullptr, a.a_e, e->dt, groups, B * HWi, HWi, b.C, 2, L.st); }
             a_e = a.a_e;
@@ -2174,7 +2192,7 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
         bool st_done;
         { OP(L, "k_dw_fwd"); st_done = k_dw_fwd(a_e, S + m.dw_off, a.y_d, e->dt, nullptr, nullptr, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p,
                  m.k, m.s, m.pad_t, m.pad_l, 0, L.st, L.rec, e->ws_part, groups); }   // + BN1 batch statistics
-        { OP(L, "bn_fwd_tensor"); bn_fwd_tensor(e, L, m.bn1, a.y_d, groups, B * HWo, HWo, mode, st_done); }
+        { OP(L, "bn_fwd_tensor"); bn_fwd_tensor(e, L, m.bn1, a.y_d, groups, B * HWo, HWo, mode, st_done ? dw_stats_tiles() : 0); }
         {
             // a_d = swish(bn1(y_d)) is never written: the pooling and the gating pass form it on load
             Bn& b = e->bns[m.bn1];
@@ -2183,12 +2201,10 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
             if (!fuse_for(e, m)) k_se_scale(a.y_d, e->dt, b.scale, b.shift, B, a.gate, a.a_s, imgs, HWo, m.ce_p, L.st);
         }
         Conv& cp = e->convs[m.c_proj];
-        if (fuse_for(e, m)) {          // a_s = swish(bn1(y_d)) * gate is formed on the project conv's operand load
-            const Prologue pro{e->bns[m.bn1].scale, e->bns[m.bn1].shift, a.gate};
-            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.y_d, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats, &pro); }
-        } else
-            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.a_s, cp.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-        { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, m.c_proj, groups, B, mode); }
+        // a_s = swish(bn1(y_d)) * gate is formed on the project conv's operand load where it fuses
+        if (fuse_for(e, m))
+            conv_fwd_train(e, L, m.c_proj, W, {a.y_d}, groups, B, mode, "proj_fwd", {e->bns[m.bn1].scale, e->bns[m.bn1].shift, a.gate});
+        else conv_fwd_train(e, L, m.c_proj, W, {a.a_s}, groups, B, mode, "proj_fwd");
         {
             Bn& b = e->bns[m.bn2];
             const float* dc = (m.skip && e->dc_dev) ? e->dc_dev + i * (size_t)imgs : nullptr;
@@ -2200,8 +2216,7 @@ void eff_forward_train(fm_engine* e, Lane& L, Acts& A, int groups, int B, BnMode
     Conv& ch = e->convs[e->c_head];
     const int HWh = ch.hout * ch.wout;
     e->ctx = 100;
-    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_head, W, cur, ch.y, imgs, groups, nullptr, nullptr, nullptr, 0, e->ws_stats); }
-    { OP(L, "bn_fwd_finalize"); bn_fwd_finalize(e, L, e->c_head, groups, B, mode); }
+    conv_fwd_train(e, L, e->c_head, W, {cur}, groups, B, mode, "conv_fwd");
     {
         Bn& b = e->bns[e->bn_head];
         { OP(L, "k_bnact_apply"); k_bnact_apply(ch.y, e->dt, b.scale, b.shift, nullptr, nullptr, A.T_mid, e->dt, groups, B * HWh, HWh, b.C, 2, L.st); }
@@ -2222,7 +2237,7 @@ void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, floa
     if (W.ev_dirty) { OP(L, "k_bn_eval_affine"); ensure_eval_affine(e, L, W); }
     auto sc = [&](int bi) { return W.ev_scale + e->bns[bi].ch_off; };
     auto sh = [&](int bi) { return W.ev_shift + e->bns[bi].ch_off; };
-    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_stem, W, e->x4, A.a0, imgs, 1, sc(e->bn_stem), sh(e->bn_stem), nullptr, 2, nullptr); }
+    { OP(L, "conv_fwd"); conv_fwd_eval(e, L, e->c_stem, W, {e->x4}, {A.a0}, imgs, ACT_SWISH); }
     const float* cur = A.a0;
     for (size_t i = 0; i < e->mbs.size(); ++i) {
         const MBConv& m = e->mbs[i];
@@ -2231,7 +2246,7 @@ void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, floa
         const int HWo = m.hout * m.wout;
         const float* a_e = cur;
         if (m.c_exp >= 0) {
-            { OP(L, "exp_fwd"); conv_fwd(e, L, m.c_exp, W, cur, a.a_e, imgs, 1, sc(m.bn0), sh(m.bn0), nullptr, 2, nullptr); }
+            { OP(L, "exp_fwd"); conv_fwd_eval(e, L, m.c_exp, W, {cur}, {a.a_e}, imgs, ACT_SWISH); }
             a_e = a.a_e;
         }
         bool pooled;                      // eval: y_d holds swish(bn1(.)) directly; its per-image channel sums come with it
@@ -2242,18 +2257,18 @@ void eff_forward_eval(fm_engine* e, Lane& L, Weights& W, Acts& A, int imgs, floa
         // the gate multiplies the activation on the project conv's operand load: bf16 wherever the conv reads it once or twice,
         // fp32 where the conv streams through conv1x1.hip (K <= 256: the high-resolution blocks)
         const Conv& cpj = e->convs[m.c_proj];
+        const In skip{m.skip ? cur : nullptr};         // the block's residual
         if (fuse_for(e, m) || (!e->precision && conv1x1_stream_takes(cpj.cin_p, cpj.cout_p, cpj.cout_p))) {
-            const Prologue pro{nullptr, nullptr, a.gate};
-            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.y_d, a.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr, &pro); }
+            { OP(L, "proj_fwd"); conv_fwd_eval(e, L, m.c_proj, W, {a.y_d}, {a.out}, imgs, ACT_NONE, skip, {.gate = a.gate}); }
         } else {
             { OP(L, "k_se_scale"); k_se_scale(a.y_d, e->dt, nullptr, nullptr, 1, a.gate, a.a_s, imgs, HWo, m.ce_p, L.st); }
-            { OP(L, "proj_fwd"); conv_fwd(e, L, m.c_proj, W, a.a_s, a.out, imgs, 1, sc(m.bn2), sh(m.bn2), m.skip ? cur : nullptr, 0, nullptr); }
+            { OP(L, "proj_fwd"); conv_fwd_eval(e, L, m.c_proj, W, {a.a_s}, {a.out}, imgs, ACT_NONE, skip); }
         }
         cur = a.out;
     }
     Conv& ch = e->convs[e->c_head];
     e->ctx = 300;
-    { OP(L, "conv_fwd"); conv_fwd(e, L, e->c_head, W, cur, A.T_mid, imgs, 1, sc(e->bn_head), sh(e->bn_head), nullptr, 2, nullptr); }
+    { OP(L, "conv_fwd"); conv_fwd_eval(e, L, e->c_head, W, {cur}, {A.T_mid}, imgs, ACT_SWISH); }
     { OP(L, "k_avgpool"); k_avgpool(A.T_mid, e->dt, feat, imgs, ch.hout * ch.wout, e->D, L.st); }
     { OP(L, "k_fc_fwd"); k_fc_fwd(feat, S + e->off_fcw, S + e->off_fcb, logits, imgs, e->D, e->C, L.st); }
 }
@@ -2321,13 +2336,9 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     Conv& ch = e->convs[e->c_head];
     const int HWh = ch.hout * ch.wout;
     const float* h = e->drop_dev ? e->hfeat : e->feat;
-    // Weight gradients on the side lane (side_begin): T_small (d y_p) for the project conv, T_mid (d y_d) for the depthwise
-    // conv, T_big (d y_e) for the expand conv, the squeeze-excite vectors, each double-buffered by block parity.  Arithmetic
+    // Weight gradients on the side lane (side_wgrad): T_small (d y_p) for the project conv, T_mid (d y_d) for the depthwise
+    // conv, T_big (d y_e) for the expand conv, the squeeze-excite vectors, each double-buffered by block parity (e->eg).  Arithmetic
     // and summation orders are those of the inline order: results are bit-identical.
-    const bool sw = e->side_w;
-    float* Tsm[2] = {e->T_small, sw ? e->T_small2 : e->T_small};
-    float* Tmd[2] = {A.T_mid, sw ? e->T_mid2 : A.T_mid};
-    float* Tbg[2] = {e->T_big, sw ? e->T_big2 : e->T_big};
     // Under a mask (bw.train; backward_and_step's note): units in forward order are the stem (0), the MBConv blocks (1 + i), the
     // head (nm + 1) and _fc (nm + 2).  Weight gradients that are launches of their own -- the pointwise and depthwise ones -- are
     // skipped for a frozen weight; those that come out of a kernel the data gradient needs (the fused expand / project backward,
@@ -2349,33 +2360,32 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         if (conv_on(e, tr, e->c_stem) || bn_on(e, tr, e->bn_stem)) first = 0;
     }
     bool forked = false;
-    auto side = [&](int k, int par) -> Lane& { forked = true; return side_begin(e, k, par); };
     if (first > nm + 2) return;        // nothing is trainable and no dx is wanted
     e->ctx = 500;
     { OP(L, "k_fc_bwd"); k_fc_bwd(e->dlogits, h, S + e->off_fcw, e->drop_dev, G + e->off_fcw, G + e->off_fcb, A.T_mid, e->dt, imgs, e->D, e->C,
              HWh, L.st, bw.dfeat); }
     if (first > nm + 1) return;        // head-only training: _fc's backward and nothing else
-    { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_head, A.T_mid, ch.y, A.T_mid, nullptr, groups, B * HWh, HWh, 2, bw.frozen); }
-    if (conv_on(e, tr, e->c_head)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_head, A.mb.back().out, A.T_mid, imgs); }
+    { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_head, A.T_mid, ch.y, A.T_mid, groups, B * HWh, HWh, ACT_SWISH, bw.frozen); }
+    if (conv_on(e, tr, e->c_head)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_head, {A.mb.back().out}, {A.T_mid}, imgs); }
     if (first > nm) return;
     float *go = e->GA, *gi = e->GB;
-    { OP(L, "conv_dgrad"); conv_dgrad(e, L, e->c_head, A.T_mid, go, imgs, nullptr, false); }
+    { OP(L, "conv_dgrad"); conv_dgrad(e, L, e->c_head, {A.T_mid}, go, imgs); }
     for (int i = nm - 1; i >= 0 && 1 + i >= first; --i) {
         const MBConv& m = e->mbs[i];
         const MBActs& a = A.mb[i];
         e->ctx = 400 + i;                          // backward ops @400..@415 (head @500, stem @399)
         const int par = i & 1;
-        float *T_small = Tsm[par], *T_mid = Tmd[par], *T_big = Tbg[par];
+        const EffGrads& g = e->eg[par];
+        float *T_small = g.dyp, *T_mid = g.dyd, *T_big = g.dye;
+        float *dgp = g.se_dg, *drp = g.se_dr;          // the squeeze-excite gradient vectors alternate too
         const float* in = i == 0 ? A.a0 : A.mb[i - 1].out;
         const int HWi = m.hin * m.win, HWo = m.hout * m.wout;
         Conv& cp = e->convs[m.c_proj];
         const float* dc = (m.skip && e->dc_dev) ? e->dc_dev + (size_t)i * imgs : nullptr;
         // out = bn2(y_p)*dc + in
         side_guard(e, 0, par);
-        { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn2, go, cp.y, T_small, dc, groups, B * HWo, HWo, 0, bw.frozen); }
+        { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn2, go, cp.y, T_small, groups, B * HWo, HWo, ACT_NONE, bw.frozen, {.rowscale = dc}); }
         Bn& b1 = e->bns[m.bn1];
-        float* dgp = (sw && par) ? e->se_dgp2 : e->se_dgp;       // the squeeze-excite gradient vectors alternate too
-        float* drp = (sw && par) ? e->se_drp2 : e->se_drp;
         // early blocks (half of the depthwise-resolution bytes): d a_s is never stored -- pw_proj_bwd_kernel forms it twice on the
         // matrix pipe, once for the five per-image sums + the weight gradient, once for the BN1-backward apply (7 passes -> 3)
         const int nch5 = proj_bwd_nch(e, cp, imgs);
@@ -2385,9 +2395,8 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
             side_guard(e, 3, par);
             { OP(L, "k_se_bwd"); k_se_bwd_bn1(das, a.y_d, e->dt, b1.scale, b1.shift, b1.mean, b1.istd, B, A.se_pool, a.gate, a.rpre,
                          S + m.w1_off, S + m.w2_off, dgp, drp, e->se_ds, e->ws_part, imgs, HWo, m.ce_p, m.cs, L.st, nch); }
-            Lane& SL = side(3, par);
-            { OP(SL, "k_se_wgrad"); k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); }
-            side_end(e, 3, par);
+            side_wgrad(e, forked, 3, par, "k_se_wgrad", [&](Lane& SL) {
+                k_se_wgrad(dgp, drp, a.rpre, a.sq, SL.ws_slab, G + m.w1_off, imgs, m.ce_p, m.cs, SL.st); });
         };
         bool pfused = false;
         if (nch5) {
@@ -2402,9 +2411,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                 se_bwd(nullptr, nch5);
                 side_guard(e, 1, par);
                 { OP(L, "proj_bwd_apply");
-                  k_bn_bwd_finalize(e->ws_part, groups, se_bwd_bn1_splits(B), b1.C, B * HWo, e->student.state + e->off_gamma + b1.ch_off, b1.mean,
-                                    b1.istd, e->ca, e->cb, e->cc, e->grad + e->off_gamma + b1.ch_off, e->grad + e->off_beta + b1.ch_off,
-                                    L.st, bw.frozen);
+                  bn_bwd_finalize(e, L, b1, groups, se_bwd_bn1_splits(B), B * HWo, bw.frozen);
                   if (launch(1) != 1) soft(e, hipErrorInvalidValue); }      // d y_d
                 pfused = true;
             }
@@ -2412,29 +2419,24 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
         if (!pfused) {
             if (!e->precision && fuse_for(e, m)) soft(e, hipErrorInvalidValue);     // fp32: a_s was not stored for this block and only
                                                                                     // the fused backward can do without it
-            if (conv_on(e, tr, m.c_proj)) {
-                Lane& SL = side(0, par);
-                if (fuse_for(e, m)) {      // the project conv's operand a_s was never stored: re-formed from y_d on load
-                    const Prologue pro{b1.scale, b1.shift, a.gate};
-                    { OP(SL, "proj_wgrad"); conv_wgrad(e, SL, m.c_proj, a.y_d, T_small, imgs, &pro, B * HWo); }
-                } else
-                    { OP(SL, "proj_wgrad"); conv_wgrad(e, SL, m.c_proj, a.a_s, T_small, imgs); }
-                side_end(e, 0, par);
-            }
+            if (conv_on(e, tr, m.c_proj))
+                side_wgrad(e, forked, 0, par, "proj_wgrad", [&](Lane& SL) {
+                    // where the project conv's operand a_s was never stored it is re-formed from y_d on load
+                    if (fuse_for(e, m)) conv_wgrad(e, SL, m.c_proj, {a.y_d}, {T_small}, imgs, {b1.scale, b1.shift, a.gate}, B * HWo);
+                    else conv_wgrad(e, SL, m.c_proj, {a.a_s}, {T_small}, imgs);
+                });
             side_guard(e, 1, par);
-            { OP(L, "proj_dgrad"); conv_dgrad(e, L, m.c_proj, T_small, T_mid, imgs, nullptr, false); }          // d a_s
+            { OP(L, "proj_dgrad"); conv_dgrad(e, L, m.c_proj, {T_small}, T_mid, imgs); }          // d a_s
             se_bwd(T_mid, 0);                 // a_s = a_d * gate(a_d)
             // d a_d = d a_s * gate + ds/HW is formed on load inside the BN backward's apply pass
-            { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn1, T_mid, a.y_d, T_mid, nullptr, groups, B * HWo, HWo, 2, bw.frozen, a.gate, e->se_ds, -1,
-                                         se_bwd_bn1_splits(B)); }   // d y_d
+            { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn1, T_mid, a.y_d, T_mid, groups, B * HWo, HWo, ACT_SWISH, bw.frozen,
+                                         {.gate = a.gate, .dsv = e->se_ds, .partials = se_bwd_bn1_splits(B)}); }   // d y_d
         }
         const float* a_e = m.c_exp >= 0 ? a.a_e : in;
-        if (ent_on(e, tr, m.dw_off)) {
-            Lane& SL = side(1, par);
-            { OP(SL, "k_dw_wgrad"); k_dw_wgrad(T_mid, a_e, e->dt, SL.ws_slab, G + m.dw_off, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s,
-                       m.pad_t, m.pad_l, SL.st); }
-            side_end(e, 1, par);
-        }
+        if (ent_on(e, tr, m.dw_off))
+            side_wgrad(e, forked, 1, par, "k_dw_wgrad", [&](Lane& SL) {
+                k_dw_wgrad(T_mid, a_e, e->dt, SL.ws_slab, G + m.dw_off, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s, m.pad_t,
+                           m.pad_l, SL.st); });
         if (m.c_exp >= 0) {
             Conv& ce = e->convs[m.c_exp];
             Bn& b0 = e->bns[m.bn0];
@@ -2449,9 +2451,7 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
                 if (!sums)
                     k_chan_reduce(T_big, e->dt, ce.y, e->dt, b0.mean, b0.istd, b0.scale, b0.shift, nullptr, e->ws_part, groups, pix,
                                   HWi, b0.C, 1, 2, nullptr, nullptr, L.st);
-                k_bn_bwd_finalize(e->ws_part, groups, sums ? dw_stats_tiles() : bn_bwd_blocks(pix), b0.C, pix,
-                                  e->student.state + e->off_gamma + b0.ch_off, b0.mean, b0.istd, e->ca, e->cb, e->cc,
-                                  e->grad + e->off_gamma + b0.ch_off, e->grad + e->off_beta + b0.ch_off, L.st, bw.frozen);
+                bn_bwd_finalize(e, L, b0, groups, sums ? dw_stats_tiles() : bn_bwd_blocks(pix), pix, bw.frozen);
                 const int sk = launch_exp_bwd(e, L, ce, T_big, ce.y, in, m.skip ? go : nullptr, gi,
                                               {b0.scale, b0.shift, nullptr, nullptr, e->ca, e->cb, e->cc}, imgs, groups);
                 if (sk > 0) {
@@ -2461,14 +2461,11 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
             }
             if (!fused) {
                 // (a refused fused launch has left ca / cb / cc and the BN gradients exactly as bnact_bwd is about to)
-                { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn0, T_big, ce.y, T_big, nullptr, groups, B * HWi, HWi, 2, bw.frozen, nullptr, nullptr, -1,
-                                             sums ? dw_stats_tiles() : 0); }
-                if (conv_on(e, tr, m.c_exp)) {
-                    Lane& SL = side(2, par);
-                    { OP(SL, "exp_wgrad"); conv_wgrad(e, SL, m.c_exp, in, T_big, imgs); }
-                    side_end(e, 2, par);
-                }
-                { OP(L, "exp_dgrad"); conv_dgrad(e, L, m.c_exp, T_big, gi, imgs, m.skip ? go : nullptr, false); }
+                { OP(L, "bnact_bwd"); bnact_bwd(e, L, m.bn0, T_big, ce.y, T_big, groups, B * HWi, HWi, ACT_SWISH, bw.frozen,
+                                             {.partials = sums ? dw_stats_tiles() : 0}); }
+                if (conv_on(e, tr, m.c_exp))
+                    side_wgrad(e, forked, 2, par, "exp_wgrad", [&](Lane& SL) { conv_wgrad(e, SL, m.c_exp, {in}, {T_big}, imgs); });
+                { OP(L, "exp_dgrad"); conv_dgrad(e, L, m.c_exp, {T_big}, gi, imgs, {.res = m.skip ? go : nullptr}); }
             }
         } else {
             { OP(L, "k_dw_dgrad"); k_dw_dgrad(T_mid, S + m.dw_off, gi, e->dt, imgs, m.hin, m.win, m.hout, m.wout, m.ce_p, m.k, m.s, m.pad_t,
@@ -2480,9 +2477,9 @@ void eff_backward_and_step(fm_engine* e, int groups, int B, const Bwd& bw)
     Conv& cs = e->convs[e->c_stem];
     e->ctx = 399;
     if (first == 0) {
-        { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_stem, go, cs.y, go, nullptr, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, 2, bw.frozen); }
+        { OP(L, "bnact_bwd"); bnact_bwd(e, L, e->bn_stem, go, cs.y, go, groups, B * cs.hout * cs.wout, cs.hout * cs.wout, ACT_SWISH, bw.frozen); }
         if (bw.dx[0] || bw.dx[1]) { OP(L, "stem_dgrad"); stem_dgrad_views(e, L, go, groups, B, bw.dx); }
-        if (conv_on(e, tr, e->c_stem)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_stem, e->x4, go, imgs); }
+        if (conv_on(e, tr, e->c_stem)) { OP(L, "conv_wgrad"); conv_wgrad(e, L, e->c_stem, {e->x4}, {go}, imgs); }
     }
     if (forked) side_join(e);                    // every weight gradient is in G before the optimizer reads it
     if (bw.step) { OP(L, "adam_step"); adam_step(e, e->grad); }
@@ -3877,17 +3874,17 @@ int fm_debug_pw(fm_engine* e, int32_t op, int32_t conv, const void* x_dev, const
     const Prologue pro{psc_dev, psh_dev, gate_dev};
     if (op == 0) {
         ARGCHK(x_dev, "x");
-        conv_fwd(e, e->main, conv, e->student, reinterpret_cast<const float*>(x_dev), reinterpret_cast<float*>(out_dev), imgs, groups,
-                 nullptr, nullptr, nullptr, 0, stats_dev ? e->ws_stats : nullptr, gate_dev ? &pro : nullptr);
+        conv_fwd(e, e->main, conv, e->student, {reinterpret_cast<const float*>(x_dev)}, {reinterpret_cast<float*>(out_dev)}, imgs, groups,
+                 {.stats = stats_dev ? e->ws_stats : nullptr, .pro = pro});
         if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     } else if (op == 1) {
         ARGCHK(dy_dev, "dy");
-        conv_dgrad(e, e->main, conv, reinterpret_cast<const float*>(dy_dev), reinterpret_cast<float*>(out_dev), imgs,
-                   reinterpret_cast<const float*>(x_dev), false);      // x_dev = optional residual [npix][cin_p] bf16
+        conv_dgrad(e, e->main, conv, {reinterpret_cast<const float*>(dy_dev)}, reinterpret_cast<float*>(out_dev), imgs,
+                   {.res = reinterpret_cast<const float*>(x_dev)});      // x_dev = optional residual [npix][cin_p] bf16
     } else if (op == 2) {
         ARGCHK(x_dev && dy_dev, "x/dy");
-        conv_wgrad(e, e->main, conv, reinterpret_cast<const float*>(x_dev), reinterpret_cast<const float*>(dy_dev), imgs,
-                   gate_dev ? &pro : nullptr, (imgs / groups) * c.hout * c.wout);
+        conv_wgrad(e, e->main, conv, {reinterpret_cast<const float*>(x_dev)}, {reinterpret_cast<const float*>(dy_dev)}, imgs, pro,
+                   (imgs / groups) * c.hout * c.wout);
         HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->main.st));
     } else {
         ARGCHK(false, "op");
@@ -3919,8 +3916,8 @@ int fm_debug_pw_fwd(fm_engine* e, int32_t conv, const void* x_dev, void* out_dev
     ensure_packed(e);
     if (stem) debug_stem_col(e, c, reinterpret_cast<const float*>(x_dev), imgs, groups);
     const Prologue pr{psc_dev, psh_dev, gate_dev};
-    conv_fwd(e, e->main, conv, e->student, reinterpret_cast<const float*>(x_dev), reinterpret_cast<float*>(out_dev), imgs, groups,
-             scale_dev, shift_dev, reinterpret_cast<const float*>(res_dev), act, stats_dev ? e->ws_stats : nullptr, pro ? &pr : nullptr);
+    conv_fwd(e, e->main, conv, e->student, {reinterpret_cast<const float*>(x_dev)}, {reinterpret_cast<float*>(out_dev)}, imgs, groups,
+             {stats_dev ? e->ws_stats : nullptr, pr, {scale_dev, shift_dev, {reinterpret_cast<const float*>(res_dev)}, act}});
     if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -4050,14 +4047,14 @@ int fm_debug_activation(fm_engine* e, int32_t kind, int32_t block, int32_t imgs,
     ARGCHK(e && dims4 && e->model == 0, "ResNet-18 engine only");
     ARGCHK(block >= 0 && block < (int)e->blocks.size() && (kind == 0 || kind == 1), "kind/block");
     ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
-    const BlockActs& b = e->acts.blk[block];
+    const Out t = kind == 0 ? e->acts.blk[block].z1 : e->acts.blk[block].out;
     const Conv& c = e->convs[e->blocks[block].c1];
     dims4[0] = imgs; dims4[1] = c.hout; dims4[2] = c.wout; dims4[3] = c.cout;
     if (host_nhwc) {
         // planes mode: z1 / out (all blocks but the last) live only as planes: re-form the fp32 values in the idle fp32 buffer
         if (e->planes && (kind == 0 || block + 1 < (int)e->blocks.size()))
-            k_planes_to_f32(kind == 0 ? b.z1p : b.outp, kind == 0 ? b.z1 : b.out, (long long)imgs * c.hout * c.wout, c.cout, e->main.st);
-        HIPCHK(hipMemcpyAsync(host_nhwc, kind == 0 ? b.z1 : b.out, (size_t)imgs * c.hout * c.wout * c.cout * 4,
+            k_planes_to_f32(t.p, t.f, (long long)imgs * c.hout * c.wout, c.cout, e->main.st);
+        HIPCHK(hipMemcpyAsync(host_nhwc, t.f, (size_t)imgs * c.hout * c.wout * c.cout * 4,
                               hipMemcpyDeviceToHost, e->main.st));
         HIPCHK(hipStreamSynchronize(e->main.st));
     }
@@ -4151,9 +4148,9 @@ int fm_debug_block_dgrad(fm_engine* e, int32_t block, const float* dy1_dev, cons
     ARGCHK(imgs >= 1 && imgs <= e->maxB, "imgs");
     ensure_packed(e);
     const Block& blk = e->blocks[block];
-    if (!block_dgrad(e, e->main, blk.c1, blk.ds, dy1_dev, dyd_dev, dx_dev, imgs)) {     // (the fp32-operand engine: its two calls)
-        conv_dgrad(e, e->main, blk.ds, dyd_dev, dx_dev, imgs, nullptr, false);
-        conv_dgrad(e, e->main, blk.c1, dy1_dev, dx_dev, imgs, nullptr, true);
+    if (!block_dgrad(e, e->main, blk.c1, blk.ds, {dy1_dev}, {dyd_dev}, dx_dev, imgs)) {     // (the fp32-operand engine: its two calls)
+        conv_dgrad(e, e->main, blk.ds, {dyd_dev}, dx_dev, imgs);
+        conv_dgrad(e, e->main, blk.c1, {dy1_dev}, dx_dev, imgs, {.acc_cls0 = true});
     }
     return FM_OK;
 }
@@ -4180,8 +4177,7 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
     ensure_packed(e);           // the forward reads the weight planes, the data gradient the transposed packs
     if (op == 0) {
         ARGCHK(x_dev, "x");
-        conv_fwd(e, e->main, conv, e->student, x_dev, out_dev, imgs, groups, nullptr, nullptr, nullptr, 0,
-                 stats_dev ? e->ws_stats : nullptr);
+        conv_fwd(e, e->main, conv, e->student, {x_dev}, {out_dev}, imgs, groups, {.stats = stats_dev ? e->ws_stats : nullptr});
         if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     } else if (op == 1) {
         ARGCHK(dy_dev && (c.ncls > 0 || c.cin == 3), "dgrad unavailable for this conv");
@@ -4189,10 +4185,10 @@ int fm_debug_conv(fm_engine* e, int32_t op, int32_t conv, const float* x_dev, co
         if (c.cin == 3) {           // the stem: stem_dgrad.hip with its NHWC store, dx [imgs][hin][win][3]
             RCCHK(ensure_stem_dpack(e));
             stem_dgrad(e, e->main, dy_dev, out_dev, imgs, true);
-        } else conv_dgrad(e, e->main, conv, dy_dev, out_dev, imgs, nullptr, false);
+        } else conv_dgrad(e, e->main, conv, {dy_dev}, out_dev, imgs);
     } else if (op == 2) {
         ARGCHK(x_dev && dy_dev, "x/dy");
-        conv_wgrad(e, e->main, conv, x_dev, dy_dev, imgs);
+        conv_wgrad(e, e->main, conv, {x_dev}, {dy_dev}, imgs);
         HIPCHK(hipMemcpyAsync(out_dev, e->grad + c.w_off, c.w_numel * 4, hipMemcpyDeviceToDevice, e->main.st));
     } else {
         ARGCHK(false, "op");
@@ -4231,8 +4227,8 @@ int fm_debug_conv_fwd(fm_engine* e, int32_t conv, const float* x_dev, float* out
         k_frame_nhwc3(x_dev, e->x3, imgs, c.hin, c.win, c.Hp, c.Wp, 3, 3, 1, e->main.st, e->stem_rows ? e->x3p : nullptr, e->x3p_plane_elems);
     ensure_packed(e);
     const Prologue pr{psc_dev, psh_dev, gate_dev};
-    conv_fwd(e, e->main, conv, e->student, x_dev, out_dev, imgs, groups, scale_dev, shift_dev, res_dev, act,
-             stats_dev ? e->ws_stats : nullptr, pro ? &pr : nullptr);
+    conv_fwd(e, e->main, conv, e->student, {x_dev}, {out_dev}, imgs, groups,
+             {stats_dev ? e->ws_stats : nullptr, pr, {scale_dev, shift_dev, {res_dev}, act}});
     if (stats_dev) RCCHK(debug_fold_stats(e, conv, groups, stats_dev));
     HIPCHK(hipGetLastError());
     return FM_OK;
@@ -4253,8 +4249,7 @@ int fm_debug_conv_planes(fm_engine* e, int32_t conv, const uint16_t* xp_dev, int
     ARGCHK(c.cin != 3 && conv_uses_pconv(e, c, imgs), "a convolution the planes kernel runs (not the stem)");
     ensure_packed(e);
     // as forward_eval: the operand's planes, one group, no statistics, the output and the residual in either form
-    conv_fwd(e, e->main, conv, e->student, nullptr, out_dev, imgs, 1, scale_dev, shift_dev, res_dev, relu, nullptr, nullptr, xp_dev,
-             outp_dev, resp_dev);
+    conv_fwd(e, e->main, conv, e->student, {.p = xp_dev}, {out_dev, outp_dev}, imgs, 1, {.epi = {scale_dev, shift_dev, {res_dev, resp_dev}, relu}});
     HIPCHK(hipStreamSynchronize(e->main.st));
     STEP_DONE(e);
     return FM_OK;
