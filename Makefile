@@ -2,7 +2,9 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 SRC   := $(wildcard fedmlp_amd/csrc/*.hip)
-HDR   := $(wildcard fedmlp_amd/csrc/*.h) include/fedmlp_hip.h include/fedmlp_hip_debug.h include/fedmlp_hip_rofl.h
+HDR   := $(wildcard fedmlp_amd/csrc/*.h) include/fedmlp_hip.h include/fedmlp_hip_debug.h include/fedmlp_hip_rofl.h \
+         include/fedmlp_hip_drift.h
+# every fedmlp_amd/csrc/*.hip is a translation unit of the library (drift.hip, the client-drift correction, among them)
 OBJ   := $(patsubst fedmlp_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB   := fedmlp_amd/libfedmlp_hip.so
 

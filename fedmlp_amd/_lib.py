@@ -157,6 +157,14 @@ ROFL_SYMBOLS = {
     "fm_step_rofl": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, C.c_float, C.c_float, _I32, _P, _P, _I64, _P]),
 }
 
+# client-drift correction (FedProx / SCAFFOLD): include/fedmlp_hip_drift.h, wrapped by fedmlp_amd/drift.py
+DRIFT_SYMBOLS = {
+    "fm_drift_begin": (C.c_int, [_P, C.c_float, _P, _I32]),
+    "fm_drift_last": (C.c_int, [_P, _P]),
+    "fm_drift_end": (C.c_int, [_P, _P, C.POINTER(_I64)]),
+    "fm_drift_active": (C.c_int, [_P]),
+}
+
 _lib = None
 
 
@@ -173,7 +181,7 @@ def load():
     # (loading ours first leaves two runtimes and hipMalloc reports "no ROCm-capable device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(ROFL_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(ROFL_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)    # AttributeError if the .so lacks a declared symbol
         except AttributeError:

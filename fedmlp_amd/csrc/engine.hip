@@ -27,6 +27,7 @@
 #include "../../include/fedmlp_hip.h"
 #include "../../include/fedmlp_hip_debug.h"
 #include "../../include/fedmlp_hip_rofl.h"
+#include "../../include/fedmlp_hip_drift.h"
 #include "comm.h"
 #include "common.h"
 #include "kernels.h"
@@ -295,6 +296,14 @@ struct fm_engine {
     double *rofl_rowloss = nullptr, *rofl_dist = nullptr;
     float* rofl_cos = nullptr;
     int* rofl_keep = nullptr;
+    // client-drift correction (fm_drift_begin .. fm_drift_end, include/fedmlp_hip_drift.h): while `drift_on`, every optimizer
+    // step reads drift_gcorr, written by one launch in front of it (drift_grad), in place of its gradient.  NP floats each,
+    // allocated by the first install that needs them: the anchor (the student's parameters at begin) and the corrected gradient
+    // always, the shift with a shift, the running sum of raw gradients with track.  drift_steps: optimizer steps since begin
+    bool drift_on = false, drift_shifted = false, drift_track = false;
+    float drift_mu = 0.f;
+    int64_t drift_steps = 0;
+    float *drift_anchor = nullptr, *drift_shift = nullptr, *drift_gsum = nullptr, *drift_gcorr = nullptr;
     int* tag_buf = nullptr;           // fm_select_topk_rows: [pool sizes ncls | counts 2 ncls | top ncls*cap | bot ncls*cap | rows ncls*stride]
     size_t tag_buf_ints = 0;
     // profiling
@@ -1826,10 +1835,27 @@ OptSgdHp sgd_hp(const fm_sgd& hp, bool first)
     return {(double)hp.lr, (double)hp.momentum, 1.0 - (double)hp.dampening, (double)hp.weight_decay,
             (hp.momentum != 0.f && hp.nesterov != 0) ? 1 : 0, hp.momentum == 0.f ? 0 : (first ? 1 : 2)};
 }
+// The gradient an optimizer step reads: g itself, or, while a client-drift correction is installed (fm_drift_begin), the
+// corrected copy that one launch on the main lane writes in front of the optimizer kernel (drift.hip has the rule).  g is only
+// read: the accumulator, fm_get_grads, the norm and the clips keep the raw gradient.  Under a requires_grad mask the table form
+// runs (frozen entries: a zero gradient, no sum).  With nothing installed this is the branch below and nothing else.
+OptSel mask_sel(const fm_engine* e, const int32_t* tr);
+const float* drift_grad(fm_engine* e, const float* g)
+{
+    if (!e->drift_on) return g;
+    OP(e->main, "drift_correct");
+    const DriftOps a{g, e->student.state, e->drift_anchor, e->drift_shifted ? e->drift_shift : nullptr,
+                     e->drift_track ? e->drift_gsum : nullptr, e->drift_gcorr, e->drift_mu};
+    if (e->trainable.empty()) k_drift_correct(a, (int64_t)e->NP, e->main.st, e->dev_err);
+    else k_drift_correct_masked(a, e->opt_chunks, e->n_opt_chunks, mask_sel(e, e->trainable.data()), e->main.st, e->dev_err);
+    e->drift_steps += 1;
+    return e->drift_gcorr;
+}
 // optimizer.step(): one kernel over the whole trainable arena.  torch Adam with coupled L2 and the handle's hyper-parameters:
 // g = e->grad (fused steps) or the autograd path's accumulator (fm_adam_step)
 void adam_step(fm_engine* e, const float* g)
 {
+    g = drift_grad(e, g);
     e->adam_t += 1;
     k_adam(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, adam_hp(e->hp, e->adam_t), e->main.st, e->dev_err);
     weights_stepped(e);
@@ -1837,15 +1863,17 @@ void adam_step(fm_engine* e, const float* g)
 // torch.optim.AdamW / torch.optim.SGD over the autograd path's accumulator, with the handle's moment arenas and step count
 void adamw_step(fm_engine* e, const fm_adam& hp)
 {
+    const float* g = drift_grad(e, e->gacc);
     e->adam_t += 1;
-    k_adamw(e->student.state, e->gacc, e->adam_m, e->adam_v, (int64_t)e->NP, adamw_hp(hp, e->adam_t), e->main.st, e->dev_err);
+    k_adamw(e->student.state, g, e->adam_m, e->adam_v, (int64_t)e->NP, adamw_hp(hp, e->adam_t), e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void sgd_step(fm_engine* e, const fm_sgd& hp)
 {
+    const float* g = drift_grad(e, e->gacc);
     const bool first = e->adam_t == 0;
     e->adam_t += 1;
-    k_sgd(e->student.state, e->gacc, e->adam_m, (int64_t)e->NP, sgd_hp(hp, first), e->main.st, e->dev_err);
+    k_sgd(e->student.state, g, e->adam_m, (int64_t)e->NP, sgd_hp(hp, first), e->main.st, e->dev_err);
     weights_stepped(e);
 }
 // both moment arenas and the step count: a fresh optimizer of any kind
@@ -1966,27 +1994,30 @@ OptSel mask_sel(const fm_engine* e, const int32_t* tr)
 // step calls (adam_hp / adamw_hp / sgd_hp).  One step count per engine, as there.
 void adam_step_groups(fm_engine* e, const fm_adam* hp, int n)
 {
+    const float* g = drift_grad(e, e->gacc);
     e->adam_t += 1;
     OptAdamArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = adam_hp(hp[i], e->adam_t);
-    k_adam_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_adam_groups(e->student.state, g, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void adamw_step_groups(fm_engine* e, const fm_adam* hp, int n)
 {
+    const float* g = drift_grad(e, e->gacc);
     e->adam_t += 1;
     OptAdamWArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = adamw_hp(hp[i], e->adam_t);
-    k_adamw_groups(e->student.state, e->gacc, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_adamw_groups(e->student.state, g, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void sgd_step_groups(fm_engine* e, const fm_sgd* hp, int n)
 {
+    const float* g = drift_grad(e, e->gacc);
     const bool first = e->adam_t == 0;
     e->adam_t += 1;
     OptSgdArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = sgd_hp(hp[i], first);
-    k_sgd_groups(e->student.state, e->gacc, e->adam_m, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_sgd_groups(e->student.state, g, e->adam_m, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 
@@ -3782,6 +3813,62 @@ int fm_optim_set_state(fm_engine* e, const float* m_dev, const float* v_dev, int
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
+
+// ---- client-drift correction (include/fedmlp_hip_drift.h) --------------------------------------------------------------
+int fm_drift_begin(fm_engine* e, float mu, const float* shift_dev, int32_t track)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(!e->drift_on, "fm_drift_begin: a correction is already installed (fm_drift_end first)");
+    ARGCHK(mu >= 0.f && std::isfinite(mu), "fm_drift_begin: mu must be finite and >= 0");
+    ARGCHK(mu != 0.f || shift_dev || track, "fm_drift_begin: nothing to install (mu == 0, no shift, track == 0)");
+    // first install: the arenas this one needs, zeroed at allocation like every arena (padding)
+    for (float** p : {&e->drift_anchor, &e->drift_gcorr, shift_dev ? &e->drift_shift : nullptr, track ? &e->drift_gsum : nullptr}) {
+        if (!p || *p) continue;
+        DALLOC(*p, e->NP);
+        HIPCHK(hipMemsetAsync(*p, 0, e->NP * 4, e->main.st));
+    }
+    HIPCHK(hipMemcpyAsync(e->drift_anchor, e->student.state, e->NP * 4, hipMemcpyDeviceToDevice, e->main.st));
+    if (shift_dev) {
+        HIPCHK(hipMemsetAsync(e->drift_shift, 0, e->NP * 4, e->main.st));      // the padding of the arena is zero from here on
+        RCCHK(state_dict_to_arena(e, shift_dev, e->drift_shift, true));
+    }
+    if (track) HIPCHK(hipMemsetAsync(e->drift_gsum, 0, e->NP * 4, e->main.st));
+    e->drift_mu = mu; e->drift_shifted = shift_dev != nullptr; e->drift_track = track != 0;
+    e->drift_steps = 0;
+    e->drift_on = true;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_drift_last(fm_engine* e, float* out_dev)
+{
+    ARGCHK(e && out_dev, "null");
+    ARGCHK(e->drift_gcorr && e->drift_steps > 0, "fm_drift_last: no optimizer step since fm_drift_begin");
+    RCCHK(arena_to_state_dict(e, e->drift_gcorr, out_dev, true));
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_drift_end(fm_engine* e, float* mean_dev, int64_t* steps_host)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->drift_on, "fm_drift_end: no correction is installed");
+    if (mean_dev) {
+        if (e->drift_track && e->drift_steps > 0) {
+            // the division commutes with the change of layout: S in net.grads() order first, then S / (float)K in place
+            RCCHK(arena_to_state_dict(e, e->drift_gsum, mean_dev, true));
+            k_drift_div(mean_dev, (float)e->drift_steps, e->nf_sd, e->main.st);
+        } else {
+            HIPCHK(hipMemsetAsync(mean_dev, 0, (size_t)e->nf_sd * 4, e->main.st));
+        }
+    }
+    if (steps_host) *steps_host = e->drift_steps;
+    e->drift_on = false;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_drift_active(fm_engine* e) { return e && e->drift_on ? 1 : 0; }
 
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
 {

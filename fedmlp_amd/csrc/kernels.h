@@ -321,6 +321,15 @@ void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, 
 // written as zeros; floats outside every entry are not touched
 void k_grad_accumulate_masked(float* acc, const float* g, const OptChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
                               hipStream_t s, const int* skip);
+// ---- client-drift correction (drift.hip): r = g [+ mu (p - a)] [+ s], S += g, each operation rounded on its own ------------
+// Arenas of n floats (a multiple of 4).  mu == 0: p and a are not read; s null: no shift; S null: no running sum.  g is never
+// written.  The masked form runs over the optimizer's entry table: sel 0 = trainable (the flat form's bits), anything else =
+// frozen (r = 0 over the entry's span, S untouched); floats outside every entry are not touched.
+struct DriftOps { const float* g; const float* p; const float* a; const float* s; float* S; float* r; float mu; };
+void k_drift_correct(const DriftOps& a, int64_t n, hipStream_t s, const int* skip);
+void k_drift_correct_masked(const DriftOps& a, const OptChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip);
+// x[i] = x[i] / k, n floats at any alignment
+void k_drift_div(float* x, float k, int64_t n, hipStream_t s);
 
 // ---- prototypes / tagging ----------------------------------------------------------
 void k_proto_accumulate(const float* feat, const float* logits, const float* labels, int B, int D, int C,

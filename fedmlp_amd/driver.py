@@ -71,12 +71,30 @@ def build_parser():
                    help="globaltest of the new global model every K rounds (main.py:322-357 uses 10), the forward dealt over "
                         "the ranks and the metrics from fm_eval_metrics; 0 = never")
     p.add_argument("--n_test", type=int, default=1024, help="samples of the synthetic test set (--eval_every)")
+    p.add_argument("--prox_mu", type=float, default=0.0,
+                   help="FedProx: mu of the proximal term mu/2 |w - w_glob|^2 in every local step (fedmlp_amd/drift.py); 0 = off")
+    p.add_argument("--scaffold", type=int, default=0, choices=[0, 1],
+                   help="1: SCAFFOLD control variates in every local step (fedmlp_amd/drift.py)")
     return p
+
+
+DRIFT_EXPS = ("FedAVG", "FedAVG+FixMatch", "FedMLP")     # the trainers that install LocalUpdate.drift
+
+
+def check_drift_flags(p, args):
+    """--prox_mu / --scaffold: one of them at most, and only with the trainers that install a correction"""
+    if not (args.prox_mu >= 0.0 and args.prox_mu != float("inf")):
+        p.error("--prox_mu must be finite and >= 0")
+    if args.prox_mu > 0 and args.scaffold:
+        p.error("--prox_mu and --scaffold are two client-drift corrections: give one of them")
+    if (args.prox_mu > 0 or args.scaffold) and args.exp not in DRIFT_EXPS:
+        p.error(f"--prox_mu / --scaffold are built for --exp {', '.join(DRIFT_EXPS)} (got {args.exp})")
 
 
 def args_parser(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    check_drift_flags(p, args)
     if args.exp == "RSCFed" and args.n_clients < RSCFED_K:
         p.error(f"--exp RSCFed draws groups of {RSCFED_K} clients (main.py:116-119): --n_clients must be >= {RSCFED_K}")
     if args.exp == "FedNoRo" and args.rounds_warmup > args.rounds_FedNoRo_warmup:
@@ -294,6 +312,17 @@ def main(args=None, module="fedmlp_amd.driver"):
         # RSCFed likewise (main.py:164-166: train_RSCFed blends into the client's own teacher_neg)
         ema = build_model(args) if args.exp in ("FedIRM", "RSCFed") else None
         clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C], teacher_neg=ema)
+    # client-drift correction (fedmlp_amd/drift.py), installed by the trainers of DRIFT_EXPS around their local steps
+    scaffold = None
+    if getattr(args, "scaffold", 0):
+        from fedmlp_amd.drift import Scaffold
+        scaffold = Scaffold(eng.nf, args.n_clients, dev)
+        for c in mine:
+            clients[c].drift = scaffold.client(c)
+    elif getattr(args, "prox_mu", 0.0) > 0:
+        from fedmlp_amd.drift import FedProx
+        for c in mine:
+            clients[c].drift = FedProx(args.prox_mu)
     test = None
     if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
         test = ShardedTestSet(args.n_test, C, args.hw, args.seed + 500, 4 * args.batch_size, rank, world, dev)
@@ -400,6 +429,8 @@ def main(args=None, module="fedmlp_amd.driver"):
                     f_locals = {k: v for part in parts for k, v in part.items()}
                 f_G = fedavg.rofl_centroids(f_G, [f_locals[c] for c in range(args.n_clients)])
         glob.copy_(eng.state_tensor())
+        if scaffold is not None:                          # c += sum_i delta c_i / n_clients; the models went through FedAvg above
+            scaffold.server_update()
         if tao_new is not None:
             tao, Prototype = tao_new, proto_new
         if args.exp == "FedIRM" and rnd >= SI - 1:        # main.py:245-251: FedAvg above, then FedAvg_rela with lam = 1
@@ -427,6 +458,10 @@ def main(args=None, module="fedmlp_amd.driver"):
         if metrics is not None:
             rec["test"] = metrics
             rec["eval_sec"] = round(eval_sec, 3)
+        if scaffold is not None:
+            rec["scaffold"] = {"c_norm": float(scaffold.c_global.double().norm())}
+        elif getattr(args, "prox_mu", 0.0) > 0:
+            rec["prox_mu"] = args.prox_mu
         if rank == 0:
             print(json.dumps(rec), flush=True)
             if args.save_every and (rnd + 1) % args.save_every == 0:     # torch.save(netglob.state_dict(), ...) main.py:237

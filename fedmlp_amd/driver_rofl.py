@@ -16,6 +16,7 @@ def args_parser(argv=None):
     args = p.parse_args(argv)
     if args.exp != "RoFL":
         p.error("fedmlp_amd.driver_rofl runs the RoFL row only; the other rows are fedmlp_amd.driver's")
+    driver.check_drift_flags(p, args)             # --prox_mu / --scaffold: refused, train_RoFL installs no correction
     return args
 
 

@@ -102,6 +102,9 @@ class LocalUpdate(object):
         self.idxss = []
         self.flag = True                    # :54: the first relation-phase call of train_FedIRM loads the EMA model from net
         self._dev = {}
+        # client-drift correction (fedmlp_amd.drift: FedProx(mu), Scaffold(...).client(i)), or None: train, train_FixMatch and
+        # both stages of train_FedMLP install it where they reset Adam and uninstall it where they mark the net trained
+        self.drift = None
 
     # ---- data plumbing -------------------------------------------------------------------
     def _order(self, n):
@@ -187,6 +190,14 @@ class LocalUpdate(object):
         self.teacher_neg._version += 1
         eng.teacher_swap()
 
+    def _drift_begin(self, eng):
+        if self.drift is not None:
+            self.drift.begin(eng)
+
+    def _drift_end(self, eng):
+        if self.drift is not None:
+            self.drift.end(eng)
+
     def _result(self, net, epoch_loss, neg=None):
         """the head of every trainer's return tuple (positions 3-4: the reference's placeholders)"""
         return (self._sd(net), np.array(epoch_loss).mean(), None, None,
@@ -197,12 +208,14 @@ class LocalUpdate(object):
         a = self.args
         eng = self._bind(net, "image")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        self._drift_begin(eng)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
         epoch_loss = []
         for batches in self._epochs(eng, epoch_loss):
             for pos, loss in batches:
                 eng.step_bce(self._images(eng, "image", pos), self._rows(y, pos, eng), self.loss_w, a.batch_size, loss)
                 self.iter_num += 1
+        self._drift_end(eng)
         net.mark_trained()
         return self._result(net, epoch_loss)
 
@@ -211,6 +224,7 @@ class LocalUpdate(object):
         a = self.args
         eng = self._bind(net, "image_aug_1")
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        self._drift_begin(eng)
         y = self._labels_dev(eng, self._y_masked, "y_masked")
         act = self._mask(self.active_class_list)
         epoch_loss = []
@@ -220,6 +234,7 @@ class LocalUpdate(object):
                                   self._rows(y, pos, eng), self.loss_w, self.loss_w_unknown, act,
                                   a.annotation_num, a.batch_size, loss)
                 self.iter_num += 1
+        self._drift_end(eng)
         net.mark_trained()
         return self._result(net, epoch_loss)
 
@@ -485,6 +500,7 @@ class LocalUpdate(object):
         if rnd < a.rounds_FedMLP_stage1:                                   # ---- stage 1
             eng.teacher_snapshot()                                         # glob_model = deepcopy(net) :909
             eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+            self._drift_begin(eng)
             y = self._labels_dev(eng, self._y_masked, "y_masked")
             act = self._mask(self.active_class_list)
             epoch_loss = []
@@ -495,6 +511,7 @@ class LocalUpdate(object):
                     self.iter_num += 1
             for c in self.negative_class_list:                             # :932 "try noro"
                 self.class_num_list[c] = 0
+            self._drift_end(eng)
             net.mark_trained()
             ret = self._result(net, epoch_loss)
             if rnd == a.rounds_FedMLP_stage1 - 1:                          # first tao and proto :971
@@ -544,12 +561,14 @@ class LocalUpdate(object):
         yp_d = torch.from_numpy(yp).to(eng.device)
         dist_d = torch.from_numpy(dist).to(eng.device)
         eng.adam_reset(self.lr, (0.9, 0.999), 1e-8, 5e-4)
+        self._drift_begin(eng)
         epoch_loss = []
         for batches in self._epochs(eng, epoch_loss):
             for pos, loss in batches:
                 eng.step_stage2(self._images(eng, "image_aug_1", pos), self._rows(yp_d, pos, eng),
                                 self._rows(dist_d, pos, eng), loss)
                 self.iter_num += 1
+        self._drift_end(eng)
         net.mark_trained()
         self.idxss = []
         for k in range(len(self.traindata_idx) // 2):                      # :1197-1204
