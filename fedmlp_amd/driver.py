@@ -3,7 +3,8 @@
 reference's main.py (main.py:106-319, with the 'FeMLP' typos normalised) on the HIP engine, one process
 per GPU, clients dealt round-robin over the ranks, aggregation as RCCL all-reduces
 (fedmlp_amd/fedavg.py).  Data is synthetic and HBM-resident (the reference's datasets and
-ImageNet weights are not available offline).
+ImageNet weights are not available offline).  main() sets the process up; run_rounds() is the loop over rounds, which asks
+the row's object (fedmlp_amd/rows.py, one class per --exp value) for everything that differs between the rows.
 
   python -m fedmlp_amd.driver --gpus 8 --exp FedMLP --n_clients 8 --rounds_warmup 4 --rounds_FedMLP_stage1 2
   python -m fedmlp_amd.driver --exp FedIRM --rounds_warmup 4 --rounds_FedIRM_sup 2
@@ -17,12 +18,13 @@ import time
 import numpy as np
 import torch
 
+from fedmlp_amd.rows import ROWS, RSCFED_K, RSCFED_M         # noqa: F401  (tests read RSCFED_M / RSCFED_K from here)
+
 
 def build_parser():
     """the driver's flags, before any are parsed (fedmlp_amd/driver_rofl.py starts from the same parser)"""
     p = argparse.ArgumentParser()      # flag names/defaults follow utils/options.py:4-81
-    p.add_argument("--exp", default="FedMLP", choices=["FedMLP", "FedAVG", "FedAVG+FixMatch", "FedLSR", "FedIRM", "RSCFed", "FedNoRo",
-                                                      "CBAFed"])
+    p.add_argument("--exp", default="FedMLP", choices=[e for e in ROWS if e != "RoFL"])      # RoFL: fedmlp_amd.driver_rofl
     p.add_argument("--model", default="Resnet18")
     p.add_argument("--seed", type=int, default=1037)
     p.add_argument("--batch_size", type=int, default=32)
@@ -78,7 +80,7 @@ def build_parser():
     return p
 
 
-DRIFT_EXPS = ("FedAVG", "FedAVG+FixMatch", "FedMLP")     # the trainers that install LocalUpdate.drift
+DRIFT_EXPS = tuple(e for e, row in ROWS.items() if row.trains_with_drift)     # the trainers that install LocalUpdate.drift
 
 
 def check_drift_flags(p, args):
@@ -101,9 +103,6 @@ def args_parser(argv=None):
         p.error("--exp FedNoRo: --rounds_warmup may not exceed --rounds_FedNoRo_warmup (after its warm-up the reference "
                 "trains and aggregates nothing, main.py:140-148, 269-272)")
     return args
-
-
-RSCFED_M, RSCFED_K = 10, 6        # main.py:115-116: M groups of K clients per round
 
 
 def gather_client_states(eng, states, counters, n_clients, rank, world, dist):
@@ -215,23 +214,24 @@ class RoundAccumulator:
         self.t = np.zeros(C); self.tn = np.zeros(C)              # FedAvg_tao numerators / weights of this rank
         self.p = torch.zeros((2 * C, D)); self.pn = np.zeros(C)  # FedAvg_proto numerators / weights
 
-    def add(self, n_c, state, counters, active_class_list, ret):
+    def add(self, n_c, state, counters, active_class_list, t=None, proto=None):
+        """t, proto: what a prototype pass of train_FedMLP returned for this client (else None)"""
         w = n_c / self.n_total
         self.acc.add_(state, alpha=w)                            # FedAvg numerator (utils/FedAvg.py:9-13)
         self.acc_cnt += w * np.asarray(counters, np.float64)
-        if len(ret) == 8:                                        # (..., t, proto) of a prototype pass
+        if t is not None:
             neg = np.array([0.0 if k in active_class_list else 1.0 for k in range(self.C)])
             act = 1.0 - neg
-            self.t += np.asarray(ret[6]) * n_c * neg; self.tn += n_c * neg
+            self.t += np.asarray(t) * n_c * neg; self.tn += n_c * neg
             pa = np.repeat(act, 2)
-            self.p += torch.where(torch.from_numpy(pa > 0)[:, None], torch.as_tensor(ret[7]) * n_c, torch.zeros(()))
+            self.p += torch.where(torch.from_numpy(pa > 0)[:, None], torch.as_tensor(proto) * n_c, torch.zeros(()))
             self.pn += n_c * act
 
     def reduce(self, eng, dev, with_tao_proto, scale=1.0):
         """-> (global num_batches_tracked counters, tao or None, Prototype or None); the averaged state is in the engine.
         scale: a factor common to every rank applied to the sums (CBAFed's 1 / sum(data_num)); cnt_float keeps the
         counters' means before their truncation."""
-        from fedmlp_amd.fedavg import fedavg_allreduce, tao_allreduce, proto_allreduce, state_agreement
+        from fedmlp_amd.fedavg import fedavg_allreduce, tao_allreduce, proto_allreduce, state_agreement, trunc_counters
         eng.state_tensor().copy_(self.acc)
         eng.counters(np.zeros(len(self.acc_cnt), np.int64))      # the counters are reduced as float64 below
         fedavg_allreduce(eng, scale)                             # fm_fedavg_allreduce: ncclAllReduce of the state arena
@@ -239,7 +239,7 @@ class RoundAccumulator:
         if not agree:
             raise RuntimeError(f"the ranks' states differ after the FedAvg all-reduce (checksum spread {worst:.3e})")
         self.cnt_float = rank_sum(self.acc_cnt, dev) * scale
-        cnt = np.trunc(self.cnt_float + 1e-9).astype(np.int64)   # utils/FedAvg.py:13 + load_state_dict
+        cnt = trunc_counters(self.cnt_float)
         eng.counters(cnt)
         if not with_tao_proto:
             return cnt, None, None
@@ -278,9 +278,9 @@ def main(args=None, module="fedmlp_amd.driver"):
     from fedmlp_amd.engine import Engine
     from fedmlp_amd.model import ResidentNet, build_model
     from fedmlp_amd.local_training import LocalUpdate
-    from fedmlp_amd.fedavg import comm_init, tao_allreduce, proto_allreduce
+    from fedmlp_amd.fedavg import comm_init
 
-    C, S1 = args.n_classes, args.rounds_FedMLP_stage1
+    C = args.n_classes
     args.feature_dim = args.feature_dim or spec.FEATURE_DIM[args.model]
     eng = Engine(args.model, C, args.hw, args.hw, 4 * args.batch_size, device=str(dev), precision=args.precision,
                  streams=args.streams)
@@ -294,12 +294,11 @@ def main(args=None, module="fedmlp_amd.driver"):
         host.load_state_dict(torch.load(args.init_ckpt, map_location="cpu"))
     host._pull()
     eng.set_state(host.flat, host.counters)
-    glob = eng.state_tensor().clone()                     # netglob, replicated on every rank
-    glob_cnt = eng.counters().copy()                      # its num_batches_tracked counters
     net = ResidentNet(eng)
 
     mine = [c for c in range(args.n_clients) if c % world == rank]
     n_all = [args.n_local] * args.n_clients
+    row = ROWS[args.exp](args, eng, n_all, rank, world, dist, dev)
     clients = {}
     for c in mine:                                       # client c annotates class c mod C
         if args.augment:
@@ -308,167 +307,76 @@ def main(args=None, module="fedmlp_amd.driver"):
             ds = DeviceDataset(args.n_local, C, args.hw, args.seed + 1000 * c, dev)
         pos = [np.where(ds.targets[:, k] == 1)[0] for k in range(C)]
         a = argparse.Namespace(**vars(args))
-        # FedIRM: every client keeps its own EMA model (main.py hands LocalUpdate a teacher_neg; :31, 393-395)
-        # RSCFed likewise (main.py:164-166: train_RSCFed blends into the client's own teacher_neg)
-        ema = build_model(args) if args.exp in ("FedIRM", "RSCFed") else None
+        ema = build_model(args) if row.client_ema else None          # the client's own EMA model
         clients[c] = LocalUpdate(a, c % C, ds, list(range(args.n_local)), pos, pos, active_class_list=[c % C], teacher_neg=ema)
     # client-drift correction (fedmlp_amd/drift.py), installed by the trainers of DRIFT_EXPS around their local steps
     scaffold = None
-    if getattr(args, "scaffold", 0):
+    if args.scaffold:
         from fedmlp_amd.drift import Scaffold
         scaffold = Scaffold(eng.nf, args.n_clients, dev)
         for c in mine:
             clients[c].drift = scaffold.client(c)
-    elif getattr(args, "prox_mu", 0.0) > 0:
+    elif args.prox_mu > 0:
         from fedmlp_amd.drift import FedProx
         for c in mine:
             clients[c].drift = FedProx(args.prox_mu)
     test = None
     if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
         test = ShardedTestSet(args.n_test, C, args.hw, args.seed + 500, 4 * args.batch_size, rank, world, dev)
-    tao, Prototype = [0] * C, None
-    SI = args.rounds_FedIRM_sup
-    # main.py:200-208: class k is annotated by the clients c with c mod C == k (every rank knows the whole assignment)
-    class_active_client_list = [[c for c in range(args.n_clients) if c % C == k] for k in range(C)]
+    log = run_rounds(args, row, eng, net, clients, rank, world, dev, test=test, scaffold=scaffold)
+    if dist is not None:
+        dist.barrier(); dist.destroy_process_group()
+    return log
+
+
+def run_rounds(args, row, eng, net, clients, rank, world, dev, test=None, scaffold=None):
+    """The loop over rounds (main.py:106-357) for one row (fedmlp_amd/rows.py) on this rank's clients {c: LocalUpdate}, from the
+    global model the engine holds -> the per-round records (rank 0 prints them).  Nothing here needs a GPU of its own: with
+    stand-ins for the engine and the clients it runs on the CPU."""
+    sync = torch.cuda.synchronize if torch.device(dev).type == "cuda" else (lambda: None)
+    C = args.n_classes
+    glob = eng.state_tensor().clone()                     # netglob, replicated on every rank
+    glob_cnt = eng.counters().copy()                      # its num_batches_tracked counters
     log = []
-    # RSCFed: ONE generator seeded without the rank offset and stepped alike on every rank: the same DMA everywhere
-    dma_rng = random.Random(args.seed)
-    WC = args.rounds_CBAFed_warmup
-    cba_pt = cba_tao = None                              # CBAFed: pt and tao of main.py:289-300
-    cba_res = cba_res_cnt = None                         # CBAFed: the last blended model (w_glob_res) and its float counters
-    # RoFL: the global centroids (main.py:99) from a CPU generator seeded without the rank offset: the same f_G on every rank
-    f_G = torch.randn((2 * C, args.feature_dim), generator=torch.Generator().manual_seed(args.seed))
     for rnd in range(args.rounds_warmup):
         t0 = time.perf_counter()
-        cba2 = args.exp == "CBAFed" and rnd >= WC        # stage 2: FedAvg weights data_num_c / sum(data_num), main.py:302
-        # (the sum is known only after every client trained: accumulate with the raw data_num, scale the all-reduce by 1 / sum)
-        acc = RoundAccumulator(glob, len(glob_cnt), C, args.feature_dim, 1.0 if cba2 else float(sum(n_all)))
+        acc = RoundAccumulator(glob, len(glob_cnt), C, args.feature_dim, row.fedavg_total(rnd))
         losses = []
-        DMA = None
-        if args.exp == "RSCFed":                          # main.py:114-121
-            DMA = [dma_rng.sample(range(args.n_clients), RSCFED_K) for _ in range(RSCFED_M)]
-        if args.exp == "FedNoRo":                         # main.py:127-128
-            from fedmlp_amd.fedavg import consistency_weight
-            weight_kd = consistency_weight(rnd, args.begin, args.end) * args.a
-        rsc_states, rsc_cnt = {}, {}                      # RSCFed: client -> device state / counters
-        cba_counts = {}                                   # CBAFed: client -> (class_num_list, data_num)
-        relas = {}                                        # FedIRM: client -> its relation matrix (host), main.py:192-193
-        f_locals = {}                                     # RoFL: client -> its centroids f_k (host)
-        for c in mine:
-            loc = clients[c]
+        row.begin_round(rnd)
+        for c, loc in clients.items():
             eng.state_tensor().copy_(glob)                # net = deepcopy(netglob)  (main.py:181-184)
             eng.counters(glob_cnt)
-            if args.exp == "FedAVG":
-                ret = loc.train(rnd, net, None)
-            elif args.exp == "FedAVG+FixMatch":
-                ret = loc.train_FixMatch(rnd, net)
-            elif args.exp == "FedLSR":
-                ret = loc.train_FedLSR(rnd, net)          # main.py:161-163
-            elif args.exp == "RSCFed":                    # main.py:164-166
-                ret = loc.train_RSCFed(rnd, net)
-                rsc_states[c], rsc_cnt[c] = eng.state_tensor().clone(), eng.counters().copy()
-            elif args.exp == "FedNoRo":                   # main.py:140-144
-                ret = loc.train_FedNoRo(c, rnd, net, None, weight_kd=weight_kd)
-            elif args.exp == "CBAFed":                    # main.py:149-157
-                ret = loc.train_CBAFed(rnd, net) if rnd < WC else loc.train_CBAFed(rnd, net, pt=cba_pt, tao=cba_tao)
-                cba_counts[c] = (ret[6].clone(), int(ret[7]))
-            elif args.exp == "RoFL":                      # main.py:167-168
-                ret = loc.train_RoFL(net, f_G, rnd)
-                f_locals[c] = ret[2]
-            elif args.exp == "FedIRM":                    # main.py:169-177
-                if rnd < SI - 1:
-                    ret = loc.train_FedIRM(rnd, Prototype, None, None, None, net=net)
-                else:
-                    ret = loc.train_FedIRM(rnd, Prototype, None, loc.negative_class_list, loc.active_class_list, net=net)
-                    relas[c] = ret[6].detach().cpu()
-            elif rnd < S1 - 1:
-                ret = loc.train_FedMLP(rnd, tao, Prototype, None, None, None, net=net)
-            else:
-                ret = loc.train_FedMLP(rnd, tao, Prototype, None, loc.negative_class_list,
-                                       loc.active_class_list, net=net)
+            ret = row.train(rnd, c, loc, net)
             losses.append(float(ret[1]))
-            if args.exp != "RSCFed":
-                # (CBAFed's return tuple is as long as a prototype pass's: only FedMLP's carries t and proto)
-                acc.add(cba_counts[c][1] if cba2 else n_all[c], eng.state_tensor(), eng.counters(), loc.active_class_list,
-                        ret if args.exp == "FedMLP" else ())
-        # ---- aggregation (main.py:213-319): every sum over clients is an RCCL all-reduce in the library
-        tao_new = proto_new = None
-        if args.exp == "RSCFed":                          # main.py:213-215
-            glob_cnt = rscfed_round(eng, DMA, rsc_states, rsc_cnt, n_all, rank, world, dist)
-        else:
-            scale = 1.0
-            if args.exp == "CBAFed":                      # every client's class_num_list / data_num on every rank
-                if dist is not None:
-                    parts = [None] * world
-                    dist.all_gather_object(parts, cba_counts)
-                    cba_counts = {k: v for part in parts for k, v in part.items()}
-                if cba2:
-                    scale = 1.0 / float(sum(cba_counts[c][1] for c in range(args.n_clients)))
-            glob_cnt, tao_new, proto_new = acc.reduce(eng, dev, with_tao_proto=(args.exp == "FedMLP" and rnd >= S1 - 1),
-                                                      scale=scale)
-            if args.exp == "CBAFed":
-                from fedmlp_amd.fedavg import cbafed_blend, cbafed_tao
-                w_new, w_res, store = cbafed_blend(rnd, WC)           # main.py:274-288, 303-316
-                cnt_f = acc.cnt_float
-                if w_res != 0.0:
-                    # two rounded products, then their sum: the reference's 0.2 * w + 0.8 * res (no fused multiply-add)
-                    eng.state_tensor().mul_(w_new).add_(cba_res * w_res)
-                    cnt_f = w_new * cnt_f + w_res * cba_res_cnt      # the counters follow the blend in float ...
-                    glob_cnt = np.trunc(cnt_f + 1e-9).astype(np.int64)   # ... and are truncated on load
-                    eng.counters(glob_cnt)
-                if store:
-                    cba_res, cba_res_cnt = eng.state_tensor().clone(), cnt_f
-                if rnd >= WC - 1:                                     # main.py:289-300
-                    order = range(args.n_clients)
-                    cba_pt, cba_tao = cbafed_tao([cba_counts[c][0] for c in order], [cba_counts[c][1] for c in order])
-            if args.exp == "RoFL":                        # main.py:253-268: FedAvg above, then the centroids' cosine-weighted fold
-                from fedmlp_amd import fedavg
-                if dist is not None:                      # 2C x D floats per client: gathered as objects, folded on every rank alike
-                    parts = [None] * world
-                    dist.all_gather_object(parts, f_locals)
-                    f_locals = {k: v for part in parts for k, v in part.items()}
-                f_G = fedavg.rofl_centroids(f_G, [f_locals[c] for c in range(args.n_clients)])
+            row.contribute(rnd, acc, c, loc, ret)
+        # aggregation (main.py:213-319): every sum over clients is an RCCL all-reduce in the library
+        glob_cnt = row.aggregate(rnd, acc)
         glob.copy_(eng.state_tensor())
         if scaffold is not None:                          # c += sum_i delta c_i / n_clients; the models went through FedAvg above
             scaffold.server_update()
-        if tao_new is not None:
-            tao, Prototype = tao_new, proto_new
-        if args.exp == "FedIRM" and rnd >= SI - 1:        # main.py:245-251: FedAvg above, then FedAvg_rela with lam = 1
-            from fedmlp_amd.fedavg import FedAvg_rela
-            if dist is not None:                          # C x C floats per client: gathered as objects, folded on every rank alike
-                parts = [None] * world
-                dist.all_gather_object(parts, relas)
-                relas = {k: v for part in parts for k, v in part.items()}
-            rela = FedAvg_rela([relas[c] for c in range(args.n_clients)], n_all, class_active_client_list)
-            if rnd == SI - 1:
-                Prototype = rela
-            else:
-                lam = 1.0
-                Prototype = (1 - lam) * Prototype + lam * rela
+        row.end_round(rnd)
         metrics = None
         if test is not None and (rnd + 1) % args.eval_every == 0:     # globaltest of the new netglob (main.py:322-331)
-            torch.cuda.synchronize()
+            sync()
             t1 = time.perf_counter()
             metrics = evaluate_sharded(net, eng, test, C, rank, world, dev)
             eval_sec = time.perf_counter() - t1
-        torch.cuda.synchronize()
+        sync()
         dt = time.perf_counter() - t0
         rec = {"round": rnd, "sec": round(dt, 3), "mean_loss": float(np.mean(losses)) if losses else None,
-               "samples_per_sec_per_gpu": round(len(mine) * args.n_local / dt, 1)}
+               "samples_per_sec_per_gpu": round(len(clients) * args.n_local / dt, 1)}
         if metrics is not None:
             rec["test"] = metrics
             rec["eval_sec"] = round(eval_sec, 3)
         if scaffold is not None:
             rec["scaffold"] = {"c_norm": float(scaffold.c_global.double().norm())}
-        elif getattr(args, "prox_mu", 0.0) > 0:
+        elif args.prox_mu > 0:
             rec["prox_mu"] = args.prox_mu
         if rank == 0:
             print(json.dumps(rec), flush=True)
             if args.save_every and (rnd + 1) % args.save_every == 0:     # torch.save(netglob.state_dict(), ...) main.py:237
                 torch.save(net.state_dict(), os.path.join(args.save_dir, f"model_{rnd}.pth"))
         log.append(rec)
-    if dist is not None:
-        dist.barrier(); dist.destroy_process_group()
     return log
 
 
@@ -487,7 +395,7 @@ def rscfed_round(eng, DMA, states, counters, n_all, rank, world, dist):
         all_s, all_c = gather_client_states(eng, states, counters, n_clients, rank, world, dist)
         st, cnt_f = fedavg.rscfed_device(eng, all_s, np.stack(all_c), DMA, n_all)
     eng.state_tensor().copy_(st)
-    cnt = np.trunc(np.asarray(cnt_f, np.float64) + 1e-9).astype(np.int64)
+    cnt = fedavg.trunc_counters(cnt_f)
     eng.counters(cnt)
     agree, worst = fedavg.state_agreement(eng)
     if not agree:

@@ -246,6 +246,22 @@ def allreduce_weighted_(tensor, w):
     return tensor
 
 
+def trunc_counters(cnt_float):
+    """float num_batches_tracked means -> the int64 counters load_state_dict leaves (utils/FedAvg.py:13): truncated, the 1e-9
+    keeping a mean that rounded just below its integer"""
+    return np.trunc(np.asarray(cnt_float, np.float64) + 1e-9).astype(np.int64)
+
+
+def gather_dicts(dist, mine):
+    """{client: value} of this rank -> the merged dict of every rank, on every rank (all_gather_object); dist None: one rank,
+    the identity"""
+    if dist is None:
+        return mine
+    parts = [None] * dist.get_world_size()
+    dist.all_gather_object(parts, mine)
+    return {k: v for part in parts for k, v in part.items()}
+
+
 def comm_init(engine):
     """Create the library's own RCCL communicator (fm_comm_init) over the ranks of the current
     torch.distributed job: rank 0 draws the ncclUniqueId, torch.distributed only carries those

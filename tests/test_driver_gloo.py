@@ -41,8 +41,7 @@ def _run_rank(rank, world, with_tp=True):
         if c % world != rank:
             continue
         state, cnt, t, proto = _client(c)
-        ret = (None, 0.0, None, None, None, None, t, proto)
-        acc.add(N_LOCAL[c], state, cnt, ACT[c], ret)
+        acc.add(N_LOCAL[c], state, cnt, ACT[c], t, proto)
     eng = FakeEngine(torch.zeros(NSTATE), np.zeros(2, np.int64))
     cnt, tao, proto = acc.reduce(eng, "cpu", with_tao_proto=with_tp)
     return eng.state.numpy().copy(), cnt, tao, proto.numpy()
