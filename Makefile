@@ -3,8 +3,9 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 SRC   := $(wildcard fedmlp_amd/csrc/*.hip)
 HDR   := $(wildcard fedmlp_amd/csrc/*.h) include/fedmlp_hip.h include/fedmlp_hip_debug.h include/fedmlp_hip_rofl.h \
-         include/fedmlp_hip_drift.h
-# every fedmlp_amd/csrc/*.hip is a translation unit of the library (drift.hip, the client-drift correction, among them)
+         include/fedmlp_hip_drift.h include/fedmlp_hip_server.h
+# every fedmlp_amd/csrc/*.hip is a translation unit of the library (drift.hip, the client-drift correction, and server_opt.hip,
+# the server optimizers, among them)
 OBJ   := $(patsubst fedmlp_amd/csrc/%.hip,build/%.o,$(SRC))
 LIB   := fedmlp_amd/libfedmlp_hip.so
 

@@ -26,6 +26,10 @@ class FmAdam(C.Structure):
                 ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
+class FmServerOpt(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("tau", C.c_float)]
+
+
 class FmSgd(C.Structure):
     _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float),
                 ("weight_decay", C.c_float), ("nesterov", C.c_int32)]
@@ -165,6 +169,16 @@ DRIFT_SYMBOLS = {
     "fm_drift_active": (C.c_int, [_P]),
 }
 
+# server optimizers (FedAvgM / FedAdagrad / FedAdam / FedYogi): include/fedmlp_hip_server.h, wrapped by fedmlp_amd/server_opt.py
+SERVER_SYMBOLS = {
+    "fm_server_opt_begin": (C.c_int, [_P, C.POINTER(FmServerOpt)]),
+    "fm_server_opt_step": (C.c_int, [_P, _P, _P]),
+    "fm_server_opt_get_state": (C.c_int, [_P, _P, _P, C.POINTER(_I64)]),
+    "fm_server_opt_set_state": (C.c_int, [_P, _P, _P, _I64]),
+    "fm_server_opt_end": (C.c_int, [_P]),
+    "fm_server_opt_active": (C.c_int, [_P]),
+}
+
 _lib = None
 
 
@@ -181,7 +195,8 @@ def load():
     # (loading ours first leaves two runtimes and hipMalloc reports "no ROCm-capable device")
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(ROFL_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(ROFL_SYMBOLS.items()) + list(DRIFT_SYMBOLS.items())
+                              + list(SERVER_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)    # AttributeError if the .so lacks a declared symbol
         except AttributeError:

@@ -28,6 +28,7 @@
 #include "../../include/fedmlp_hip_debug.h"
 #include "../../include/fedmlp_hip_rofl.h"
 #include "../../include/fedmlp_hip_drift.h"
+#include "../../include/fedmlp_hip_server.h"
 #include "comm.h"
 #include "common.h"
 #include "kernels.h"
@@ -304,6 +305,18 @@ struct fm_engine {
     float drift_mu = 0.f;
     int64_t drift_steps = 0;
     float *drift_anchor = nullptr, *drift_shift = nullptr, *drift_gsum = nullptr, *drift_gcorr = nullptr;
+    // server optimizer (fm_server_opt_begin .. fm_server_opt_end, include/fedmlp_hip_server.h): while `srv_on`, fm_server_opt_step
+    // -- and nothing else -- enqueues server_opt.hip's launch.  The two moments are NP floats each, allocated by the first install
+    // (v by the first adaptive one); srv_chunks: the chunks of fm_state_dist's entry table that lie in the parameter arena,
+    // srv_part one fp64 partial per chunk, srv_omb1 / srv_omb2 = 1.0f - beta in fp32
+    bool srv_on = false;
+    fm_server_opt srv_hp{};
+    float srv_omb1 = 0.f, srv_omb2 = 0.f;
+    int64_t srv_steps = 0;
+    float *srv_m = nullptr, *srv_v = nullptr;
+    DistChunk* srv_chunks = nullptr;
+    double* srv_part = nullptr;
+    int srv_n_chunks = 0;
     int* tag_buf = nullptr;           // fm_select_topk_rows: [pool sizes ncls | counts 2 ncls | top ncls*cap | bot ncls*cap | rows ncls*stride]
     size_t tag_buf_ints = 0;
     // profiling
@@ -3869,6 +3882,134 @@ int fm_drift_end(fm_engine* e, float* mean_dev, int64_t* steps_host)
 }
 
 int fm_drift_active(fm_engine* e) { return e && e->drift_on ? 1 : 0; }
+
+// ---- server optimizers (include/fedmlp_hip_server.h) -------------------------------------------------------------------
+namespace {
+inline bool srv_adaptive(int rule) { return rule != FM_SERVER_AVGM; }
+// the chunks of ensure_dist_table's entries that are parameters (their index there counts the fp32 entries in state_dict order)
+int ensure_server_table(fm_engine* e)
+{
+    RCCHK(ensure_dist_table(e));
+    if (e->srv_chunks) return FM_OK;
+    std::vector<DistChunk> chunks;
+    int idx = 0;
+    for (auto& en : e->entries) {
+        if (en.kind == 2) continue;
+        if (en.eng_off < e->NP) {
+            const long long len = en.span().len;
+            if (len <= 0 || en.eng_off + (size_t)len > e->NP) { g_err = "a parameter entry lies outside the trainable arena"; return FM_ERR_ARG; }
+            for (long long st = 0; st < len; st += FM_DIST_CHUNK) chunks.push_back({idx, (int)st});
+        }
+        ++idx;
+    }
+    DistChunk* dc = nullptr;
+    double* dp = nullptr;
+    DALLOC(dc, chunks.size()); DALLOC(dp, chunks.size());
+    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(DistChunk), hipMemcpyHostToDevice));
+    e->srv_part = dp; e->srv_n_chunks = (int)chunks.size();
+    e->srv_chunks = dc;
+    return FM_OK;
+}
+inline int srv_fill(fm_engine* e, float* p, float value)
+{
+    uint32_t bits;
+    memcpy(&bits, &value, 4);
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)bits, e->NP, e->main.st));
+    return FM_OK;
+}
+}  // namespace
+
+int fm_server_opt_begin(fm_engine* e, const fm_server_opt* hp)
+{
+    ARGCHK(e && hp, "null");
+    ARGCHK(!e->srv_on, "fm_server_opt_begin: a server optimizer is already installed (fm_server_opt_end first)");
+    ARGCHK(hp->rule >= FM_SERVER_AVGM && hp->rule <= FM_SERVER_YOGI, "fm_server_opt_begin: unknown rule");
+    ARGCHK(hp->lr >= 0.f && std::isfinite(hp->lr), "fm_server_opt_begin: lr must be finite and >= 0");
+    ARGCHK(hp->beta1 >= 0.f && hp->beta1 < 1.f, "fm_server_opt_begin: beta1 must lie in [0, 1)");
+    const bool second = hp->rule == FM_SERVER_ADAM || hp->rule == FM_SERVER_YOGI;
+    ARGCHK(!second || (hp->beta2 >= 0.f && hp->beta2 < 1.f), "fm_server_opt_begin: beta2 must lie in [0, 1)");
+    ARGCHK(!srv_adaptive(hp->rule) || (std::isfinite(hp->tau) && hp->tau > 0.f), "fm_server_opt_begin: tau must be finite and > 0");
+    RCCHK(ensure_server_table(e));
+    if (!e->srv_m) DALLOC(e->srv_m, e->NP);
+    if (srv_adaptive(hp->rule) && !e->srv_v) DALLOC(e->srv_v, e->NP);
+    HIPCHK(hipMemsetAsync(e->srv_m, 0, e->NP * 4, e->main.st));
+    if (srv_adaptive(hp->rule)) {
+#pragma clang fp contract(off)
+        const float v0 = hp->tau * hp->tau;
+        RCCHK(srv_fill(e, e->srv_v, v0));
+    }
+    e->srv_hp = *hp;
+    e->srv_omb1 = 1.0f - hp->beta1; e->srv_omb2 = 1.0f - hp->beta2;
+    e->srv_steps = 0;
+    e->srv_on = true;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_server_opt_step(fm_engine* e, const float* x_old_dev, double* delta_norm_dev)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->srv_on, "fm_server_opt_step: no server optimizer is installed");
+    ARGCHK(x_old_dev, "fm_server_opt_step: null x_old_dev");
+    ARGCHK(x_old_dev + e->NS <= e->student.state || x_old_dev >= e->student.state + e->NS,
+           "fm_server_opt_step: x_old_dev is the engine's own state buffer");
+    // the state as a writer gets it: fm_state_device raises every staleness flag fm_state_scale and fm_fedavg_allreduce raise
+    float* st = nullptr;
+    int64_t ns = 0;
+    RCCHK(fm_state_device(e, &st, &ns));
+    OP(e->main, "server_opt");
+    const fm_server_opt& hp = e->srv_hp;
+    const ServerOps a{x_old_dev, st, e->srv_m, e->srv_v, hp.lr, hp.beta1, e->srv_omb1, hp.beta2, e->srv_omb2, hp.tau};
+    k_server_opt(hp.rule, a, e->dist_ent, e->srv_chunks, e->srv_n_chunks, e->srv_part, delta_norm_dev, e->main.st, e->dev_err);
+    e->srv_steps += 1;
+    STEP_DONE(e);
+    return FM_OK;
+}
+
+int fm_server_opt_get_state(fm_engine* e, float* m_dev, float* v_dev, int64_t* steps_host)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->srv_on, "fm_server_opt_get_state: no server optimizer is installed");
+    if (m_dev) RCCHK(arena_to_state_dict(e, e->srv_m, m_dev, true));
+    if (v_dev) {
+        if (srv_adaptive(e->srv_hp.rule)) RCCHK(arena_to_state_dict(e, e->srv_v, v_dev, true));
+        else HIPCHK(hipMemsetAsync(v_dev, 0, (size_t)e->nf_sd * 4, e->main.st));
+    }
+    if (steps_host) *steps_host = e->srv_steps;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_server_opt_set_state(fm_engine* e, const float* m_dev, const float* v_dev, int64_t steps)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->srv_on, "fm_server_opt_set_state: no server optimizer is installed");
+    const bool adaptive = srv_adaptive(e->srv_hp.rule);
+    ARGCHK(m_dev && (v_dev || !adaptive), "fm_server_opt_set_state: null moment");
+    ARGCHK(steps >= 0, "fm_server_opt_set_state: steps must be >= 0");
+    // the floats outside the entries' matrices keep a legal value: m = 0, v = tau^2 as at the install
+    HIPCHK(hipMemsetAsync(e->srv_m, 0, e->NP * 4, e->main.st));
+    RCCHK(state_dict_to_arena(e, m_dev, e->srv_m, true));
+    if (adaptive) {
+#pragma clang fp contract(off)
+        const float v0 = e->srv_hp.tau * e->srv_hp.tau;
+        RCCHK(srv_fill(e, e->srv_v, v0));
+        RCCHK(state_dict_to_arena(e, v_dev, e->srv_v, true));
+    }
+    e->srv_steps = steps;
+    HIPCHK(hipGetLastError());
+    return FM_OK;
+}
+
+int fm_server_opt_end(fm_engine* e)
+{
+    ARGCHK(e, "null engine");
+    ARGCHK(e->srv_on, "fm_server_opt_end: no server optimizer is installed");
+    e->srv_on = false;
+    return FM_OK;
+}
+
+int fm_server_opt_active(fm_engine* e) { return e && e->srv_on ? 1 : 0; }
 
 int fm_teacher_axpby(fm_engine* e, float w_teacher, float w_student)
 {

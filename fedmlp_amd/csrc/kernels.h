@@ -330,6 +330,14 @@ void k_drift_correct(const DriftOps& a, int64_t n, hipStream_t s, const int* ski
 void k_drift_correct_masked(const DriftOps& a, const OptChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip);
 // x[i] = x[i] / k, n floats at any alignment
 void k_drift_div(float* x, float k, int64_t n, hipStream_t s);
+// ---- server optimizers (server_opt.hip): FedAvgM / FedAdagrad / FedAdam / FedYogi on the pseudo-gradient st - x ------------
+// One block per chunk of the DistEntry / DistChunk table of the trainable entries.  x: the round's starting model (read only);
+// st: the aggregate, overwritten by x'; m, v: NP floats each, in place (v is not named by AVGM).  omb1 / omb2: 1.0f - beta, formed
+// by the host.  part: n_chunks doubles; norm (may be null): |st - x|_2 over the entries' real elements as one double.
+// (rule: FM_SERVER_AVGM .. FM_SERVER_YOGI of include/fedmlp_hip_server.h, which the callers include)
+struct ServerOps { const float* x; float* st; float* m; float* v; float lr, beta1, omb1, beta2, omb2, tau; };
+void k_server_opt(int rule, const ServerOps& a, const DistEntry* ent, const DistChunk* chunks, int n_chunks, double* part,
+                  double* norm, hipStream_t s, const int* skip);
 
 // ---- prototypes / tagging ----------------------------------------------------------
 void k_proto_accumulate(const float* feat, const float* logits, const float* labels, int B, int D, int C,

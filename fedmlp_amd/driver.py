@@ -77,6 +77,15 @@ def build_parser():
                    help="FedProx: mu of the proximal term mu/2 |w - w_glob|^2 in every local step (fedmlp_amd/drift.py); 0 = off")
     p.add_argument("--scaffold", type=int, default=0, choices=[0, 1],
                    help="1: SCAFFOLD control variates in every local step (fedmlp_amd/drift.py)")
+    p.add_argument("--server_opt", default="none", choices=["none", "avgm", "adagrad", "adam", "yogi"],
+                   help="server optimizer on the aggregated model (fedmlp_amd/server_opt.py): FedAvgM, FedAdagrad, FedAdam, FedYogi")
+    p.add_argument("--server_lr", type=float, default=None, help="default: the class's own (1.0 avgm, 1e-2 the adaptive rules)")
+    p.add_argument("--server_beta1", type=float, default=None, help="momentum of avgm; default 0.9")
+    p.add_argument("--server_beta2", type=float, default=None, help="adam, yogi; default 0.99")
+    p.add_argument("--server_tau", type=float, default=None, help="adagrad, adam, yogi; default 1e-3")
+    p.add_argument("--init_server_opt", default=None,
+                   help="a server_opt_{rnd}.pth of --save_every to resume the server optimizer from; its hyper-parameters are "
+                        "taken, and a --server_* flag that contradicts them is refused")
     return p
 
 
@@ -93,10 +102,31 @@ def check_drift_flags(p, args):
         p.error(f"--prox_mu / --scaffold are built for --exp {', '.join(DRIFT_EXPS)} (got {args.exp})")
 
 
+SERVER_OWN_EXPS = ("RSCFed", "CBAFed")                  # rows whose aggregation is server arithmetic of its own
+
+
+def check_server_flags(p, args):
+    """--server_opt and its hyper-parameters: not with the rows that have server arithmetic of their own, values the rule accepts"""
+    given = [f for f in ("server_lr", "server_beta1", "server_beta2", "server_tau", "init_server_opt") if getattr(args, f) is not None]
+    if args.server_opt == "none":
+        if given:
+            p.error(f"--{given[0]} needs --server_opt")
+        return
+    if args.exp in SERVER_OWN_EXPS:
+        p.error(f"--server_opt is not built for --exp {' / '.join(SERVER_OWN_EXPS)}, whose aggregation has server arithmetic of "
+                f"its own (got {args.exp})")
+    from fedmlp_amd import server_opt
+    try:
+        server_opt.make(args.server_opt, args.server_lr, args.server_beta1, args.server_beta2, args.server_tau)
+    except ValueError as ex:
+        p.error(f"--server_opt {args.server_opt}: {ex}")
+
+
 def args_parser(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
     check_drift_flags(p, args)
+    check_server_flags(p, args)
     if args.exp == "RSCFed" and args.n_clients < RSCFED_K:
         p.error(f"--exp RSCFed draws groups of {RSCFED_K} clients (main.py:116-119): --n_clients must be >= {RSCFED_K}")
     if args.exp == "FedNoRo" and args.rounds_warmup > args.rounds_FedNoRo_warmup:
@@ -323,16 +353,33 @@ def main(args=None, module="fedmlp_amd.driver"):
     test = None
     if args.eval_every > 0:                              # its own seed: no client's data (seed + 1000 c) is the test set
         test = ShardedTestSet(args.n_test, C, args.hw, args.seed + 500, 4 * args.batch_size, rank, world, dev)
-    log = run_rounds(args, row, eng, net, clients, rank, world, dev, test=test, scaffold=scaffold)
+    # server optimizer (fedmlp_amd/server_opt.py): one launch on the aggregated model per round, the same on every rank
+    server = None
+    if args.server_opt != "none":
+        from fedmlp_amd import server_opt
+        server = server_opt.make(args.server_opt, args.server_lr, args.server_beta1, args.server_beta2, args.server_tau)
+        if args.init_server_opt:                          # the file's hyper-parameters win: a flag that says otherwise is refused
+            saved = torch.load(args.init_server_opt, map_location="cpu")
+            asked = server.hyper()
+            for flag, key in (("server_lr", "lr"), ("server_beta1", "beta1"), ("server_beta2", "beta2"), ("server_tau", "tau")):
+                if getattr(args, flag) is not None and asked[key] != float(saved["hyper"][key]):
+                    raise SystemExit(f"--{flag} {getattr(args, flag)} contradicts {args.init_server_opt}, which was saved with "
+                                     f"{key} = {saved['hyper'][key]}: drop the flag or start a fresh optimizer")
+            server.load_state_dict(saved)
+        server.begin(eng)
+    log = run_rounds(args, row, eng, net, clients, rank, world, dev, test=test, scaffold=scaffold, server=server)
+    if server is not None:
+        server.end(eng)
     if dist is not None:
         dist.barrier(); dist.destroy_process_group()
     return log
 
 
-def run_rounds(args, row, eng, net, clients, rank, world, dev, test=None, scaffold=None):
+def run_rounds(args, row, eng, net, clients, rank, world, dev, test=None, scaffold=None, server=None):
     """The loop over rounds (main.py:106-357) for one row (fedmlp_amd/rows.py) on this rank's clients {c: LocalUpdate}, from the
     global model the engine holds -> the per-round records (rank 0 prints them).  Nothing here needs a GPU of its own: with
-    stand-ins for the engine and the clients it runs on the CPU."""
+    stand-ins for the engine and the clients it runs on the CPU.  server: a fedmlp_amd.server_opt optimizer installed on the
+    engine (or None): its step turns the round's aggregate into the new global model."""
     sync = torch.cuda.synchronize if torch.device(dev).type == "cuda" else (lambda: None)
     C = args.n_classes
     glob = eng.state_tensor().clone()                     # netglob, replicated on every rank
@@ -351,6 +398,13 @@ def run_rounds(args, row, eng, net, clients, rank, world, dev, test=None, scaffo
             row.contribute(rnd, acc, c, loc, ret)
         # aggregation (main.py:213-319): every sum over clients is an RCCL all-reduce in the library
         glob_cnt = row.aggregate(rnd, acc)
+        delta_norm = None
+        if server is not None:                            # x' from the pseudo-gradient aggregate - glob; every rank the same bits
+            from fedmlp_amd.fedavg import state_agreement
+            delta_norm = server.step(eng, glob)
+            agree, worst = state_agreement(eng)
+            if not agree:
+                raise RuntimeError(f"the ranks' states differ after the server optimizer's step (checksum spread {worst:.3e})")
         glob.copy_(eng.state_tensor())
         if scaffold is not None:                          # c += sum_i delta c_i / n_clients; the models went through FedAvg above
             scaffold.server_update()
@@ -372,10 +426,14 @@ def run_rounds(args, row, eng, net, clients, rank, world, dev, test=None, scaffo
             rec["scaffold"] = {"c_norm": float(scaffold.c_global.double().norm())}
         elif args.prox_mu > 0:
             rec["prox_mu"] = args.prox_mu
+        if server is not None:
+            rec["server_opt"] = {"rule": server.rule, "step": int(server.steps), "delta_norm": float(delta_norm)}
         if rank == 0:
             print(json.dumps(rec), flush=True)
             if args.save_every and (rnd + 1) % args.save_every == 0:     # torch.save(netglob.state_dict(), ...) main.py:237
                 torch.save(net.state_dict(), os.path.join(args.save_dir, f"model_{rnd}.pth"))
+                if server is not None:
+                    torch.save(server.state_dict(), os.path.join(args.save_dir, f"server_opt_{rnd}.pth"))
         log.append(rec)
     return log
 

@@ -17,6 +17,7 @@ def args_parser(argv=None):
     if args.exp != "RoFL":
         p.error("fedmlp_amd.driver_rofl runs the RoFL row only; the other rows are fedmlp_amd.driver's")
     driver.check_drift_flags(p, args)             # --prox_mu / --scaffold: refused, train_RoFL installs no correction
+    driver.check_server_flags(p, args)            # --server_opt: the driver's, RoFL aggregates with plain FedAvg
     return args
 
 
