@@ -8,9 +8,8 @@
 // The engine layout is not the state_dict layout: a conv weight is [O][KH][Wpad][Ipad] with a row stride that may exceed the
 // dense row (packed stem), and only wp < KW, ip < I are state_dict elements.  Padding inside a matrix is zero after
 // fm_set_state but nothing here relies on it, and the gaps outside the matrices hold whatever the caller left there: an
-// element counts only if the entry's geometry says it is real.  The kernel is driven by a table built once per engine from
-// its state entries: one DistEntry per fp32 entry (arena span + geometry) and one DistChunk per <= FM_DIST_CHUNK consecutive
-// arena floats of a span, so a chunk never straddles an entry.
+// element counts only if the entry's geometry says it is real.  The kernel is driven by the engine's entry / chunk table
+// (arena_table.h): one block per chunk, all of them.
 //
 // Precision and determinism: the difference in fp32 (what torch.norm(w1 - w2) sees), its square and every sum in fp64.  No
 // atomics: stage 1 is one block per chunk, a thread's serial sum, xor-shuffles over the wave and (w0 + w1) + (w2 + w3) through
@@ -36,15 +35,14 @@ __device__ __forceinline__ void dist_load4(const float* __restrict__ p, int64_t 
 
 template <int KMAX>
 __global__ void __launch_bounds__(256) state_dist_kernel(FoldArgs a, int K, const float* __restrict__ ref,
-                                                         const DistEntry* __restrict__ ent, const DistChunk* __restrict__ chunks,
+                                                         const ArenaEntry* __restrict__ ent, const ArenaChunk* __restrict__ chunks,
                                                          int64_t NS, int aligned, double* __restrict__ part)
 {
 #pragma clang fp contract(off)
     __shared__ double sm[4][KMAX];
-    const DistChunk ch = chunks[blockIdx.x];
-    const DistEntry en = ent[ch.entry];
-    const int64_t begin = en.off + ch.start;
-    const int64_t end = en.off + min(ch.start + FM_DIST_CHUNK, en.len);
+    const ArenaChunk ch = chunks[blockIdx.x];
+    const ArenaEntry en = ent[ch.ent];
+    const int64_t begin = ch.begin, end = begin + ch.len;
     const float Kf = (float)K;
     double acc[KMAX];
 #pragma unroll
@@ -75,12 +73,7 @@ __global__ void __launch_bounds__(256) state_dist_kernel(FoldArgs a, int K, cons
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int64_t g = g4 + c;
-            ok[c] = g >= begin && g < end;
-            if (!en.all_real) {
-                const unsigned pos = (unsigned)(g - en.off) % (unsigned)en.row;      // inside the row of one output channel
-                const unsigned ip = pos % (unsigned)en.Ipad, wp = (pos / (unsigned)en.Ipad) % (unsigned)en.Wpad;
-                ok[c] = ok[c] && pos < (unsigned)en.dense && ip < (unsigned)en.I && wp < (unsigned)en.W;
-            }
+            ok[c] = g >= begin && g < end && real_element(en, g);
         }
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
@@ -92,22 +85,12 @@ __global__ void __launch_bounds__(256) state_dist_kernel(FoldArgs a, int K, cons
                 }
             }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-            double s = acc[k];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
-            if (lane == 0) sm[wave][k] = s;
-        }
-    __syncthreads();
-    if ((int)threadIdx.x < K)
-        part[(int64_t)blockIdx.x * K + threadIdx.x] = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+    const double s = block_sum_f64(acc, K, sm);
+    if ((int)threadIdx.x < K) part[(int64_t)blockIdx.x * K + threadIdx.x] = s;
 }
 
 // one thread per (entry, k), k fastest: the entry's partials in chunk order, square root, one rounding to fp32
-__global__ void __launch_bounds__(64) state_dist_final_kernel(const double* __restrict__ part, const DistEntry* __restrict__ ent,
+__global__ void __launch_bounds__(64) state_dist_final_kernel(const double* __restrict__ part, const ArenaEntry* __restrict__ ent,
                                                               int n_entries, int K, float* __restrict__ norms)
 {
     const int idx = blockIdx.x * 64 + threadIdx.x;
@@ -121,7 +104,7 @@ __global__ void __launch_bounds__(64) state_dist_final_kernel(const double* __re
     norms[(int64_t)k * n_entries + e] = (float)sqrt(s);
 }
 
-void k_state_dist(const FoldArgs& a, int K, const float* ref, const DistEntry* ent, int n_entries, const DistChunk* chunks,
+void k_state_dist(const FoldArgs& a, int K, const float* ref, const ArenaEntry* ent, int n_entries, const ArenaChunk* chunks,
                   int n_chunks, int64_t NS, double* part, float* norms, hipStream_t s)
 {
     bool al = ref == nullptr || (reinterpret_cast<uintptr_t>(ref) & 15) == 0;

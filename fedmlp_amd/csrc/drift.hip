@@ -18,12 +18,10 @@
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// a thread holds DRIFT_QPT quads of every operand: all its 16-byte loads are in flight before the first use
-#define DRIFT_QPT (FM_DIST_CHUNK / 4 / 256)
-
 template <bool PROX, bool SHIFT, bool TRACK>
 struct DriftRule {
     DriftOps a;
+    struct Hp {};             // the scalars travel with the operands
     struct Quad { f32x4 g, p, a, s, S, r; };
     __device__ __forceinline__ void load(Quad& q, int64_t o) const
     {
@@ -32,7 +30,7 @@ struct DriftRule {
         if (SHIFT) q.s = *reinterpret_cast<const f32x4*>(a.s + o);
         if (TRACK) q.S = *reinterpret_cast<const f32x4*>(a.S + o);
     }
-    __device__ __forceinline__ void update(Quad& q) const
+    __device__ __forceinline__ void update(Quad& q, const Hp& = Hp{}) const
     {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -48,35 +46,28 @@ struct DriftRule {
             q.r[k] = r;
         }
     }
+    __device__ __forceinline__ void store(const Quad& q, int64_t o, int64_t begin, int64_t end) const
+    {
+        store_own(a.r, o, begin, end, q.r);
+        if (TRACK) store_own(a.S, o, begin, end, q.S);
+    }
 };
 
-// the floats of the quad at o that lie in [begin, end): 16 bytes inside, lane by lane at an entry's edges (optim.hip's rule)
-__device__ __forceinline__ void drift_store_own(float* __restrict__ a, int64_t o, int64_t begin, int64_t end, const f32x4 v)
-{
-    if (o >= begin && o + 4 <= end) {
-        *reinterpret_cast<f32x4*>(a + o) = v;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (o + k >= begin && o + k < end) a[o + k] = v[k];
-    }
-}
-
-// ---- the flat form: [0, 4 n4), no requires_grad mask.  Block b owns the DRIFT_QPT * 256 quads from b * DRIFT_QPT * 256 on;
-// thread t takes quads t, t + 256, ...
+// ---- the flat form: [0, 4 n4), no requires_grad mask.  Block b owns the ARENA_QPT * 256 quads from b * ARENA_QPT * 256 on;
+// thread t takes quads t, t + 256, ...; all its 16-byte loads are in flight before the first use
 template <bool PROX, bool SHIFT, bool TRACK>
 __global__ void __launch_bounds__(256) drift_flat_kernel(const DriftRule<PROX, SHIFT, TRACK> r, int64_t n4, const int* __restrict__ skip)
 {
     if (skip && *skip) return;
-    const int64_t i0 = (int64_t)blockIdx.x * (DRIFT_QPT * 256) + threadIdx.x;
-    typename DriftRule<PROX, SHIFT, TRACK>::Quad q[DRIFT_QPT];
+    const int64_t i0 = (int64_t)blockIdx.x * (ARENA_QPT * 256) + threadIdx.x;
+    typename DriftRule<PROX, SHIFT, TRACK>::Quad q[ARENA_QPT];
 #pragma unroll
-    for (int j = 0; j < DRIFT_QPT; ++j) {
+    for (int j = 0; j < ARENA_QPT; ++j) {
         const int64_t i = i0 + (int64_t)j * 256;
         if (i < n4) r.load(q[j], 4 * i);
     }
 #pragma unroll
-    for (int j = 0; j < DRIFT_QPT; ++j) {
+    for (int j = 0; j < ARENA_QPT; ++j) {
         const int64_t i = i0 + (int64_t)j * 256;
         if (i < n4) {
             r.update(q[j]);
@@ -86,72 +77,45 @@ __global__ void __launch_bounds__(256) drift_flat_kernel(const DriftRule<PROX, S
     }
 }
 
-// ---- the table form: one block per chunk of the trainable arena's entry table (engine.hip: ensure_opt_table), under a
-// requires_grad mask.  sel = 0 marks a trainable entry: corrected and tracked with the flat form's arithmetic.  Anything else is
-// a frozen one: r = 0 over its span, S untouched, no load.  An entry begins and ends at any element offset, so a chunk's first
-// quad starts at the 16-byte boundary at or below `begin`; a block reads whole quads and WRITES only its own floats
-// (drift_store_own).  A full chunk that starts off a 16-byte boundary has one quad more than DRIFT_QPT * 256: the tail loop.
-// Floats outside every entry are touched by nobody and stay the zeros r and S were allocated with.
-__device__ __forceinline__ unsigned drift_sel_get(const OptSel& t, int ent) { return (t.w[ent >> 3] >> ((ent & 7) * 4)) & 15u; }
-
+// ---- the table form: one block per parameter chunk of the engine's entry / chunk table (arena_table.h), under a
+// requires_grad mask.  sel = 0 marks a trainable entry: corrected and tracked with the flat form's arithmetic, arena_walk's
+// boundary rule (whole quads read, own floats written).  Anything else is a frozen one: r = 0 over its span, S untouched, no
+// load.  Floats outside every entry are touched by nobody and stay the zeros r and S were allocated with.
 template <bool PROX, bool SHIFT, bool TRACK>
-__global__ void __launch_bounds__(256) drift_masked_kernel(const DriftRule<PROX, SHIFT, TRACK> r, const OptChunk* __restrict__ chunks,
+__global__ void __launch_bounds__(256) drift_masked_kernel(const DriftRule<PROX, SHIFT, TRACK> r, const ArenaChunk* __restrict__ chunks,
                                                            const OptSel sel, const int* __restrict__ skip)
 {
     if (skip && *skip) return;
-    const OptChunk ch = chunks[blockIdx.x];
-    const int64_t begin = ch.begin, end = begin + ch.len;
-    const int64_t o0 = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x;
-    if (drift_sel_get(sel, ch.ent) != 0u) {
+    const ArenaChunk ch = chunks[blockIdx.x];
+    if (opt_sel_get(sel, ch.ent) != 0u) {
+        const int64_t begin = ch.begin, end = begin + ch.len;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int64_t o = o0; o < end; o += 1024) drift_store_own(r.a.r, o, begin, end, z);
+        for (int64_t o = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x; o < end; o += 1024) store_own(r.a.r, o, begin, end, z);
         return;
     }
-    typename DriftRule<PROX, SHIFT, TRACK>::Quad q[DRIFT_QPT];
-#pragma unroll
-    for (int j = 0; j < DRIFT_QPT; ++j) {
-        const int64_t o = o0 + (int64_t)j * 1024;
-        if (o < end) r.load(q[j], o);
-    }
-#pragma unroll
-    for (int j = 0; j < DRIFT_QPT; ++j) {
-        const int64_t o = o0 + (int64_t)j * 1024;
-        if (o < end) {
-            r.update(q[j]);
-            drift_store_own(r.a.r, o, begin, end, q[j].r);
-            if (TRACK) drift_store_own(r.a.S, o, begin, end, q[j].S);
-        }
-    }
-    const int64_t o = o0 + (int64_t)DRIFT_QPT * 1024;
-    if (o < end) {
-        typename DriftRule<PROX, SHIFT, TRACK>::Quad t;
-        r.load(t, o);
-        r.update(t);
-        drift_store_own(r.a.r, o, begin, end, t.r);
-        if (TRACK) drift_store_own(r.a.S, o, begin, end, t.S);
-    }
+    arena_walk(r, ch, {});
 }
 
 template <bool PROX, bool SHIFT, bool TRACK>
-static void drift_launch(const DriftOps& a, int64_t n, const OptChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
+static void drift_launch(const DriftOps& a, int64_t n, const ArenaChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
                          const int* skip)
 {
     const DriftRule<PROX, SHIFT, TRACK> r{a};
     if (!chunks) {
         const int64_t n4 = n / 4;
-        hipLaunchKernelGGL((drift_flat_kernel<PROX, SHIFT, TRACK>), dim3(cdiv(n4, DRIFT_QPT * 256)), dim3(256), 0, s, r, n4, skip);
+        hipLaunchKernelGGL((drift_flat_kernel<PROX, SHIFT, TRACK>), dim3(cdiv(n4, ARENA_QPT * 256)), dim3(256), 0, s, r, n4, skip);
     } else {
         hipLaunchKernelGGL((drift_masked_kernel<PROX, SHIFT, TRACK>), dim3(n_chunks), dim3(256), 0, s, r, chunks, *sel, skip);
     }
 }
 template <bool PROX, bool SHIFT>
-static void drift_launch_t(const DriftOps& a, int64_t n, const OptChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
+static void drift_launch_t(const DriftOps& a, int64_t n, const ArenaChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
                            const int* skip)
 {
     if (a.S) drift_launch<PROX, SHIFT, true>(a, n, chunks, n_chunks, sel, s, skip);
     else drift_launch<PROX, SHIFT, false>(a, n, chunks, n_chunks, sel, s, skip);
 }
-static void drift_dispatch(const DriftOps& a, int64_t n, const OptChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
+static void drift_dispatch(const DriftOps& a, int64_t n, const ArenaChunk* chunks, int n_chunks, const OptSel* sel, hipStream_t s,
                            const int* skip)
 {
     const bool prox = a.mu != 0.f, shift = a.s != nullptr;
@@ -165,7 +129,7 @@ void k_drift_correct(const DriftOps& a, int64_t n, hipStream_t s, const int* ski
 {
     drift_dispatch(a, n, nullptr, 0, nullptr, s, skip);
 }
-void k_drift_correct_masked(const DriftOps& a, const OptChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip)
+void k_drift_correct_masked(const DriftOps& a, const ArenaChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip)
 {
     drift_dispatch(a, 0, chunks, n_chunks, &sel, s, skip);
 }

@@ -195,13 +195,22 @@ struct StateEntry {           // one state_dict entry, in reference key order
     int Ostride = 0;          // engine row stride when it exceeds KH*Wpad*Ipad (packed stem: 176), 0 = dense
     // the entry's span in the arena: a conv weight's O rows of `dense` floats, `row` apart, the last row ending with its matrix; a
     // vector's n elements as one row
-    struct Span { int dense, row; long long len; };
+    using Span = ArenaSpan;
     Span span() const
     {
         if (kind != 0) return {(int)n, (int)n, (long long)n};
         const int dense = KH * Wpad * Ipad, row = Ostride ? Ostride : dense;
         return {dense, row, (long long)(O - 1) * row + dense};
     }
+};
+
+// The entry / chunk table of the state arena (arena_table.h), a property of the model: built and uploaded once by fm_create
+// (build_arena_table).  ent / chunks / ent_of / n_param_chunks are the host copy, d_ent / d_chunks the device arrays; ent_at maps
+// an arena offset to the state entry (parameter) that starts there
+struct ArenaTable : ArenaTableHost {
+    ArenaEntry* d_ent = nullptr;
+    ArenaChunk* d_chunks = nullptr;
+    std::unordered_map<size_t, int> ent_at;
 };
 
 struct EvPair { hipEvent_t a, b; int family; double flops; };
@@ -238,11 +247,8 @@ struct fm_engine {
     // (allocated on first use)
     double* norm_part = nullptr;
     float* norm_word = nullptr;
-    // fm_state_dist: the entry / chunk table of the fp32 state entries and the per-(chunk, k) partial sums (built on first use)
-    DistEntry* dist_ent = nullptr;
-    DistChunk* dist_chunks = nullptr;
-    double* dist_part = nullptr;
-    int dist_n_ent = 0, dist_n_chunks = 0;
+    ArenaTable tab;                   // the entry / chunk table every chunked kernel walks
+    double* dist_part = nullptr;      // fm_state_dist: the per-(chunk, k) partial sums (allocated on first use)
     uint8_t* strong_ws = nullptr;     // fm_augment_strong's uint8 images and LUTs for maxB samples, allocated on first use
     uint8_t* metrics_ws = nullptr;    // fm_eval_metrics' workspace (class-major scores, chunk counts, partials): grows on demand
     size_t metrics_ws_bytes = 0;
@@ -252,15 +258,10 @@ struct fm_engine {
     // per-layer requires_grad and optimizer parameter groups (autograd path only).  `trainable`: one flag per state entry,
     // EMPTY = the default mask (every parameter trainable: every code path is then the one it was before masks existed);
     // `pending_trainable` the mask of the pending forward (its backward takes that one, like pending_fixed).  `group_of`: the
-    // parameter group of each state entry, -1 = not optimized (fm_optim_groups; empty = no table).  The entry / chunk table
-    // of the trainable arena behind both (ensure_opt_table): opt_ent maps a state entry to its index in the table's entry
-    // list (-1: running statistic or counter), ent_at an arena offset to the state entry that starts there
+    // parameter group of each state entry, -1 = not optimized (fm_optim_groups; empty = no table).  Both are carried to the
+    // kernels over `tab`'s parameter chunks as a selector (group_sel / mask_sel)
     std::vector<int32_t> trainable, pending_trainable, group_of;
     int n_groups = 0;
-    OptChunk* opt_chunks = nullptr;
-    int n_opt_chunks = 0;
-    std::vector<int> opt_ent;
-    std::unordered_map<size_t, int> ent_at;
     std::vector<StateEntry> entries;
     int n_bn_ch = 0;
     size_t NP = 0, NS = 0;            // trainable floats (padded to 4), whole state floats
@@ -307,16 +308,14 @@ struct fm_engine {
     float *drift_anchor = nullptr, *drift_shift = nullptr, *drift_gsum = nullptr, *drift_gcorr = nullptr;
     // server optimizer (fm_server_opt_begin .. fm_server_opt_end, include/fedmlp_hip_server.h): while `srv_on`, fm_server_opt_step
     // -- and nothing else -- enqueues server_opt.hip's launch.  The two moments are NP floats each, allocated by the first install
-    // (v by the first adaptive one); srv_chunks: the chunks of fm_state_dist's entry table that lie in the parameter arena,
-    // srv_part one fp64 partial per chunk, srv_omb1 / srv_omb2 = 1.0f - beta in fp32
+    // (v by the first adaptive one), like srv_part, one fp64 partial per parameter chunk of `tab`; srv_omb1 / srv_omb2 =
+    // 1.0f - beta in fp32
     bool srv_on = false;
     fm_server_opt srv_hp{};
     float srv_omb1 = 0.f, srv_omb2 = 0.f;
     int64_t srv_steps = 0;
     float *srv_m = nullptr, *srv_v = nullptr;
-    DistChunk* srv_chunks = nullptr;
     double* srv_part = nullptr;
-    int srv_n_chunks = 0;
     int* tag_buf = nullptr;           // fm_select_topk_rows: [pool sizes ncls | counts 2 ncls | top ncls*cap | bot ncls*cap | rows ncls*stride]
     size_t tag_buf_ints = 0;
     // profiling
@@ -1860,7 +1859,7 @@ const float* drift_grad(fm_engine* e, const float* g)
     const DriftOps a{g, e->student.state, e->drift_anchor, e->drift_shifted ? e->drift_shift : nullptr,
                      e->drift_track ? e->drift_gsum : nullptr, e->drift_gcorr, e->drift_mu};
     if (e->trainable.empty()) k_drift_correct(a, (int64_t)e->NP, e->main.st, e->dev_err);
-    else k_drift_correct_masked(a, e->opt_chunks, e->n_opt_chunks, mask_sel(e, e->trainable.data()), e->main.st, e->dev_err);
+    else k_drift_correct_masked(a, e->tab.d_chunks, e->tab.n_param_chunks, mask_sel(e, e->trainable.data()), e->main.st, e->dev_err);
     e->drift_steps += 1;
     return e->drift_gcorr;
 }
@@ -1925,36 +1924,17 @@ int grad_norm(fm_engine* e, float* norm)
 // ---- per-layer requires_grad, parameter groups ----------------------------------------------------------------------
 // a state entry is a PARAMETER if it is a float entry inside the trainable arena (running statistics and counters are buffers)
 inline bool is_param(const fm_engine* e, const StateEntry& en) { return en.kind != 2 && en.eng_off < e->NP; }
-// The entry / chunk table of the trainable arena: ensure_dist_table's construction restricted to the parameters -- one table
-// entry per parameter in state_dict order, its arena span (a conv weight: its O rows with the row stride, the packed stem's row
-// tails included) cut into chunks of FM_DIST_CHUNK floats, so a chunk never straddles an entry.  Built and uploaded once per
-// engine, at the first fm_set_trainable / fm_optim_groups; plain host code up to the upload.
-int build_opt_table(const std::vector<StateEntry>& entries, size_t NP, std::vector<OptChunk>& chunks, std::vector<int>& opt_ent,
-                    std::unordered_map<size_t, int>& ent_at)
+// The engine's entry / chunk table (arena_table.h has its layout and the contract): one descriptor per state entry in
+// state_dict order; plain host code up to the upload.
+int build_arena_table(fm_engine* e)
 {
-    chunks.clear(); ent_at.clear();
-    opt_ent.assign(entries.size(), -1);
-    int n_ent = 0;
-    for (size_t i = 0; i < entries.size(); ++i) {
-        const StateEntry& en = entries[i];
-        if (en.kind == 2 || en.eng_off >= NP) continue;
-        const long long len = en.span().len;
-        if (len <= 0 || en.eng_off + (size_t)len > NP) return -1;
-        opt_ent[i] = n_ent;
-        ent_at[en.eng_off] = (int)i;
-        for (long long st = 0; st < len; st += FM_DIST_CHUNK)
-            chunks.push_back({(long long)en.eng_off + st, (int)std::min<long long>(FM_DIST_CHUNK, len - st), n_ent});
-        ++n_ent;
-    }
-    return n_ent;
-}
-int ensure_opt_table(fm_engine* e)
-{
-    if (e->opt_chunks) return FM_OK;
-    std::vector<OptChunk> chunks;
-    const int n_ent = build_opt_table(e->entries, e->NP, chunks, e->opt_ent, e->ent_at);
-    if (n_ent < 0) { g_err = "a parameter entry lies outside the trainable arena"; return FM_ERR_ARG; }
-    if (n_ent > OPT_MAX_ENT) { g_err = "more parameter entries than the optimizer table holds"; return FM_ERR_ARG; }
+    ArenaTable& t = e->tab;
+    std::vector<ArenaDesc> descs;
+    for (const StateEntry& en : e->entries)
+        descs.push_back({en.kind, (long long)en.eng_off, en.span(), en.Ipad, en.I, en.Wpad, en.KW, is_param(e, en)});
+    if (const char* why = arena_table_build(descs, (long long)e->NP, (long long)e->NS, t)) { g_err = why; return FM_ERR_ARG; }
+    for (size_t i = 0; i < e->entries.size(); ++i)
+        if (is_param(e, e->entries[i])) t.ent_at[e->entries[i].eng_off] = (int)i;
     // every offset the backward asks ent_on() about must start a table entry: a layout change fails here, not by quietly
     // switching truncation and the skipped weight gradients off (checked before anything is allocated)
     std::vector<size_t> offs = {e->off_fcw, e->off_fcb};
@@ -1962,33 +1942,32 @@ int ensure_opt_table(fm_engine* e)
     for (auto& b : e->bns) { offs.push_back(e->off_gamma + b.ch_off); offs.push_back(e->off_beta + b.ch_off); }
     for (auto& m : e->mbs) { offs.push_back(m.dw_off); offs.push_back(m.w1_off); offs.push_back(m.b1_off); offs.push_back(m.w2_off); offs.push_back(m.b2_off); }
     for (size_t o : offs)
-        if (!e->ent_at.count(o)) { g_err = "a layer's arena offset starts no state entry (optimizer entry table)"; return FM_ERR_ARG; }
-    OptChunk* dc = nullptr;
-    DALLOC(dc, chunks.size());
-    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(OptChunk), hipMemcpyHostToDevice));
-    e->n_opt_chunks = (int)chunks.size();
-    e->opt_chunks = dc;
+        if (!t.ent_at.count(o)) { g_err = "a layer's arena offset starts no state entry (optimizer entry table)"; return FM_ERR_ARG; }
+    DALLOC(t.d_ent, t.ent.size()); DALLOC(t.d_chunks, t.chunks.size());
+    HIPCHK(hipMemcpy(t.d_ent, t.ent.data(), t.ent.size() * sizeof(ArenaEntry), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.d_chunks, t.chunks.data(), t.chunks.size() * sizeof(ArenaChunk), hipMemcpyHostToDevice));
     return FM_OK;
 }
 // is the parameter that starts at arena offset `off` trainable under the mask `tr` (null: yes)
 inline bool ent_on(const fm_engine* e, const int32_t* tr, size_t off)
 {
     if (!tr) return true;
-    const auto it = e->ent_at.find(off);             // (ensure_opt_table checked that every offset asked about resolves)
-    return it == e->ent_at.end() || tr[it->second] != 0;
+    const auto it = e->tab.ent_at.find(off);         // (build_arena_table checked that every offset asked about resolves)
+    return it == e->tab.ent_at.end() || tr[it->second] != 0;
 }
 inline bool conv_on(const fm_engine* e, const int32_t* tr, int ci) { return ent_on(e, tr, e->convs[ci].w_off); }
 inline bool bn_on(const fm_engine* e, const int32_t* tr, int bi)
 {
     return ent_on(e, tr, e->off_gamma + e->bns[bi].ch_off) || ent_on(e, tr, e->off_beta + e->bns[bi].ch_off);
 }
-// the launch's selector: the parameter group of every table entry, OPT_SKIP where nobody steps it (no group, or frozen)
+// the launch's selector: the parameter group of every parameter's table entry, OPT_SKIP where nobody steps it (no group, or
+// frozen)
 OptSel group_sel(const fm_engine* e)
 {
     OptSel sel{};
     for (size_t i = 0; i < e->entries.size(); ++i) {
-        const int t = e->opt_ent[i];
-        if (t < 0) continue;
+        if (!is_param(e, e->entries[i])) continue;
+        const int t = e->tab.ent_of[i];
         const int g = e->group_of[i];
         const bool on = g >= 0 && (e->trainable.empty() || e->trainable[i] != 0);
         opt_sel_set(sel, t, on ? (unsigned)g : OPT_SKIP);
@@ -2000,7 +1979,7 @@ OptSel mask_sel(const fm_engine* e, const int32_t* tr)
 {
     OptSel sel{};
     for (size_t i = 0; i < e->entries.size(); ++i)
-        if (e->opt_ent[i] >= 0) opt_sel_set(sel, e->opt_ent[i], tr[i] != 0 ? 0u : 1u);
+        if (is_param(e, e->entries[i])) opt_sel_set(sel, e->tab.ent_of[i], tr[i] != 0 ? 0u : 1u);
     return sel;
 }
 // The grouped steps: hp[i] belongs to group i of fm_optim_groups' table, and each group's scalars come from the function the flat
@@ -2011,7 +1990,7 @@ void adam_step_groups(fm_engine* e, const fm_adam* hp, int n)
     e->adam_t += 1;
     OptAdamArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = adam_hp(hp[i], e->adam_t);
-    k_adam_groups(e->student.state, g, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_adam_groups(e->student.state, g, e->adam_m, e->adam_v, e->tab.d_chunks, e->tab.n_param_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void adamw_step_groups(fm_engine* e, const fm_adam* hp, int n)
@@ -2020,7 +1999,7 @@ void adamw_step_groups(fm_engine* e, const fm_adam* hp, int n)
     e->adam_t += 1;
     OptAdamWArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = adamw_hp(hp[i], e->adam_t);
-    k_adamw_groups(e->student.state, g, e->adam_m, e->adam_v, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_adamw_groups(e->student.state, g, e->adam_m, e->adam_v, e->tab.d_chunks, e->tab.n_param_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 void sgd_step_groups(fm_engine* e, const fm_sgd* hp, int n)
@@ -2030,7 +2009,7 @@ void sgd_step_groups(fm_engine* e, const fm_sgd* hp, int n)
     e->adam_t += 1;
     OptSgdArgs a{};
     for (int i = 0; i < n; ++i) a.hp[i] = sgd_hp(hp[i], first);
-    k_sgd_groups(e->student.state, g, e->adam_m, e->opt_chunks, e->n_opt_chunks, group_sel(e), a, e->main.st, e->dev_err);
+    k_sgd_groups(e->student.state, g, e->adam_m, e->tab.d_chunks, e->tab.n_param_chunks, group_sel(e), a, e->main.st, e->dev_err);
     weights_stepped(e);
 }
 
@@ -2631,45 +2610,6 @@ int debug_fold_stats(fm_engine* e, int ci, int groups, float* stats_dev)
     return FM_OK;
 }
 
-// fm_state_dist's table from the engine's own state entries: one DistEntry per fp32 entry in state_dict order, its arena span
-// cut into chunks of FM_DIST_CHUNK floats (a chunk never straddles an entry).  A conv weight's span is its O rows with the
-// row stride; a vector's span is its n elements.  Uploaded once per engine.
-int ensure_dist_table(fm_engine* e)
-{
-    if (e->dist_ent) return FM_OK;
-    std::vector<DistEntry> ent;
-    std::vector<DistChunk> chunks;
-    for (auto& en : e->entries) {
-        if (en.kind == 2) continue;
-        DistEntry d{};
-        d.off = (long long)en.eng_off;
-        const StateEntry::Span sp = en.span();
-        d.dense = sp.dense; d.row = sp.row; d.len = (int)sp.len;
-        if (en.kind == 0) {
-            d.Ipad = en.Ipad; d.I = en.I; d.Wpad = en.Wpad; d.W = en.KW;
-            d.all_real = d.row == d.dense && en.Ipad == en.I && en.Wpad == en.KW;
-        } else {
-            d.Ipad = d.I = d.Wpad = d.W = 1;
-            d.all_real = 1;
-        }
-        if (d.len <= 0 || d.off < 0 || (size_t)d.off + (size_t)d.len > e->NS) { g_err = "state entry outside the arena"; return FM_ERR_ARG; }
-        d.chunk0 = (int)chunks.size();
-        for (int st = 0; st < d.len; st += FM_DIST_CHUNK) chunks.push_back({(int)ent.size(), st});
-        d.nchunks = (int)chunks.size() - d.chunk0;
-        ent.push_back(d);
-    }
-    DistEntry* de = nullptr;
-    DistChunk* dc = nullptr;
-    double* dp = nullptr;
-    DALLOC(de, ent.size()); DALLOC(dc, chunks.size()); DALLOC(dp, chunks.size() * FM_FOLD_MAX);
-    HIPCHK(hipMemcpy(de, ent.data(), ent.size() * sizeof(DistEntry), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(DistChunk), hipMemcpyHostToDevice));
-    e->dist_chunks = dc; e->dist_part = dp;
-    e->dist_n_ent = (int)ent.size(); e->dist_n_chunks = (int)chunks.size();
-    e->dist_ent = de;
-    return FM_OK;
-}
-
 // the launch of fm_fedavg_fold / fm_fed_w: fp32 weights and the divisor as the caller formed them
 int fold_states(fm_engine* e, const FoldArgs& a, int K, float tot, float* out_dev)
 {
@@ -2877,6 +2817,7 @@ int fm_create(const fm_config* cfg, fm_engine** out)
     e->model = cfg->model;
     int rc = e->model == 1 ? build_effnet_b0(e) : build_resnet18(e);
     if (rc == FM_OK) rc = build_tables(e);
+    if (rc == FM_OK) rc = build_arena_table(e);
     if (rc == FM_OK) rc = alloc_workspaces(e);
     if (rc != FM_OK) { fm_destroy(e); return rc; }
     *out = e;
@@ -3023,15 +2964,15 @@ int fm_state_dist(fm_engine* e, const float* const* states_dev, int32_t K, const
 {
     ARGCHK(e && states_dev && norms_dev, "null argument");
     ARGCHK(K >= 1 && K <= FM_FOLD_MAX, "fm_state_dist: 1 <= K <= FM_FOLD_MAX");
-    RCCHK(ensure_dist_table(e));
-    ARGCHK(n_entries == e->dist_n_ent, "fm_state_dist: n_entries is not the engine's number of fp32 state_dict entries");
+    ARGCHK(n_entries == (int32_t)e->tab.ent.size(), "fm_state_dist: n_entries is not the engine's number of fp32 state_dict entries");
     FoldArgs a{};
     for (int k = 0; k < K; ++k) {
         ARGCHK(states_dev[k], "fm_state_dist: null state pointer");
         a.s[k] = states_dev[k];
     }
-    k_state_dist(a, K, ref_dev, e->dist_ent, e->dist_n_ent, e->dist_chunks, e->dist_n_chunks, (int64_t)e->NS, e->dist_part, norms_dev,
-                 e->main.st);
+    if (!e->dist_part) DALLOC(e->dist_part, e->tab.chunks.size() * FM_FOLD_MAX);
+    k_state_dist(a, K, ref_dev, e->tab.d_ent, (int)e->tab.ent.size(), e->tab.d_chunks, (int)e->tab.chunks.size(), (int64_t)e->NS,
+                 e->dist_part, norms_dev, e->main.st);
     HIPCHK(hipGetLastError());
     return FM_OK;
 }
@@ -3619,7 +3560,7 @@ int fm_backward_grads_x(fm_engine* e, const float* dlogits_dev, const float* dfe
     // zeros over the frozen ones (stale in e->grad where a launch was skipped) and touches nothing outside the entries (zero
     // since the accumulator was allocated)
     if (!masked) k_grad_accumulate(e->gacc, e->grad, (int64_t)e->NP, !e->gacc_full, e->main.st, e->dev_err);
-    else k_grad_accumulate_masked(e->gacc, e->grad, e->opt_chunks, e->n_opt_chunks, mask_sel(e, bw.train), !e->gacc_full, e->main.st,
+    else k_grad_accumulate_masked(e->gacc, e->grad, e->tab.d_chunks, e->tab.n_param_chunks, mask_sel(e, bw.train), !e->gacc_full, e->main.st,
                                   e->dev_err);
     e->pending_views = 0;
     STEP_DONE(e);
@@ -3701,7 +3642,6 @@ int fm_set_trainable(fm_engine* e, const int32_t* flags, int32_t n_entries)
 {
     ARGCHK(e && flags, "null");
     ARGCHK(n_entries == (int32_t)e->entries.size(), "fm_set_trainable: one flag per state entry (fm_state_sizes' entry count)");
-    RCCHK(ensure_opt_table(e));
     bool all = true;
     for (size_t i = 0; i < e->entries.size(); ++i)
         if (is_param(e, e->entries[i]) && !flags[i]) all = false;
@@ -3731,7 +3671,6 @@ int fm_optim_groups(fm_engine* e, const int32_t* group_of_entry, int32_t n_entri
     for (size_t i = 0; i < e->entries.size(); ++i)
         ARGCHK(!is_param(e, e->entries[i]) || (group_of_entry[i] >= -1 && group_of_entry[i] < n_groups),
                "fm_optim_groups: a group index outside -1 .. n_groups - 1");
-    RCCHK(ensure_opt_table(e));
     e->group_of.assign(e->entries.size(), -1);
     for (size_t i = 0; i < e->entries.size(); ++i)
         if (is_param(e, e->entries[i])) e->group_of[i] = group_of_entry[i];
@@ -3886,30 +3825,6 @@ int fm_drift_active(fm_engine* e) { return e && e->drift_on ? 1 : 0; }
 // ---- server optimizers (include/fedmlp_hip_server.h) -------------------------------------------------------------------
 namespace {
 inline bool srv_adaptive(int rule) { return rule != FM_SERVER_AVGM; }
-// the chunks of ensure_dist_table's entries that are parameters (their index there counts the fp32 entries in state_dict order)
-int ensure_server_table(fm_engine* e)
-{
-    RCCHK(ensure_dist_table(e));
-    if (e->srv_chunks) return FM_OK;
-    std::vector<DistChunk> chunks;
-    int idx = 0;
-    for (auto& en : e->entries) {
-        if (en.kind == 2) continue;
-        if (en.eng_off < e->NP) {
-            const long long len = en.span().len;
-            if (len <= 0 || en.eng_off + (size_t)len > e->NP) { g_err = "a parameter entry lies outside the trainable arena"; return FM_ERR_ARG; }
-            for (long long st = 0; st < len; st += FM_DIST_CHUNK) chunks.push_back({idx, (int)st});
-        }
-        ++idx;
-    }
-    DistChunk* dc = nullptr;
-    double* dp = nullptr;
-    DALLOC(dc, chunks.size()); DALLOC(dp, chunks.size());
-    HIPCHK(hipMemcpy(dc, chunks.data(), chunks.size() * sizeof(DistChunk), hipMemcpyHostToDevice));
-    e->srv_part = dp; e->srv_n_chunks = (int)chunks.size();
-    e->srv_chunks = dc;
-    return FM_OK;
-}
 inline int srv_fill(fm_engine* e, float* p, float value)
 {
     uint32_t bits;
@@ -3929,7 +3844,7 @@ int fm_server_opt_begin(fm_engine* e, const fm_server_opt* hp)
     const bool second = hp->rule == FM_SERVER_ADAM || hp->rule == FM_SERVER_YOGI;
     ARGCHK(!second || (hp->beta2 >= 0.f && hp->beta2 < 1.f), "fm_server_opt_begin: beta2 must lie in [0, 1)");
     ARGCHK(!srv_adaptive(hp->rule) || (std::isfinite(hp->tau) && hp->tau > 0.f), "fm_server_opt_begin: tau must be finite and > 0");
-    RCCHK(ensure_server_table(e));
+    if (!e->srv_part) DALLOC(e->srv_part, (size_t)e->tab.n_param_chunks);
     if (!e->srv_m) DALLOC(e->srv_m, e->NP);
     if (srv_adaptive(hp->rule) && !e->srv_v) DALLOC(e->srv_v, e->NP);
     HIPCHK(hipMemsetAsync(e->srv_m, 0, e->NP * 4, e->main.st));
@@ -3960,7 +3875,7 @@ int fm_server_opt_step(fm_engine* e, const float* x_old_dev, double* delta_norm_
     OP(e->main, "server_opt");
     const fm_server_opt& hp = e->srv_hp;
     const ServerOps a{x_old_dev, st, e->srv_m, e->srv_v, hp.lr, hp.beta1, e->srv_omb1, hp.beta2, e->srv_omb2, hp.tau};
-    k_server_opt(hp.rule, a, e->dist_ent, e->srv_chunks, e->srv_n_chunks, e->srv_part, delta_norm_dev, e->main.st, e->dev_err);
+    k_server_opt(hp.rule, a, e->tab.d_ent, e->tab.d_chunks, e->tab.n_param_chunks, e->srv_part, delta_norm_dev, e->main.st, e->dev_err);
     e->srv_steps += 1;
     STEP_DONE(e);
     return FM_OK;
@@ -4218,19 +4133,13 @@ int fm_debug_optim_arena(fm_engine* e, int32_t which, float** dev_ptr, int64_t* 
 int fm_debug_entry_spans(fm_engine* e, int64_t* off_len, int32_t n_entries)
 {
     ARGCHK(e && off_len && n_entries == (int32_t)e->entries.size(), "null / entry count");
-    RCCHK(ensure_opt_table(e));
-    std::vector<OptChunk> chunks;
-    std::vector<int> ent;
-    std::unordered_map<size_t, int> at;
-    build_opt_table(e->entries, e->NP, chunks, ent, at);
-    for (int32_t i = 0; i < n_entries; ++i) { off_len[2 * i] = -1; off_len[2 * i + 1] = 0; }
-    std::vector<int> of_table(chunks.empty() ? 0 : chunks.back().ent + 1, -1);
-    for (int32_t i = 0; i < n_entries; ++i)
-        if (ent[i] >= 0) of_table[ent[i]] = i;
-    for (const OptChunk& c : chunks) {
-        const int i = of_table[c.ent];
-        if (off_len[2 * i] < 0) off_len[2 * i] = c.begin;
-        off_len[2 * i + 1] += c.len;
+    // a parameter's span as the table's chunks give it: the first one's begin, the sum of their lengths
+    for (int32_t i = 0; i < n_entries; ++i) {
+        off_len[2 * i] = -1; off_len[2 * i + 1] = 0;
+        if (!is_param(e, e->entries[i])) continue;
+        const ArenaEntry& a = e->tab.ent[e->tab.ent_of[i]];
+        off_len[2 * i] = e->tab.chunks[a.chunk0].begin;
+        for (int j = 0; j < a.nchunks; ++j) off_len[2 * i + 1] += e->tab.chunks[a.chunk0 + j].len;
     }
     return FM_OK;
 }

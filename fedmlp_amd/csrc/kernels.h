@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "arena_table.h"
 #include "common.h"
 
 #define FM_MAXC 32
@@ -61,14 +62,9 @@ struct FoldArgs { const float* s[FM_FOLD_MAX]; float n[FM_FOLD_MAX]; };
 void k_fedavg_fold(const FoldArgs& a, int K, float tot, float* out, int64_t n, hipStream_t s);
 void k_axpby(float* y, const float* x, float a, float b, int64_t n, hipStream_t s);   // y = a*y + b*x
 // agg.hip: norms[k][entry] = || s_k - ref || over the real elements of every fp32 state_dict entry (ref null: the states'
-// unweighted Fed_w mean, formed in registers), fp64 sums in a fixed order.  One DistEntry per fp32 entry: the arena span
-// [off, off + len), rows of `row` floats of which the first `dense` are [..][Wpad][Ipad] with wp < W, ip < I real (all_real:
-// every element of the span is); its chunks are chunk0 .. chunk0 + nchunks - 1, FM_DIST_CHUNK floats of the span each.
-// part: n_chunks * K doubles.
-#define FM_DIST_CHUNK 8192
-struct DistEntry { long long off; int len, row, dense, Ipad, I, Wpad, W, chunk0, nchunks, all_real; };
-struct DistChunk { int entry, start; };
-void k_state_dist(const FoldArgs& a, int K, const float* ref, const DistEntry* ent, int n_entries, const DistChunk* chunks,
+// unweighted Fed_w mean, formed in registers), fp64 sums in a fixed order.  ent / chunks: the engine's whole entry / chunk table
+// (arena_table.h), whose entry index is the output column.  part: n_chunks * K doubles.
+void k_state_dist(const FoldArgs& a, int K, const float* ref, const ArenaEntry* ent, int n_entries, const ArenaChunk* chunks,
                   int n_chunks, int64_t NS, double* part, float* norms, hipStream_t s);
 
 // metrics.hip: globaltest's per-class metrics of fp32 [N][C] scores / labels (include/fedmlp_hip.h, fm_eval_metrics).
@@ -297,46 +293,42 @@ void k_grad_norm(const float* g, int64_t n, double* part, float* norm, hipStream
 // g *= min(1, max_norm / (*norm + 1e-6)) in fp32; g = clamp(g, -clip, clip)
 void k_grad_clip_norm(float* g, int64_t n, const float* norm, float max_norm, hipStream_t s, const int* skip = nullptr);
 void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int* skip = nullptr);
-// ---- parameter groups and frozen entries (optim.hip): one block per chunk of the trainable arena's entry table -------------
-// OptChunk: <= FM_DIST_CHUNK consecutive arena floats of ONE trainable state entry (index `ent` into the table's entry list).
-// OptSel: four bits per table entry, by value with the launch (no device table to keep in step): the entry's parameter group
-// 0 .. FM_MAX_GROUPS - 1, or OPT_SKIP = nobody steps it (no group, or frozen).  For the masked accumulate: 0 = trainable.
-#define OPT_MAX_ENT 512
+// ---- parameter groups and frozen entries (optim.hip): one block per parameter chunk of the engine's entry / chunk table ---
+// chunks / n_chunks: the table's parameter prefix (arena_table.h); sel: four bits per table entry, by value with the launch --
+// the entry's parameter group 0 .. FM_MAX_GROUPS - 1, or OPT_SKIP = nobody steps it (no group, or frozen).  For the masked
+// accumulate: 0 = trainable.
 #define OPT_MAX_GROUPS 8
 #define OPT_SKIP 15u
-struct OptChunk { long long begin; int len; int ent; };
-struct OptSel { unsigned w[OPT_MAX_ENT / 8]; };
-static inline void opt_sel_set(OptSel& t, int ent, unsigned v) { t.w[ent >> 3] = (t.w[ent >> 3] & ~(15u << ((ent & 7) * 4))) | (v << ((ent & 7) * 4)); }
 // one Hp per group, by value with the launch
 struct OptAdamArgs { OptAdamHp hp[OPT_MAX_GROUPS]; };
 struct OptAdamWArgs { OptAdamWHp hp[OPT_MAX_GROUPS]; };
 struct OptSgdArgs { OptSgdHp hp[OPT_MAX_GROUPS]; };
-void k_adam_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_adam_groups(float* p, const float* g, float* m, float* v, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                    const OptAdamArgs& a, hipStream_t s, const int* skip);
-void k_adamw_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_adamw_groups(float* p, const float* g, float* m, float* v, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                     const OptAdamWArgs& a, hipStream_t s, const int* skip);
-void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_sgd_groups(float* p, const float* g, float* buf, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                   const OptSgdArgs& a, hipStream_t s, const int* skip);
 // the accumulate pass under a mask: a trainable entry's span is copied / added like k_grad_accumulate, a frozen entry's span is
 // written as zeros; floats outside every entry are not touched
-void k_grad_accumulate_masked(float* acc, const float* g, const OptChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
+void k_grad_accumulate_masked(float* acc, const float* g, const ArenaChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
                               hipStream_t s, const int* skip);
 // ---- client-drift correction (drift.hip): r = g [+ mu (p - a)] [+ s], S += g, each operation rounded on its own ------------
 // Arenas of n floats (a multiple of 4).  mu == 0: p and a are not read; s null: no shift; S null: no running sum.  g is never
-// written.  The masked form runs over the optimizer's entry table: sel 0 = trainable (the flat form's bits), anything else =
+// written.  The masked form runs over the table's parameter chunks: sel 0 = trainable (the flat form's bits), anything else =
 // frozen (r = 0 over the entry's span, S untouched); floats outside every entry are not touched.
 struct DriftOps { const float* g; const float* p; const float* a; const float* s; float* S; float* r; float mu; };
 void k_drift_correct(const DriftOps& a, int64_t n, hipStream_t s, const int* skip);
-void k_drift_correct_masked(const DriftOps& a, const OptChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip);
+void k_drift_correct_masked(const DriftOps& a, const ArenaChunk* chunks, int n_chunks, const OptSel& sel, hipStream_t s, const int* skip);
 // x[i] = x[i] / k, n floats at any alignment
 void k_drift_div(float* x, float k, int64_t n, hipStream_t s);
 // ---- server optimizers (server_opt.hip): FedAvgM / FedAdagrad / FedAdam / FedYogi on the pseudo-gradient st - x ------------
-// One block per chunk of the DistEntry / DistChunk table of the trainable entries.  x: the round's starting model (read only);
+// One block per parameter chunk of the engine's entry / chunk table (ent: the whole entry list).  x: the round's starting model (read only);
 // st: the aggregate, overwritten by x'; m, v: NP floats each, in place (v is not named by AVGM).  omb1 / omb2: 1.0f - beta, formed
 // by the host.  part: n_chunks doubles; norm (may be null): |st - x|_2 over the entries' real elements as one double.
 // (rule: FM_SERVER_AVGM .. FM_SERVER_YOGI of include/fedmlp_hip_server.h, which the callers include)
 struct ServerOps { const float* x; float* st; float* m; float* v; float lr, beta1, omb1, beta2, omb2, tau; };
-void k_server_opt(int rule, const ServerOps& a, const DistEntry* ent, const DistChunk* chunks, int n_chunks, double* part,
+void k_server_opt(int rule, const ServerOps& a, const ArenaEntry* ent, const ArenaChunk* chunks, int n_chunks, double* part,
                   double* norm, hipStream_t s, const int* skip);
 
 // ---- prototypes / tagging ----------------------------------------------------------

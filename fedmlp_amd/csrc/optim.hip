@@ -21,17 +21,7 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // inlining -- it differed between two kernels holding the same AdamW expressions.  The fmas spelled out are the ones the
 // kernels held when each rule was still written as plain expressions, so the trajectories recorded then still hold.
 // A rule also carries its operand arenas: load() reads a quad of every operand at float offset o (a multiple of 4), store()
-// writes the floats of the quad that lie in [begin, end).
-__device__ __forceinline__ void store_own(float* __restrict__ a, int64_t o, int64_t begin, int64_t end, const f32x4 v)
-{
-    if (o >= begin && o + 4 <= end) {
-        *reinterpret_cast<f32x4*>(a + o) = v;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (o + k >= begin && o + k < end) a[o + k] = v[k];
-    }
-}
+// writes the floats of the quad that lie in [begin, end) (arena_table.h: store_own, and the walker's concept).
 
 // the operands of the two rules with two moments
 struct PgmvRule {
@@ -261,90 +251,53 @@ void k_grad_clip_value(float* g, int64_t n, float clip, hipStream_t s, const int
 }
 
 // ------------------------------------------- parameter groups, frozen entries --------
-// The three steps again, over the entry table of the trainable arena (engine.hip: ensure_opt_table) instead of the flat arena:
-// one block of 256 threads per chunk of <= FM_DIST_CHUNK floats of ONE state entry, whose parameter group the block fetches
-// once from the launch's own argument block (OptSel: four bits per entry).  An entry nobody steps -- in no group, or frozen --
-// costs its blocks one kernel-argument read: they return before any load.  The hyper-parameters are an argument array of
-// OPT_MAX_GROUPS structs holding what the single-group launchers pass to their kernels, formed the same way on the host.
+// The three steps again, over the parameter chunks of the engine's entry / chunk table (arena_table.h) instead of the flat
+// arena: one block of 256 threads per chunk of <= FM_DIST_CHUNK floats of ONE state entry, whose parameter group the block
+// fetches once from the launch's own argument block (OptSel: four bits per entry).  An entry nobody steps -- in no group, or
+// frozen -- costs its blocks one kernel-argument read: they return before any load.  The hyper-parameters are an argument
+// array of OPT_MAX_GROUPS structs holding what the single-group launchers pass to their kernels, formed the same way on the host.
 //
-// An entry begins at any element offset, so a chunk's first quad starts at the 16-byte boundary at or below `begin`
-// (state_dist_kernel's rule) and that quad -- like the last one -- may hold floats of the neighbouring entry, which belongs to
-// another block and possibly to another group or to nobody.  A block therefore WRITES only its own floats: the first and the
-// last quad of a chunk are stored lane by lane (4-byte stores of the lanes inside [begin, end)), interior quads as 16 bytes.  It
-// still reads and computes whole quads: the neighbour's lanes are computed and dropped.  Floats outside every entry (the gaps
-// between matrices and vectors, a padded BatchNorm vector's tail) are touched by nobody and stay zero; padding inside an entry's
-// span (padded input channels and taps, the packed stem's row tails) is stepped with its entry and stays zero under all three
+// arena_walk has the boundary rule (whole quads read, own floats written).  Floats outside every entry (the gaps between
+// matrices and vectors, a padded BatchNorm vector's tail) are touched by nobody and stay zero; padding inside an entry's span
+// (padded input channels and taps, the packed stem's row tails) is stepped with its entry and stays zero under all three
 // rules (zero weight, zero gradient: DESIGN.md section 1's padding note).
 //
 // The arithmetic per element is the rule's update(), the one the flat steps call.
-// A thread holds OPT_QPT quads of every operand: all its 16-byte loads are in flight before the first use.  A full chunk that
-// starts off a 16-byte boundary has one quad more (2049): thread 0 takes it after the others.
-#define OPT_QPT (FM_DIST_CHUNK / 4 / 256)
-
-__device__ __forceinline__ unsigned opt_sel_get(const OptSel& t, int ent) { return (t.w[ent >> 3] >> ((ent & 7) * 4)) & 15u; }
-
-template <class R>
-__device__ __forceinline__ void opt_chunk(const R& r, const OptChunk ch, const typename R::Hp& hp)
-{
-    const int64_t begin = ch.begin, end = begin + ch.len;
-    const int64_t o0 = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x;
-    typename R::Quad q[OPT_QPT];
-#pragma unroll
-    for (int j = 0; j < OPT_QPT; ++j) {
-        const int64_t o = o0 + (int64_t)j * 1024;
-        if (o < end) r.load(q[j], o);
-    }
-#pragma unroll
-    for (int j = 0; j < OPT_QPT; ++j) {
-        const int64_t o = o0 + (int64_t)j * 1024;
-        if (o < end) {
-            R::update(q[j], hp);
-            r.store(q[j], o, begin, end);
-        }
-    }
-    const int64_t o = o0 + (int64_t)OPT_QPT * 1024;
-    if (o < end) {
-        typename R::Quad t;
-        r.load(t, o);
-        R::update(t, hp);
-        r.store(t, o, begin, end);
-    }
-}
 template <class R, class Args>
-__global__ void __launch_bounds__(256) opt_groups_kernel(const R r, const Args a, const OptChunk* __restrict__ chunks, const OptSel sel,
+__global__ void __launch_bounds__(256) opt_groups_kernel(const R r, const Args a, const ArenaChunk* __restrict__ chunks, const OptSel sel,
                                                          const int* __restrict__ skip)
 {
     if (skip && *skip) return;
-    const OptChunk ch = chunks[blockIdx.x];
+    const ArenaChunk ch = chunks[blockIdx.x];
     const unsigned gi = opt_sel_get(sel, ch.ent);
     if (gi >= OPT_MAX_GROUPS) return;             // in no group, or frozen: before any load
-    opt_chunk(r, ch, a.hp[gi]);
+    arena_walk(r, ch, a.hp[gi]);
 }
 __global__ void __launch_bounds__(256) sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                         const OptSgdArgs a, const OptChunk* __restrict__ chunks, const OptSel sel,
+                                                         const OptSgdArgs a, const ArenaChunk* __restrict__ chunks, const OptSel sel,
                                                          const int* __restrict__ skip)
 {
     if (skip && *skip) return;
-    const OptChunk ch = chunks[blockIdx.x];
+    const ArenaChunk ch = chunks[blockIdx.x];
     const unsigned gi = opt_sel_get(sel, ch.ent);
     if (gi >= OPT_MAX_GROUPS) return;
     const int mode = a.hp[gi].mode;
-    if (mode == 0) opt_chunk(SgdRule<0>{p, g, buf}, ch, a.hp[gi]);
-    else if (mode == 1) opt_chunk(SgdRule<1>{p, g, buf}, ch, a.hp[gi]);
-    else opt_chunk(SgdRule<2>{p, g, buf}, ch, a.hp[gi]);
+    if (mode == 0) arena_walk(SgdRule<0>{p, g, buf}, ch, a.hp[gi]);
+    else if (mode == 1) arena_walk(SgdRule<1>{p, g, buf}, ch, a.hp[gi]);
+    else arena_walk(SgdRule<2>{p, g, buf}, ch, a.hp[gi]);
 }
 
-void k_adam_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_adam_groups(float* p, const float* g, float* m, float* v, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                    const OptAdamArgs& a, hipStream_t s, const int* skip)
 {
     hipLaunchKernelGGL((opt_groups_kernel<AdamRule, OptAdamArgs>), dim3(n_chunks), dim3(256), 0, s, AdamRule{{p, g, m, v}}, a, chunks, sel, skip);
 }
-void k_adamw_groups(float* p, const float* g, float* m, float* v, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_adamw_groups(float* p, const float* g, float* m, float* v, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                     const OptAdamWArgs& a, hipStream_t s, const int* skip)
 {
     hipLaunchKernelGGL((opt_groups_kernel<AdamWRule, OptAdamWArgs>), dim3(n_chunks), dim3(256), 0, s, AdamWRule{{p, g, m, v}}, a, chunks, sel, skip);
 }
-void k_sgd_groups(float* p, const float* g, float* buf, const OptChunk* chunks, int n_chunks, const OptSel& sel,
+void k_sgd_groups(float* p, const float* g, float* buf, const ArenaChunk* chunks, int n_chunks, const OptSel& sel,
                   const OptSgdArgs& a, hipStream_t s, const int* skip)
 {
     hipLaunchKernelGGL(sgd_groups_kernel, dim3(n_chunks), dim3(256), 0, s, p, g, buf, a, chunks, sel, skip);
@@ -373,11 +326,11 @@ void k_grad_accumulate(float* acc, const float* g, int64_t n, bool copy, hipStre
 // acc += g, the flat kernel's one addition), anything else a frozen one, whose span becomes exact zeros in both forms -- whatever
 // e->grad holds there (a skipped weight gradient leaves it stale).
 __global__ void __launch_bounds__(256) grad_accumulate_masked_kernel(float* __restrict__ acc, const float* __restrict__ g,
-                                                                     const OptChunk* __restrict__ chunks, const OptSel sel, int copy,
+                                                                     const ArenaChunk* __restrict__ chunks, const OptSel sel, int copy,
                                                                      const int* __restrict__ skip)
 {
     if (skip && *skip) return;
-    const OptChunk ch = chunks[blockIdx.x];
+    const ArenaChunk ch = chunks[blockIdx.x];
     const bool frozen = opt_sel_get(sel, ch.ent) != 0u;
     const int64_t begin = ch.begin, end = begin + ch.len;
     for (int64_t o = (begin & ~(int64_t)3) + 4 * (int64_t)threadIdx.x; o < end; o += 1024) {
@@ -389,7 +342,7 @@ __global__ void __launch_bounds__(256) grad_accumulate_masked_kernel(float* __re
         store_own(acc, o, begin, end, r);
     }
 }
-void k_grad_accumulate_masked(float* acc, const float* g, const OptChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
+void k_grad_accumulate_masked(float* acc, const float* g, const ArenaChunk* chunks, int n_chunks, const OptSel& sel, bool copy,
                               hipStream_t s, const int* skip)
 {
     hipLaunchKernelGGL(grad_accumulate_masked_kernel, dim3(n_chunks), dim3(256), 0, s, acc, g, chunks, sel, copy ? 1 : 0, skip);
